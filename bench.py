@@ -38,6 +38,7 @@ Extra objects on the JSON line:
                  issue roof of that kernel when it is the NFM forward kernel, and every HBM-bound kernel's own fraction.
   cpu_baseline — the CPU oracle (oracle/pss_oracle.c, a port of the reference's NumPy/SciPy path with the
                  filters designed once) timed on this box's host cores on a bounded sample (rank 0, N=1 only).
+  dumped_outputs — with --dump-outputs DIR: the files written there (rank 0's outputs of the last timed step, see dump_outputs).
 """
 import argparse
 import hashlib
@@ -298,6 +299,34 @@ def verify_step(eng, iq, fs, d_db, d_lo, d_hi, pk, o_col, o_pcm, n_out, window, 
     return res
 
 
+DUMP_MAX_BYTES = 64_000_000    # --dump-outputs: every file together stays under 64 MB
+DUMP_SEED = 20260928           # the frame sample of a batch too large to dump whole: the same frames on every run
+
+
+def dump_outputs(dirname, outputs, nf):
+    """--dump-outputs DIR: what the last timed step left in HBM, as a caller of the step receives it, written as DIR/<name>.npy so that two
+    builds can be compared output for output (the IQ is seeded: the same arguments give the same inputs).  float32 / float64 outputs keep
+    their type, the int8 display cells and the int16 PCM are widened to float32 (exact).  outputs: name -> device tensor with the frame as
+    its first dimension.  A batch whose outputs would pass DUMP_MAX_BYTES is sampled: the same seeded, ascending set of frames from every
+    output, its indices in frame_index.npy (float64)."""
+    conv = {n: (torch.float64 if t.dtype == torch.float64 else torch.float32) for n, t in outputs.items()}
+    per_frame = 8 + sum(t[0].numel() * torch.empty((), dtype=conv[n]).element_size() for n, t in outputs.items())   # (+ the frame index)
+    fit = (DUMP_MAX_BYTES - 4096 * (len(outputs) + 1)) // per_frame     # (4096: an upper bound on one .npy header)
+    keep = nf if nf <= fit else 1 << (int(fit).bit_length() - 1)           # a sample: the largest power of two of frames that fits
+    idx = np.arange(nf) if keep == nf else np.sort(np.random.default_rng(DUMP_SEED).choice(nf, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {n: (t if keep == nf else t.index_select(0, torch.from_numpy(idx).to(t.device))).to(conv[n]).cpu().numpy() for n, t in outputs.items()}
+    arrays["frame_index"] = idx.astype(np.float64)
+    total = 0
+    for n, a in arrays.items():
+        p = os.path.join(dirname, n + ".npy")
+        np.save(p, a)
+        total += os.path.getsize(p)
+    assert total <= DUMP_MAX_BYTES, total
+    return {"dir": os.path.abspath(dirname), "frames": int(keep), "frames_in_batch": nf, "bytes": total,
+            "files": {n: {"shape": list(a.shape), "dtype": str(a.dtype)} for n, a in arrays.items()}}
+
+
 SUMMARY_MAX_CHARS = 1500
 SUMMARY_CONFIGS = ("cfg2_f32_rows", "cfg2_exact_cells", "cfg3", "cfg4", "cfg5_resident", "cfg5_streamed", "wfm_step")
 
@@ -385,7 +414,13 @@ def main():
                     help="skip the other BASELINE.json configs (cfg 3, cfg 4, cfg 5 resident + streamed, the WFM step) that the default one-GPU "
                          "run times and verifies after the headline (tools/bench_configs.py)")
     ap.add_argument("--dry-run", action="store_true", help="launch path only (gloo rendezvous, no GPU work): what the CPU test runs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's dB rows, row extremes, display lines, PCM; "
+                         "--materialise-post: the post-processed rows) as DIR/<name>.npy in float32 / float64, under 64 MB in all "
+                         "(a seeded sample of the frames when the batch is larger)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # N ranks for --gpus N: re-executes under torch.distributed.run when started bare; exits 2 on any mismatch (pyspecsdr_amd/launch.py)
     from pyspecsdr_amd.launch import ensure_ranks
@@ -549,6 +584,18 @@ def main():
         live_all.append(sum(live) / len(live))
     eng.timing_filter(None)
     eng.enable_timing(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the buffers of the last timed step (k = steps - 1), before any untimed step below writes them again
+        b = (args.steps - 1) & 1
+        pk = packed[b]
+        outs = {"db_rows": d_db[b % len(d_db)], "row_lo": d_lo, "row_hi": d_hi,
+                "waterfall_glyph": pk[:o_col].view(torch.int8).view(nf, DISP_W),
+                "waterfall_colour": pk[o_col:o_pcm].view(torch.int8).view(nf, DISP_W),
+                "pcm": pk[o_pcm:].view(torch.int16).view(nf, n_out, 2)}
+        if step_post is not None:
+            outs["post_rows"] = step_post
+        dumped = dump_outputs(args.dump_outputs, outs, nf)
     clk1 = clock_under_load()
     order = sorted(range(len(regions)), key=lambda i: regions[i])
     mid = order[len(order) // 2]
@@ -782,6 +829,8 @@ def main():
                                              "exchange_display_ms >> 0.25 = RCCL serialises the peers; (iii) per_rank.shader_clock_mhz / "
                                              "dominant_kernel_ms differ = a slower GPU"}
         out.update(side)
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if other is not None:
             out["other_configs"] = other
         if world == 1 and not args.no_cpu_baseline:
