@@ -484,3 +484,35 @@ def waterfall_rows(rows, window, disp_w, n_threads=1):
     c = np.empty((rows.shape[0], disp_w), np.int8)
     lib().pss_o_waterfall_rows(rows.reshape(-1), rows.shape[0], rows.shape[1], window, disp_w, g.reshape(-1), c.reshape(-1), n_threads)
     return g, c
+
+
+_POOLS = {}
+
+
+def map_frames(fn, items, threads=None):
+    """[fn(x) for x in items], evaluated on a pool of `threads` host threads (default: min(threads_available(), 16)); results in order.
+
+    ctypes releases the GIL for the length of every oracle call, so frames run in parallel.  What was checked for that to be safe:
+    oracle/pss_oracle.c and oracle/pss_pocketfft.c keep no mutable state outside a call but the two caches of compute_fft's window /
+    twiddle tables (np.hamming of the latest length, the transform's twiddles), which are `static __thread`; every other static is a
+    const table; the transforms (pocketfft restatement included) allocate their scratch per call; nothing touches the floating-point
+    environment, errno-dependent paths, getenv or the OpenMP runtime outside the batch entry points (pss_o_batch_*, *_rows), which
+    must not be handed to this pool.  Of the bindings above, those that set argtypes inside the call (the *_c128 ones) only assign the
+    same values again.  The pools persist per thread count, so their per-thread caches are made once, not once per call."""
+    items = list(items)
+    if threads is None:
+        threads = min(threads_available(), 16)
+    threads = max(1, int(threads))
+    lib()                                    # bind once, before any worker can race to it
+    if threads == 1 or len(items) < 2:
+        return [fn(x) for x in items]
+    from concurrent.futures import ThreadPoolExecutor
+    pool = _POOLS.get(threads)
+    if pool is None:
+        pool = _POOLS[threads] = ThreadPoolExecutor(max_workers=threads, thread_name_prefix="oracle")
+    step = max(1, -(-len(items) // (threads * 8)))     # a few blocks per thread: Python per-task overhead paid once per block
+    blocks = [items[i:i + step] for i in range(0, len(items), step)]
+    out = []
+    for r in pool.map(lambda blk: [fn(x) for x in blk], blocks):
+        out.extend(r)
+    return out
