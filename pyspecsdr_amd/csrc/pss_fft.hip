@@ -1433,11 +1433,31 @@ extern "C" int pss_hilbert(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     return r;
 }
 
+// one-sample frames: np.hamming(1) == [1.0] and the fft / fftshift of one value is that value, so the row is 10 log10(|x|^2 + 1e-10)
+__global__ __launch_bounds__(256) void k_spectrum_one(const float2 *__restrict__ iq, float *__restrict__ db, long n_frames, int flags)
+{
+    for (long f = (long)blockIdx.x * blockDim.x + threadIdx.x; f < n_frames; f += (long)gridDim.x * blockDim.x) {
+        const float2 v = iq[f];
+        db[f] = db_of(pss_r16::power_of(make_double2((double)v.x, (double)v.y)), flags);
+    }
+}
+
 extern "C" int pss_spectrum_db(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, float *d_db)
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_db && n_frames > 0) return pss_fail(ctx, PSS_E_ARG, "d_db is null");
+    if (n_fft == 1) {
+        if (n_frames < 0 || (n_frames > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "null iq / negative n_frames");
+        if (n_frames == 0) return PSS_OK;
+        pss_time_begin(ctx);
+        pss_kernel_begin(ctx, "k_spectrum_one");
+        hipLaunchKernelGGL(k_spectrum_one, dim3((unsigned)((n_frames + 255) / 256 < 1024 ? (n_frames + 255) / 256 : 1024)), dim3(256), 0, PSS_STREAM(ctx),
+                           reinterpret_cast<const float2 *>(d_iq), d_db, n_frames, spec_flags(ctx));
+        pss_kernel_end(ctx);
+        pss_time_end(ctx);
+        return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_one launch");
+    }
     if (n_frames > 0 && d_iq && n_fft >= 2 && !(is_pow2(n_fft) && n_fft >= 16)) return bluestein_db(ctx, d_iq, n_frames, n_fft, true, d_db);
     return launch_spectrum<false>(ctx, d_iq, n_frames, n_fft, d_db, nullptr, nullptr, nullptr, 0.0);
 }

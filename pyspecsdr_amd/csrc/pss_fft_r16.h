@@ -240,8 +240,15 @@ __device__ __forceinline__ float db_of_exact(double pw, const double2 *tab = DB_
 // issue slots.  This is the default; option "db_exact" = 1 selects db_of_exact (spectrum kernel 0.17 -> 0.20 ms at cfg 2, bench step + 3 %).
 __device__ __forceinline__ float db_of_fast(double pw)
 {
+    // |X|^2 past FLT_MAX (amplitudes above ~3e16 at 1024 points) has no float32 value, its row value has: such a pw is scaled by 2^-200
+    // (its exponent field lowered, exact) and log2 pw = __log2f((float)(pw 2^-200)) + 200.  Every |X|^2 + 1e-10 of a complex64 frame of up
+    // to 2^20 points is below 2^296, so the scaled value is a normal float32.  Three selects and an add, no branch: a per-element
+    // branch (or the float64 evaluation behind one) cost the 4096-point kernel 50 registers, one wavefront per SIMD instead of two.  Every
+    // other pw (NaN included: the compare is false) goes through unchanged, to the same bits as before (x + 0.0f == x); +inf stays +inf.
+    const bool big = pw >= 0x1.ffffffp+127;                                // (float)pw would round to +inf
+    const double ps = __hiloint2double(__double2hiint(pw) - (big ? (200 << 20) : 0), __double2loint(pw));
     const float t = (float)(pw - 1.0);
-    const float far = 3.0102999566398120f * __log2f((float)pw);
+    const float far = 3.0102999566398120f * (__log2f((float)ps) + (big ? 200.0f : 0.0f));
     const float s = t * __builtin_amdgcn_rcpf(2.0f + t);
     const float s2 = s * s;
 #ifdef PSS_EXP_NOFMA

@@ -26,6 +26,7 @@ torch = pytest.importorskip("torch")
 
 import oracle_lib as O
 import gpu_util as G
+from spectrum_bounds import exact_rows_bad, scan_ulp_bound
 from pyspecsdr_amd import _lib as L
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
@@ -116,22 +117,6 @@ def close_bad(got, want, atol=None, rel=None):
     gn, wn = np.isnan(g), np.isnan(w)
     with np.errstate(invalid="ignore"):
         ok = np.where(gn | wn, gn & wn, np.abs(g - w) <= tol)
-    return np.nonzero(~_rows(ok, len(g)).all(axis=1))[0]
-
-
-def exact_rows_bad(got, ref, rel=1e-12):
-    """db_exact rows: frames with a float32 value outside [float32(ref - d), float32(ref + d)], d = rel * max(|row|, 1) — the float32
-    rounding of a value within float64 accuracy of the oracle's row.  Bit equality with float32(ref) holds on every golden row
-    (test_spectrum_db_exact_is_the_float32_rounding_of_the_reference_rows), but not on every value of 134 million: two float64
-    transforms agree to ~1e-16 of the row's LARGEST bin, so a value near 0 dB (a bin of power ~1 beside a 73 dB peak), whose float32
-    ulp is far finer than that, can round to the neighbouring float32 value.  Measured on cfg 3's 8192 x 16 384 AM rows: 75 values in
-    75 frames (93, 193, 267, ...), each 1 float32 ulp from float32(ref), the oracle's value at most 1.4e-12 dB from the float32
-    rounding midpoint (20 ppt of the row's peak) in the 40 inspected; the bound is 1e-12 of the row's peak."""
-    g = np.asarray(got, np.float32)
-    ref = np.asarray(ref, np.float64)
-    with np.errstate(invalid="ignore"):
-        d = rel * np.maximum(np.nanmax(np.abs(ref.reshape(len(ref), -1)), axis=1), 1.0).reshape((-1,) + (1,) * (ref.ndim - 1))
-        ok = ((g >= (ref - d).astype(np.float32)) & (g <= (ref + d).astype(np.float32))) | (np.isnan(g) & np.isnan(ref))
     return np.nonzero(~_rows(ok, len(g)).all(axis=1))[0]
 
 
@@ -392,14 +377,6 @@ def test_cfg3_ssb_every_frame(nf, mode):
 # kernel's and the oracle's, agree to ~1e-16 of the largest bin: a weak bin beside a strong carrier can round the other way in float32).
 # Measured on 8192 x 4096 synth("scan") slices: 5 of 33 554 432 values differ (slices 540, 1950, 2371, 4860, 5550).
 SCAN_DIFF_RATE = 3 / 146912
-
-
-def scan_ulp_bound(ref):
-    """One float32 ulp in a spectrum component moves 10 log10(|X|^2 + 1e-10) by up to 20 / ln 10 * 2^-23 ~ 1.04e-6 dB: two ulp of the
-    dB value where |dB| >= 4, more below (a 1-ulp component at -1.83 dB moved the value by 8 ulp, slice 4860 of 8192 x 4096).  The
-    bound is two ulp of max(|dB|, 4): the 2-ulp rule of the per-family test wherever its argument holds, the same absolute 9.5e-7 dB
-    below."""
-    return 2.0 * np.spacing(np.maximum(np.abs(np.asarray(ref, np.float32)), np.float32(4.0))).astype(np.float64)
 
 
 @pytest.mark.parametrize("ns", [8192, 8200])
