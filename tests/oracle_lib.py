@@ -95,6 +95,13 @@ def lib():
         L.pss_o_waterfall_rows_f64.argtypes = [_f64p, _f64p, _f64p, C.c_long, C.c_int, C.c_int, C.c_int, _i8p, _i8p, C.c_int]
         L.pss_o_persistence_rows_f64.argtypes = [_f64p, _f64p, _f64p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _i8p, C.c_int]
         L.pss_o_persistence_rows.argtypes = [_f32p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _i8p, C.c_int]
+        # bound here, once: assigning argtypes while another thread calls the same function races (map_frames)
+        L.pss_o_compute_fft_c128.argtypes, L.pss_o_compute_fft_c128.restype = [_f64p, C.c_int, _f64p], None
+        L.pss_o_mean_power_c128.argtypes, L.pss_o_mean_power_c128.restype = [_f64p, C.c_int, _f64p], C.c_double
+        L.pss_o_demod_am_c128.argtypes, L.pss_o_demod_am_c128.restype = [_f64p, C.c_int, _f64p, C.c_int, _f64p], None
+        L.pss_o_demod_ssb_c128.argtypes, L.pss_o_demod_ssb_c128.restype = [_f64p, C.c_int, _f64p, _f64p, C.c_int], None
+        L.pss_o_morse_edges_thr.restype = None
+        L.pss_o_morse_edges_thr.argtypes = [_f32p, C.c_long, C.c_double, _i32p, _i32p, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
         _lib = L
     return _lib
 
@@ -131,18 +138,14 @@ def compute_fft_c128(iq):
     """compute_fft of a complex128 buffer (float64 window product)."""
     x = np.ascontiguousarray(iq, np.complex128)
     out = np.empty(len(x), np.float64)
-    f = lib().pss_o_compute_fft_c128
-    f.argtypes, f.restype = [_f64p, C.c_int, _f64p], None
-    f(x.view(np.float64), len(x), out)
+    lib().pss_o_compute_fft_c128(x.view(np.float64), len(x), out)
     return out
 
 
 def mean_power_c128(iq):
     """np.mean(np.abs(x) ** 2) of a complex128 buffer in float64 (the array part of measure_signal_power)."""
     x = np.ascontiguousarray(iq, np.complex128)
-    f = lib().pss_o_mean_power_c128
-    f.argtypes, f.restype = [_f64p, C.c_int, _f64p], C.c_double
-    return np.float64(f(x.view(np.float64), len(x), np.empty(len(x), np.float64)))
+    return np.float64(lib().pss_o_mean_power_c128(x.view(np.float64), len(x), np.empty(len(x), np.float64)))
 
 
 def demod_am_c128(iq, sos):
@@ -150,9 +153,7 @@ def demod_am_c128(iq, sos):
     x = np.ascontiguousarray(iq, np.complex128)
     sos = np.ascontiguousarray(sos, np.float64)
     out = np.empty(len(x), np.float64)
-    f = lib().pss_o_demod_am_c128
-    f.argtypes, f.restype = [_f64p, C.c_int, _f64p, C.c_int, _f64p], None
-    f(x.view(np.float64), len(x), sos, sos.shape[0], out)
+    lib().pss_o_demod_am_c128(x.view(np.float64), len(x), sos, sos.shape[0], out)
     return out
 
 
@@ -266,11 +267,7 @@ def morse_edges(iq, threshold=-20):
     rise, fall = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32)
     nr, nf = C.c_long(), C.c_long()
     if float(threshold) != -20.0:
-        L = lib()
-        L.pss_o_morse_edges_thr.restype = None
-        L.pss_o_morse_edges_thr.argtypes = [_f32p, C.c_long, C.c_double, np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"),
-                                            np.ctypeslib.ndpointer(np.int32, flags="C_CONTIGUOUS"), C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]
-        L.pss_o_morse_edges_thr(_iq(iq), n, float(threshold), rise, fall, n, C.byref(nr), C.byref(nf))
+        lib().pss_o_morse_edges_thr(_iq(iq), n, float(threshold), rise, fall, n, C.byref(nr), C.byref(nf))
         return rise[:nr.value].copy(), fall[:nf.value].copy()
     lib().pss_o_morse_edges(_iq(iq), n, rise, fall, n, C.byref(nr), C.byref(nf))
     return rise[:nr.value].copy(), fall[:nf.value].copy()
@@ -331,9 +328,7 @@ def demod_ssb_c128(iq, taps, hilbert=True):
     """demodulate_ssb of a complex128 buffer."""
     x = np.ascontiguousarray(iq, np.complex128)
     out = np.empty(len(x), np.float64)
-    f = lib().pss_o_demod_ssb_c128
-    f.argtypes, f.restype = [_f64p, C.c_int, _f64p, _f64p, C.c_int], None
-    f(x.view(np.float64), len(x), np.ascontiguousarray(taps, np.float64), out, 1 if hilbert else 0)
+    lib().pss_o_demod_ssb_c128(x.view(np.float64), len(x), np.ascontiguousarray(taps, np.float64), out, 1 if hilbert else 0)
     return out
 
 
@@ -497,8 +492,8 @@ def map_frames(fn, items, threads=None):
     twiddle tables (np.hamming of the latest length, the transform's twiddles), which are `static __thread`; every other static is a
     const table; the transforms (pocketfft restatement included) allocate their scratch per call; nothing touches the floating-point
     environment, errno-dependent paths, getenv or the OpenMP runtime outside the batch entry points (pss_o_batch_*, *_rows), which
-    must not be handed to this pool.  Of the bindings above, those that set argtypes inside the call (the *_c128 ones) only assign the
-    same values again.  The pools persist per thread count, so their per-thread caches are made once, not once per call."""
+    must not be handed to this pool.  Every binding's argtypes are set once, in lib(), before any worker starts: ctypes' argument
+    converters are not safe to reassign while another thread calls the same function.  The pools persist per thread count, so their per-thread caches are made once, not once per call."""
     items = list(items)
     if threads is None:
         threads = min(threads_available(), 16)
