@@ -1158,21 +1158,49 @@ int pss_o_agc_step(float power_db, int idx, int n_gains)
     return idx;
 }
 
+/* One sample of np.interp between the knots (j, fp0) and (j + 1, fp1), x in [j, j + 1), as numpy compiled_base.c arr_interp
+ * evaluates it: x on the knot returns fp[j] itself; otherwise slope*(x - xp[j]) + fp[j], and if that is NaN (a non-finite knot)
+ * slope*(x - xp[j+1]) + fp[j+1], and if that is NaN too while fp[j] == fp[j+1], fp[j].  For finite knots only the sign of a zero
+ * result can differ from the plain formula. */
+static inline double np_interp_seg(double fp0, double fp1, double x, int j)
+{
+    if (x == (double)j) return fp0;
+    const double slope = (fp1 - fp0) / ((double)(j + 1) - (double)j);
+    double r = slope * (x - (double)j) + fp0;
+    if (isnan(r)) {
+        r = slope * (x - (double)(j + 1)) + fp1;
+        if (isnan(r) && fp0 == fp1) r = fp0;
+    }
+    return r;
+}
+
 /* np.interp(np.linspace(0, len-1, W), np.arange(len), row): linspace = start + i*step with the last
- * point forced to stop; interp = slope*(x - xp[j]) + fp[j] (numpy compiled_base.c arr_interp). */
+ * point forced to stop; the interpolation rules of np_interp_seg.  ROW: double or float elements. */
+#define NP_INTERP_ROW(row, len, W, i, out)                                                  \
+    do {                                                                                    \
+        const double stop_ = (double)((len) - 1);                                           \
+        double x_;                                                                          \
+        if ((W) == 1) x_ = 0.0;                                                             \
+        else x_ = ((i) == (W) - 1) ? stop_ : (double)(i) * (stop_ / (double)((W) - 1));     \
+        if (x_ >= stop_) (out) = (double)(row)[(len) - 1];                                  \
+        else {                                                                              \
+            const int j_ = (int)x_;                                                         \
+            (out) = np_interp_seg((double)(row)[j_], (double)(row)[j_ + 1], x_, j_);        \
+        }                                                                                   \
+    } while (0)
+
 static double interp_row(const double *row, int len, int W, int i)
 {
-    double stop = (double)(len - 1);
-    double x;
-    if (W == 1) x = 0.0;
-    else {
-        double step = stop / (double)(W - 1);
-        x = (i == W - 1) ? stop : (double)i * step;
-    }
-    if (x >= stop) return row[len - 1];
-    int j = (int)x;
-    double slope = (row[j + 1] - row[j]) / ((double)(j + 1) - (double)j);
-    return slope * (x - (double)j) + row[j];
+    double v;
+    NP_INTERP_ROW(row, len, W, i, v);
+    return v;
+}
+
+static double interp_row_f32(const float *row, int len, int W, int i)
+{
+    double v;
+    NP_INTERP_ROW(row, len, W, i, v);
+    return v;
 }
 
 static void ring_minmax(const double *rows, long count, double *mn, double *mx)
@@ -1447,20 +1475,8 @@ void pss_o_waterfall_rows(const float *rows, long n_frames, int len, int window,
             hi = rhi[p] > hi ? rhi[p] : hi;
         }
         const float *row = rows + f * len;
-        const double stop = (double)(len - 1);
         for (int x = 0; x < disp_w; x++) {
-            double xp, v;
-            if (disp_w == 1) xp = 0.0;
-            else {
-                const double step = stop / (double)(disp_w - 1);
-                xp = (x == disp_w - 1) ? stop : (double)x * step;
-            }
-            if (xp >= stop) v = (double)row[len - 1];
-            else {
-                const int j = (int)xp;
-                const double slope = ((double)row[j + 1] - (double)row[j]) / ((double)(j + 1) - (double)j);
-                v = slope * (xp - (double)j) + (double)row[j];
-            }
+            const double v = interp_row_f32(row, len, disp_w, x);
             int8_t g = -1, ci = -1;
             if (isfinite(v)) {
                 const double nv = (v - lo) / (hi - lo);
@@ -1508,20 +1524,8 @@ void pss_o_persistence_rows(const float *rows, long n_frames, int len, int windo
         double range = hi - lo;
         if (range == 0) range = 1;
         const float *row = rows + f * len;
-        const double stop = (double)(len - 1);
         for (int x = 0; x < disp_w; x++) {
-            double xp, v;
-            if (disp_w == 1) xp = 0.0;
-            else {
-                const double step = stop / (double)(disp_w - 1);
-                xp = (x == disp_w - 1) ? stop : (double)x * step;
-            }
-            if (xp >= stop) v = (double)row[len - 1];
-            else {
-                const int j = (int)xp;
-                const double slope = ((double)row[j + 1] - (double)row[j]) / ((double)(j + 1) - (double)j);
-                v = slope * (xp - (double)j) + (double)row[j];
-            }
+            const double v = interp_row_f32(row, len, disp_w, x);
             int8_t y8 = -1;
             if (isfinite(v)) {
                 const int y = (int)((1 - (v - lo) / range) * (disp_h - 1));

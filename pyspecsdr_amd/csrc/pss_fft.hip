@@ -400,20 +400,11 @@ __global__ __launch_bounds__(256) void k_post_f64(const double *__restrict__ db,
     }
 }
 
-// np.interp(np.linspace(0, len-1, W), np.arange(len), row)[i]
+// np.interp(np.linspace(0, len-1, W), np.arange(len), row)[i] (numpy's knot and NaN rules: pss_post::interp_at)
 template <class T>
 __device__ __forceinline__ double interp_row(const T *row, int len, int W, int i)
 {
-    double stop = (double)(len - 1), x;
-    if (W == 1) x = 0.0;
-    else {
-        double step = stop / (double)(W - 1);
-        x = (i == W - 1) ? stop : (double)i * step;
-    }
-    if (x >= stop) return (double)row[len - 1];
-    int j = (int)x;
-    double slope = ((double)row[j + 1] - (double)row[j]) / ((double)(j + 1) - (double)j);
-    return slope * (x - (double)j) + (double)row[j];
+    return pss_post::interp_at(row, len, W, i);
 }
 
 // draw_spectrogram (pyspecsdr.py:398-498) for one post-processed dB row per workgroup: noise floor = np.percentile(., 20)
@@ -515,21 +506,7 @@ __global__ __launch_bounds__(1024) void k_spectrogram(const T *__restrict__ rows
         };
         for (int x = tid; x < disp_w; x += nthr) {
             // np.interp(np.linspace(0, len-1, W), np.arange(len), shaped)[x]
-            const double stop = (double)(len - 1);
-            double xp;
-            if (disp_w == 1) xp = 0.0;
-            else {
-                const double step = stop / (double)(disp_w - 1);
-                xp = (x == disp_w - 1) ? stop : (double)x * step;
-            }
-            double value;
-            if (xp >= stop) value = shaped(len - 1);
-            else {
-                const int j = (int)xp;
-                const double p0 = shaped(j), p1 = shaped(j + 1);
-                const double slope = (p1 - p0) / ((double)(j + 1) - (double)j);
-                value = slope * (xp - (double)j) + p0;
-            }
+            const double value = pss_post::interp_at(pss_post::fn_row(shaped), len, disp_w, x);
             if (!isfinite(value)) continue;
             int height = (int)(value * disp_h);
             if (height > disp_h) height = disp_h;
@@ -610,23 +587,10 @@ __global__ __launch_bounds__(1024) void k_cells(const T *__restrict__ rows, int 
         __syncthreads();
         const int w = disp_w - 8;
         const T *row = rowp(0);
+        const auto normalised = [&](int j) { return ((double)row[j] - lo) / range; };
         for (int x = tid; x < w; x += CT) {
             // np.interp over the NORMALISED row: normalisation is affine and applied per sample before interpolating
-            const double stop = (double)(len - 1);
-            double xp;
-            if (w == 1) xp = 0.0;
-            else {
-                const double step = stop / (double)(w - 1);
-                xp = (x == w - 1) ? stop : (double)x * step;
-            }
-            double value;
-            if (xp >= stop) value = ((double)row[len - 1] - lo) / range;
-            else {
-                const int j = (int)xp;
-                const double p0 = ((double)row[j] - lo) / range, p1 = ((double)row[j + 1] - lo) / range;
-                const double slope = (p1 - p0) / ((double)(j + 1) - (double)j);
-                value = slope * (xp - (double)j) + p0;
-            }
+            const double value = pss_post::interp_at(pss_post::fn_row(normalised), len, w, x);
             if (!isfinite(value)) continue;
             const int mag = (int)(value * 20);
             for (int y = 0; y < mag; y++) {

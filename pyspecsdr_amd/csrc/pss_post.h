@@ -601,7 +601,13 @@ __device__ __forceinline__ void row_sync()
     }
 }
 
-// np.interp(np.linspace(0, len-1, W), np.arange(len), row)[x] in float64 (pyspecsdr.py:1379-1383 / :1550-1554)
+// np.interp(np.linspace(0, len-1, W), np.arange(len), row)[x] in float64 (pyspecsdr.py:1379-1383 / :1550-1554), with numpy's rules
+// (compiled_base.c arr_interp) for x in [j, j + 1): x on the knot returns row[j] itself; otherwise slope*(x - j) + row[j], and if that is
+// NaN, slope*(x - (j + 1)) + row[j + 1], and if that is NaN too while row[j] == row[j + 1], row[j].  Off the knot the first form is NaN
+// only for a NaN knot, or for row[j] = +-inf (inf - inf); the retry then yields row[j] exactly when row[j + 1] is finite or equal to row[j],
+// i.e. when row[j] + row[j + 1] == row[j] — so the rules are one select (this runs inside k_spectrum_post and k_post_sel: no branches).
+// For finite knots only the sign of a zero result can differ from the plain formula.
+// Row: anything with operator[](int) convertible to double — a pointer, StagedRow, PostFromDb, FnRow.
 template <class Row>
 __device__ __forceinline__ double interp_at(const Row &row, int len, int W, int x)
 {
@@ -614,11 +620,22 @@ __device__ __forceinline__ double interp_at(const Row &row, int len, int W, int 
     }
     if (xp >= stop) return (double)row[len - 1];
     const int j = (int)xp;
+    const double dj = (double)j;
+    const double f0 = (double)row[j], f1 = (double)row[j + 1];
     // np.interp divides the difference by xp[j + 1] - xp[j]: np.arange's step, exactly 1.0, and x / 1.0 is x for every x — no division here
     // (35 float64-class instructions per value otherwise)
-    const double slope = (double)row[j + 1] - (double)row[j];
-    return slope * (xp - (double)j) + (double)row[j];
+    const double v = (f1 - f0) * (xp - dj) + f0;
+    return (xp == dj || (v != v && f0 + f1 == f0)) ? f0 : v;
 }
+
+// a row given by a functor (element j computed on the fly: the spectrogram's shaped values, the surface's normalised values)
+template <class F>
+struct FnRow {
+    F f;
+    __device__ __forceinline__ double operator[](int j) const { return f(j); }
+};
+template <class F>
+__device__ __forceinline__ FnRow<F> fn_row(F f) { return FnRow<F>{f}; }
 
 // a row in the staging layout (element e at buf[(e / EPL) * S + e % EPL])
 template <int EPL, class T>

@@ -629,8 +629,9 @@ def gen_scanner():
     save("scanner", **d)
 
 
-def gen_caller():
-    """Caller-side state machines: AGC stepper and the waterfall / persistence quantisers."""
+def caller_module():
+    """The reference's caller (pyspecsdr.py), imported with sounddevice / SoapySDR stubbed, curses.color_pair(n) = n << 8 (the pair
+    number is read back from the attribute) and the module's signal handlers undone."""
     import curses
     sd = types.ModuleType("sounddevice")
     sd.PortAudioError = type("PortAudioError", (Exception,), {})
@@ -646,6 +647,20 @@ def gen_caller():
     old = (_signal.getsignal(_signal.SIGINT), _signal.getsignal(_signal.SIGTERM))
     import pyspecsdr as P
     _signal.signal(_signal.SIGINT, old[0]); _signal.signal(_signal.SIGTERM, old[1])
+    return P
+
+
+class Scr:
+    """A fake curses screen of h x w cells: records every addstr call."""
+    def __init__(s, h, w): s.h, s.w, s.calls = h, w, []
+    def getmaxyx(s): return s.h, s.w
+    def addstr(s, *a): s.calls.append(a)
+    def refresh(s): pass
+
+
+def gen_caller():
+    """Caller-side state machines: AGC stepper and the waterfall / persistence quantisers."""
+    P = caller_module()
 
     class Sdr:
         valid_gains_db = list(np.arange(0, 50, 1.7))
@@ -661,12 +676,6 @@ def gen_caller():
         d[f"agc_traj_{start}"] = np.array(traj)
     d["agc_powers"] = powers
     d["agc_ngains"] = np.array(len(Sdr.valid_gains_db))
-
-    class Scr:
-        def __init__(s, h, w): s.h, s.w, s.calls = h, w, []
-        def getmaxyx(s): return s.h, s.w
-        def addstr(s, *a): s.calls.append(a)
-        def refresh(s): pass
 
     H, W = 40, 120
     iq = fm_iq(34, 1024, 2.4e6, 71)
