@@ -79,8 +79,8 @@ int pss_device_count(void);
  *                              at cfg 2, 0.75 -> 0.91 ms at 8192 x 16384) and the bench step 3 %
  *   "scan_exact" (1)           0: scanner slices (pss_scan, pss_scan_threshold) get their dB values from compute_fft's float64 / hardware-log2
  *                              evaluation (1e-4 relative; 30 % faster at 8192 x 4096) instead of NumPy's float32 chain bit for bit
- * Kernel-selection knobs of earlier rounds' A/B measurements ("fft_split", "fft_prefetch", "fft_xl4096", "fft_big_scratch", "post_legacy",
- * "post_sort_max") exist only in builds with -DPSS_VARIANTS (tools/build_variant.py); the experiments that lost — the FIR on the matrix
+ * Any other key is refused with PSS_E_ARG ("unknown option").  The kernel-selection knobs of earlier rounds' A/B measurements are gone
+ * with the kernels they selected; those experiments and the others that lost — the FIR on the matrix
  * pipe, discriminator rows handed from the spectrum kernel, the fused spectrum + post-process kernel, the 112-VGPR spectrum kernel, the
  * alternative pipeline schedules, CU-mask partitioning — are documented with their measurements in DESIGN.md and no longer compiled in. */
 int pss_set_option(pss_ctx *ctx, const char *key, int value);

@@ -228,16 +228,6 @@ extern "C" int pss_set_option(pss_ctx *ctx, const char *key, int value)
     if (!strcmp(key, "db_exact")) { ctx->db_exact = value != 0; return PSS_OK; }
     if (!strcmp(key, "f64_plain")) { ctx->f64_plain = value != 0; return PSS_OK; }
     if (!strcmp(key, "wfm_corr_copy")) { ctx->wfm_corr_copy = value != 0; return PSS_OK; }
-#ifdef PSS_VARIANTS   // kernel-selection knobs for A/B measurements: variant builds only (tools/build_variant.py <name> -DPSS_VARIANTS)
-    if (!strcmp(key, "ssb_unfused")) { ctx->ssb_unfused = value != 0; return PSS_OK; }
-    if (!strcmp(key, "fft_two_per_wg")) { ctx->fft_two_per_wg = value != 0; return PSS_OK; }
-    if (!strcmp(key, "fft_split")) { ctx->fft_split = value; return PSS_OK; }
-    if (!strcmp(key, "fft_big_scratch")) { ctx->fft_big_scratch = value != 0; return PSS_OK; }
-    if (!strcmp(key, "fft_prefetch")) { ctx->fft_prefetch = value; return PSS_OK; }
-    if (!strcmp(key, "fft_xl4096")) { ctx->fft_xl4096 = value; return PSS_OK; }
-    if (!strcmp(key, "post_sort_max")) { ctx->post_sort_max = value; return PSS_OK; }
-    if (!strcmp(key, "post_legacy")) { ctx->post_legacy = value != 0; return PSS_OK; }
-#endif
     return pss_fail(ctx, PSS_E_ARG, std::string("unknown option: ") + key);
 }
 

@@ -93,8 +93,6 @@ struct pss_ctx {
     size_t scratch_hil_bytes = 0;
     void *stage = nullptr;         // device staging of the host-buffer convenience calls (grow-only)
     size_t stage_bytes = 0;
-    bool ssb_unfused = false;      // (-DPSS_VARIANTS builds) demodulate_ssb at 8192 / 16384 samples as k_ssb_fir + k_hilbert_xl (the round-2 shape)
-    bool fft_two_per_wg = false;   // (-DPSS_VARIANTS builds) N = 2048 spectra with two frames per 256-thread workgroup (the round-2 shape)
     bool no_wfm_fused = false;  // option "wfm_fused" = 0: k_wfm_front + k_nfm_iir path (A/B testing)
     long small_batch_max = 8192;  // option "small_batch_max": largest frame count that takes the small-batch path (measured crossover ~12000)
     long wfm_small_batch_max = 6000;  // option "wfm_small_batch_max" (crossover with the fused kernels, 1024-sample frames: ~12000 frames in round 2, ~6000 since the small-batch path is one array: 0.58 / 1.13 ms at 4096 / 8192 frames against 0.83)
@@ -104,12 +102,6 @@ struct pss_ctx {
     bool db_exact = false;         // true: compute_fft's dB rows evaluated to float64 accuracy and rounded once (= float32 of the reference's float64 rows); false: float32 evaluation, 1-2 ulp off, 15-25 % faster kernels
     bool f64_plain = false;        // option "f64_plain": the float64-row entry points (pss_spectrum_db_f64, pss_spectrum_post_f64, pss_frame_pipeline_nfm_f64) on the plain round-3 kernels (generic LDS transform with hypot / log10, radix select) instead of the register kernels: A/B reference
     bool scan_exact = true;        // scanner slices: NumPy's float32 chain bit for bit (scan_db_np); false: the float64 / hardware-log2 dB of compute_fft
-    int fft_xl4096 = -1;           // N = 4096 on the component-wise-exchange kernel (pss_fft_xl.h, R4 = 1) instead of k_spectrum_r16<4>; -1 = scanner slices only
-    bool post_legacy = false;  // option "post_legacy": LDS bitonic sort / LDS-histogram radix select instead of the register select
-    int post_sort_max = 8192;  // option "post_sort_max": longest row that takes the LDS bitonic sort, else radix select (measured crossover 8192..16384)
-    bool fft_big_scratch = false;  // option "fft_big_scratch": N = 8192 / 16384 on the scratch-based radix-R pre-pass kernel (A/B reference)
-    int fft_prefetch = -1;  // option "fft_prefetch": request the next frame's samples before transforming the current one; -1 = automatic
-    int fft_split = -1;  // option "fft_split": component-wise LDS exchanges in k_spectrum_r16; -1 = automatic (N = 256 only)
     bool no_small_batch = false;  // option "small_batch" = 0: never take the systolic small-batch NFM path (A/B testing)
     bool no_fused = false;  // PSS_NO_FUSED=1: use the three-kernel NFM path (A/B and fallback testing)
     void *comm = nullptr;          // pss_comm_init: the RCCL communicator (ncclComm_t) of this context's rank; collectives run on the context's stream
@@ -182,7 +174,7 @@ int pss_hilbert_rows(pss_ctx *ctx, const double *d_x, long n_rows, int n, double
 int pss_fft_tables(pss_ctx *ctx, int n, const double2 **tw, const double **win);
 // pss_frame_pipeline's display chain behind the dB rows (rows of either type): thresholds + extremes + the rows resampled to the display
 // width in one pass (no post-processed rows in memory), sliding extremes, the line of every frame.  d_vals: n_frames x disp_w doubles.
-bool pss_post_sel_serves(const pss_ctx *ctx, int n_fft, bool f64);
+bool pss_post_sel_serves(int n_fft, bool f64);
 bool pss_spec_post_serves(const pss_ctx *ctx, int n_fft);
 int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, float *d_db32, double *d_db64, double *d_lo, double *d_hi, int n_halo,
                         int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals);

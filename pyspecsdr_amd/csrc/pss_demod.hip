@@ -868,17 +868,6 @@ __global__ __launch_bounds__(128) void k_iir4_sys(const double *__restrict__ in,
         // all lanes must walk the block in lockstep for the in-place hand-off: one code path per macro-step, chosen wave-wide
         if (__all(!active || cnt == IS_T)) {
             if (active) {
-#ifdef PSS_EXP_SYS_NOPF
-                for (int t0 = 0; t0 < IS_T; t0 += 8) {
-                    double e8[8], y8[8];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) e8[k] = src[t0 + k];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) y8[k] = step(e8[k]);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) dst[t0 + k] = y8[k];
-                }
-#else
                 // two groups of eight per turn, each group's inputs requested from LDS before the OTHER group's recurrence steps (a lone
                 // wavefront: the LDS round trip of a group otherwise stands in front of its 8 x 48 clocks); reading ahead is safe for the
                 // in-place hand-off — a position is read before this macro-step's write of it either way.  No register copies: the two
@@ -904,7 +893,6 @@ __global__ __launch_bounds__(128) void k_iir4_sys(const double *__restrict__ in,
 #pragma unroll
                     for (int k = 0; k < 8; k++) dst[t0 + 8 + k] = y8[k];
                 }
-#endif
             }
         } else {
             for (int t = 0; t < IS_T; t++) {  // a partial block somewhere: masked steps, read-then-write per position
@@ -992,7 +980,6 @@ __device__ __forceinline__ float wg_rsum(const PlanDev &p, float *part, float *v
     }
     for (int slot = tid; slot < p.n_leaves * 8; slot += T) {
         const int l = slot >> 3, k = slot & 7, off = p.leaf_off[l], len = p.leaf_len[l];
-#ifndef PSS_EXP_RSUM4
         if (len == 128) {
             // a full leaf: all 16 operands of this accumulator requested before the dependent chain of additions starts (four ahead,
             // a CU's 2048 threads kept ~64 KB in flight and the pass ran at 3.7 TB/s)
@@ -1003,9 +990,7 @@ __device__ __forceinline__ float wg_rsum(const PlanDev &p, float *part, float *v
 #pragma unroll
             for (int j = 1; j < 16; j++) r = __fadd_rn(r, v[j]);
             part[slot] = r;
-        } else
-#endif
-        if (len >= 8) {
+        } else if (len >= 8) {
             // the additions are a dependent chain in numpy's order; the operands are not: fetch four ahead of the chain
             float r = elem(off + k);
             const int end = len - (len % 8);
@@ -1617,423 +1602,45 @@ __global__ __launch_bounds__(256) void k_wfm_rows_q1(const double *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// WFM for SMALL batches (the interactive loop: one frame per call).  k_wfm_fwd steps ~200 float64 instructions per sample
-// on ONE lane per frame; here every filter section is its own lane (systolic array, one frame per 16-lane DPP row, four
-// frames per wavefront) and the chain runs as two cascaded passes with float64 rows in memory between them:
-//   pass 1  d -> LP15k (3 lanes) -> a ; d -> BP pilot (5) -> 1-pole -> y -> pilot value p ; d -> BP 23..53k (5) -> m
-//   pass 2  m * (2 p) -> LP15k (3) -> (a +- .)/2 -> de-emphasis, once per channel (two 4-lane groups) -> u_l, u_r,
-//           written with SciPy's odd extension around them in the layout the small-batch decimator (k_iir4_sys) reads.
-// Every lane executes sosfilt's step on its own section; a 1-pole stage is that step with b1 = +0.0 and its second state
-// pinned to -0.0 (v + -0.0 == v bit for bit), which is lfilter's  y = z + b0 x ; z = x*0 - y*a1.  All stages start from a
-// zero state, so filling and draining the pipeline with zeros is exact.
-// ---------------------------------------------------------------------------------------------------
-struct CascLane {
-    Biquad c;
-    int head;      // 1: takes the staged input instead of its left neighbour's output
-    int onepole;   // 1: 1-pole stage (second state pinned to -0.0)
-    int mix;       // +1 / -1: input = (a +- left neighbour) * 0.5 (the L/R matrix), 0: plain
-    int out_slot;  // >= 0: this lane's output is row out_slot of the write-back buffer
-};
-struct CascArg { CascLane lane[16]; };
-constexpr int CS_T = 64;
-
-// (Kept for A/B builds, -DPSS_EXP_CASC_SAMPLE; the product runs k_wfm_blk below.)  Two wavefronts per workgroup (round 3, as k_am_sys /
-// k_iir4_sys): wavefront 0 runs the sample-systolic recurrence, wavefront 1 the
-// memory side — raw inputs of block m + 3 requested, block m + 1 computed (the discriminator in pass 1, m * 2p in pass 2) and staged,
-// block m - 1 written back — through double-buffered LDS blocks and LDS-only barriers.  As one wavefront the kernel computed four
-// discriminator samples per lane and waited for its own loads and stores between any two 64-step blocks.
-template <int MODE>  // 1: discriminator -> a, p, m      2: m, p, a -> u_l, u_r (+ odd extension)
-__global__ __launch_bounds__(128) void k_wfm_casc(const float2 *__restrict__ iq, double *__restrict__ Aa, double *__restrict__ Pp,
-                                                  double *__restrict__ Mm, double *U, int n, long n_frames, long Lp, int swapped,
-                                                  CascArg arg)
-{
-    constexpr int NIN = 2, NOUT = 3;
-    __shared__ double ebuf[2][4][NIN][CS_T + 1];
-    __shared__ double ybuf[2][4][NOUT + 1][CS_T + 1];  // row NOUT: dump row
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long f0 = (long)blockIdx.x * 4;
-    const int M = n - 1;
-    const int DA = (MODE == 1) ? 2 : 3, DB = (MODE == 1) ? 5 : 3, DC = 4;  // pipeline delay of each output row
-    const long TT = (long)M + 5;  // steps incl. drain of the deepest cascade
-    const long nblk = (TT + CS_T - 1) / CS_T;
-    const double SIN_PI = 0x1.1a62633145c07p-53;  // np.sin(np.pi)
-    if (wave == 1) {
-        // ---------------- memory wavefront: lane = sample inside a block ----------------
-        struct Raw { float2 x0[4], x1[4]; double m[4], p[4], a[4]; };
-        Raw rawA, rawB;
-        auto load = [&](long blk, Raw &r) __attribute__((always_inline)) {
-            const long i = blk * CS_T + lane;
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const long f = f0 + g;
-                const bool ok = f < n_frames && i < M;
-                if (MODE == 1) {
-                    const float2 *x = iq + (size_t)(f < n_frames ? f : 0) * n;
-                    r.x0[g] = ok ? x[i] : make_float2(0.0f, 0.0f);
-                    r.x1[g] = ok ? x[i + 1] : make_float2(0.0f, 0.0f);
-                } else {
-                    const size_t o = (size_t)(f < n_frames ? f : 0) * M;
-                    r.m[g] = ok ? Mm[o + i] : 0.0;
-                    r.p[g] = ok ? Pp[o + i] : 0.0;
-                    r.a[g] = (f < n_frames && i - 3 >= 0 && i - 3 < M) ? Aa[o + i - 3] : 0.0;   // a[], aligned with the mixing lanes
-                }
-            }
-        };
-        auto stage = [&](long blk, const Raw &r) __attribute__((always_inline)) {
-            const long i = blk * CS_T + lane;
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const long f = f0 + g;
-                double e0 = 0.0, e1 = 0.0;
-                if (f < n_frames) {
-                    if (MODE == 1) {
-                        if (i < M) e0 = (double)disc_sample(r.x1[g], r.x0[g], 1.0f, swapped != 0);  // :122
-                    } else {
-                        if (i < M) e0 = __dmul_rn(r.m[g], __dmul_rn(2.0, r.p[g]));  // :134
-                        if (i - 3 >= 0 && i - 3 < M) e1 = r.a[g];
-                    }
-                }
-                ebuf[blk & 1][g][0][lane] = e0;
-                ebuf[blk & 1][g][1][lane] = e1;
-            }
-        };
-        auto writeback = [&](long blk) __attribute__((always_inline)) {   // ybuf[blk & 1] holds what the array produced during block blk
-            const long c0 = blk * CS_T;
-            const int par = (int)(blk & 1);
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const long f = f0 + g;
-                if (f >= n_frames) continue;
-                const long ia = c0 + lane - DA, ib = c0 + lane - DB, ic = c0 + lane - DC;
-                if (MODE == 1) {
-                    if (ia >= 0 && ia < M) Aa[(size_t)f * M + ia] = ybuf[par][g][0][lane];
-                    if (ib >= 0 && ib < M) {
-                        const double y = ybuf[par][g][1][lane];  // :130 np.sin(np.unwrap(np.angle(real))) = 0 or sin(pi)
-                        Pp[(size_t)f * M + ib] = (y != y) ? y : ((y < 0.0 || (y == 0.0 && __builtin_signbit(y))) ? SIN_PI : 0.0);
-                    }
-                    if (ic >= 0 && ic < M) Mm[(size_t)f * M + ic] = ybuf[par][g][2][lane];
-                } else {
-                    if (ia >= 0 && ia < M) U[(size_t)(2 * f) * Lp + EDGE + ia] = ybuf[par][g][0][lane];
-                    if (ib >= 0 && ib < M) U[(size_t)(2 * f + 1) * Lp + EDGE + ib] = ybuf[par][g][1][lane];
-                }
-            }
-        };
-        load(0, rawA);
-        stage(0, rawA);
-        if (nblk > 1) load(1, rawB);
-        if (nblk > 2) load(2, rawA);
-        fused::lds_barrier();
-        auto beside = [&](long m, Raw &r) __attribute__((always_inline)) {     // r: the set holding block m + 1
-            if (m + 1 < nblk) stage(m + 1, r);
-            if (m + 3 < nblk) load(m + 3, r);
-            if (m >= 1) writeback(m - 1);
-            fused::lds_barrier();
-        };
-        for (long m = 0; m < nblk; m += 2) {
-            beside(m, rawB);
-            if (m + 1 < nblk) beside(m + 1, rawA);
-        }
-        writeback(nblk - 1);
-        if (MODE == 2) {
-            // odd extension (scipy _arraytools.odd_ext) of both channel rows from this wavefront's own stores
-            __threadfence();
-            for (int g = 0; g < 4; g++) {
-                const long f = f0 + g;
-                if (f >= n_frames) continue;
-                for (int ch = 0; ch < 2; ch++) {
-                    double *u = U + (size_t)(2 * f + ch) * Lp + EDGE;
-                    if (lane < EDGE) {
-                        const double u0 = __builtin_nontemporal_load(u), ul = __builtin_nontemporal_load(u + M - 1);
-                        const double a = __builtin_nontemporal_load(u + EDGE - lane), b = __builtin_nontemporal_load(u + M - 2 - lane);
-                        u[lane - EDGE] = __dsub_rn(__dmul_rn(2.0, u0), a);
-                        u[M + lane] = __dsub_rn(__dmul_rn(2.0, ul), b);
-                    }
-                }
-            }
-        }
-        return;
-    }
-    // ---------------- recurrence wavefront: one frame per 16-lane DPP row, one filter section per lane ----------------
-    const int row = lane >> 4, r = lane & 15;
-    const CascLane me = arg.lane[r];
-    double z0 = 0.0, z1 = me.onepole ? -0.0 : 0.0, xprev = 0.0;
-    const int oslot = me.out_slot >= 0 ? me.out_slot : NOUT;
-    fused::lds_barrier();
-    for (long blk = 0; blk < nblk; blk++) {
-        const long c0 = blk * CS_T;
-        const int par = (int)(blk & 1);
-        const double *e0p = ebuf[par][row][0], *e1p = ebuf[par][row][1];
-        double *const yp = ybuf[par][row][oslot];
-        const int cnt = (TT - c0) < CS_T ? (int)(TT - c0) : CS_T;
-        auto one = [&](int t, double e, double a) {
-            const double from_prev = dpp_row_shr1(xprev);
-            double x = me.head ? e : from_prev;
-            if (MODE == 2) {
-                const double mixed = __dmul_rn(me.mix > 0 ? __dadd_rn(a, from_prev) : __dsub_rn(a, from_prev), 0.5);  // :140-141
-                x = me.mix ? mixed : x;
-            }
-            const double xn = __dadd_rn(__dmul_rn(me.c.b0, x), z0);
-            z0 = __dadd_rn(__dsub_rn(__dmul_rn(me.c.b1, x), __dmul_rn(me.c.a1, xn)), z1);
-            const double n1 = __dsub_rn(__dmul_rn(me.c.b2, x), __dmul_rn(me.c.a2, xn));
-            z1 = me.onepole ? -0.0 : n1;
-            xprev = xn;
-            yp[t] = xn;
-        };
-        if (cnt == CS_T) {
-            for (int t0 = 0; t0 < CS_T; t0 += 8) {
-                double e8[8], a8[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) { e8[k] = e0p[t0 + k]; a8[k] = (MODE == 2) ? e1p[t0 + k] : 0.0; }
-#pragma unroll
-                for (int k = 0; k < 8; k++) one(t0 + k, e8[k], a8[k]);
-            }
-        } else {
-            for (int t = 0; t < cnt; t++) one(t, e0p[t], (MODE == 2) ? e1p[t] : 0.0);
-        }
-        fused::lds_barrier();
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// WFM for small batches, BLOCK-systolic (late round 3): the same two passes as k_wfm_casc, but a lane filters a whole
-// 64-sample block of its section and leaves it in LDS for the next section's lane (as k_iir4_sys / k_am_sys do) instead of
-// handing every sample to its neighbour by DPP.  The recurrence step is then nothing but sosfilt's nine float64 operations and
-// the one-pole pin (no DPP moves, no head / mix selects: ~11 instead of 15-22 instructions on a lone wavefront), and the L / R
-// matrix of pass 2 is computed by the memory wavefront, sample-parallel, between the LP15k chain and the de-emphasis lanes.
-//   pass 1 (14 lanes per frame): d -> LP15k (3) -> a ; d -> BP pilot (5) -> 1-pole -> y -> pilot value p ; d -> BP 23..53k (5) -> m
-//   pass 2 ( 5 lanes per frame): m * (2 p) -> LP15k (3) -> lp ; memory wavefront: (a +- lp) / 2 ; de-emphasis 1-pole per channel -> u_l, u_r
-// Same operations on the same sample sequences as k_wfm_casc (zero initial state everywhere), so the same bits.
-// ---------------------------------------------------------------------------------------------------
-struct BlkLane {
-    Biquad c;
-    int src, dst;    // LDS row (per frame) read / written; rows >= dbl0 are double-buffered by macro-step parity
-    int depth;       // the lane works on block (macro-step - depth); -1: idle lane
-    int onepole;
-};
-struct BlkArg { BlkLane lane[16]; };
-constexpr int WB_T = 64, WB_G = 4;
-
-template <int MODE>
-__global__ __launch_bounds__(128) void k_wfm_blk(const float2 *__restrict__ iq, double *__restrict__ Aa, double *__restrict__ Pp,
-                                                 double *__restrict__ Mm, double *U, int n, long n_frames, long Lp, int swapped,
-                                                 BlkArg arg)
-{
-    // rows per frame.  Pass 1: 0,1 = d (staged, two blocks in flight); 2,3 hand-offs of chain a; 4,5 = a out; 6..10 hand-offs of the pilot
-    // chain; 11,12 = y out; 13..16 hand-offs of the m chain; 17,18 = m out.  Pass 2: 0,1 = m*2p; 2,3 hand-offs; 4,5 = lp out; 6,7 = l in;
-    // 8,9 = r in; 10,11 = u_l out; 12,13 = u_r out.  (src / dst name the EVEN row of a double-buffered pair; the odd one is + 1.)
-    constexpr int NROWS = MODE == 1 ? 19 : 14;
-    __shared__ double rows[WB_G][NROWS][WB_T + 1];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const long f0 = (long)blockIdx.x * WB_G;
-    const int M = n - 1;
-    const long nblk = ((long)M + WB_T - 1) / WB_T;
-    constexpr int DEEP = MODE == 1 ? 5 : 4;       // depth of the deepest lane
-    const long nstep = nblk + DEEP;
-    const double SIN_PI = 0x1.1a62633145c07p-53;  // np.sin(np.pi)
-    auto is_dbl = [](int row) { return MODE == 1 ? (row <= 1 || row == 4 || row == 5 || row == 11 || row == 12 || row >= 17)
-                                                 : (row <= 1 || row >= 4); };
-    if (wave == 1) {
-        // ---------------- memory wavefront: lane = sample inside a block ----------------
-        struct Raw { float2 x0[WB_G], x1[WB_G]; double m[WB_G], p[WB_G]; };
-        Raw rawA, rawB;
-        auto load = [&](long blk, Raw &r) __attribute__((always_inline)) {
-            const long i = blk * WB_T + lane;
-#pragma unroll
-            for (int g = 0; g < WB_G; g++) {
-                const long f = f0 + g;
-                const bool ok = f < n_frames && i < M;
-                if (MODE == 1) {
-                    const float2 *x = iq + (size_t)(f < n_frames ? f : 0) * n;
-                    r.x0[g] = ok ? x[i] : make_float2(0.0f, 0.0f);
-                    r.x1[g] = ok ? x[i + 1] : make_float2(0.0f, 0.0f);
-                } else {
-                    const size_t o = (size_t)(f < n_frames ? f : 0) * M;
-                    r.m[g] = ok ? Mm[o + i] : 0.0;
-                    r.p[g] = ok ? Pp[o + i] : 0.0;
-                }
-            }
-        };
-        auto stage = [&](long blk, const Raw &r) __attribute__((always_inline)) {
-            const long i = blk * WB_T + lane;
-#pragma unroll
-            for (int g = 0; g < WB_G; g++) {
-                double e = 0.0;
-                if (f0 + g < n_frames && i < M) {
-                    if (MODE == 1) e = (double)disc_sample(r.x1[g], r.x0[g], 1.0f, swapped != 0);  // :122
-                    else e = __dmul_rn(r.m[g], __dmul_rn(2.0, r.p[g]));                             // :134
-                }
-                rows[g][(int)(blk & 1)][lane] = e;
-            }
-        };
-        // what the recurrence wavefront finished during macro-step ms (ms >= 0): written back / passed on
-        auto drain = [&](long ms) __attribute__((always_inline)) {
-            const int par = (int)(ms & 1);
-#pragma unroll
-            for (int g = 0; g < WB_G; g++) {
-                const long f = f0 + g;
-                if (f >= n_frames) continue;
-                if (MODE == 1) {
-                    const long ba = ms - 2, by = ms - 5, bm = ms - 4;
-                    const long ia = ba * WB_T + lane, iy = by * WB_T + lane, im = bm * WB_T + lane;
-                    if (ba >= 0 && ba < nblk && ia < M) Aa[(size_t)f * M + ia] = rows[g][4 + par][lane];
-                    if (by >= 0 && by < nblk && iy < M) {
-                        const double y = rows[g][11 + par][lane];  // :130 np.sin(np.unwrap(np.angle(real))) = 0 or sin(pi)
-                        Pp[(size_t)f * M + iy] = (y != y) ? y : ((y < 0.0 || (y == 0.0 && __builtin_signbit(y))) ? SIN_PI : 0.0);
-                    }
-                    if (bm >= 0 && bm < nblk && im < M) Mm[(size_t)f * M + im] = rows[g][17 + par][lane];
-                } else {
-                    // the LP15k chain finished block ms - 2: L / R matrix (:140-141), staged for the de-emphasis lanes (macro-step ms + 2)
-                    const long bl = ms - 2, il = bl * WB_T + lane;
-                    if (bl >= 0 && bl < nblk) {
-                        double l = 0.0, r = 0.0;
-                        if (il < M) {
-                            const double a = Aa[(size_t)f * M + il], lp = rows[g][4 + par][lane];
-                            l = __dmul_rn(__dadd_rn(a, lp), 0.5);
-                            r = __dmul_rn(__dsub_rn(a, lp), 0.5);
-                        }
-                        rows[g][6 + par][lane] = l;      // read by the de-emphasis lanes at macro-step ms + 2 (same parity)
-                        rows[g][8 + par][lane] = r;
-                    }
-                    const long bu = ms - 4, iu = bu * WB_T + lane;
-                    if (bu >= 0 && bu < nblk && iu < M) {
-                        U[(size_t)(2 * f) * Lp + EDGE + iu] = rows[g][10 + par][lane];
-                        U[(size_t)(2 * f + 1) * Lp + EDGE + iu] = rows[g][12 + par][lane];
-                    }
-                }
-            }
-        };
-        load(0, rawA);
-        stage(0, rawA);
-        if (nblk > 1) load(1, rawB);
-        if (nblk > 2) load(2, rawA);
-        fused::lds_barrier();
-        auto beside = [&](long m, Raw &r) __attribute__((always_inline)) {     // r: the set holding block m + 1
-            if (m + 1 < nblk) stage(m + 1, r);
-            if (m + 3 < nblk) load(m + 3, r);
-            if (m >= 1) drain(m - 1);
-            fused::lds_barrier();
-        };
-        for (long m = 0; m < nstep; m += 2) {
-            beside(m, rawB);
-            if (m + 1 < nstep) beside(m + 1, rawA);
-        }
-        drain(nstep - 1);
-        if (MODE == 2) {
-            // odd extension (scipy _arraytools.odd_ext) of both channel rows from this wavefront's own stores
-            __threadfence();
-            for (int g = 0; g < WB_G; g++) {
-                const long f = f0 + g;
-                if (f >= n_frames) continue;
-                for (int ch = 0; ch < 2; ch++) {
-                    double *u = U + (size_t)(2 * f + ch) * Lp + EDGE;
-                    if (lane < EDGE) {
-                        const double u0 = __builtin_nontemporal_load(u), ul = __builtin_nontemporal_load(u + M - 1);
-                        const double a = __builtin_nontemporal_load(u + EDGE - lane), b = __builtin_nontemporal_load(u + M - 2 - lane);
-                        u[lane - EDGE] = __dsub_rn(__dmul_rn(2.0, u0), a);
-                        u[M + lane] = __dsub_rn(__dmul_rn(2.0, ul), b);
-                    }
-                }
-            }
-        }
-        return;
-    }
-    // ---------------- recurrence wavefront: one frame per 16 lanes, one filter section per lane ----------------
-    const int g = lane >> 4;
-    const BlkLane me = arg.lane[lane & 15];
-    const bool lane_on = me.depth >= 0;
-    const bool src_dbl = is_dbl(me.src), dst_dbl = is_dbl(me.dst);
-    double z0 = 0.0, z1 = me.onepole ? -0.0 : 0.0;
-    auto step = [&](double x) {
-        const double xn = __dadd_rn(__dmul_rn(me.c.b0, x), z0);
-        z0 = __dadd_rn(__dsub_rn(__dmul_rn(me.c.b1, x), __dmul_rn(me.c.a1, xn)), z1);
-        const double n1 = __dsub_rn(__dmul_rn(me.c.b2, x), __dmul_rn(me.c.a2, xn));
-        z1 = me.onepole ? -0.0 : n1;
-        return xn;
-    };
-    fused::lds_barrier();
-    for (long m = 0; m < nstep; m++) {
-        const long blk = m - me.depth;
-        const bool active = lane_on && blk >= 0 && blk < nblk;
-        const int par = (int)(m & 1);
-        const double *src = rows[g][me.src + (src_dbl ? par : 0)];
-        double *dst = rows[g][me.dst + (dst_dbl ? par : 0)];
-        const int cnt = !active ? 0 : (((long)M - blk * WB_T) < WB_T ? (int)((long)M - blk * WB_T) : WB_T);
-        // in-place hand-off: all lanes walk the block in lockstep, reads of a group of eight before its writes (k_iir4_sys)
-        if (__all(!active || cnt == WB_T)) {
-            if (active) {
-                double ea[8], eb[8], y8[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) ea[k] = src[k];
-#pragma unroll 1
-                for (int t0 = 0; t0 < WB_T; t0 += 16) {
-#pragma unroll
-                    for (int k = 0; k < 8; k++) eb[k] = src[t0 + 8 + k];
-#pragma unroll
-                    for (int k = 0; k < 8; k++) y8[k] = step(ea[k]);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) dst[t0 + k] = y8[k];
-                    if (t0 + 16 < WB_T) {
-#pragma unroll
-                        for (int k = 0; k < 8; k++) ea[k] = src[t0 + 16 + k];
-                    }
-#pragma unroll
-                    for (int k = 0; k < 8; k++) y8[k] = step(eb[k]);
-#pragma unroll
-                    for (int k = 0; k < 8; k++) dst[t0 + 8 + k] = y8[k];
-                }
-            }
-        } else {
-            for (int t = 0; t < WB_T; t++) {
-                if (t < cnt) {
-                    const double e = src[t];
-                    dst[t] = step(e);
-                }
-            }
-        }
-        fused::lds_barrier();
-    }
-}
-
-
-// ---------------------------------------------------------------------------------------------------
-// Both WFM passes in ONE block-systolic array (late round 3): 19 lanes per frame (the 14 of pass 1, the LP15k chain and the two
-// de-emphasis lanes of pass 2), three frames per wavefront.  The memory wavefront feeds pass 2 from pass 1's LDS rows — pilot value
-// and m * 2p when the pilot chain has finished a block, the L / R matrix when the second LP15k chain has — so a, p and m never go
-// through global memory and the second pass's latency (~1.1 ms for a 32768-sample frame) disappears.  Every buffer a lane or the memory
-// wavefront writes is a ring indexed by BLOCK number, as long as its value has to live (a: 9 blocks, m: 3, the rest 2).
+// WFM for SMALL batches (the interactive loop: one frame per call).  k_wfm_fwd steps ~200 float64 instructions per sample on ONE lane
+// per frame; here every filter section is its own lane of a block-systolic array (late round 3): a lane filters a whole 64-sample block
+// of its section and leaves it in LDS for the next section's lane (as k_iir4_sys / k_am_sys do), so its recurrence step is nothing but
+// sosfilt's nine float64 operations.  27 lanes per frame, two frames per wavefront:
+//   pass 1     d -> LP15k (3 lanes) -> a ; d -> BP pilot (5) -> 1-pole -> y -> pilot value p ; d -> BP 23..53k (5) -> m
+//   pass 2     m * (2 p) -> LP15k (3) -> lp ; (a +- lp) / 2 -> de-emphasis 1-pole per channel (2) -> u_l, u_r
+//   decimator  odd extension of u_l, u_r -> forward half of the zero-phase decimator (4 lanes per channel) -> y_fwd
+// A 1-pole stage is sosfilt's step with b1 = +0.0 and its second state pinned to -0.0 (v + -0.0 == v bit for bit), which is lfilter's
+// y = z + b0 x ; z = x*0 - y*a1.  Every stage starts from a zero state except the decimator's sections (sosfiltfilt: zi times the
+// extended sequence's first sample).  The memory wavefront stages the discriminator, computes m * 2p and the L / R matrix sample-parallel
+// between the chains, builds SciPy's odd extension (_arraytools.odd_ext: 27 reflected samples either side) from the u_l / u_r rings block
+// by block — the extended sequence's blocks are 27 samples out of step with u's — and writes y_fwd in the layout the backward launch of
+// k_iir4_sys reads: a, p, m and u never leave the CU.  Every buffer a lane or the memory wavefront writes is a ring indexed by BLOCK
+// number, as long as its value has to live (a: 9 blocks, m: 3, the rest 2).
 // Timeline of block b (macro-steps): staged b-1 | a ready b+2 | m ready b+4 | y ready b+5 | m*2p staged b+6 | LP15k b+7..b+9 |
-// matrix staged b+10 | de-emphasis b+11 | u_l, u_r written back b+12.
+// matrix staged b+10 | de-emphasis b+11 | extended block staged b+12 | y_fwd written back b+17.
 // ---------------------------------------------------------------------------------------------------
 struct MrgLane {
     Biquad c;
     int src, src_ring, dst, dst_ring;   // first row of the ring read / written, ring length (1: a plain hand-off row)
     int depth;                          // the lane works on block (macro-step - depth); -1: idle lane
     int onepole;
-    double zi0, zi1;                    // FWD decimator lanes: initial state per unit of the sequence's first sample (sosfilt_zi); else 0
-    int chan;                           // FWD decimator lanes: 0 / 1 = left / right (whose first sample scales zi); else -1
+    double zi0, zi1;                    // decimator lanes: initial state per unit of the sequence's first sample (sosfilt_zi); else 0
+    int chan;                           // decimator lanes: 0 / 1 = left / right (whose first sample scales zi); else -1
 };
 struct MrgArg { MrgLane lane[27]; };
 constexpr int WM_T = 64;
 // rows per frame: D1 0-1 | a hand-offs 2-3 | A 4-12 | pilot hand-offs 13-17 | Y 18-19 | m hand-offs 20-23 | Mo 24-26 | D2 27-28 |
-// lp hand-offs 29-30 | LP 31-32 | DL 33-34 | DR 35-36 | UL 37-39 | UR 40-42 | (FWD) EL 43-44 | ER 45-46 | decimator hand-offs 47-49 (left),
+// lp hand-offs 29-30 | LP 31-32 | DL 33-34 | DR 35-36 | UL 37-39 | UR 40-42 | EL 43-44 | ER 45-46 | decimator hand-offs 47-49 (left),
 // 50-52 (right) | YL 53-54 | YR 55-56
 constexpr int WM_D1 = 0, WM_A = 4, WM_Y = 18, WM_MO = 24, WM_D2 = 27, WM_LP = 31, WM_DL = 33, WM_DR = 35, WM_UL = 37, WM_UR = 40,
               WM_EL = 43, WM_ER = 45, WM_YL = 53, WM_YR = 55;
 
-// FWD: the FORWARD half of the zero-phase decimator runs in the same array (8 more lanes per frame, two frames per wavefront): the
-// memory wavefront builds SciPy's odd extension (_arraytools.odd_ext: 27 reflected samples either side) from the u_l / u_r rings block by
-// block — the extended sequence's blocks are 27 samples out of step with u's — and writes y_fwd in the layout the backward launch of
-// k_iir4_sys reads.  u itself then never leaves the CU either.
-template <bool FWD>
 __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, double *UY, int n, long n_frames, long row_stride, int swapped,
                                                  MrgArg arg)
 {
-    constexpr int NL = FWD ? 27 : 19, G = FWD ? 2 : 3, NROWS = FWD ? 57 : 43;
+    constexpr int NL = 27, G = 2, NROWS = 57;
     __shared__ double rows[G][NROWS][WM_T + 1];
-    __shared__ double x0s[G][2];                 // FWD: first sample of each channel's extended sequence
+    __shared__ double x0s[G][2];                 // first sample of each channel's extended sequence
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const long f0 = (long)blockIdx.x * G;
@@ -2041,8 +1648,8 @@ __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, 
     const long L = (long)M + 2 * EDGE;
     const long nblk = ((long)M + WM_T - 1) / WM_T;
     const long nblk_e = (L + WM_T - 1) / WM_T;   // blocks of the odd-extended sequence
-    constexpr int DEEP = FWD ? 16 : 11;
-    const long nstep = (FWD ? nblk_e : nblk) + DEEP;
+    constexpr int DEEP = 16;
+    const long nstep = nblk_e + DEEP;
     const double SIN_PI = 0x1.1a62633145c07p-53;  // np.sin(np.pi)
     if (wave == 1) {
         // ---------------- memory wavefront: lane = sample inside a block ----------------
@@ -2087,37 +1694,27 @@ __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, 
                     rows[g][WM_DL + (int)(b9 & 1)][lane] = in ? __dmul_rn(__dadd_rn(a, lp), 0.5) : 0.0;
                     rows[g][WM_DR + (int)(b9 & 1)][lane] = in ? __dmul_rn(__dsub_rn(a, lp), 0.5) : 0.0;
                 }
-                if constexpr (!FWD) {
-                    if (b11 >= 0 && b11 < nblk) {
-                        const long iu = b11 * WM_T + lane;
-                        if (iu < M) {
-                            UY[(size_t)(2 * f) * row_stride + EDGE + iu] = rows[g][WM_UL + (int)(b11 % 3)][lane];
-                            UY[(size_t)(2 * f + 1) * row_stride + EDGE + iu] = rows[g][WM_UR + (int)(b11 % 3)][lane];
-                        }
-                    }
-                } else {
-                    if (b11 >= 0 && b11 < nblk_e) {
-                        // block b11 of the odd-extended sequences (scipy _arraytools.odd_ext): ext[p] = 2 u[0] - u[27 - p] (p < 27),
-                        // u[p - 27], 2 u[M-1] - u[2M + 25 - p] (p >= 27 + M); u[i] sits in ring row (i / 64) % 3, column i % 64
-                        const long pidx = b11 * WM_T + lane;
+                if (b11 >= 0 && b11 < nblk_e) {
+                    // block b11 of the odd-extended sequences (scipy _arraytools.odd_ext): ext[p] = 2 u[0] - u[27 - p] (p < 27),
+                    // u[p - 27], 2 u[M-1] - u[2M + 25 - p] (p >= 27 + M); u[i] sits in ring row (i / 64) % 3, column i % 64
+                    const long pidx = b11 * WM_T + lane;
 #pragma unroll
-                        for (int ch = 0; ch < 2; ch++) {
-                            const int ub = ch ? WM_UR : WM_UL;
-                            auto uat = [&](long i) { return rows[g][ub + (int)((i / WM_T) % 3)][(int)(i % WM_T)]; };
-                            double v = 0.0;
-                            if (pidx < EDGE) v = __dsub_rn(__dmul_rn(2.0, uat(0)), uat(EDGE - pidx));
-                            else if (pidx < EDGE + M) v = uat(pidx - EDGE);
-                            else if (pidx < L) v = __dsub_rn(__dmul_rn(2.0, uat(M - 1)), uat(2L * M + 25 - pidx));
-                            rows[g][(ch ? WM_ER : WM_EL) + (int)(b11 & 1)][lane] = v;
-                            if (pidx == 0) x0s[g][ch] = v;
-                        }
+                    for (int ch = 0; ch < 2; ch++) {
+                        const int ub = ch ? WM_UR : WM_UL;
+                        auto uat = [&](long i) { return rows[g][ub + (int)((i / WM_T) % 3)][(int)(i % WM_T)]; };
+                        double v = 0.0;
+                        if (pidx < EDGE) v = __dsub_rn(__dmul_rn(2.0, uat(0)), uat(EDGE - pidx));
+                        else if (pidx < EDGE + M) v = uat(pidx - EDGE);
+                        else if (pidx < L) v = __dsub_rn(__dmul_rn(2.0, uat(M - 1)), uat(2L * M + 25 - pidx));
+                        rows[g][(ch ? WM_ER : WM_EL) + (int)(b11 & 1)][lane] = v;
+                        if (pidx == 0) x0s[g][ch] = v;
                     }
-                    if (b16 >= 0 && b16 < nblk_e) {   // forward decimator pass done with block b16: y_fwd rows [2 f + channel][L]
-                        const long iy = b16 * WM_T + lane;
-                        if (iy < L) {
-                            UY[(size_t)(2 * f) * row_stride + iy] = rows[g][WM_YL + (int)(b16 & 1)][lane];
-                            UY[(size_t)(2 * f + 1) * row_stride + iy] = rows[g][WM_YR + (int)(b16 & 1)][lane];
-                        }
+                }
+                if (b16 >= 0 && b16 < nblk_e) {   // forward decimator pass done with block b16: y_fwd rows [2 f + channel][L]
+                    const long iy = b16 * WM_T + lane;
+                    if (iy < L) {
+                        UY[(size_t)(2 * f) * row_stride + iy] = rows[g][WM_YL + (int)(b16 & 1)][lane];
+                        UY[(size_t)(2 * f + 1) * row_stride + iy] = rows[g][WM_YR + (int)(b16 & 1)][lane];
                     }
                 }
             }
@@ -2138,23 +1735,6 @@ __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, 
             if (m + 1 < nstep) beside(m + 1, rawA);
         }
         drain(nstep - 1);
-        if constexpr (!FWD) {
-            // odd extension (scipy _arraytools.odd_ext) of both channel rows from this wavefront's own stores
-            __threadfence();
-            for (int g = 0; g < G; g++) {
-                const long f = f0 + g;
-                if (f >= n_frames) continue;
-                for (int ch = 0; ch < 2; ch++) {
-                    double *u = UY + (size_t)(2 * f + ch) * row_stride + EDGE;
-                    if (lane < EDGE) {
-                        const double u0 = __builtin_nontemporal_load(u), ul = __builtin_nontemporal_load(u + M - 1);
-                        const double a = __builtin_nontemporal_load(u + EDGE - lane), b = __builtin_nontemporal_load(u + M - 2 - lane);
-                        u[lane - EDGE] = __dsub_rn(__dmul_rn(2.0, u0), a);
-                        u[M + lane] = __dsub_rn(__dmul_rn(2.0, ul), b);
-                    }
-                }
-            }
-        }
         return;
     }
     // ---------------- recurrence wavefront: NL lanes per frame, one filter section per lane ----------------
@@ -2163,8 +1743,8 @@ __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, 
     const int g = lane_in ? g_raw : 0;
     const MrgLane me = arg.lane[role];
     const bool lane_on = lane_in && me.depth >= 0;
-    const long my_nblk = (FWD && me.chan >= 0) ? nblk_e : nblk;   // the decimator lanes walk the extended sequence
-    const long my_len = (FWD && me.chan >= 0) ? L : (long)M;
+    const long my_nblk = me.chan >= 0 ? nblk_e : nblk;   // the decimator lanes walk the extended sequence
+    const long my_len = me.chan >= 0 ? L : (long)M;
     double z0 = 0.0, z1 = me.onepole ? -0.0 : 0.0;
     auto step = [&](double x) {
         const double xn = __dadd_rn(__dmul_rn(me.c.b0, x), z0);
@@ -2181,7 +1761,7 @@ __global__ __launch_bounds__(128) void k_wfm_mrg(const float2 *__restrict__ iq, 
         const double *src = rows[g][me.src + si];      // si, di = blk % ring, counted up (a 64-bit modulo by a lane's ring length here cost
         double *dst = rows[g][me.dst + di];            // ~250 instructions per macro-step: a fifth of the step on a lone wavefront)
         const int cnt = !active ? 0 : ((my_len - blk * WM_T) < WM_T ? (int)(my_len - blk * WM_T) : WM_T);
-        if (FWD && active && blk == 0 && me.chan >= 0) {   // sosfiltfilt: every section starts from zi * (first sample of the extended sequence)
+        if (active && blk == 0 && me.chan >= 0) {   // sosfiltfilt: every section starts from zi * (first sample of the extended sequence)
             const double x0 = x0s[g][me.chan];
             z0 = __dmul_rn(me.zi0, x0);
             z1 = __dmul_rn(me.zi1, x0);
@@ -3118,6 +2698,21 @@ extern "C" int pss_agc_steps(pss_ctx *ctx, const float *d_power, long n, int sta
     return pss_hip_check(ctx, hipGetLastError(), "k_agc launch");
 }
 
+// one SciPy SOS row (b0, b1, b2, a0 = 1, a1, a2) as the kernels' section coefficients
+static Biquad sos_biquad(const double *row) { return Biquad{row[0], row[1], row[2], row[4], row[5]}; }
+static void sos_biquads(Biquad *dst, const double *sos, int nsec)
+{
+    for (int s = 0; s < nsec; s++) dst[s] = sos_biquad(sos + 6 * s);
+}
+
+// decimator sections 1..3 with numerator exactly [1, 2, 1] (always so for cheby1 low-pass SOS): the shape the fused kernels are written for
+static bool sections_b121(const double *sos)
+{
+    for (int s = 1; s < 4; s++)
+        if (!(sos[6 * s] == 1.0 && sos[6 * s + 1] == 2.0 && sos[6 * s + 2] == 1.0)) return false;
+    return true;
+}
+
 extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm,
                          double *d_audio)
 {
@@ -3143,16 +2738,11 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
         double *U = nullptr, *Y = nullptr, *A = nullptr;  // three-kernel path only; each path sizes the (grow-only) scratch itself
         const TapsArg targ = make_taps(flt->taps);
         NfmCoef c;
-        for (int s = 0; s < 4; s++) {
-            const double *row = flt->sos + 6 * s;
-            c.s[s] = Biquad{row[0], row[1], row[2], row[4], row[5]};
-        }
+        sos_biquads(c.s, flt->sos, 4);
         for (int i = 0; i < 8; i++) c.zi[i] = flt->zi[i];
         const float kscale = (float)(fs / (2.0 * M_PI));          // python float -> float32 scalar (:97)
         const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;  // NumPy temporary elision threshold
-        bool b121 = true;  // sections 1..3 with numerator exactly [1, 2, 1] (always so for cheby1 low-pass SOS)
-        for (int s = 1; s < 4; s++)
-            b121 = b121 && flt->sos[6 * s] == 1.0 && flt->sos[6 * s + 1] == 2.0 && flt->sos[6 * s + 2] == 1.0;
+        const bool b121 = sections_b121(flt->sos);
         // a handful of long frames (the interactive loop: one 32768-sample buffer per call) cannot fill lane-per-frame
         // wavefronts: below this many frames the decimator runs as a 4-lane systolic array per frame instead
         const bool small_batch = !ctx->no_small_batch && n_frames <= ctx->small_batch_max;
@@ -3286,7 +2876,7 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
         double sos[30];
         pss_am_bandpass_sos(sos);
         AmCoef c;
-        for (int s = 0; s < 5; s++) c.s[s] = Biquad{sos[6 * s], sos[6 * s + 1], sos[6 * s + 2], sos[6 * s + 4], sos[6 * s + 5]};
+        sos_biquads(c.s, sos, 5);
         pss_time_begin(ctx);
         // (pss_demod_power: measure_signal_power of the same frames comes out of the same pass over the IQ)
         r = ctx->power_out ? launch_pairwise2(ctx, d_iq, n_frames, n, ctx->power_out, mu, env) : launch_pairwise<1>(ctx, d_iq, n_frames, n, mu, env);
@@ -3319,7 +2909,7 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
         const TapsArg targ = make_taps(taps);
         pss_time_begin(ctx);
         PSS_HIP(ctx, hipMemsetAsync(mxb, 0, (size_t)n_frames * sizeof(double), PSS_STREAM(ctx)));
-        if (ctx->ssb_hilbert && pss_ssb_fused_supported(n) && !ctx->ssb_unfused && !ctx->hilbert_exact && !ctx->iq_c128) {
+        if (ctx->ssb_hilbert && pss_ssb_fused_supported(n) && !ctx->hilbert_exact && !ctx->iq_c128) {
             // frames of 8192 / 16 384 samples: FIR, hilbert() round trip, normalisation and PCM in ONE kernel (no float64 round trip of
             // the FIR output through HBM)
             r = pss_ssb_hilbert_fused(ctx, d_iq, n_frames, n, taps, d_audio, d_pcm);
@@ -3396,27 +2986,21 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
         const size_t szY = align256((size_t)T2 * L * TILE * sizeof(double));
         const size_t szA = align256((size_t)T2 * n_out * TILE * sizeof(double));
         const size_t szM = align256((size_t)T2 * TILE * sizeof(double));
-        bool b121_dec = true;  // decimator sections 1..3 with numerator exactly [1, 2, 1]: the fused kernels' shape
-        for (int s1 = 1; s1 < 4; s1++)
-            b121_dec = b121_dec && flt->sos[6 * s1] == 1.0 && flt->sos[6 * s1 + 1] == 2.0 && flt->sos[6 * s1 + 2] == 1.0;
-        r = pss_ensure_scratch(ctx, ((ctx->no_wfm_fused || !b121_dec || q1) ? szU : 0) + szY + szA + szM);
+        const bool b121 = sections_b121(flt->sos);
+        r = pss_ensure_scratch(ctx, ((ctx->no_wfm_fused || !b121 || q1) ? szU : 0) + szY + szA + szM);
         if (r) return r;
         char *base = reinterpret_cast<char *>(ctx->scratch);
         double *U = reinterpret_cast<double *>(base), *Y = reinterpret_cast<double *>(base + szU);
         double *A = reinterpret_cast<double *>(base + szU + szY), *MX = reinterpret_cast<double *>(base + szU + szY + szA);
         WfmCoef wc;
-        auto fill = [](Biquad *dst, const double *sos, int ns) {
-            for (int s2 = 0; s2 < ns; s2++) dst[s2] = Biquad{sos[6 * s2], sos[6 * s2 + 1], sos[6 * s2 + 2], sos[6 * s2 + 4], sos[6 * s2 + 5]};
-        };
-        fill(wc.lp, wf->lp, 3); fill(wc.pil, wf->pilot, 5); fill(wc.lmr, wf->lmr, 5);
+        sos_biquads(wc.lp, wf->lp, 3);
+        sos_biquads(wc.pil, wf->pilot, 5);
+        sos_biquads(wc.lmr, wf->lmr, 5);
         wc.b0d = 1.0 - wf->alpha;
         wc.a1d = -wf->alpha;
         NfmCoef c;
-        fill(c.s, flt->sos, 4);
+        sos_biquads(c.s, flt->sos, 4);
         for (int i = 0; i < 8; i++) c.zi[i] = flt->zi[i];
-        bool b121 = true;
-        for (int s2 = 1; s2 < 4; s2++)
-            b121 = b121 && flt->sos[6 * s2] == 1.0 && flt->sos[6 * s2 + 1] == 2.0 && flt->sos[6 * s2 + 2] == 1.0;
         const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;
         // SciPy's zero pairing gives every Butterworth SOS the same numerator shapes; anything else takes the generic steps
         auto is_num = [](const double *row, double b0, double b1, double b2) { return row[0] == b0 && row[1] == b1 && row[2] == b2; };
@@ -3445,106 +3029,40 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
             if (r) { pss_time_end(ctx); return r; }
         }
         if (!q1 && !ctx->no_small_batch && n_frames <= ctx->wfm_small_batch_max) {
-            // a handful of frames: one lane per filter SECTION instead of one lane per frame (k_wfm_casc, k_iir4_sys)
-            const int M = n - 1;
-            const size_t szR = align256((size_t)n_frames * M * sizeof(double));
+            // a handful of frames: one lane per filter SECTION instead of one lane per frame (k_wfm_mrg up to the forward half of the
+            // decimator, then its backward half in k_iir4_sys)
             const size_t szY2 = align256((size_t)rows * L * sizeof(double));
             const size_t szA2 = align256((size_t)rows * n_out * sizeof(double));
-            r = pss_ensure_scratch(ctx, 3 * szR + szU + szY2 + szA2 + align256((size_t)rows * sizeof(double)));
+            r = pss_ensure_scratch(ctx, szY2 + szA2 + align256((size_t)rows * sizeof(double)));
             if (r) return r;
             char *b2 = reinterpret_cast<char *>(ctx->scratch);
-            double *Aa = reinterpret_cast<double *>(b2), *Pp = reinterpret_cast<double *>(b2 + szR), *Mm = reinterpret_cast<double *>(b2 + 2 * szR);
-            double *U2 = reinterpret_cast<double *>(b2 + 3 * szR), *Y2 = reinterpret_cast<double *>(b2 + 3 * szR + szU);
-            double *A2 = reinterpret_cast<double *>(b2 + 3 * szR + szU + szY2), *MX2 = reinterpret_cast<double *>(b2 + 3 * szR + szU + szY2 + szA2);
-#ifdef PSS_EXP_CASC_SAMPLE
-            CascArg a1, a2;
+            double *Y2 = reinterpret_cast<double *>(b2), *A2 = reinterpret_cast<double *>(b2 + szY2), *MX2 = reinterpret_cast<double *>(b2 + szY2 + szA2);
+            MrgArg am;
             const Biquad idle{0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int i = 0; i < 16; i++) a1.lane[i] = a2.lane[i] = CascLane{idle, 1, 0, 0, -1};
-            for (int i = 0; i < 3; i++) a1.lane[i] = CascLane{wc.lp[i], i == 0, 0, 0, i == 2 ? 0 : -1};             // a
-            for (int i = 0; i < 5; i++) a1.lane[3 + i] = CascLane{wc.pil[i], i == 0, 0, 0, -1};                       // pilot band-pass
-            a1.lane[8] = CascLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 0, 1, 0, 1};                                     // lfilter([1],[1,-0.99]) -> y
-            for (int i = 0; i < 5; i++) a1.lane[9 + i] = CascLane{wc.lmr[i], i == 0, 0, 0, i == 4 ? 2 : -1};          // m
-            for (int ch = 0; ch < 2; ch++) {
-                for (int i = 0; i < 3; i++) a2.lane[4 * ch + i] = CascLane{wc.lp[i], i == 0, 0, 0, -1};               // :137
-                a2.lane[4 * ch + 3] = CascLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, 0, 1, ch ? -1 : 1, ch};         // matrix + de-emphasis
-            }
-            const unsigned gc = (unsigned)((n_frames + 3) / 4);
+            for (int i = 0; i < 27; i++) am.lane[i] = MrgLane{idle, 0, 1, 0, 1, -1, 0, 0.0, 0.0, -1};
+            // pass 1: a (rows D1 -> 2 -> 3 -> A ring), pilot band-pass (D1 -> 13..17) + 1-pole (17 -> Y), m (D1 -> 20..23 -> Mo ring)
+            for (int i = 0; i < 3; i++)
+                am.lane[i] = MrgLane{wc.lp[i], i == 0 ? WM_D1 : 1 + i, i == 0 ? 2 : 1, i == 2 ? WM_A : 2 + i, i == 2 ? 9 : 1, i, 0, 0.0, 0.0, -1};
+            for (int i = 0; i < 5; i++) am.lane[3 + i] = MrgLane{wc.pil[i], i == 0 ? WM_D1 : 12 + i, i == 0 ? 2 : 1, 13 + i, 1, i, 0, 0.0, 0.0, -1};
+            am.lane[8] = MrgLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 17, 1, WM_Y, 2, 5, 1, 0.0, 0.0, -1};            // lfilter([1],[1,-0.99]) -> y
+            for (int i = 0; i < 5; i++)
+                am.lane[9 + i] = MrgLane{wc.lmr[i], i == 0 ? WM_D1 : 19 + i, i == 0 ? 2 : 1, i == 4 ? WM_MO : 20 + i, i == 4 ? 3 : 1, i, 0, 0.0, 0.0, -1};
+            // pass 2: LP15k on m * 2p (D2 -> 29 -> 30 -> LP), de-emphasis per channel (DL -> UL, DR -> UR)
+            for (int i = 0; i < 3; i++)
+                am.lane[14 + i] = MrgLane{wc.lp[i], i == 0 ? WM_D2 : 28 + i, i == 0 ? 2 : 1, i == 2 ? WM_LP : 29 + i, i == 2 ? 2 : 1, 7 + i, 0, 0.0, 0.0, -1};
+            am.lane[17] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DL, 2, WM_UL, 3, 11, 1, 0.0, 0.0, -1};
+            am.lane[18] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DR, 2, WM_UR, 3, 11, 1, 0.0, 0.0, -1};
+            // forward half of the zero-phase decimator, per channel (EL -> 47 -> 48 -> 49 -> YL, ER -> 50 -> 51 -> 52 -> YR)
+            for (int ch = 0; ch < 2; ch++)
+                for (int i = 0; i < 4; i++)
+                    am.lane[19 + 4 * ch + i] = MrgLane{c.s[i], i == 0 ? (ch ? WM_ER : WM_EL) : 46 + 3 * ch + i, i == 0 ? 2 : 1,
+                                                       i == 3 ? (ch ? WM_YR : WM_YL) : 47 + 3 * ch + i, i == 3 ? 2 : 1, 13 + i, 0, c.zi[2 * i], c.zi[2 * i + 1], ch};
+            const unsigned gm = (unsigned)((n_frames + 1) / 2);
             pss_kernel_begin(ctx, "k_wfm_casc");
-            constexpr int CASC_THREADS = 128;
-            hipLaunchKernelGGL(k_wfm_casc<1>, dim3(gc), dim3(CASC_THREADS), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Aa, Pp, Mm,
-                               U2, n, n_frames, Lp, swapped, a1);
+            hipLaunchKernelGGL(k_wfm_mrg, dim3(gm), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Y2, n, n_frames, L,
+                               swapped, am);
             pss_kernel_end(ctx);
-            pss_kernel_begin(ctx, "k_wfm_casc");
-            hipLaunchKernelGGL(k_wfm_casc<2>, dim3(gc), dim3(CASC_THREADS), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Aa, Pp, Mm,
-                               U2, n, n_frames, Lp, swapped, a2);
-            pss_kernel_end(ctx);
-#else
-#ifdef PSS_EXP_WFM_TWOPASS
-            BlkArg a1, a2;
-            const Biquad idle{0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int i = 0; i < 16; i++) a1.lane[i] = a2.lane[i] = BlkLane{idle, 0, 0, -1, 0};
-            // pass 1 (rows: 0,1 d | 2,3 | 4,5 a | 6..10 | 11,12 y | 13..16 | 17,18 m)
-            for (int i = 0; i < 3; i++) a1.lane[i] = BlkLane{wc.lp[i], i == 0 ? 0 : 1 + i, i == 2 ? 4 : 2 + i, i, 0};               // a: rows 0 -> 2 -> 3 -> 4
-            for (int i = 0; i < 5; i++) a1.lane[3 + i] = BlkLane{wc.pil[i], i == 0 ? 0 : 5 + i, 6 + i, i, 0};                          // pilot band-pass: 0 -> 6 .. 10
-            a1.lane[8] = BlkLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 10, 11, 5, 1};                                                       // lfilter([1],[1,-0.99]) -> y
-            for (int i = 0; i < 5; i++) a1.lane[9 + i] = BlkLane{wc.lmr[i], i == 0 ? 0 : 12 + i, i == 4 ? 17 : 13 + i, i, 0};           // m: 0 -> 13 .. 16 -> 17
-            // pass 2 (rows: 0,1 m*2p | 2,3 | 4,5 lp | 6,7 l | 8,9 r | 10,11 u_l | 12,13 u_r)
-            for (int i = 0; i < 3; i++) a2.lane[i] = BlkLane{wc.lp[i], i == 0 ? 0 : 1 + i, i == 2 ? 4 : 2 + i, i, 0};               // :137
-            a2.lane[3] = BlkLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, 6, 10, 4, 1};                                                    // de-emphasis, left
-            a2.lane[4] = BlkLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, 8, 12, 4, 1};                                                    // de-emphasis, right
-            const unsigned gc = (unsigned)((n_frames + WB_G - 1) / WB_G);
-            pss_kernel_begin(ctx, "k_wfm_casc");
-            hipLaunchKernelGGL(k_wfm_blk<1>, dim3(gc), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Aa, Pp, Mm,
-                               U2, n, n_frames, Lp, swapped, a1);
-            pss_kernel_end(ctx);
-            pss_kernel_begin(ctx, "k_wfm_casc");
-            hipLaunchKernelGGL(k_wfm_blk<2>, dim3(gc), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Aa, Pp, Mm,
-                               U2, n, n_frames, Lp, swapped, a2);
-            pss_kernel_end(ctx);
-#else
-            {
-                MrgArg am;
-                const Biquad idle{0.0, 0.0, 0.0, 0.0, 0.0};
-                for (int i = 0; i < 27; i++) am.lane[i] = MrgLane{idle, 0, 1, 0, 1, -1, 0, 0.0, 0.0, -1};
-                // pass 1: a (rows D1 -> 2 -> 3 -> A ring), pilot band-pass (D1 -> 13..17) + 1-pole (17 -> Y), m (D1 -> 20..23 -> Mo ring)
-                for (int i = 0; i < 3; i++)
-                    am.lane[i] = MrgLane{wc.lp[i], i == 0 ? WM_D1 : 1 + i, i == 0 ? 2 : 1, i == 2 ? WM_A : 2 + i, i == 2 ? 9 : 1, i, 0, 0.0, 0.0, -1};
-                for (int i = 0; i < 5; i++) am.lane[3 + i] = MrgLane{wc.pil[i], i == 0 ? WM_D1 : 12 + i, i == 0 ? 2 : 1, 13 + i, 1, i, 0, 0.0, 0.0, -1};
-                am.lane[8] = MrgLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 17, 1, WM_Y, 2, 5, 1, 0.0, 0.0, -1};            // lfilter([1],[1,-0.99]) -> y
-                for (int i = 0; i < 5; i++)
-                    am.lane[9 + i] = MrgLane{wc.lmr[i], i == 0 ? WM_D1 : 19 + i, i == 0 ? 2 : 1, i == 4 ? WM_MO : 20 + i, i == 4 ? 3 : 1, i, 0, 0.0, 0.0, -1};
-                // pass 2: LP15k on m * 2p (D2 -> 29 -> 30 -> LP), de-emphasis per channel (DL -> UL, DR -> UR)
-                for (int i = 0; i < 3; i++)
-                    am.lane[14 + i] = MrgLane{wc.lp[i], i == 0 ? WM_D2 : 28 + i, i == 0 ? 2 : 1, i == 2 ? WM_LP : 29 + i, i == 2 ? 2 : 1, 7 + i, 0, 0.0, 0.0, -1};
-                am.lane[17] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DL, 2, WM_UL, 3, 11, 1, 0.0, 0.0, -1};
-                am.lane[18] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DR, 2, WM_UR, 3, 11, 1, 0.0, 0.0, -1};
-#ifdef PSS_EXP_WFM_NOFWD
-                const unsigned gm = (unsigned)((n_frames + 2) / 3);
-                pss_kernel_begin(ctx, "k_wfm_casc");
-                hipLaunchKernelGGL(k_wfm_mrg<false>, dim3(gm), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), U2, n, n_frames, Lp,
-                                   swapped, am);
-                pss_kernel_end(ctx);
-#else
-                // forward half of the zero-phase decimator, per channel (EL -> 47 -> 48 -> 49 -> YL, ER -> 50 -> 51 -> 52 -> YR)
-                for (int ch = 0; ch < 2; ch++)
-                    for (int i = 0; i < 4; i++)
-                        am.lane[19 + 4 * ch + i] = MrgLane{c.s[i], i == 0 ? (ch ? WM_ER : WM_EL) : 46 + 3 * ch + i, i == 0 ? 2 : 1,
-                                                           i == 3 ? (ch ? WM_YR : WM_YL) : 47 + 3 * ch + i, i == 3 ? 2 : 1, 13 + i, 0, c.zi[2 * i], c.zi[2 * i + 1], ch};
-                const unsigned gm = (unsigned)((n_frames + 1) / 2);
-                pss_kernel_begin(ctx, "k_wfm_casc");
-                hipLaunchKernelGGL(k_wfm_mrg<true>, dim3(gm), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Y2, n, n_frames, L,
-                                   swapped, am);
-                pss_kernel_end(ctx);
-#endif
-            }
-#endif
-#endif
             const unsigned gs = (unsigned)((rows + IS_G - 1) / IS_G);
-#if defined(PSS_EXP_CASC_SAMPLE) || defined(PSS_EXP_WFM_TWOPASS) || defined(PSS_EXP_WFM_NOFWD)
-            pss_kernel_begin(ctx, "k_iir4_sys");
-            hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), U2, Lp, 0, L, L, c, Y2, L, q, n_out, nullptr, rows);
-            pss_kernel_end(ctx);
-#endif
             pss_kernel_begin(ctx, "k_iir4_sys");
             hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), Y2, L, 1, L, L - EDGE, c, A2, (long)n_out, q, n_out, MX2, rows);
             pss_kernel_end(ctx);
@@ -3667,10 +3185,7 @@ extern "C" int pss_sosfilt(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     if (n_rows == 0 || n == 0) return PSS_OK;
     SosArg a;
     a.nsec = nsec;
-    for (int s2 = 0; s2 < 8; s2++) {
-        const double *row = sos + 6 * (s2 < nsec ? s2 : 0);
-        a.s[s2] = Biquad{row[0], row[1], row[2], row[4], row[5]};
-    }
+    for (int s2 = 0; s2 < 8; s2++) a.s[s2] = sos_biquad(sos + 6 * (s2 < nsec ? s2 : 0));
     pss_time_begin(ctx);
     pss_kernel_begin(ctx, "k_sosfilt");
     hipLaunchKernelGGL(k_sosfilt, dim3((unsigned)((n_rows + TILE - 1) / TILE)), dim3(TILE), 0, PSS_STREAM(ctx), d_x, d_y, n, n_rows, a);
@@ -4239,7 +3754,7 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
         return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: null buffer");
     double *d_vals = nullptr;
     if (n_frames > 0 && !d_post) {
-        const bool direct = pss_post_sel_serves(ctx, n, F64) && !(F64 && ctx->f64_plain);
+        const bool direct = pss_post_sel_serves(n, F64) && !(F64 && ctx->f64_plain);
         const size_t need = direct ? (size_t)n_frames * disp_w * sizeof(double) : (size_t)n_frames * (n - 4) * sizeof(TR);
         int rq = pss_ensure_buffer(ctx, &ctx->scratch_post, &ctx->scratch_post_bytes, need, "post-process scratch");
         if (rq) return rq;
@@ -4469,6 +3984,3 @@ extern "C" int pss_get_ssb_taps(pss_ctx *ctx, double fs, double *taps65)
     return PSS_OK;
 }
 
-#ifdef PSS_UBENCH   // role micro-benchmarks of the fused NFM forward kernel: variant builds only (tools/build_variant.py ubench -DPSS_UBENCH)
-#include "pss_ubench.h"
-#endif

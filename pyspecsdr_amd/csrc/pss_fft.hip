@@ -648,31 +648,12 @@ int launch_r16(pss_ctx *ctx, const float *d_iq, long n_frames, float *d_db, cons
     // 0.200 ms per 2^26 samples against 0.210 without the prefetch and 0.233 for k_spectrum_xl<0>; 256: the split kernel wins
     // "db_exact" (compute_fft rows only): its own instantiations (244 VGPRs with the prefetch: no spill)
     const bool exact = !SCAN && ctx->db_exact;
-    int fpw = C::FPW;
-#ifdef PSS_VARIANTS   // every combination, steered by the options "fft_split" / "fft_prefetch" / "fft_two_per_wg" (A/B builds)
-    const bool split = ctx->fft_split >= 0 ? ctx->fft_split != 0 : LOG_R3 == 0;
-    const bool prefetch = !split && (ctx->fft_prefetch >= 0 ? ctx->fft_prefetch != 0 : (LOG_R3 >= 1 && !(LOG_R3 == 4 && SCAN)));
-    auto kern = exact ? (split ? pss_r16::k_spectrum_r16<LOG_R3, false, true, false, true>
-                         : prefetch ? pss_r16::k_spectrum_r16<LOG_R3, false, false, true, true> : pss_r16::k_spectrum_r16<LOG_R3, false, false, false, true>)
-                : split ? pss_r16::k_spectrum_r16<LOG_R3, SCAN, true, false>
-                : prefetch ? pss_r16::k_spectrum_r16<LOG_R3, SCAN, false, true> : pss_r16::k_spectrum_r16<LOG_R3, SCAN, false, false>;
-    size_t lds = split ? (size_t)C::FPW * C::EX * sizeof(double) + (size_t)C::TW2 * sizeof(double2) : C::LDS;
-    if constexpr (LOG_R3 == 3 && !SCAN) {
-        // N = 2048 (two wavefronts per frame): one frame per 128-thread workgroup
-        if (!split && !ctx->fft_two_per_wg) {
-            kern = exact ? (prefetch ? pss_r16::k_spectrum_r16<3, false, false, true, true, true> : pss_r16::k_spectrum_r16<3, false, false, false, true, true>)
-                         : (prefetch ? pss_r16::k_spectrum_r16<3, false, false, true, false, true> : pss_r16::k_spectrum_r16<3, false, false, false, false, true>);
-            fpw = 1;
-            lds = (size_t)C::EX * sizeof(double2) + (size_t)C::TW2 * sizeof(double2);
-        }
-    }
-#else                 // the product library carries the measured winner per length only (12 instantiations instead of 49)
+    // the measured winner per length; one: N = 2048 (two wavefronts per frame) with one frame per 128-thread workgroup
     constexpr bool split = LOG_R3 == 0, prefetch = LOG_R3 >= 1 && !(LOG_R3 == 4 && SCAN), one = LOG_R3 == 3 && !SCAN;
     auto kern = exact ? pss_r16::k_spectrum_r16<LOG_R3, false, split, prefetch, true, one> : pss_r16::k_spectrum_r16<LOG_R3, SCAN, split, prefetch, false, one>;
-    if (one) fpw = 1;
+    const int fpw = one ? 1 : C::FPW;
     const size_t lds = split ? (size_t)C::FPW * C::EX * sizeof(double) + (size_t)C::TW2 * sizeof(double2)
                              : (size_t)fpw * C::EX * sizeof(double2) + (size_t)C::TW2 * sizeof(double2);
-#endif
     if (lds > 64 * 1024)
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -745,17 +726,11 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
         // compute_fft rows: the three-stage kernel with complex exchanges (two workgroups per CU, next frame prefetched): 4.0 TB/s since
         // round 3 (conflict-free layouts, fused multiply-adds); scanner slices: the component-wise-exchange kernel below (128 VGPRs,
         // 35 KB LDS: four workgroups per CU), which hides the exact float32 chain's dependent arithmetic better.
-        // "fft_xl4096" = 0 / 1 (variant builds): one of the two for both.
-#ifdef PSS_VARIANTS
-        if ((ctx->fft_xl4096 >= 0 ? !ctx->fft_xl4096 : !SCAN) || ctx->fft_big_scratch)
-            return launch_r16<4, SCAN>(ctx, d_iq, n_frames, d_db, tw, win, d_peak, d_bw, d_count, bin_hz);
-#else
         if constexpr (!SCAN) return launch_r16<4, SCAN>(ctx, d_iq, n_frames, d_db, tw, win, d_peak, d_bw, d_count, bin_hz);
-#endif
         break;
     default: break;
     }
-    if (((!SCAN && (n_fft == 8192 || n_fft == 16384)) || n_fft == 4096) && !ctx->fft_big_scratch) {
+    if ((!SCAN && (n_fft == 8192 || n_fft == 16384)) || n_fft == 4096) {
         // N = 16 x 16 x 16 x R4 in registers + LDS: the frame is read once, the dB row written once
         auto go = [&](auto kern, size_t lds, int threads, int per_cu) -> int {
             PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -769,21 +744,14 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
             return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_xl launch");
         };
         if (!SCAN && ctx->db_exact) {
-#ifdef PSS_VARIANTS
-            if (n_fft == 4096) return go(pss_xl::k_spectrum_xl<0, true, false, true>, pss_xl::CfgX<0>::LDS, 256, 4);
-#endif
             if (n_fft == 8192) return go(pss_xl::k_spectrum_xl<1, true, false, true>, pss_xl::CfgX<1>::LDS, 512, 2);
             return go(pss_xl::k_spectrum_xl<2, true, false, true>, pss_xl::CfgX<2>::LDS, 1024, 1);
         }
-#ifdef PSS_VARIANTS
-        if (n_fft == 4096) return go(pss_xl::k_spectrum_xl<0, !SCAN, SCAN>, pss_xl::CfgX<0>::LDS, 256, 4);
-#else
         if constexpr (SCAN) return go(pss_xl::k_spectrum_xl<0, false, true>, pss_xl::CfgX<0>::LDS, 256, 4);
-#endif
         if (n_fft == 8192) return go(pss_xl::k_spectrum_xl<1, true>, pss_xl::CfgX<1>::LDS, 512, 2);
         return go(pss_xl::k_spectrum_xl<2, true>, pss_xl::CfgX<2>::LDS, 1024, 1);
     }
-    if (!SCAN && n_fft >= 8192 && n_fft <= 65536) {
+    if (!SCAN && (n_fft == 32768 || n_fft == 65536)) {
         // N = R * 4096: radix-R pre-pass + register-resident 4096-point transforms, one workgroup per frame
         using C = pss_r16::Cfg<4>;
         const long cap = 512;  // workgroups (each owns N complex float64 of L2-resident scratch)
@@ -792,10 +760,7 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
                               "spectrum scratch");
         if (r) return r;
         double2 *scr = reinterpret_cast<double2 *>(ctx->scratch_fft);
-        void (*kern)(const float2 *, float *, const double2 *, const double *, long, double2 *, int) =
-            n_fft == 8192 ? pss_r16::k_spectrum_r16_big<1, true>
-            : n_fft == 16384 ? pss_r16::k_spectrum_r16_big<2, true>
-            : n_fft == 32768 ? pss_r16::k_spectrum_r16_big<3, true> : pss_r16::k_spectrum_r16_big<4, true>;
+        auto kern = n_fft == 32768 ? pss_r16::k_spectrum_r16_big<3, true> : pss_r16::k_spectrum_r16_big<4, true>;
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)C::LDS));
         pss_time_begin(ctx);
@@ -1570,7 +1535,10 @@ int launch_post_sel(pss_ctx *ctx, const TR *d_db, long n_frames, int n_fft, TR *
 
 // the register select kernel (k_post_sel) serves rows of a multiple of 4 points up to 32 772 (float64 rows: up to 16 388 — the staging
 // buffer of a longer row does not fit the LDS); only it can leave the rows unwritten
-bool post_sel_serves(const pss_ctx *ctx, int n_fft, bool f64 = false) { return !ctx->post_legacy && n_fft - 4 <= (f64 ? 16384 : 32768) && (n_fft & 3) == 0; }
+bool post_sel_serves(int n_fft, bool f64 = false) { return n_fft - 4 <= (f64 ? 16384 : 32768) && (n_fft & 3) == 0; }
+
+// longest row the other kernels take through the LDS bitonic sort, else the radix select (measured crossover 8192..16384)
+constexpr int POST_SORT_MAX = 8192;
 
 // the register select over rows of either type: rows written (d_post) or not, thresholds (d_thr), extremes, resampled rows (d_vals)
 template <class TR>
@@ -1594,9 +1562,9 @@ int post_sel_any(pss_ctx *ctx, const TR *d_db, long n_frames, int n_fft, TR *d_p
 int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, float *d_post, float *d_lo, float *d_hi, float *d_thr = nullptr,
                   double *d_vals = nullptr, int disp_w = 0)
 {
-    if (d_vals && !post_sel_serves(ctx, n_fft)) return pss_fail(ctx, PSS_E_ARG, "resampled rows: only from the register select kernel");
+    if (d_vals && !post_sel_serves(n_fft)) return pss_fail(ctx, PSS_E_ARG, "resampled rows: only from the register select kernel");
     if (n_frames < 0 || (n_frames > 0 && (!d_db || (!d_post && !(d_thr && d_lo))))) return pss_fail(ctx, PSS_E_ARG, "null pointer");
-    if (!d_post && n_fft >= 8 && !post_sel_serves(ctx, n_fft))
+    if (!d_post && n_fft >= 8 && !post_sel_serves(n_fft))
         return pss_fail(ctx, PSS_E_ARG, "post-process without materialised rows: n_fft must be a multiple of 4 and at most 32772");
     if ((d_lo == nullptr) != (d_hi == nullptr)) return pss_fail(ctx, PSS_E_ARG, "row extremes: pass both arrays or neither");
     if (n_fft < 8 || n_fft > (1 << 20)) return pss_fail(ctx, PSS_E_ARG, "post-process supports 8 <= n_fft <= 1048576");
@@ -1604,10 +1572,10 @@ int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, flo
     const int m = n_fft - 4;
     int r = PSS_OK;
     pss_time_begin(ctx);
-    if (post_sel_serves(ctx, n_fft)) {
+    if (post_sel_serves(n_fft)) {
         // register-resident binary-search select: one wavefront per row up to 2048 points, 4 / 16 wavefronts above
         r = post_sel_any<float>(ctx, d_db, n_frames, n_fft, d_post, d_lo, d_hi, d_thr, d_vals, disp_w);
-    } else if (n_fft > ctx->post_sort_max) {
+    } else if (n_fft > POST_SORT_MAX) {
         // rows too long for registers / the LDS sort: MSD radix select with an LDS histogram
         pss_kernel_begin(ctx, "k_post");
         const int thr = n_fft <= 2048 ? 256 : 1024;
@@ -1616,7 +1584,7 @@ int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, flo
         pss_kernel_end(ctx);
         r = pss_hip_check(ctx, hipGetLastError(), "k_post_select launch");
     } else {
-        // option "post_legacy": bitonic sort of the smoothed row in LDS (kept as an A/B reference)
+        // rows the register select does not serve, up to POST_SORT_MAX points: bitonic sort of the smoothed row in LDS
         int P = 1;
         while (P < n_fft - 4) P <<= 1;
         const size_t lds = (size_t)P * sizeof(float);
@@ -1632,7 +1600,7 @@ int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, flo
         pss_kernel_end(ctx);
         r = pss_hip_check(ctx, hipGetLastError(), "k_post launch");
     }
-    if (!r && d_lo && (ctx->post_legacy || m > 32768 || (n_fft & 3) != 0)) {
+    if (!r && d_lo && !post_sel_serves(n_fft)) {
         pss_kernel_begin(ctx, "k_row_extremes");
         hipLaunchKernelGGL(pss_post::k_row_extremes<float>, dim3((unsigned)((n_frames + 3) / 4 < 8192 ? (n_frames + 3) / 4 : 8192)),
                            dim3(256), 0, PSS_STREAM(ctx), d_post, n_frames, m, d_lo, d_hi);
@@ -1754,7 +1722,7 @@ extern "C" int pss_spectrum_post_f64(pss_ctx *ctx, const double *d_db, long n_fr
     if (n_frames < 0 || n_fft < 5 || (n_frames > 0 && (!d_db || !d_post))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_f64: bad argument");
     if ((d_row_lo == nullptr) != (d_row_hi == nullptr)) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_f64: row_lo and row_hi go together");
     if (n_frames == 0) return PSS_OK;
-    if (!ctx->f64_plain && n_fft >= 8 && post_sel_serves(ctx, n_fft, true)) {   // the register select on 64-bit keys (option "f64_plain" = 1: the radix-select kernel below)
+    if (!ctx->f64_plain && n_fft >= 8 && post_sel_serves(n_fft, true)) {   // the register select on 64-bit keys (option "f64_plain" = 1: the radix-select kernel below)
         pss_time_begin(ctx);
         const int rq = post_sel_any<double>(ctx, d_db, n_frames, n_fft, d_post, d_row_lo, d_row_hi, nullptr, nullptr, 0);
         pss_time_end(ctx);
@@ -1801,7 +1769,7 @@ extern "C" int pss_persistence_rows_db(pss_ctx *ctx, const float *d_db, long n_f
 // thresholds, extremes and the rows resampled to the display width in ONE pass over the dB rows (k_post_sel's `vals`) —, then the sliding
 // extremes and the line of every frame from the resampled values.  display 0: waterfall (a = glyph, b = colour), 1: persistence (a = y).
 // Serves the lengths the register select serves (pss_post_sel_serves); d_vals: n_frames x disp_w doubles of scratch.
-bool pss_post_sel_serves(const pss_ctx *ctx, int n_fft, bool f64) { return n_fft >= 8 && post_sel_serves(ctx, n_fft, f64); }
+bool pss_post_sel_serves(int n_fft, bool f64) { return n_fft >= 8 && post_sel_serves(n_fft, f64); }
 template <class TR>
 static int chain_vals(pss_ctx *ctx, const TR *d_db, long n_frames, int n_fft, TR *d_lo, TR *d_hi, int n_halo, int window, int display, int disp_h,
                       int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals)
@@ -1827,7 +1795,7 @@ int pss_chain_vals_f64(pss_ctx *ctx, const double *d_db, long n_frames, int n_ff
 
 // The fused transform + post-process (pss_spec_post.h) and the lines from its resampled rows: compute_fft -> cells for 1024-point frames without
 // the float64 rows going through HBM.  d_db32 / d_db64: the dB row as float32 and / or float64 (either may be NULL, not both).
-bool pss_spec_post_serves(const pss_ctx *ctx, int n_fft) { return n_fft == 1024 && !ctx->f64_plain && !ctx->post_legacy; }
+bool pss_spec_post_serves(const pss_ctx *ctx, int n_fft) { return n_fft == 1024 && !ctx->f64_plain; }
 int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, float *d_db32, double *d_db64, double *d_lo, double *d_hi,
                         int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals)
 {
@@ -1839,13 +1807,8 @@ int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_ff
     if (r) return r;
     using C = pss_r16::Cfg<2>;
     auto kern = d_db32 ? (d_db64 ? pss_sp::k_spectrum_post<true, true> : pss_sp::k_spectrum_post<true, false>) : pss_sp::k_spectrum_post<false, true>;
-#ifdef PSS_EXP_FUSE_LDS      // timing experiment (with PSS_EXP_FUSE_NOFFT: the staged rows only)
-    const size_t lds = PSS_EXP_FUSE_LDS;
-    const long cap = 256L * PSS_EXP_FUSE_WAVES * 2;
-#else
     const size_t lds = (size_t)C::FPW * C::EX * sizeof(double2) + (size_t)C::TW2 * sizeof(double2);
     const long cap = 256L * 2 * 2;       // two 256-thread workgroups per CU (LDS, registers), two rounds
-#endif
     if (lds > 64 * 1024) PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long groups = (n_frames + C::FPW - 1) / C::FPW;
     pss_time_begin(ctx);

@@ -22,13 +22,8 @@ namespace pss_r16 {
 // Complex product with explicit fused multiply-adds (4 instructions instead of 6).  pss_device.h switches contraction off for
 // everything that includes it — the demodulators' bit-exactness contract — so nothing in the transforms was fused until round 3;
 // their results are tolerance-bound (or rounded to float32 with ~1e-15 of margin), and the float64 pipe is what paces them.
-#ifdef PSS_EXP_NOFMA
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ double power_of(double2 X) { return X.x * X.x + X.y * X.y + 1e-10; }
-#else
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(fma(a.x, b.x, -(a.y * b.y)), fma(a.x, b.y, a.y * b.x)); }
 __device__ __forceinline__ double power_of(double2 X) { return fma(X.x, X.x, fma(X.y, X.y, 1e-10)); }   // |X|^2 + 1e-10
-#endif
 __device__ __forceinline__ double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 
@@ -251,11 +246,7 @@ __device__ __forceinline__ float db_of_fast(double pw)
     const float far = 3.0102999566398120f * (__log2f((float)ps) + (big ? 200.0f : 0.0f));
     const float s = t * __builtin_amdgcn_rcpf(2.0f + t);
     const float s2 = s * s;
-#ifdef PSS_EXP_NOFMA
-    const float p = s * (2.0f + s2 * (0.66666667f + s2 * (0.4f + s2 * (0.28571429f + s2 * 0.22222222f))));
-#else
     const float p = s * fmaf(s2, fmaf(s2, fmaf(s2, fmaf(s2, 0.22222222f, 0.28571429f), 0.4f), 0.66666667f), 2.0f);
-#endif
     return fabsf(t) < 0.25f ? 4.342944819032518f * p : far;
 }
 
@@ -316,15 +307,9 @@ struct Cfg {
     //    R3-way conflict on each of the 15 reads).
     // Rounds 1-2 used pad1 = 4, pad2 = 2, rows of 16 for every length: SQ_LDS_BANK_CONFLICT was 29 / 58 % of the LDS cycles at
     // 1024 / 2048 points (profiles/r03_lds_bank_conflicts.txt has both layouts).
-#ifdef PSS_EXP_OLDPAD
-    static constexpr int E1_STRIDE = T + 4;
-    static constexpr int E2_STRIDE = 256 + 2;
-    static constexpr int TW2S = 16;
-#else
     static constexpr int E1_STRIDE = T + (R3 == 1 ? 4 : R3 % 16);                     // complex elements per k2 row
     static constexpr int E2_STRIDE = 256 + (R3 == 1 ? 2 : R3 <= 8 ? 8 / R3 : 1);     // complex elements per m1 plane
     static constexpr int TW2S = 17;                                                   // complex elements per stage-2 twiddle row
-#endif
     static constexpr int TW2 = R3 * TW2S;                                             // stage-2 twiddle table, complex elements
     static __device__ __forceinline__ int tw2_slot(int i) { return (i / 16) * TW2S + (i % 16); }   // of entry m1 * 16 + j2
     static constexpr int EX = (16 * E1_STRIDE > R3 * E2_STRIDE) ? 16 * E1_STRIDE : R3 * E2_STRIDE;  // per frame
@@ -369,7 +354,6 @@ __device__ __forceinline__ void r16_core(double2 (&v)[16], double2 *ex, const do
 #pragma unroll
     for (int m2 = 0; m2 < 16; m2++) v[m2] = ex[k2s * C::E1_STRIDE + m1s + R3 * m2];
     frame_sync<WAVE_LOCAL>();
-#ifndef PSS_EXP_TW2_AT_USE
     // the stage-2 twiddles W_T^(m1 j2) come from LDS: requested TWD outputs ahead of their use, the first ones before the
     // butterflies (read at the use, each of the 15 products waited for an LDS round trip with six instructions to cover it)
     constexpr int TWD = 4;
@@ -380,30 +364,18 @@ __device__ __forceinline__ void r16_core(double2 (&v)[16], double2 *ex, const do
         for (int d = 0; d < TWD; d++) tq[d] = twp[1 + d];
         __builtin_amdgcn_sched_barrier(0);
     }
-#endif
     fft_reg<16>(v);
-#ifdef PSS_EXP_TW2_AT_USE
 #pragma unroll
-    for (int j2 = 0; j2 < 16; j2++) {
+    for (int j2 = 0; j2 < 16; j2++) {   // j2 = 0 is a product with 1
         double2 z = v[brev(j2, 4)];
-        if (R3 > 1) z = cmul(z, tw2[m1s * C::TW2S + j2]);
+        if constexpr (R3 > 1) {
+            if (j2 >= 1) {
+                z = cmul(z, tq[(j2 - 1) % TWD]);
+                if (j2 + TWD < 16) tq[(j2 - 1) % TWD] = twp[j2 + TWD];
+            }
+        }
         ex[m1s * C::E2_STRIDE + 16 * j2 + k2s] = z;
     }
-#else
-    {
-#pragma unroll
-        for (int j2 = 0; j2 < 16; j2++) {   // j2 = 0 is a product with 1
-            double2 z = v[brev(j2, 4)];
-            if constexpr (R3 > 1) {
-                if (j2 >= 1) {
-                    z = cmul(z, tq[(j2 - 1) % TWD]);
-                    if (j2 + TWD < 16) tq[(j2 - 1) % TWD] = twp[j2 + TWD];
-                }
-            }
-            ex[m1s * C::E2_STRIDE + 16 * j2 + k2s] = z;
-        }
-    }
-#endif
     frame_sync<WAVE_LOCAL>();
 #pragma unroll
     for (int c = 0; c < 16 / R3; c++) {
@@ -525,11 +497,7 @@ __global__ __launch_bounds__(256) void k_spectrum_r16(const float2 *__restrict__
     float2 nx[16];
     auto fetch = [&](long g) {
         const long f = g * FPW + fl;
-#ifdef PSS_EXP_SPEC_L2IQ   // timing experiment: every load hits the cache
-        const float2 *x = iq + (size_t)(f < n_frames ? (f & 15) : 0) * N;
-#else
         const float2 *x = iq + (size_t)(f < n_frames ? f : 0) * N;
-#endif
 #pragma unroll
         for (int n2 = 0; n2 < 16; n2++) nx[n2] = x[t + T * n2];
     };
@@ -566,9 +534,6 @@ __global__ __launch_bounds__(256) void k_spectrum_r16(const float2 *__restrict__
             float d;
             if constexpr (SCAN) d = (flags & FLAG_SCAN_EXACT) ? pss::scan_db_np(X.x, X.y, l10) : db_of_fast(power_of(X));
             else d = EXACT ? db_of_exact(power_of(X)) : db_of_fast(power_of(X));
-#ifdef PSS_EXP_SPEC_NODB
-            d = (float)X.x + (float)X.y;
-#endif
             // fftshift; T consecutive bins per store instruction (k - t is a multiple of T, so the row offset is a compile-time constant)
             if constexpr (PREFETCH) buf_store_f32(ro, ro_lane, (((k - t) + N / 2) & (N - 1)) * 4, d);
             else if (out) out[(k + N / 2) & (N - 1)] = d;
@@ -609,7 +574,7 @@ __global__ __launch_bounds__(256) void k_spectrum_r16(const float2 *__restrict__
     }
 }
 
-// N = R * 4096, R in {2,4,8,16}: a radix-R decimation-in-frequency pre-pass, then R register-resident 4096-point
+// N = R * 4096, R in {8, 16} (8192 and 16 384 points go to k_spectrum_xl): a radix-R decimation-in-frequency pre-pass, then R register-resident 4096-point
 // transforms (r16_core<4>) one after the other:
 //   X[R k' + r] = FFT_4096( y_r )[k'],  y_r[n] = W_N^(n r) * sum_q x[n + 4096 q] w[n + 4096 q] W_R^(q r).
 // One 256-thread workgroup per frame.  The pre-pass reads the frame once (each thread: 16 R-point register DFTs) and

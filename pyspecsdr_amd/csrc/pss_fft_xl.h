@@ -34,13 +34,9 @@ struct CfgX {
     static constexpr int N = 16 * T;
     static constexpr int T2 = 16 * R4;              // T / 16
     static constexpr int E2 = T2 + R4;              // row stride of exchange 2 (doubles): groups of R4 lanes land R4 apart mod 32
-#ifdef PSS_EXP_OLDPAD
-    static constexpr int P3 = 16 * 272 + 32 / R4;
-#else
     // plane stride of exchange 3 (doubles): 17-double rows; a ds_write_b64 is served 16 consecutive lanes at a time against 32 banks
     // (16 eight-byte slots): 16 / R4 values of r2 x R4 planes -> slots 17 r2 + P3 c, all different iff P3 = 16 / R4 (mod 16)
     static constexpr int P3 = 16 * 272 + 16 / R4;
-#endif
     static constexpr int EXD = (R4 * P3 > 256 * E2) ? R4 * P3 : 256 * E2;   // doubles (>= 16 T for exchange 1)
     static constexpr size_t LDS = (size_t)EXD * sizeof(double);
 };
@@ -144,12 +140,8 @@ __device__ __forceinline__ void xl_core(double2 (&v)[16], double *ex, double2 w1
         // barrier inside; the one behind it keeps exchange 3's buffer-wide writes away from wavefronts still reading here
         // (exchange 1 ended with a workgroup barrier after its reads)
         double *wb = ex + (r_s * 16) * E2 + b_s, *rb = ex + g3 * E2 + c_s;
-#ifdef PSS_EXP_XL_BARRIERS
-        exchange(v, [&](int r2) { return wb + r2 * E2; }, [&](int q) { return rb + R4 * q; });
-#else
         exchange<true>(v, [&](int r2) { return wb + r2 * E2; }, [&](int q) { return rb + R4 * q; });
         __syncthreads();
-#endif
     }
     // ---- stage 3
     fft_reg<16>(v);
@@ -203,16 +195,8 @@ __global__ __launch_bounds__(256 << LOG_R4, 4) void k_spectrum_xl(const float2 *
     const double2 w3 = tw[(size_t)(t % R4) * 256];             // W_T2^c = W_N^(256 c)
     const __amdgpu_buffer_rsrc_t rw = make_rsrc(win, WINDOW ? N * 8 : 0);
     for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
-#ifdef PSS_EXP_SPEC_L2IQ   // timing experiment: every load hits the cache
-        const __amdgpu_buffer_rsrc_t rx = make_rsrc(iq + (size_t)(f & 15) * N, N * 8);
-#else
         const __amdgpu_buffer_rsrc_t rx = make_rsrc(iq + (size_t)f * N, N * 8);
-#endif
-#ifdef PSS_EXP_SPEC_NOSTORE   // timing experiment: the row is computed and dropped by the bounds check
-        const __amdgpu_buffer_rsrc_t ro = make_rsrc(db + (size_t)f * N, (flags & 0x100) ? N * 4 : 0);
-#else
         const __amdgpu_buffer_rsrc_t ro = make_rsrc(db ? db + (size_t)f * N : nullptr, db ? N * 4 : 0);   // no rows wanted: every store dropped
-#endif
         // the 45 twiddle powers are loop-invariant and the compiler would compute them once, park them in scratch memory
         // (180 VGPRs) and reload them every frame; recomputing them from the three bases is cheaper than that traffic
         double2 u1 = w1, u2 = w2, u3 = w3;
@@ -237,9 +221,6 @@ __global__ __launch_bounds__(256 << LOG_R4, 4) void k_spectrum_xl(const float2 *
             float d;
             if constexpr (SCAN) d = (flags & pss_r16::FLAG_SCAN_EXACT) ? pss::scan_db_np(X.x, X.y, l10) : pss_r16::db_of_fast(pss_r16::power_of(X));
             else d = EXACT ? pss_r16::db_of_exact(pss_r16::power_of(X)) : pss_r16::db_of_fast(pss_r16::power_of(X));
-#ifdef PSS_EXP_SPEC_NODB
-            d = (float)X.x + (float)X.y;
-#endif
             buf_store_f32(ro, t * 4, ((4096 * k + T * j + N / 2) & (N - 1)) * 4, d);
             if (SCAN) { held[i * T + t] = d; lmax = fmaxf(lmax, d); }
         });

@@ -407,11 +407,10 @@ __device__ __forceinline__ double2 rf_cq(int q)     // exp(-2 pi i q / 32) = W_N
     return make_double2(tab[q][0], tab[q][1]);
 }
 
-#ifndef PSS_EXP_SSB_WAVES    // timing experiment: -DPSS_EXP_SSB_WAVES=2 gives the kernel 256 VGPRs (no spill) at one resident frame per CU
-#define PSS_EXP_SSB_WAVES 4
-#endif
+// 4 wavefronts per SIMD (128 VGPRs, 13 / 19 spilled): two 512-thread or four 256-thread workgroups per CU.  At 2 (no spill, one / three
+// workgroups per CU) the kernel was 6 % slower on 16 384-sample frames and equal on 8192 (NOTEBOOK R6-06).
 template <int LOG_R4>   // of the M-point transform: M = 4096 << LOG_R4, frames of N = 2 M samples
-__global__ __launch_bounds__(256 << LOG_R4, PSS_EXP_SSB_WAVES) void k_ssb_rfft(const float2 *__restrict__ iq, double *out, const double2 *__restrict__ tw,
+__global__ __launch_bounds__(256 << LOG_R4, 4) void k_ssb_rfft(const float2 *__restrict__ iq, double *out, const double2 *__restrict__ tw,
                                                                long n_rows, unsigned *__restrict__ pcm, SsbTaps taps)
 {
     __shared__ double red[2][8];
@@ -425,10 +424,6 @@ __global__ __launch_bounds__(256 << LOG_R4, PSS_EXP_SSB_WAVES) void k_ssb_rfft(c
     const int t = threadIdx.x;
     if (t < 72) ltaps[t] = taps.fwd[t];
     constexpr double INV_M = 1.0 / (double)M;
-#ifdef PSS_EXP_STAGGER   // timing experiment: the second workgroup of a CU starts late, so that the two are in different phases
-    if ((blockIdx.x / 256) & 1)
-        for (int i = 0; i < PSS_EXP_STAGGER; i++) __builtin_amdgcn_s_sleep(127);
-#endif
     for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
         const __amdgpu_buffer_rsrc_t rx = pss_xl::make_rsrc(iq + (size_t)f * N, N * 8);
         const __amdgpu_buffer_rsrc_t ro = pss_xl::make_rsrc(out + (out ? (size_t)f * N : 0), out ? N * 8 : 0);

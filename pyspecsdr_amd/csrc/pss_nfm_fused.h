@@ -19,10 +19,6 @@
 #pragma once
 #include "pss_fir_ring_asm.h"
 
-#ifdef PSS_UBENCH   // per-workgroup start / end times of k_nfm_fwd (s_memrealtime, 100 MHz): dispatch skew and tail (tools/ubench_fwd.py stamps)
-__device__ unsigned long long pss_dbg_stamps[4 * 4096];
-#endif
-
 namespace fused {
 
 using namespace pss;
@@ -47,19 +43,7 @@ constexpr size_t LDS_BYTES = (size_t)TILE * WSTR * sizeof(float) + (size_t)TILE 
 // draining them twice per chunk serialised the whole pipeline on the store round trip.
 __device__ __forceinline__ void lds_barrier()
 {
-#ifdef PSS_EXP_NOBAR   // timing experiment only (results are wrong): no workgroup barriers inside the chunk loop
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
-}
-__device__ __forceinline__ void lds_barrier_b()
-{
-#ifdef PSS_EXP_NOBAR_B  // timing experiment only: barrier B dropped
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#else
-    lds_barrier();
-#endif
 }
 
 // Balanced issue priority.  The SIMD's arbiter serves the OLDEST ready wavefront first: of the four workgroups a CU holds (they all
@@ -219,9 +203,6 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
     double *Uht = Uh + (size_t)tile * HEAD * TILE + lane;
     double *Utt = Utl + (size_t)tile * (EDGE + 1) * TILE + lane;
 #define YAT(p) Yt[(size_t)(p) * TILE]
-#ifdef PSS_UBENCH
-    if (threadIdx.x == 0 && blockIdx.x < 4096) pss_dbg_stamps[4 * blockIdx.x] = wall_clock64();
-#endif
     if (tid >= 128 && tid < 192) ltab[tid - 128] = RCP14_AB[tid - 128];
     // ---- prologue: discriminator of times 0..87 into logical columns 8..95 (physical = logical at chunk 0).
     // Thread (frame tid / 4, part tid % 4) fills the 24 columns 8 + 24 part .. of its frame: its 26 samples come as thirteen 16-byte
@@ -271,9 +252,6 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
         }
     }
     __syncthreads();
-#ifdef PSS_UBENCH
-    if (threadIdx.x == 0 && blockIdx.x < 4096) pss_dbg_stamps[4 * blockIdx.x + 2] = wall_clock64();
-#endif
     // The first 64 FIR outputs have windows shorter than 65 samples, i.e. each its own ddot shape.  With lane = frame
     // the length is wave-uniform: the four waves take 16 outputs each (interleaved, so the dot lengths balance) and
     // park them in Uh (L2) for the IIR wave.
@@ -286,20 +264,13 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
-#ifdef PSS_UBENCH
-    if (threadIdx.x == 0 && blockIdx.x < 4096) pss_dbg_stamps[4 * blockIdx.x + 3] = wall_clock64();
-#endif
     if (wave == 0) {
         // =============================== IIR wave ===============================
         Iir4 st;
         long p = 0;  // stream position of the next input; outputs lag by 3
-#ifdef PSS_EXP_NOSTORE   // timing experiment only: y_fwd rows all land on the tile's first rows (L2-resident)
-        auto emit = [&](double v) { YAT((p - 3) & 15) = v; };
-#else
         // (non-temporal stores here, so that the 614 MB of y_fwd rows do not push IQ lines out of the L2 between the two chunks that touch them:
         // FETCH_SIZE 747 -> 693 MB, launch time unchanged at 0.459 / 0.460 ms in a paired A/B — NOTEBOOK R5-07; not kept)
         auto emit = [&](double v) { YAT(p - 3) = v; };
-#endif
         // odd extension head + u[0..63] from the prologue (scipy odd_ext: ext[p] = 2u[0] - u[27-p])
         const double u0 = Uht[0];
         const double two_u0 = __dmul_rn(2.0, u0);
@@ -331,7 +302,6 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
                 }
             }
             if (ch < NC) {
-#ifndef PSS_EXP_NOPRIO
                 // progress balancing: the workgroup publishes its chunk index and ranks it among the (up to) four workgroups of its CU —
                 // the one furthest behind issues first
                 {
@@ -349,11 +319,10 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
                     if (lane == 0) *lprio = rank;
                     prio_rotate(rank);
                 }
-#endif
                 lds_barrier();  // A: workers finished FIR(ch) -> ubuf
 #pragma unroll
                 for (int t = 0; t < FC; t++) reg[t] = ubuf[t * TILE + lane];
-                lds_barrier_b();  // B
+                lds_barrier();  // B
             } else {
                 __syncthreads();  // final A/B: full fences, the workers' global Utt rows must be visible
                 __syncthreads();
@@ -400,11 +369,7 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
                 v2u_t raw[OPT + 1];
 #pragma unroll
                 for (int e = 0; e <= OPT; e++) {
-#ifdef PSS_EXP_L2IQ   // timing experiment only: every chunk re-reads the frame's first samples (always cache hits)
-                    raw[e] = __builtin_amdgcn_raw_buffer_load_b64(rs_iq, voff_iq, ((tn & 31) + e) * 8, 0);
-#else
                     raw[e] = __builtin_amdgcn_raw_buffer_load_b64(rs_iq, voff_iq, (tn + e) * 8, 0);
-#endif
                 }
 #pragma unroll 1
                 for (int h = 0; h < OPT / FBH; h++) {
@@ -453,9 +418,7 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
                     for (int e = 0; e < OPT; e++) dn[e] = (e < left) ? dn[e] : 0.0f;
                 }
                 lds_barrier();  // A
-#ifndef PSS_EXP_NOPRIO
                 prio_rotate(__builtin_amdgcn_readfirstlane(*lprio));
-#endif
                 // the oldest block (logical 0) becomes the newest (logical 3 of the next chunk)
                 {
                     float4 *nb = reinterpret_cast<float4 *>(row + rot * FC + OPT * J);   // 16-byte stores (rows are 16-byte aligned, 25 x 16 bytes apart)
@@ -463,7 +426,7 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
                     for (int e = 0; e < OPT / 4; e++) nb[e] = make_float4(dn[4 * e], dn[4 * e + 1], dn[4 * e + 2], dn[4 * e + 3]);
                 }
                 rot = (rot + 1) & (NB - 1);
-                lds_barrier_b();  // B
+                lds_barrier();  // B
             } else {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __syncthreads();  // A
@@ -471,9 +434,6 @@ __global__ __launch_bounds__(WG, 1 + NFW) void k_nfm_fwd(const float2 *__restric
             }
         }
     }
-#ifdef PSS_UBENCH
-    if (lane == 0 && blockIdx.x < 4096) atomicMax(&pss_dbg_stamps[4 * blockIdx.x + 1], wall_clock64());
-#endif
 #undef YAT
 }
 
@@ -489,9 +449,6 @@ __global__ __launch_bounds__(WFM ? 2 * TILE : TILE) void k_nfm_bwd(const double 
                                                   int n_out, long n_frames, NfmCoef c, int16_t *__restrict__ pcm,
                                                   double *__restrict__ audio)
 {
-#ifdef PSS_EXP_BWD_PRIO     // timing experiment: the backward pass's user priority while it runs beside the display chain (reset at the end)
-    __builtin_amdgcn_s_setprio(PSS_EXP_BWD_PRIO);
-#endif
     const int lane = threadIdx.x & (TILE - 1);
     const int chan = WFM ? (int)(threadIdx.x >> 6) : 0;
     const long tile = WFM ? 2 * (long)blockIdx.x + chan : (long)blockIdx.x;
@@ -500,11 +457,7 @@ __global__ __launch_bounds__(WFM ? 2 * TILE : TILE) void k_nfm_bwd(const double 
     const long L = (long)M + 2 * EDGE;
     const double *Yt = Y + (size_t)tile * L * TILE + lane;
     double *At = A + (size_t)tile * n_out * TILE + lane;
-#ifdef PSS_EXP_BWD_NOLOAD   // timing experiment only (results wrong): the backward pass without its y_fwd reads
-#define YAT(p) ((double)(p) * 1e-3 + (double)lane)
-#else
 #define YAT(p) Yt[(size_t)(p) * TILE]
-#endif
     const double ylast = YAT(L - 1);
     double z[8];
 #pragma unroll
@@ -554,9 +507,6 @@ __global__ __launch_bounds__(WFM ? 2 * TILE : TILE) void k_nfm_bwd(const double 
             }
         }
     }
-#ifdef PSS_EXP_BWD_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 #undef YAT
 }
 

@@ -17,11 +17,9 @@ namespace pss_sp {
 
 using namespace pss_r16;
 
-#ifndef PSS_EXP_FUSE_WAVES
-#define PSS_EXP_FUSE_WAVES 2     // minimum workgroups per CU the register allocation has to allow: two wavefronts per SIMD = at most 256 VGPRs
-#endif
+// 2: minimum workgroups per CU the register allocation has to allow: two wavefronts per SIMD = at most 256 VGPRs
 template <bool ROW32, bool ROW64>
-__global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const float2 *__restrict__ iq, float *__restrict__ db32, double *__restrict__ db64,
+__global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restrict__ iq, float *__restrict__ db32, double *__restrict__ db64,
                                                        const double2 *__restrict__ tw, const double *__restrict__ win, long n_frames,
                                                        double *__restrict__ row_lo, double *__restrict__ row_hi, double *__restrict__ vals,
                                                        int disp_w)
@@ -34,20 +32,11 @@ __global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const
     static_assert((size_t)(T + 1) * PC::S * sizeof(double) <= (size_t)C::EX * sizeof(double2), "the staged row fits the frame's exchange buffer");
     extern __shared__ __align__(16) unsigned char smem[];
     double2 *ex_all = reinterpret_cast<double2 *>(smem);
-#ifdef PSS_EXP_FUSE_LDS
-    constexpr size_t EXS = PSS_EXP_FUSE_LDS / FPW / sizeof(double2);
-    double2 *tw2 = ex_all;
-#else
-    constexpr size_t EXS = C::EX;
     double2 *tw2 = ex_all + (size_t)FPW * C::EX;
-#endif
-#ifdef PSS_EXP_POST_PRIO    // timing experiment: this kernel's user priority beside the backward pass (reset at the end)
-    __builtin_amdgcn_s_setprio(PSS_EXP_POST_PRIO);
-#endif
     const int tid = threadIdx.x;
     const int fl = __builtin_amdgcn_readfirstlane(tid / T);   // frame slot = wavefront of the workgroup
     const int t = tid % T;
-    double2 *ex = ex_all + (size_t)fl * EXS;
+    double2 *ex = ex_all + (size_t)fl * C::EX;
     double *stage = reinterpret_cast<double *>(ex);
     double2 tw1[16];
     double w[16];
@@ -56,12 +45,10 @@ __global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const
     for (int k2 = 1; k2 < 16; k2++) tw1[k2] = tw[(size_t)t * k2];
 #pragma unroll
     for (int n2 = 0; n2 < 16; n2++) w[n2] = win[t + T * n2];
-#ifndef PSS_EXP_FUSE_LDS
     if (tid < R3 * 16) {
         const int m1 = tid / 16, j2 = tid % 16;
         tw2[C::tw2_slot(tid)] = tw[(size_t)(m1 * j2) * 16];
     }
-#endif
     __syncthreads();
     const long groups = (n_frames + FPW - 1) / FPW;
     float2 nx[16];
@@ -78,11 +65,7 @@ __global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const
         const bool valid = f < n_frames;                      // wave-uniform
         double2 v[16];
 #pragma unroll
-#ifdef PSS_EXP_FUSE_NOFFT
-        for (int n2 = 0; n2 < 16; n2++) v[n2] = make_double2((double)nx[n2].x, (double)nx[n2].y);
-#else
         for (int n2 = 0; n2 < 16; n2++) v[n2] = make_double2((double)nx[n2].x * w[n2], (double)nx[n2].y * w[n2]);
-#endif
         if (g + gridDim.x < groups) fetch(g + gridDim.x);
         // row stores through buffer resources over the workgroup's FPW rows (frames past the end fall outside and are dropped): unconditional
         // in the instruction stream, see k_spectrum_r16
@@ -99,12 +82,7 @@ __global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const
             if constexpr (ROW32) buf_store_f32(ro32, lane_el * 4, e0 * 4, (float)d64);
             dbv[i] = d64;
         };
-#ifdef PSS_EXP_FUSE_NOFFT   // timing experiment (results wrong): no transform, the dB values are the windowed samples
-#pragma unroll
-        for (int i = 0; i < 16; i++) emit(i, 256 * (i % R3) + t + T * (i / R3), v[i]);
-#else
         r16_core<2, true>(v, ex, tw1, tw2, t, emit);
-#endif
         frame_sync<true>();                                    // every lane has read its stage-3 operands: the exchange buffer is free
         // the row into k_post_sel's staging layout: element e (after fftshift) at stage[(e / EPL) * S + e % EPL]
 #pragma unroll
@@ -114,19 +92,14 @@ __global__ __launch_bounds__(256, PSS_EXP_FUSE_WAVES) void k_spectrum_post(const
             stage[(e / EPL) * PC::S + (e % EPL)] = dbv[i];
         }
         frame_sync<true>();
-#ifndef PSS_EXP_FUSE_NOPOST  // timing experiment (results wrong): no post-process
         if (valid) {
             int slot[PC::Q];
 #pragma unroll
             for (int j = 0; j < PC::Q; j++) slot[j] = 0;       // (only used for materialised post-processed rows: none here)
             pss_post::post_row_staged<EPL, 1, true, double>(stage, slot, t, N - 4, nullptr, fl, t, phase, nullptr, row_lo, row_hi, f, nullptr, vals, disp_w);
         }
-#endif
         frame_sync<true>();                                    // the next frame's stage 1 overwrites the buffer
     }
-#ifdef PSS_EXP_POST_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 }  // namespace pss_sp

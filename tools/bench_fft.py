@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel time of pss_spectrum_db per frame length (HIP events on the library's stream); options as key=value.
-    python tools/bench_fft.py 16384 8192 [fft_big_scratch=1]"""
+    python tools/bench_fft.py 16384 8192 [db_exact=1]"""
 import os
 import sys
 

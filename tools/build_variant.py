@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Build a second copy of libpss.so with extra compiler flags (kernel experiments), next to the product library:
 
-    python tools/build_variant.py nohead -DPSS_EXP_NOHEAD        ->  pyspecsdr_amd/libpss_nohead.so
-    PSS_LIBRARY=pyspecsdr_amd/libpss_nohead.so python tools/bench_alone.py
+    python tools/build_variant.py exp -DSOME_MACRO        ->  pyspecsdr_amd/libpss_exp.so
+    PSS_LIBRARY=pyspecsdr_amd/libpss_exp.so python tools/bench_alone.py
 
 The product build (pyspecsdr_amd/build.py) is not touched; variant objects live in pyspecsdr_amd/_build/<name>/."""
 import os
