@@ -266,6 +266,52 @@ int pss_frame_pipeline_cells(pss_ctx *ctx, int mode, const float *d_iq, long n_f
 int pss_spectrum_cells(pss_ctx *ctx, const float *d_iq, long n_frames, int n, float *d_db32, double *d_db64, double *d_row_lo,
                        double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_line_a, int8_t *d_line_b);
 
+/* Squelch and the header's Peak / Avg meter.  The reference does not demodulate every read buffer: its loop gates the audio,
+ *     if PEAK_POWER >= SQUELCH: audio = demodulate_signal(...); audio_buffer.append(audio)          (pyspecsdr.py:2261-2263)
+ * where draw_header sets PEAK_POWER = np.max(freq_data) of the post-processed row and prints np.mean(freq_data) beside it ("Peak: x dB
+ * Avg: y dB", :388-392).  draw_header runs on every third iteration only (ui_update_counter, :2288-2291); PEAK_POWER starts at 0 and
+ * SQUELCH at -60 (:171-172).  Frames 0 .. n_frames-1 of a batch are successive iterations (VFO mode), with a counter that stands at
+ * `phase` before frame 0:
+ *     open[i]  = held >= squelch, `held` being the value BEFORE iteration i (a NaN compares false: closed; +inf opens);
+ *     then the counter is incremented and, if counter % every == 0, frame i is METERED: held = np.max(row_i).
+ * every = 3 in the reference; every = 0: never metered (its MR mode draws no header), phase must then be 0.  A batch cut into several
+ * calls carries (held_out, (phase + n_frames) % every) from one call into the next.
+ *
+ *   pss_row_meter_f64   float64 rows [n_rows][len], len >= 1 -> d_peak [n_rows] = np.max (a NaN in the row gives NaN; otherwise NumPy's
+ *                       bits, except that a maximum of zero may carry either sign) and d_avg [n_rows] = np.mean on every bit (NumPy's
+ *                       pairwise tree in 8192-element chunks added in order, / len).  Either output may be NULL, not both.  One pass
+ *                       over the rows; rows of up to 2048 values one wavefront each, longer rows one workgroup.
+ *   pss_squelch_gate    d_peak [n_frames] -> d_open uint8 [n_frames] (nullable), d_open_idx int32 [n_frames] (nullable): the open
+ *                       frames' indices in ascending order, *n_open their number, *held_out the carry.  THIS CALL WAITS: the count has
+ *                       to reach the host to size the demodulator's launches — one asynchronous 16-byte copy (count, carry) into pinned
+ *                       memory and one synchronisation of the context's stream.  It cannot be captured into a graph.
+ *   pss_h_squelch_gate  the same on host arrays, pure C, no context and no GPU (open nullable).
+ *   pss_demod_gated     pss_demod_signal (dispatcher semantics: WFM frames IQ-corrected) on the n_open frames d_open_idx names, the
+ *                       results written COMPACTED in frame order — d_pcm int16 [n_open][n_out][2], d_audio as pss_demod_signal's with
+ *                       n_open rows: the concatenation the reference appends to audio_buffer.  Stream-ordered, no host wait: n_open
+ *                       and the list as pss_squelch_gate left them, or any ascending list of the caller's (PSS_E_ARG for n_open
+ *                       outside [0, n_frames]; indices outside the batch are clamped into it).  n_open = n_frames: the demodulator
+ *                       reads d_iq itself, nothing is copied; n_open = 0: nothing is launched, the outputs stay untouched; otherwise
+ *                       the open frames are gathered into context scratch (never more than the batch) in front of the demodulator
+ *                       (16 bytes per lane; d_iq aligned to one sample, 8 bytes: PSS_E_ARG otherwise).
+ *   pss_frame_pipeline_squelch   pss_frame_pipeline_cells' arguments and display results (d_db32, d_db64, extremes, lines: the same
+ *                       kernels), then d_peak / d_avg [n_frames] of every frame's post-processed row, the gate (d_open, *n_open,
+ *                       *held_out) and d_pcm [n_open][n_out][2] of the open frames.  The post-processed float64 rows are materialised
+ *                       in context scratch for the meter (one HBM round trip more than pss_frame_pipeline_cells, and the demodulator
+ *                       starts behind the display half instead of beside it).  Contains the gate, hence its wait: not capturable.
+ * PSS_E_ARG: every < 0, phase outside [0, every) (every = 0: phase != 0), null buffers, len < 1, n_frames >= 2^31. */
+int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, double *d_peak, double *d_avg);
+int pss_squelch_gate(pss_ctx *ctx, const double *d_peak, long n_frames, double squelch, int every, int phase, double held_in, uint8_t *d_open,
+                     int32_t *d_open_idx, long *n_open, double *held_out);
+int pss_h_squelch_gate(const double *peak, long n_frames, double squelch, int every, int phase, double held_in, uint8_t *open, long *n_open,
+                       double *held_out);
+int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, const int32_t *d_open_idx, long n_open,
+                    int16_t *d_pcm, double *d_audio);
+int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                               double *d_row_lo, double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
+                               int8_t *d_line_a, int8_t *d_line_b, int16_t *d_pcm, double squelch, int every, int phase, double held_in,
+                               double *d_peak, double *d_avg, uint8_t *d_open, long *n_open, double *held_out);
+
 /* complex128 read buffers.  The reference's SDR buffer is complex64 (pyspecsdr.py:1887), but its functions accept any array, and handed
  * complex128 they compute in float64 from the first statement on.  These entry points serve compute_fft (signal_processing.py:243-264: the
  * window product is float64 x float64) and demodulate_am (:179-195: np.abs / np.mean / the subtraction in float64 — the same scaled hypot and

@@ -78,6 +78,12 @@ _SIGS = {
     "pss_h_mean_power_c128": (C.c_int, [_p, _p, C.c_int, _p]),
     "pss_frame_pipeline_cells": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
     "pss_spectrum_cells": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "pss_row_meter_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p]),
+    "pss_squelch_gate": (C.c_int, [_p, _p, C.c_long, C.c_double, C.c_int, C.c_int, C.c_double, _p, _p, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
+    "pss_h_squelch_gate": (C.c_int, [_p, C.c_long, C.c_double, C.c_int, C.c_int, C.c_double, _p, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
+    "pss_demod_gated": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, C.c_long, _p, _p]),
+    "pss_frame_pipeline_squelch": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p,
+                                             C.c_double, C.c_int, C.c_int, C.c_double, _p, _p, _p, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
     "pss_spectrum_db_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),
     "pss_spectrum_post_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, _p]),
     "pss_h_np_f64": (C.c_int, [C.c_int, _p, C.c_long, _p]),

@@ -24,6 +24,7 @@ UNITS = [
     # LLVM's default of 300 users instcombine no longer forwards the reads to the kernarg segment and the whole table is copied to
     # scratch at kernel entry (measured: 412 spilled VGPRs in k_nfm_fwd instead of 3)
     ("pss_demod.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-instcombine-max-copied-from-constant-users=4000"]),
+    ("pss_squelch.hip", ["-ffp-contract=off"]),   # NumPy's summation tree and np.max, bit for bit: no fused multiply-adds either
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("pss_decode.cpp", ["-x", "hip", "-ffp-contract=off"]),   # host only: the decoders' per-message halves

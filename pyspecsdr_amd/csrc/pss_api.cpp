@@ -160,6 +160,8 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->scratch_post) hipFree(ctx->scratch_post);
     if (ctx->prog) hipFree(ctx->prog);
     if (ctx->stage) hipFree(ctx->stage);
+    for (auto &b : ctx->sq_buf) if (b) hipFree(b);
+    if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

@@ -106,6 +106,11 @@ struct pss_ctx {
     bool no_fused = false;  // PSS_NO_FUSED=1: use the three-kernel NFM path (A/B and fallback testing)
     void *comm = nullptr;          // pss_comm_init: the RCCL communicator (ncclComm_t) of this context's rank; collectives run on the context's stream
     int comm_rank = 0, comm_n = 1;
+    // squelch path (pss_squelch.hip), grow-only: [0] the gate's tile counts and result, [1] the open frames gathered for the demodulator,
+    // [2] pss_frame_pipeline_squelch's float64 rows and index list; sq_pin: 16 pinned bytes the gate's count and carry-out land in
+    void *sq_buf[3] = {};
+    size_t sq_cap[3] = {};
+    void *sq_pin = nullptr;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;

@@ -1,0 +1,276 @@
+// pss_squelch.h — device code of the squelch path (pss_squelch.hip): the header's Peak / Avg meter over float64 rows, the squelch gate
+// over the rows' peaks, and the gather of the open frames in front of the demodulator.
+//
+// Reference: draw_header sets PEAK_POWER = np.max(freq_data) and prints np.mean(freq_data) beside it (pyspecsdr.py:388-392), on every
+// third loop iteration (:2288-2291); the loop demodulates a read buffer only if PEAK_POWER >= SQUELCH (:2261-2263); PEAK_POWER starts at
+// 0, SQUELCH at -60 (:171-172).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+namespace pss_sq {
+
+// ---- row meter ------------------------------------------------------------------------------------------------------------------------
+// np.mean of a float64 row is add.reduce / len, and add.reduce is NumPy's pairwise sum over buffer chunks of 8192 elements added up in
+// order.  Inside a chunk: a block of more than 128 elements is split at n / 2 rounded down to a multiple of 8 and the halves are added;
+// a block of 8 .. 128 elements runs 8 strided accumulators r[j] += x[i + j], folds them as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and adds the
+// last len % 8 elements one by one; fewer than 8 elements are added one by one from 0.  Every addition is therefore fixed; what is free
+// is WHO performs it.  Here 8 lanes share a leaf block, lane j holding accumulator j (a wave reads 8 segments of 64 contiguous bytes per
+// load instruction), the fold is three xor shuffles, the leaf sums go to LDS and the tree above them is added level by level.
+// The tree of one chunk length is the same for every row, so the host walks it once per call (MeterPlan, passed by value).
+constexpr int CHUNK = 8192;     // NumPy's reduction buffer, in elements
+constexpr int LEAF = 128;       // PW_BLOCKSIZE
+constexpr int MAX_LEAVES = 128; // a chunk of <= 8192 elements has at most 128 leaf blocks (depth <= 7, no leaf below depth-6 blocks of > 128)
+
+struct MeterPlan {
+    uint16_t leaf_off[MAX_LEAVES];   // leaf blocks in element order: offset inside the chunk, length (1 .. 128)
+    uint8_t leaf_len[MAX_LEAVES];
+    uint8_t node_l[MAX_LEAVES];      // inner node k (value slot n_leaves + k) = slot node_l[k] + slot node_r[k]; sorted by height
+    uint8_t node_r[MAX_LEAVES];
+    uint8_t level_start[12];         // inner nodes of height h + 1: [level_start[h], level_start[h + 1])
+    int n_leaves, n_levels, root;    // root: value slot of the chunk's sum
+};
+struct MeterPlans {
+    MeterPlan full;   // a chunk of 8192 elements (rows longer than 8192)
+    MeterPlan tail;   // the last, shorter chunk — or the whole row when len <= 8192
+    int n_full;       // chunks that use `full`
+    int n_chunks;
+};
+
+// host side: the pairwise tree of one chunk of n <= 8192 elements
+inline void build_plan(int n, MeterPlan &p)
+{
+    struct Inner { int l, r, h; };
+    std::vector<Inner> inner;
+    int n_leaves = 0;
+    constexpr int INNER0 = 1000;   // temporary ids: leaves 0 .., inner nodes INNER0 ..
+    struct Walk {
+        std::vector<Inner> &inner;
+        MeterPlan &p;
+        int &n_leaves;
+        int go(int off, int len, int &h)
+        {
+            if (len <= LEAF) {
+                p.leaf_off[n_leaves] = (uint16_t)off;
+                p.leaf_len[n_leaves] = (uint8_t)len;
+                h = 0;
+                return n_leaves++;
+            }
+            int n2 = len / 2;
+            n2 -= n2 % 8;
+            int hl, hr;
+            const int l = go(off, n2, hl), r = go(off + n2, len - n2, hr);
+            h = std::max(hl, hr) + 1;
+            inner.push_back({l, r, h});
+            return INNER0 + (int)inner.size() - 1;
+        }
+    } walk{inner, p, n_leaves};
+    p = MeterPlan{};
+    int h_root = 0;
+    const int root = walk.go(0, n, h_root);
+    std::vector<int> order(inner.size()), pos(inner.size());
+    for (size_t k = 0; k < order.size(); k++) order[k] = (int)k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return inner[a].h < inner[b].h; });
+    for (size_t k = 0; k < order.size(); k++) pos[order[k]] = (int)k;
+    auto slot = [&](int id) { return id < INNER0 ? id : n_leaves + pos[id - INNER0]; };
+    for (size_t k = 0; k < order.size(); k++) {
+        p.node_l[k] = (uint8_t)slot(inner[order[k]].l);
+        p.node_r[k] = (uint8_t)slot(inner[order[k]].r);
+    }
+    for (int h = 1, k = 0; h <= h_root; h++) {
+        p.level_start[h - 1] = (uint8_t)k;
+        while (k < (int)order.size() && inner[order[k]].h == h) k++;
+        p.level_start[h] = (uint8_t)k;
+    }
+    p.n_leaves = n_leaves;
+    p.n_levels = h_root;
+    p.root = slot(root);
+}
+
+__device__ __forceinline__ double nan_max(double a, double b)   // np.max's step: a NaN wins
+{
+    return (b > a || b != b) ? b : a;
+}
+
+// G lanes per row: 64 (one wavefront per row, four rows per workgroup) or 256 (one workgroup per row)
+template <int G>
+__global__ __launch_bounds__(256) void k_row_meter(const double *__restrict__ rows, long n_rows, int len, const MeterPlans plans,
+                                                   double *__restrict__ peak, double *__restrict__ avg)
+{
+    constexpr int RPW = 256 / G, SLOTS = G / 8;
+    constexpr int PLAN_WORDS = (int)(sizeof(MeterPlan) / 4);
+    static_assert(sizeof(MeterPlan) % 4 == 0, "copied word by word");
+    __shared__ int pl_words[2][PLAN_WORDS];
+    __shared__ double val[RPW][2 * MAX_LEAVES];
+    __shared__ double red[256];
+    {
+        const int *src = reinterpret_cast<const int *>(&plans);   // `full` then `tail`, contiguous
+        for (int i = threadIdx.x; i < 2 * PLAN_WORDS; i += 256) (&pl_words[0][0])[i] = src[i];
+    }
+    __syncthreads();
+    const int slot = threadIdx.x / G, t = threadIdx.x % G, j = t & 7, ls = t >> 3;
+    for (long base = (long)blockIdx.x * RPW; base < n_rows; base += (long)gridDim.x * RPW) {
+        const long row = base + slot;
+        const bool live = row < n_rows;
+        const double *x = rows + (size_t)(live ? row : 0) * len;
+        double m = -__builtin_inf(), acc = 0.0;
+        for (int c = 0; c < plans.n_chunks; c++) {
+            const MeterPlan &p = *reinterpret_cast<const MeterPlan *>(pl_words[c < plans.n_full ? 0 : 1]);
+            const double *xc = x + (size_t)c * CHUNK;
+            for (int l0 = 0; l0 < p.n_leaves; l0 += SLOTS) {
+                const int l = l0 + ls;
+                const bool has = live && l < p.n_leaves;
+                const int ll = has ? p.leaf_len[l] : 0;
+                const double *xl = xc + (has ? p.leaf_off[l] : 0);
+                const int n8 = ll - (ll & 7);
+                double v[LEAF / 8];
+#pragma unroll
+                for (int k = 0; k < LEAF / 8; k++) v[k] = 8 * k < n8 ? xl[8 * k + j] : 0.0;
+                double r = v[0];
+                if (n8 > 0) m = nan_max(m, r);
+#pragma unroll
+                for (int k = 1; k < LEAF / 8; k++)
+                    if (8 * k < n8) {
+                        r = __dadd_rn(r, v[k]);
+                        m = nan_max(m, v[k]);
+                    }
+                r = __dadd_rn(r, __shfl_xor(r, 1));
+                r = __dadd_rn(r, __shfl_xor(r, 2));
+                r = __dadd_rn(r, __shfl_xor(r, 4));
+                if (n8 == 0) r = 0.0;
+                for (int i = n8; i < ll; i++) {   // the last len % 8 elements (or all of a block shorter than 8), one by one
+                    const double e = xl[i];
+                    r = __dadd_rn(r, e);
+                    m = nan_max(m, e);
+                }
+                if (has && j == 0) val[slot][l] = r;
+            }
+            __syncthreads();
+            for (int lv = 0; lv < p.n_levels; lv++) {
+                for (int k = p.level_start[lv] + t; k < p.level_start[lv + 1]; k += G)
+                    val[slot][p.n_leaves + k] = __dadd_rn(val[slot][p.node_l[k]], val[slot][p.node_r[k]]);
+                __syncthreads();
+            }
+            if (t == 0) acc = c == 0 ? val[slot][p.root] : __dadd_rn(acc, val[slot][p.root]);
+            __syncthreads();
+        }
+        red[threadIdx.x] = m;
+        __syncthreads();
+        for (int st = G / 2; st > 0; st >>= 1) {
+            if (t < st) red[threadIdx.x] = nan_max(red[threadIdx.x], red[threadIdx.x + st]);
+            __syncthreads();
+        }
+        if (t == 0 && live) {
+            if (peak) peak[row] = red[threadIdx.x];
+            if (avg) avg[row] = __ddiv_rn(acc, (double)len);
+        }
+        __syncthreads();
+    }
+}
+
+// ---- gate -----------------------------------------------------------------------------------------------------------------------------
+// Frame i of a batch is loop iteration i; the counter (ui_update_counter modulo `every`) stands at `phase` before frame 0.  A frame is
+// metered if the incremented counter is a multiple of `every`, i.e. frame j with (phase + j + 1) % every == 0, and the value the gate of
+// frame i compares is the peak of the last metered frame before i, or held_in if there is none: no serial scan.
+__device__ __forceinline__ double gate_held(const double *__restrict__ peak, long i, long phase, int every, double held_in)
+{
+    if (every <= 0) return held_in;
+    const long j = i - (phase + i) % every - 1;
+    return j >= 0 ? peak[j] : held_in;
+}
+
+constexpr int GATE_TILE = 256;   // frames per workgroup pass
+
+struct GateResult {   // what pss_squelch_gate hands to the host
+    long n_open;
+    double held_out;
+};
+
+// flags of every frame (d_open, nullable) and the number of open frames per tile of 256
+__global__ __launch_bounds__(256) void k_gate_flags(const double *__restrict__ peak, long n_frames, double squelch, int every, long phase, double held_in,
+                                                    uint8_t *__restrict__ d_open, int *__restrict__ tile_count, long n_tiles)
+{
+    __shared__ int wcount[4];
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool open = i < n_frames && gate_held(peak, i, phase, every, held_in) >= squelch;   // a NaN compares false: closed
+        if (i < n_frames && d_open) d_open[i] = open ? 1 : 0;
+        const unsigned long long b = __ballot(open);
+        if ((threadIdx.x & 63) == 0) wcount[threadIdx.x >> 6] = __popcll(b);
+        __syncthreads();
+        if (threadIdx.x == 0) tile_count[tile] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+    }
+}
+
+// exclusive prefix sum of the tile counts in place (one workgroup, 256 tiles per step with a carry), the total and the carry-out
+__global__ __launch_bounds__(256) void k_gate_scan(int *__restrict__ tile_count, long n_tiles, const double *__restrict__ peak, long n_frames, int every,
+                                                   long phase, double held_in, GateResult *__restrict__ res)
+{
+    __shared__ int s[256];
+    __shared__ long carry_s;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (long b0 = 0; b0 < n_tiles; b0 += 256) {
+        const long k = b0 + threadIdx.x;
+        const int mine = k < n_tiles ? tile_count[k] : 0;
+        s[threadIdx.x] = mine;
+        __syncthreads();
+        for (int d = 1; d < 256; d <<= 1) {
+            const int add = (int)threadIdx.x >= d ? s[threadIdx.x - d] : 0;
+            __syncthreads();
+            s[threadIdx.x] += add;
+            __syncthreads();
+        }
+        const long carry = carry_s;
+        if (k < n_tiles) tile_count[k] = (int)(carry + s[threadIdx.x] - mine);
+        __syncthreads();
+        if (threadIdx.x == 255) carry_s = carry + s[255];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        res->n_open = carry_s;
+        res->held_out = gate_held(peak, n_frames, phase, every, held_in);
+    }
+}
+
+// the ascending list of open frames: tile offset + the wavefronts in front + the open lanes below (ballot and popcount); no atomics
+__global__ __launch_bounds__(256) void k_gate_index(const double *__restrict__ peak, long n_frames, double squelch, int every, long phase, double held_in,
+                                                    const int *__restrict__ tile_off, long n_tiles, int *__restrict__ d_open_idx)
+{
+    __shared__ int wcount[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool open = i < n_frames && gate_held(peak, i, phase, every, held_in) >= squelch;
+        const unsigned long long b = __ballot(open);
+        if (lane == 0) wcount[w] = __popcll(b);
+        __syncthreads();
+        int before = 0;
+        for (int q = 0; q < w; q++) before += wcount[q];
+        if (open) d_open_idx[(long)tile_off[tile] + before + __popcll(b & ((1ull << lane) - 1ull))] = (int)i;
+        __syncthreads();
+    }
+}
+
+// ---- gather of the open frames ---------------------------------------------------------------------------------------------------------
+// dst[k] = src[idx[k]] for frames of `per_frame` elements of V (uint4: 16 bytes per lane; uint2 for an odd frame length or a batch that
+// starts 8 bytes off a 16-byte boundary).  An index outside [0, n_frames) is clamped:
+// a caller's own list cannot make the copy read outside the batch.
+template <class V>
+__global__ __launch_bounds__(256) void k_gather_frames(const V *__restrict__ src, const int *__restrict__ idx, long n_open, long n_frames, long per_frame,
+                                                       V *__restrict__ dst)
+{
+    for (long k = blockIdx.x; k < n_open; k += gridDim.x) {
+        long f = idx[k];
+        f = f < 0 ? 0 : (f >= n_frames ? n_frames - 1 : f);
+        const V *s = src + (size_t)f * per_frame;
+        V *d = dst + (size_t)k * per_frame;
+        for (long i = threadIdx.x; i < per_frame; i += 256) d[i] = s[i];
+    }
+}
+
+}  // namespace pss_sq

@@ -1,0 +1,188 @@
+// pss_squelch.hip — squelch and the header's Peak / Avg meter for batches of read buffers (include/pss.h, "squelch"): the row meter,
+// the gate with its host twin, the demodulator on the open frames only, and the one-call step built from them.  Everything here sits
+// BEHIND the existing entry points (pss_spectrum_cells, pss_spectrum_post_f64, pss_demod_signal): none of their kernels or schedules
+// changes.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "pss_ctx.h"
+#include "pss_squelch.h"
+
+namespace {
+using namespace pss_sq;
+
+constexpr int METER_WAVE_MAX_LEN = 2048;   // rows up to this length: one wavefront per row; longer rows: one workgroup per row
+
+int sq_buffer(pss_ctx *ctx, int which, size_t bytes, const char *what, void **out)
+{
+    const int r = pss_ensure_buffer(ctx, &ctx->sq_buf[which], &ctx->sq_cap[which], bytes, what);
+    *out = ctx->sq_buf[which];
+    return r;
+}
+
+bool gate_args_ok(long n_frames, int every, int phase)
+{
+    return n_frames >= 0 && n_frames <= INT32_MAX && every >= 0 && phase >= 0 && (every == 0 ? phase == 0 : phase < every);
+}
+}  // namespace
+
+extern "C" int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, double *d_peak, double *d_avg)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_rows < 0 || len < 1 || (!d_peak && !d_avg) || (n_rows > 0 && !d_rows)) return pss_fail(ctx, PSS_E_ARG, "pss_row_meter_f64: bad argument");
+    if (n_rows == 0) return PSS_OK;
+    MeterPlans pl{};
+    pl.n_full = len > CHUNK ? len / CHUNK : 0;
+    const int rem = len - pl.n_full * CHUNK;
+    pl.n_chunks = pl.n_full + (rem > 0 ? 1 : 0);
+    if (pl.n_full) build_plan(CHUNK, pl.full);
+    if (rem > 0) build_plan(rem, pl.tail);
+    pss_time_begin(ctx);
+    pss_kernel_begin(ctx, "k_row_meter");
+    if (len <= METER_WAVE_MAX_LEN) {
+        const long groups = (n_rows + 3) / 4;
+        hipLaunchKernelGGL(k_row_meter<64>, dim3((unsigned)(groups < 8192 ? groups : 8192)), dim3(256), 0, PSS_STREAM(ctx), d_rows, n_rows, len, pl, d_peak, d_avg);
+    } else {
+        hipLaunchKernelGGL(k_row_meter<256>, dim3((unsigned)(n_rows < 4096 ? n_rows : 4096)), dim3(256), 0, PSS_STREAM(ctx), d_rows, n_rows, len, pl, d_peak, d_avg);
+    }
+    pss_kernel_end(ctx);
+    pss_time_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_row_meter launch");
+}
+
+// The loop's gate as the loop runs it (pyspecsdr.py:2261, :2288-2291), one frame after the other: pure host code, no context.
+extern "C" int pss_h_squelch_gate(const double *peak, long n_frames, double squelch, int every, int phase, double held_in, uint8_t *open, long *n_open,
+                                  double *held_out)
+{
+    if (!gate_args_ok(n_frames, every, phase) || (n_frames > 0 && !peak)) return PSS_E_ARG;
+    double held = held_in;
+    long count = 0, counter = phase;
+    for (long i = 0; i < n_frames; i++) {
+        const bool o = held >= squelch;
+        if (open) open[i] = o ? 1 : 0;
+        count += o;
+        counter++;
+        if (every > 0 && counter % every == 0) held = peak[i];
+    }
+    if (n_open) *n_open = count;
+    if (held_out) *held_out = held;
+    return PSS_OK;
+}
+
+extern "C" int pss_squelch_gate(pss_ctx *ctx, const double *d_peak, long n_frames, double squelch, int every, int phase, double held_in, uint8_t *d_open,
+                                int32_t *d_open_idx, long *n_open, double *held_out)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (!gate_args_ok(n_frames, every, phase) || (n_frames > 0 && !d_peak))
+        return pss_fail(ctx, PSS_E_ARG, "pss_squelch_gate: every < 0, phase outside [0, every), a frame count outside [0, 2^31) or a null peak array");
+    if (n_frames == 0) {
+        if (n_open) *n_open = 0;
+        if (held_out) *held_out = held_in;
+        return PSS_OK;
+    }
+    const long n_tiles = (n_frames + GATE_TILE - 1) / GATE_TILE;
+    void *buf;
+    int r = sq_buffer(ctx, 0, sizeof(GateResult) + (size_t)n_tiles * sizeof(int), "gate scratch", &buf);
+    if (r) return r;
+    if (!ctx->sq_pin) PSS_HIP(ctx, hipHostMalloc(&ctx->sq_pin, sizeof(GateResult), hipHostMallocDefault));
+    GateResult *d_res = reinterpret_cast<GateResult *>(buf);
+    int *tiles = reinterpret_cast<int *>(d_res + 1);
+    const dim3 grid((unsigned)(n_tiles < 4096 ? n_tiles : 4096));
+    pss_time_begin(ctx);
+    pss_kernel_begin(ctx, "k_gate_flags");
+    hipLaunchKernelGGL(k_gate_flags, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, d_open, tiles, n_tiles);
+    pss_kernel_end(ctx);
+    pss_kernel_begin(ctx, "k_gate_scan");
+    hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(256), 0, PSS_STREAM(ctx), tiles, n_tiles, d_peak, n_frames, every, (long)phase, held_in, d_res);
+    pss_kernel_end(ctx);
+    if (d_open_idx) {
+        pss_kernel_begin(ctx, "k_gate_index");
+        hipLaunchKernelGGL(k_gate_index, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, tiles, n_tiles, d_open_idx);
+        pss_kernel_end(ctx);
+    }
+    pss_time_end(ctx);
+    r = pss_hip_check(ctx, hipGetLastError(), "squelch gate launch");
+    if (r) return r;
+    // the one place where the count reaches the host: 16 bytes into pinned memory, one stream synchronisation
+    PSS_HIP(ctx, hipMemcpyAsync(ctx->sq_pin, d_res, sizeof(GateResult), hipMemcpyDeviceToHost, PSS_STREAM(ctx)));
+    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));
+    const GateResult *h = reinterpret_cast<const GateResult *>(ctx->sq_pin);
+    if (n_open) *n_open = h->n_open;
+    if (held_out) *held_out = h->held_out;
+    return PSS_OK;
+}
+
+extern "C" int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, const int32_t *d_open_idx, long n_open,
+                               int16_t *d_pcm, double *d_audio)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
+    if (n_frames < 0 || n < 1 || n_open < 0 || n_open > n_frames) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: n_open outside [0, n_frames] or a bad size");
+    if (n_open == 0) return PSS_OK;                 // squelch closed on every frame: nothing is launched, the outputs stay as they are
+    if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: null IQ buffer");
+    if (n_open == n_frames) return pss_demod_signal(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);   // an ascending list of all frames: no copy
+    if (!d_open_idx) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: null index list");
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_iq);
+    if (a % 8) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: d_iq is not aligned to one complex64 sample (8 bytes)");
+    void *gathered;
+    int r = sq_buffer(ctx, 1, (size_t)n_open * n * 2 * sizeof(float), "open frames", &gathered);
+    if (r) return r;
+    pss_time_begin(ctx);
+    const dim3 grid((unsigned)(n_open < 2048 ? n_open : 2048));
+    pss_kernel_begin(ctx, "k_gather_frames");
+    if (n % 2 == 0 && a % 16 == 0)
+        hipLaunchKernelGGL(k_gather_frames<uint4>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint4 *>(d_iq), d_open_idx, n_open, n_frames,
+                           (long)n / 2, reinterpret_cast<uint4 *>(gathered));
+    else
+        hipLaunchKernelGGL(k_gather_frames<uint2>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint2 *>(d_iq), d_open_idx, n_open, n_frames,
+                           (long)n, reinterpret_cast<uint2 *>(gathered));
+    pss_kernel_end(ctx);
+    r = pss_hip_check(ctx, hipGetLastError(), "k_gather_frames launch");
+    if (!r) r = pss_demod_signal(ctx, mode, reinterpret_cast<const float *>(gathered), n_open, n, fs, d_pcm, d_audio);
+    pss_time_end(ctx);
+    return r;
+}
+
+// One loop iteration per read buffer WITH the squelch: the display half of pss_frame_pipeline_cells (pss_spectrum_cells: the same kernels), the
+// post-processed float64 rows materialised in context scratch, meter -> gate -> demodulator on the open frames.  The gate waits for the count.
+extern "C" int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                                          double *d_row_lo, double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_line_a,
+                                          int8_t *d_line_b, int16_t *d_pcm, double squelch, int every, int phase, double held_in, double *d_peak,
+                                          double *d_avg, uint8_t *d_open, long *n_open, double *held_out)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
+    if (!gate_args_ok(n_frames, every, phase)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: every < 0 or phase outside [0, every)");
+    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: n must be a power of two in [16, 65536]");
+    if (n_frames > 0 && (!d_db32 || !d_peak || !d_pcm)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: null buffer");
+    if (n_frames == 0) {
+        const int r0 = pss_spectrum_cells(ctx, d_iq, 0, n, d_db32, d_db64, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a, d_line_b);
+        if (r0) return r0;
+        if (n_open) *n_open = 0;
+        if (held_out) *held_out = held_in;
+        return PSS_OK;
+    }
+    const size_t row_bytes = (size_t)n_frames * n * sizeof(double), post_bytes = (size_t)n_frames * (n - 4) * sizeof(double);
+    void *buf;
+    int r = sq_buffer(ctx, 2, (d_db64 ? 0 : row_bytes) + post_bytes + (size_t)n_frames * sizeof(int32_t), "squelch rows", &buf);
+    if (r) return r;
+    char *b = reinterpret_cast<char *>(buf);
+    double *db64 = d_db64 ? d_db64 : reinterpret_cast<double *>(b);
+    double *post = reinterpret_cast<double *>(b + (d_db64 ? 0 : row_bytes));
+    int32_t *open_idx = reinterpret_cast<int32_t *>(b + (d_db64 ? 0 : row_bytes) + post_bytes);
+    pss_time_begin(ctx);
+    r = pss_spectrum_cells(ctx, d_iq, n_frames, n, d_db32, db64, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a, d_line_b);
+    if (!r) r = pss_spectrum_post_f64(ctx, db64, n_frames, n, post, nullptr, nullptr);
+    if (!r) r = pss_row_meter_f64(ctx, post, n_frames, n - 4, d_peak, d_avg);
+    long count = 0;
+    if (!r) r = pss_squelch_gate(ctx, d_peak, n_frames, squelch, every, phase, held_in, d_open, open_idx, &count, held_out);
+    if (!r) r = pss_demod_gated(ctx, mode, d_iq, n_frames, n, fs, open_idx, count, d_pcm, nullptr);
+    pss_time_end(ctx);
+    if (!r && n_open) *n_open = count;
+    return r;
+}

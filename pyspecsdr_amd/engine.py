@@ -29,6 +29,19 @@ def _ptr(x):
     return int(x)
 
 
+def h_squelch_gate(peak, squelch, every=3, phase=0, held_in=0.0, lib=None):
+    """pss_h_squelch_gate: the reference loop's squelch gate (pyspecsdr.py:2261, :2288-2291) over a host array of per-frame peaks ->
+    (open uint8 [n_frames], n_open, held_out).  Pure host code: needs the library, not a GPU."""
+    lib = lib or L.load()
+    peak = np.ascontiguousarray(peak, np.float64)
+    opened = np.empty(len(peak), np.uint8)
+    n_open, held = C.c_long(), C.c_double()
+    r = lib.pss_h_squelch_gate(_ptr(peak), len(peak), float(squelch), int(every), int(phase), float(held_in), _ptr(opened), C.byref(n_open), C.byref(held))
+    if r != 0:
+        raise PssError(r, "pss_h_squelch_gate: every < 0 or phase outside [0, every)")
+    return opened, n_open.value, held.value
+
+
 class Engine:
     """order: how calls are ordered against the caller's own GPU work.
          "torch" (default when torch is loaded): the library keeps its own non-blocking stream — which the default stream does NOT
@@ -351,6 +364,37 @@ class Engine:
         window = (30, 10)[disp] if window is None else int(window)
         self._dev(self.lib.pss_spectrum_cells, _ptr(d_iq), n_frames, n, _ptr(d_db32), _ptr(d_db64), _ptr(d_row_lo), _ptr(d_row_hi), n_halo, window,
                   disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b))
+
+    # -- squelch and the header's Peak / Avg meter (pyspecsdr.py:2261-2263, :388-392, :2288-2291)
+    def row_meter(self, d_rows, n_rows, length, d_peak=None, d_avg=None):
+        """np.max (NaN-propagating) and np.mean (NumPy's summation tree, every bit) of float64 rows: what draw_header keeps as PEAK_POWER
+        and prints as Avg."""
+        self._dev(self.lib.pss_row_meter_f64, _ptr(d_rows), n_rows, length, _ptr(d_peak), _ptr(d_avg))
+
+    def squelch_gate(self, d_peak, n_frames, squelch, every=3, phase=0, held_in=0.0, d_open=None, d_open_idx=None):
+        """The loop's gate over a batch's peaks -> (n_open, held_out); d_open uint8 [n_frames], d_open_idx int32 [n_frames] (ascending).
+        Waits for the count (one stream synchronisation): the one call of the squelch path that does."""
+        n_open, held = C.c_long(), C.c_double()
+        self._dev(self.lib.pss_squelch_gate, _ptr(d_peak), n_frames, float(squelch), int(every), int(phase), float(held_in), _ptr(d_open),
+                  _ptr(d_open_idx), C.byref(n_open), C.byref(held))
+        return n_open.value, held.value
+
+    def demod_gated(self, mode, d_iq, n_frames, n, fs, d_open_idx, n_open, d_pcm=None, d_audio=None):
+        """demod_signal on the n_open frames d_open_idx names, results compacted in frame order ([n_open][n_out][2]); no host wait."""
+        self._dev(self.lib.pss_demod_gated, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_open_idx), int(n_open), _ptr(d_pcm), _ptr(d_audio))
+
+    def frame_pipeline_squelch(self, mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_row_lo, d_row_hi, disp_w, d_line_a, d_line_b, d_pcm, squelch,
+                               d_peak, d_avg=None, d_open=None, every=3, phase=0, held_in=0.0, n_halo=0, window=None, display="waterfall",
+                               disp_h=36):
+        """frame_pipeline_cells with the squelch: its display results, every frame's Peak / Avg, the gate, and d_pcm [n_open][n_out][2] of
+        the open frames only -> (n_open, held_out).  The next batch continues with held_in = held_out, phase = (phase + n_frames) % every."""
+        disp = {"waterfall": 0, "persistence": 1}[display]
+        window = (30, 10)[disp] if window is None else int(window)
+        n_open, held = C.c_long(), C.c_double()
+        self._dev(self.lib.pss_frame_pipeline_squelch, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_row_lo),
+                  _ptr(d_row_hi), n_halo, window, disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b), _ptr(d_pcm), float(squelch), int(every),
+                  int(phase), float(held_in), _ptr(d_peak), _ptr(d_avg), _ptr(d_open), C.byref(n_open), C.byref(held))
+        return n_open.value, held.value
 
     def spectrum_db_f64(self, d_iq, n_frames, n_fft, d_db):
         """compute_fft's float64 rows (n_fft: power of two in 16..65536)."""

@@ -49,14 +49,62 @@ def pipe_bytes(pcm):
     return np.ascontiguousarray(pcm, np.int16).tobytes()
 
 
-def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chunk_frames=4096):
+def header_strength_text(peak, avg):
+    """draw_header's signal strength indicator (pyspecsdr.py:391) for a row's np.max and np.mean."""
+    return f"Peak: {peak:.1f} dB Avg: {avg:.1f} dB"
+
+
+def _squelch_args(squelch, meter_every, peak_power, frame_len, mode):
+    """demodulate_recording's argument checks for the squelch path (host only: made before anything touches the GPU)."""
+    if mode not in _MODES:
+        raise ValueError(f"unknown demodulation mode {mode!r}")
+    squelch, peak_power = float(squelch), float(peak_power)
+    if int(meter_every) != meter_every or meter_every < 0:
+        raise ValueError("meter_every must be an integer >= 0 (0: the header is never drawn)")
+    if frame_len < 16 or frame_len > 65536 or frame_len & (frame_len - 1):
+        raise ValueError("squelch needs the cell-exact rows: frame_len must be a power of two in [16, 65536]")
+    return squelch, int(meter_every), peak_power
+
+
+def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chunk_frames=4096, squelch=None, meter_every=3, peak_power=0.0):
     """Every read buffer of a recording through demodulate_signal on the GPU -> int16 [n_frames][n_out][2], i.e. the
-    audio the reference would have written had it played the recording buffer by buffer."""
+    audio the reference would have written had it played the recording buffer by buffer.
+
+    squelch (a level in dB; None: no gate, the result above): the reference's loop buffers audio only while PEAK_POWER >= SQUELCH
+    (pyspecsdr.py:2261-2263), PEAK_POWER being the maximum of the post-processed row its header last showed — every meter_every-th
+    buffer (:2288-2291), starting from peak_power (:172).  Returns (pcm int16 [n_open][n_out][2] of the open buffers in order,
+    open uint8 [n_frames], peak float64 [n_frames], avg float64 [n_frames]): the gate and every buffer's Peak / Avg as
+    header_strength_text prints them; rows from the cell-exact pipeline (float64 compute_fft, smoothing, median clamp)."""
+    if squelch is not None:
+        squelch, meter_every, peak_power = _squelch_args(squelch, meter_every, peak_power, frame_len, mode)
     frames = cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len)
     fs = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(sample_rate)
     if mode != 'AM':
         _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), fs)
-    return get_engine().h_demodulate_batch(_MODES[mode], frames, fs, chunk_frames)
+    if squelch is None:
+        return get_engine().h_demodulate_batch(_MODES[mode], frames, fs, chunk_frames)
+    import torch
+    e = get_engine()
+    nf, n = frames.shape
+    n_out = e.demod_out_len(_MODES[mode], n, fs)
+    if n_out < 0:
+        raise ValueError("sample rate below the target rate or unknown mode")
+    pcm, opened, peak, avg = [], np.empty(nf, np.uint8), np.empty(nf, np.float64), np.empty(nf, np.float64)
+    held, phase, disp_w = peak_power, 0, 112
+    for c0 in range(0, nf, int(chunk_frames)):
+        c = min(int(chunk_frames), nf - c0)
+        dev = lambda shape, dt: torch.empty(shape, dtype=dt, device=f"cuda:{e.device}")
+        d_iq = torch.from_numpy(np.ascontiguousarray(frames[c0:c0 + c]).view(np.float32)).to(f"cuda:{e.device}")
+        d_db32, d_lo, d_hi = dev((c, n), torch.float32), dev(c, torch.float64), dev(c, torch.float64)
+        d_a, d_b, d_pcm = dev((c, disp_w), torch.int8), dev((c, disp_w), torch.int8), dev((c, n_out, 2), torch.int16)
+        d_peak, d_avg, d_open = dev(c, torch.float64), dev(c, torch.float64), dev(c, torch.uint8)
+        n_open, held = e.frame_pipeline_squelch(_MODES[mode], d_iq, c, n, fs, d_db32, None, d_lo, d_hi, disp_w, d_a, d_b, d_pcm, squelch, d_peak,
+                                                d_avg, d_open, every=meter_every, phase=phase, held_in=held)
+        phase = (phase + c) % meter_every if meter_every else 0
+        pcm.append(d_pcm[:n_open].cpu().numpy())
+        opened[c0:c0 + c], peak[c0:c0 + c], avg[c0:c0 + c] = d_open.cpu().numpy(), d_peak.cpu().numpy(), d_avg.cpu().numpy()
+    pcm = np.concatenate(pcm) if pcm else np.empty((0, n_out, 2), np.int16)
+    return pcm, opened, peak, avg
 
 
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768):
