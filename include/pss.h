@@ -220,7 +220,9 @@ int pss_frame_pipeline_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n
  * default is WFM (:2855) — and for either batched display accumulator.  mode: PSS_MODE_*, with demodulate_signal's dispatcher semantics (WFM
  * frames are IQ-corrected first, signal_processing.py:222-225; compute_fft sees the samples as read, pyspecsdr.py:2275).  d_pcm int16
  * [n_frames][pss_demod_out_len(mode, n, fs)][2].  display 0: waterfall line, d_line_a = glyph, d_line_b = colour (window: 30 in the reference);
- * display 1: persistence trace, d_line_a = row index per column, d_line_b unused (may be NULL), disp_h <= 127 (window: 10 in the reference).
+ * display 1: persistence trace, d_line_a = row index per column, d_line_b unused (may be NULL), disp_h <= 127 (window: 10 in the reference);
+ * display 2: gradient line (pss_gradient_rows), d_line_a = index into ' ._-=+*#@', d_line_b = colour (window: 30 in the reference) — here and
+ * wherever `display` is an argument below (pss_frame_pipeline_f64, pss_frame_pipeline_cells, pss_spectrum_cells, pss_frame_pipeline_squelch).
  * The other arguments and the results are those of the separate calls (pss_demod_signal, pss_spectrum_db, pss_spectrum_post_extremes /
  * _thresholds, pss_waterfall_rows[_db] / pss_persistence_rows[_db]); NFM runs the schedule of pss_frame_pipeline_nfm, the other modes run the
  * display chain on the side stream beside the whole demodulator.  PSS_E_ARG for n < 8 (no post-processed row), n_halo < 0, window < 1. */
@@ -354,6 +356,44 @@ int pss_spectrogram_cells(pss_ctx *ctx, const float *d_rows, long n_rows, int le
 int pss_spectrogram_cells_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_h, int disp_w,
                               int8_t *d_glyph, int8_t *d_colour, double *d_range);
 
+/* The spectrum display in its compact per-column form ("spectrum bars") — draw_spectrogram (pyspecsdr.py:399-499), the view the reference starts
+ * in (:167, :2054), for BATCHES of rows.  Every cell the reference draws in a column follows from two small integers, so that is what a batch
+ * returns per row instead of pss_spectrogram_cells' two disp_h x disp_w grids (2 disp_w + 16 bytes per row instead of 2 disp_h disp_w + 16):
+ *   d_height int8 [n_rows][disp_w]  min(int(value * disp_h), disp_h), the bar's height in cells (:458); -1: column not drawn (value not finite, :456)
+ *   d_level  int8 [n_rows][disp_w]  3 if value > 0.8, 2 if value > 0.4, 1 if value > 0.2, else 0 (:476-491); -1 with d_height
+ *   d_range  double [n_rows][2]     (display_min, display_max) as pss_spectrogram_cells returns it (:424-436); nullable
+ * `value` is pss_spectrogram_cells' own: the two kernels call the same __device__ functions behind their selects (percentile _lerp, range,
+ * clip + x**0.7 at the knots, np.interp), so the bars ARE that kernel's grid, column by column.
+ *   pss_spectrum_bars[_f64]  rows [n_rows][len], len >= 1, 1 <= disp_h <= 127, disp_w >= 1.  Rows of up to 4092 values stay in registers as
+ *                            order-preserving 64-bit keys (one wavefront per row up to 2048 values, four above); the 20th percentile's two
+ *                            order statistics come from exact counts over the finite values, one pass over the rows.  Longer rows: the radix
+ *                            select of pss_spectrogram_cells.  A row without a finite value (the reference raises ValueError there): every
+ *                            column -1, range (NaN, NaN).  PSS_E_ARG: len < 1, disp_h outside [1, 127], disp_w < 1, n_rows < 0, null buffers.
+ *   pss_bars_cells           the expansion to pss_spectrogram_cells' grids, d_glyph / d_colour int8 [n_rows][disp_h][disp_w]: above the bar
+ *                            (4, 1); for y >= disp_h - height, rel = (y - (disp_h - height)) / height (:473) and level 3 -> (rel > 0.5 ? 3 : 2,
+ *                            14), 2 -> (rel > 0.5 ? 2 : 1, 13), 1 -> (rel > 0.5 ? 1 : 0, 12), 0 -> rel > 0.7 ? (0, 11) : (4, 10); height -1:
+ *                            (-1, -1).  PSS_E_ARG: disp_h outside [1, 127], disp_w < 1, n_rows < 0, null buffers.
+ *   pss_h_bars_cells         the same on host arrays, pure C, no context and no GPU: a curses front end draws from the 2 disp_w bytes it
+ *                            downloaded.  PSS_E_ARG also for a height above disp_h.
+ *   pss_frame_pipeline_bars  one loop iteration per read buffer with this view: pss_frame_pipeline_cells' dB rows (d_db32 [n_frames][n], d_db64
+ *                            nullable: the same bytes), the demodulator's PCM in any mode with the dispatcher's semantics (d_pcm NULL: the
+ *                            display half alone), the bars and range of every frame's post-processed row.  The view has no history: no halo,
+ *                            no window, no extremes.  d_post (nullable) receives the float64 post-processed rows [n_frames][n - 4] — what
+ *                            pss_row_meter_f64 -> pss_squelch_gate -> pss_demod_gated take for the squelch beside this view; NULL: context
+ *                            scratch.  n: a power of two in [16, 65536].  The demodulator runs on the main stream, the display chain on the
+ *                            side stream; joined before the call returns.  PSS_E_ARG: unknown mode, n, disp_h outside [1, 127], disp_w < 1,
+ *                            null d_iq / d_db32 / d_height / d_level.
+ * Not reproduced: the reference redraws only every third iteration and clears the screen itself. */
+int pss_spectrum_bars(pss_ctx *ctx, const float *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level,
+                      double *d_range);
+int pss_spectrum_bars_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level,
+                          double *d_range);
+int pss_bars_cells(pss_ctx *ctx, const int8_t *d_height, const int8_t *d_level, long n_rows, int disp_h, int disp_w, int8_t *d_glyph,
+                   int8_t *d_colour);
+int pss_h_bars_cells(const int8_t *height, const int8_t *level, long n_rows, int disp_h, int disp_w, int8_t *glyph, int8_t *colour);
+int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                            double *d_post, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range, int16_t *d_pcm);
+
 /* Gradient waterfall — draw_gradient_waterfall (pyspecsdr.py:1640-1716) over the same ring of rows: glyph = index into
  * ' ._-=+*#@' (0..8), colour index 0..5, -1 = not drawn.  d_glyph / d_colour int8 [disp_h][disp_w], disp_w = max_width - 10. */
 int pss_gradient_cells(pss_ctx *ctx, const float *d_rows, int n_rows, int len, int disp_h, int disp_w, int8_t *d_glyph,
@@ -457,6 +497,15 @@ int pss_persistence_rows(pss_ctx *ctx, const float *d_post, long n_frames, int l
                          int n_halo, int window, int disp_h, int disp_w, int8_t *d_y);
 int pss_persistence_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
                              const double *d_row_hi, int n_halo, int window, int disp_h, int disp_w, int8_t *d_y);
+/* The gradient view as a line per frame — draw_gradient_waterfall (pyspecsdr.py:1640-1716) is the waterfall accumulator with another
+ * quantiser (the same history of 30 rows, the same window extremes, np.interp to max_width - 10 columns = disp_w): pss_waterfall_rows'
+ * arguments; d_glyph int8 [n_frames][disp_w] = int(norm * 8), the index into ' ._-=+*#@', d_colour = int(norm * 5), -1 where the resampled
+ * value is not finite; norm = (v - lo) / range over the window's finite extremes with range == 0 -> 1 (:1657-1659: this view has the guard
+ * the plain waterfall lacks).  PSS_E_ARG as for pss_waterfall_rows (len < 2, disp_w < 1, window < 1, n_halo < 0, null buffers). */
+int pss_gradient_rows(pss_ctx *ctx, const float *d_post, long n_frames, int len, const float *d_row_lo, const float *d_row_hi,
+                      int n_halo, int window, int disp_w, int8_t *d_glyph, int8_t *d_colour);
+int pss_gradient_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
+                          const double *d_row_hi, int n_halo, int window, int disp_w, int8_t *d_glyph, int8_t *d_colour);
 /* The same WITHOUT materialised post-processed rows (float32 path; n_fft a multiple of 4, n_fft - 4 <= 32768).
  * pss_spectrum_post_thresholds: the post-process of pyspecsdr.py:2278-2283 reduced to what the accumulators need of every row —
  * d_row_thr float32 [n_frames] (the clamp threshold float32(median - 10)) and the finite extremes of the clamped row.

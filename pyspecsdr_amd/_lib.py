@@ -43,6 +43,8 @@ _SIGS = {
     "pss_row_extremes_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p]),
     "pss_waterfall_rows": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
     "pss_waterfall_rows_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "pss_gradient_rows": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
+    "pss_gradient_rows_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, _p, _p]),
     "pss_persistence_rows": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     "pss_persistence_rows_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     "pss_spectrum_post_thresholds": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, _p]),
@@ -91,6 +93,11 @@ _SIGS = {
     "pss_persistence_cells": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p]),
     "pss_spectrogram_cells": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
     "pss_spectrogram_cells_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "pss_spectrum_bars": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "pss_spectrum_bars_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, C.c_int, _p, _p, _p]),
+    "pss_bars_cells": (C.c_int, [_p, _p, _p, C.c_long, C.c_int, C.c_int, _p, _p]),
+    "pss_h_bars_cells": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, _p, _p]),
+    "pss_frame_pipeline_bars": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, C.c_int, C.c_int, _p, _p, _p, _p]),
     "pss_gradient_cells": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p]),
     "pss_gradient_cells_f64": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p]),
     "pss_surface_cells": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p]),

@@ -3691,13 +3691,15 @@ inline int pipe_post(pss_ctx *ctx, const double *d_db, long nf, int n, double *d
 inline int pipe_lines(pss_ctx *ctx, int display, const float *d_post, long nf, int len, const float *lo, const float *hi, int n_halo, int window, int disp_h,
                       int disp_w, int8_t *a, int8_t *b)
 {
-    return display ? pss_persistence_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
+    return display == 2 ? pss_gradient_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
+         : display ? pss_persistence_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
                    : pss_waterfall_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
 }
 inline int pipe_lines(pss_ctx *ctx, int display, const double *d_post, long nf, int len, const double *lo, const double *hi, int n_halo, int window, int disp_h,
                       int disp_w, int8_t *a, int8_t *b)
 {
-    return display ? pss_persistence_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
+    return display == 2 ? pss_gradient_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
+         : display ? pss_persistence_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
                    : pss_waterfall_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
 }
 inline int pipe_chain_vals(pss_ctx *ctx, const float *d_db, long nf, int n, float *lo, float *hi, int n_halo, int window, int display, int disp_h, int disp_w,
@@ -3713,7 +3715,7 @@ inline int pipe_chain_vals(pss_ctx *ctx, const double *d_db, long nf, int n, dou
 }  // namespace
 
 // display: 0 = the waterfall accumulator's newest line (d_glyph, d_colour), 1 = the persistence accumulator's newest trace (d_glyph = row
-// index per column, d_colour unused).
+// index per column, d_colour unused), 2 = the gradient view's newest line (d_glyph = index into ' ._-=+*#@', d_colour).
 // d_post == NULL: the post-processed rows are not materialised.  Rows the register select serves (a multiple of 4 points, up to 32 772 /
 // float64: 16 388): ONE pass over the dB rows leaves per row the extremes and the row resampled to the display width (disp_w float64
 // values: what the accumulators normalise and quantise), and the lines are quantised from those — the same bytes as from materialised rows.
@@ -3747,10 +3749,10 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
                                int8_t *d_glyph, int8_t *d_colour, int16_t *d_pcm, float *d_db32, bool demodulate)
 {
     constexpr bool F64 = sizeof(TR) == 8;
-    if (n_frames < 0 || n_halo < 0 || window < 1 || disp_w < 1 || (display != 0 && display != 1) || (display == 1 && (disp_h < 1 || disp_h > 127)))
+    if (n_frames < 0 || n_halo < 0 || window < 1 || disp_w < 1 || display < 0 || display > 2 || (display == 1 && (disp_h < 1 || disp_h > 127)))
         return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: bad frame count, halo, window or display geometry");
     if (n < 8) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: frames of fewer than 8 samples have no post-processed row to draw");
-    if (n_frames > 0 && (!d_iq || (!d_db && !d_db32) || !d_row_lo || !d_row_hi || !d_glyph || (!d_colour && display == 0) || (!d_pcm && demodulate)))
+    if (n_frames > 0 && (!d_iq || (!d_db && !d_db32) || !d_row_lo || !d_row_hi || !d_glyph || (!d_colour && display != 1) || (!d_pcm && demodulate)))
         return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: null buffer");
     double *d_vals = nullptr;
     if (n_frames > 0 && !d_post) {
@@ -3908,6 +3910,68 @@ extern "C" int pss_spectrum_cells(pss_ctx *ctx, const float *d_iq, long n_frames
     if (n_frames > 0 && !d_db32 && !d_db64) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_cells: no row buffer");
     return frame_pipeline<double>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, 0.0, d_db64, nullptr, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w,
                                   d_line_a, d_line_b, nullptr, d_db32, false);
+}
+
+// One loop iteration per read buffer with the reference's DEFAULT view (draw_spectrogram): pss_frame_pipeline_cells' dB rows, the demodulator's
+// PCM (d_pcm NULL: the display half alone) and per frame the bars and the scale's range of the post-processed float64 row.  The view has no
+// history: no halo, no window, no extremes.  Schedule: the demodulator on the main stream, compute_fft -> float32 rows -> post-process ->
+// k_spectrum_bars on the side stream (the AM branch of frame_pipeline_impl).  The float64 rows go through memory here (d_db64 / d_post, or the
+// context's scratch): the bars need the whole post-processed row for their percentile.
+extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                                       double *d_post, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range, int16_t *d_pcm)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
+    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: n must be a power of two in [16, 65536]");
+    if (n_frames < 0 || disp_h < 1 || disp_h > 127 || disp_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: bad frame count or display geometry");
+    if (n_frames > 0 && (!d_iq || !d_db32 || !d_height || !d_level)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: null buffer");
+    if (n_frames == 0) return PSS_OK;
+    if (!d_db64) {
+        int rq = pss_ensure_buffer(ctx, &ctx->scratch_db64, &ctx->scratch_db64_bytes, (size_t)n_frames * n * sizeof(double), "float64 dB rows");
+        if (rq) return rq;
+        d_db64 = reinterpret_cast<double *>(ctx->scratch_db64);
+    }
+    if (!d_post) {
+        int rq = pss_ensure_buffer(ctx, &ctx->scratch_post, &ctx->scratch_post_bytes, (size_t)n_frames * (n - 4) * sizeof(double), "post-process scratch");
+        if (rq) return rq;
+        d_post = reinterpret_cast<double *>(ctx->scratch_post);
+    }
+    auto display_chain = [&]() -> int {
+        int q = pss_spectrum_db_f64(ctx, d_iq, n_frames, n, d_db64);
+        if (q) return q;
+        const long count = n_frames * (long)n;
+        pss_kernel_begin(ctx, "k_rows_f64_to_f32");
+        hipLaunchKernelGGL(k_rows_f64_to_f32, dim3((unsigned)((count + 255) / 256 < 16384 ? (count + 255) / 256 : 16384)), dim3(256), 0, PSS_STREAM(ctx),
+                           d_db64, d_db32, count);
+        pss_kernel_end(ctx);
+        q = pss_hip_check(ctx, hipGetLastError(), "k_rows_f64_to_f32 launch");
+        if (!q) q = pss_spectrum_post_f64(ctx, d_db64, n_frames, n, d_post, nullptr, nullptr);
+        if (!q) q = pss_spectrum_bars_f64(ctx, d_post, n_frames, n - 4, disp_h, disp_w, d_height, d_level, d_range);
+        return q;
+    };
+    pss_time_begin(ctx);
+    int r;
+    if (!d_pcm) {
+        r = display_chain();
+    } else {
+        r = pss_hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
+        if (!r) r = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)");
+        if (!r) {
+            const int rd = pss_demod_signal(ctx, mode, d_iq, n_frames, n, fs, d_pcm, nullptr);   // main stream
+            int rc;
+            {
+                PssStreamScope side(ctx->cur, ctx->stream2);
+                rc = display_chain();
+            }
+            // the join is attempted whatever happened above: the main stream must never run ahead of the side stream
+            int rj = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
+            if (!rj) rj = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
+            r = rd ? rd : (rc ? rc : rj);
+        }
+    }
+    pss_time_end(ctx);
+    return r;
 }
 
 extern "C" int pss_frame_pipeline_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db, float *d_post,

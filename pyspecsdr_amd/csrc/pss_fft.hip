@@ -22,6 +22,7 @@
 #include "pss_fft_r16.h"
 #include "pss_fft_xl.h"
 #include "pss_post.h"
+#include "pss_bars.h"
 #include "pss_spec_post.h"
 #include "pss_hilbert.h"
 #include "pss_hilbert_pf.h"
@@ -412,8 +413,59 @@ __device__ __forceinline__ double interp_row(const T *row, int len, int W, int i
 // order-preserving 64-bit image of the values, then numpy's _lerp), display range (:424-427), clip + x**0.7 (:442-445),
 // np.interp to the display width (:448-452), bar height int(value*H) and the glyph / colour of every cell (:455-490).
 // glyph: 0 '.', 1 '-', 2 '=', 3 '#', 4 ' '; colour: curses pair (1 = cleared cell); -1: column not drawn (non-finite).
+//
+// What follows the select is shared, as __device__ functions, between k_spectrogram (the whole grid per row) and k_spectrum_bars
+// (two bytes per column: pss_bars.h): the same operations in the same order under this unit's contraction setting (off).
 
-template <class T>
+// ranks of np.percentile(fin, 20), method 'linear', over cnt >= 1 values, and _lerp's weight
+__device__ __forceinline__ void sg_ranks(unsigned cnt, unsigned &lo, unsigned &hi, double &g)
+{
+    const double vi = (double)(cnt - 1) * 0.2;
+    lo = (unsigned)floor(vi);
+    hi = lo + 1;
+    if (vi >= (double)(cnt - 1)) { lo = cnt - 1; hi = cnt - 1; }
+    if (hi > cnt - 1) hi = cnt - 1;
+    g = vi - floor(vi);
+}
+// numpy's _lerp(a, b, g) with its g >= 0.5 form, then the scale's range (:424-427)
+__device__ __forceinline__ void sg_range(double a, double b, double g, double mx, double &dmin, double &dmax)
+{
+    const double dba = b - a;
+    double noise = a + dba * g;
+    if (g >= 0.5) noise = b - dba * (1 - g);
+    const double range = mx - noise;
+    dmin = noise - (range * 0.1);
+    dmax = mx + (range * 0.05);
+}
+// clip((v - min) / (max - min), 0, 1) ** 0.7 (:442-445)
+__device__ __forceinline__ double sg_shaped(double v, double dmin, double dmax)
+{
+    v = (v - dmin) / (dmax - dmin);
+    v = v < 0 ? 0 : (v > 1 ? 1 : v);
+    return pow(v, 0.7);
+}
+// the shaped row as np.interp's knots (Row: anything with operator[](int) convertible to double)
+template <class Row>
+struct SgShaped {
+    Row row;
+    double dmin, dmax;
+    __device__ __forceinline__ double operator[](int j) const { return sg_shaped((double)row[j], dmin, dmax); }
+};
+// column x of the display: np.interp(np.linspace(0, len-1, W), np.arange(len), shaped)[x] and its bar (pss_bars.h)
+template <class Row>
+__device__ __forceinline__ void sg_column(const Row &row, int len, double dmin, double dmax, int disp_h, int disp_w, int x, int &height, int &level)
+{
+    const double value = pss_post::interp_at(SgShaped<Row>{row, dmin, dmax}, len, disp_w, x);
+    height = -1;
+    level = -1;
+    if (!isfinite(value)) return;
+    height = (int)(value * disp_h);
+    if (height > disp_h) height = disp_h;
+    level = value > 0.8 ? 3 : value > 0.4 ? 2 : value > 0.2 ? 1 : 0;
+}
+
+// BARS: glyph / colour are d_height / d_level, [n_rows][disp_w] (the plain path of pss_spectrum_bars: rows too long for k_spectrum_bars)
+template <class T, bool BARS = false>
 __global__ __launch_bounds__(1024) void k_spectrogram(const T *__restrict__ rows, long n_rows, int len, int disp_h, int disp_w,
                                                       int8_t *__restrict__ glyph, int8_t *__restrict__ colour,
                                                       double *__restrict__ range_out)
@@ -424,9 +476,10 @@ __global__ __launch_bounds__(1024) void k_spectrogram(const T *__restrict__ rows
     __shared__ double red[16];
     __shared__ unsigned redn[16];
     const int tid = threadIdx.x, nthr = blockDim.x;
+    const int cells = BARS ? disp_w : disp_h * disp_w;
     for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
         const T *row = rows + (size_t)f * len;
-        int8_t *gl = glyph + (size_t)f * disp_h * disp_w, *co = colour + (size_t)f * disp_h * disp_w;
+        int8_t *gl = glyph + (size_t)f * cells, *co = colour + (size_t)f * cells;
         // max and count of the finite values
         double mx = -INFINITY;
         unsigned cnt = 0;
@@ -444,8 +497,12 @@ __global__ __launch_bounds__(1024) void k_spectrogram(const T *__restrict__ rows
         mx = red[0]; cnt = redn[0];
         for (int w = 1; w < nthr / 64; w++) { mx = red[w] > mx ? red[w] : mx; cnt += redn[w]; }
         __syncthreads();
-        for (int i = tid; i < disp_h * disp_w; i += nthr) { gl[i] = -1; co[i] = -1; }
-        if (cnt == 0) { __syncthreads(); continue; }
+        for (int i = tid; i < cells; i += nthr) { gl[i] = -1; co[i] = -1; }
+        if (cnt == 0) {
+            if (BARS && range_out && tid == 0) { range_out[2 * f] = NAN; range_out[2 * f + 1] = NAN; }
+            __syncthreads();
+            continue;
+        }
         auto select = [&](unsigned k) {  // k-th smallest finite value (0-based)
             unsigned long long prefix = 0, mask = 0;
             for (int shift = 56; shift >= 0; shift -= 8) {
@@ -488,43 +545,106 @@ __global__ __launch_bounds__(1024) void k_spectrogram(const T *__restrict__ rows
             }
             return ord2d(prefix);
         };
-        // np.percentile(fin, 20), method 'linear'
-        const double vi = (double)(cnt - 1) * 0.2;
-        unsigned lo = (unsigned)floor(vi), hi = lo + 1;
-        if (vi >= (double)(cnt - 1)) { lo = cnt - 1; hi = cnt - 1; }
-        if (hi > cnt - 1) hi = cnt - 1;
-        const double g = vi - floor(vi), a = select(lo), b = (hi == lo) ? a : select(hi), dba = b - a;
-        double noise = a + dba * g;
-        if (g >= 0.5) noise = b - dba * (1 - g);
-        const double range = mx - noise;
-        const double dmin = noise - (range * 0.1), dmax = mx + (range * 0.05);
+        unsigned lo, hi;
+        double g, dmin, dmax;
+        sg_ranks(cnt, lo, hi, g);
+        const double a = select(lo), b = (hi == lo) ? a : select(hi);
+        sg_range(a, b, g, mx, dmin, dmax);
         if (range_out && tid == 0) { range_out[2 * f] = dmin; range_out[2 * f + 1] = dmax; }
-        auto shaped = [&](int j) {
-            double v = ((double)row[j] - dmin) / (dmax - dmin);
-            v = v < 0 ? 0 : (v > 1 ? 1 : v);
-            return pow(v, 0.7);
-        };
         for (int x = tid; x < disp_w; x += nthr) {
-            // np.interp(np.linspace(0, len-1, W), np.arange(len), shaped)[x]
-            const double value = pss_post::interp_at(pss_post::fn_row(shaped), len, disp_w, x);
-            if (!isfinite(value)) continue;
-            int height = (int)(value * disp_h);
-            if (height > disp_h) height = disp_h;
-            for (int y = 0; y < disp_h; y++) {
-                int gch = 4, col = 1;
-                if (y >= disp_h - height) {
-                    const double rel = height > 0 ? (double)(y - (disp_h - height)) / (double)height : 0.0;
-                    if (value > 0.8) { gch = rel > 0.5 ? 3 : 2; col = 14; }
-                    else if (value > 0.4) { gch = rel > 0.5 ? 2 : 1; col = 13; }
-                    else if (value > 0.2) { gch = rel > 0.5 ? 1 : 0; col = 12; }
-                    else if (rel > 0.7) { gch = 0; col = 11; }
-                    else { gch = 4; col = 10; }
+            int height, level;
+            sg_column(row, len, dmin, dmax, disp_h, disp_w, x, height, level);
+            if (height < 0) continue;
+            if constexpr (BARS) {
+                gl[x] = (int8_t)height;
+                co[x] = (int8_t)level;
+            } else {
+                for (int y = 0; y < disp_h; y++) {
+                    int gch, col;
+                    pss_bars::cell(height, level, disp_h, y, gch, col);
+                    gl[y * disp_w + x] = (int8_t)gch;
+                    co[y * disp_w + x] = (int8_t)col;
                 }
-                gl[y * disp_w + x] = (int8_t)gch;
-                co[y * disp_w + x] = (int8_t)col;
             }
         }
         __syncthreads();
+    }
+}
+
+// pss_spectrum_bars' register path: rows of up to 64 W EPL values, W wavefronts per row (W = 1: four independent rows per 256-thread
+// workgroup and no workgroup barrier).  Thread t keeps elements t, t + T, ... as order-preserving 64-bit keys (two words each; a value
+// that is not finite takes the padding key, so the select runs over the finite subset as np.percentile(finite, 20) does), the row itself
+// is parked in LDS for the columns.  The two order statistics and the row's finite maximum come from exact counts
+// (pss_post::select_kth64: the search on the high words, the low words from masked reductions) — no LDS atomics, no second pass over
+// global memory — and the row's threads then shape, interpolate and quantise the disp_w columns: 2 disp_w + 16 bytes leave the CU.
+template <class T, int EPL, int W>
+__global__ __launch_bounds__(W == 1 ? 256 : 64 * W) void k_spectrum_bars(const T *__restrict__ rows, long n_rows, int len, int disp_h, int disp_w,
+                                                                         int8_t *__restrict__ height, int8_t *__restrict__ level,
+                                                                         double *__restrict__ range_out)
+{
+    constexpr int TT = 64 * W, RPW = W == 1 ? 4 : 1;
+    extern __shared__ __align__(16) unsigned char smem[];
+    __shared__ unsigned long long red[2 * (W > 1 ? W : 1)];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = W == 1 ? lane : tid;
+    double *buf = reinterpret_cast<double *>(smem) + (size_t)(W == 1 ? wave : 0) * TT * EPL;
+    int phase = 0;
+    const long groups = (n_rows + RPW - 1) / RPW;
+    for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+        const long f = g * RPW + (W == 1 ? wave : 0);
+        if (W == 1 && f >= n_rows) continue;     // whole wavefront (rows are wavefront-private when W = 1)
+        const T *row = rows + (size_t)f * len;
+        unsigned kh[EPL], kl[EPL], cnt = 0;
+#pragma unroll
+        for (int r = 0; r < EPL; r++) {
+            const int j = r * TT + t;
+            const double v = j < len ? (double)row[j] : (double)NAN;
+            const bool fin = isfinite(v);
+            const unsigned long long k = fin ? pss_post::d2ord(v) : ~0ull;
+            kh[r] = (unsigned)(k >> 32);
+            kl[r] = (unsigned)k;
+            cnt += fin ? 1u : 0u;
+            if (j < len) buf[j] = v;
+        }
+        cnt = pss_post::row_reduce<pss_post::OpAdd, W>(cnt, red, wave, lane, phase);
+        pss_post::row_sync<W == 1>();            // the row is in LDS
+        int8_t *hp = height + (size_t)f * disp_w, *lp = level + (size_t)f * disp_w;
+        if (cnt == 0) {                          // (row-uniform) no finite value: nothing drawn, no range
+            for (int x = t; x < disp_w; x += TT) { hp[x] = -1; lp[x] = -1; }
+            if (range_out && t == 0) { range_out[2 * f] = NAN; range_out[2 * f + 1] = NAN; }
+        } else {
+            unsigned lo, hi;
+            double gw, dmin, dmax;
+            sg_ranks(cnt, lo, hi, gw);
+            unsigned long long v1, v2, mn, mx;
+            pss_post::select_kth64<EPL, W, 0>(kh, kl, lo, cnt, v1, v2, mn, mx, red, wave, lane, phase, __builtin_nanf(""));
+            const double a = pss_post::ord2d(v1), b = (hi == lo) ? a : pss_post::ord2d(v2);
+            sg_range(a, b, gw, pss_post::ord2d(mx), dmin, dmax);
+            if (range_out && t == 0) { range_out[2 * f] = dmin; range_out[2 * f + 1] = dmax; }
+            for (int x = t; x < disp_w; x += TT) {
+                int h, l;
+                sg_column((const double *)buf, len, dmin, dmax, disp_h, disp_w, x, h, l);
+                hp[x] = (int8_t)h;
+                lp[x] = (int8_t)l;
+            }
+        }
+        pss_post::row_sync<W == 1>();            // the LDS row may be overwritten now
+    }
+}
+
+// the grids k_spectrogram writes, from the bars (pss_bars.h): one thread per cell
+__global__ __launch_bounds__(256) void k_bars_cells(const int8_t *__restrict__ height, const int8_t *__restrict__ level, long n_rows, int disp_h, int disp_w,
+                                                    int8_t *__restrict__ glyph, int8_t *__restrict__ colour)
+{
+    const long total = n_rows * disp_h * disp_w;
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < total; c += (long)gridDim.x * blockDim.x) {
+        const long q = c / disp_w, f = q / disp_h;
+        const int x = (int)(c - q * disp_w), y = (int)(q - f * disp_h);
+        int gch, col;
+        pss_bars::cell(height[f * disp_w + x], level[f * disp_w + x], disp_h, y, gch, col);
+        glyph[c] = (int8_t)gch;
+        colour[c] = (int8_t)col;
     }
 }
 
@@ -1623,7 +1743,7 @@ int row_extremes(pss_ctx *ctx, const T *d_rows, long n_rows, int len, T *d_lo, T
     return pss_hip_check(ctx, hipGetLastError(), "k_row_extremes launch");
 }
 
-// MODE 0: waterfall line (glyph, colour); MODE 1: persistence trace (y).  d_lo / d_hi: [n_halo + n_frames] row extremes.
+// MODE 0: waterfall line (glyph, colour); MODE 1: persistence trace (y); MODE 2: gradient line (glyph index, colour).  d_lo / d_hi: [n_halo + n_frames] row extremes.
 // d_thr != nullptr: d_post holds the dB rows (len + 4 points each), the post-processed rows are rebuilt per cell
 // d_vals != nullptr: the rows already resampled to disp_w columns (k_post_sel's `vals`); d_post / d_thr are not read
 template <class T, int MODE>
@@ -1631,7 +1751,7 @@ int display_rows(pss_ctx *ctx, const T *d_post, long n_frames, int len, const T 
                  int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, const T *d_thr = nullptr, const double *d_vals = nullptr)
 {
     if (n_frames < 0 || len < 2 || disp_w < 1 || disp_h < 1 || disp_h > 127 || window < 1 || n_halo < 0 ||
-        (n_frames > 0 && ((!d_post && !d_vals) || !d_lo || !d_hi || !d_a || (MODE == 0 && !d_b))))
+        (n_frames > 0 && ((!d_post && !d_vals) || !d_lo || !d_hi || !d_a || (MODE != 1 && !d_b))))
         return pss_fail(ctx, PSS_E_ARG, "bad display-rows arguments");
     if (n_frames == 0) return PSS_OK;
     pss_time_begin(ctx);
@@ -1767,7 +1887,8 @@ extern "C" int pss_persistence_rows_db(pss_ctx *ctx, const float *d_db, long n_f
 
 // The display chain of pss_frame_pipeline behind the dB rows, for rows of either type (pss_ctx.h): post-process WITHOUT materialised rows —
 // thresholds, extremes and the rows resampled to the display width in ONE pass over the dB rows (k_post_sel's `vals`) —, then the sliding
-// extremes and the line of every frame from the resampled values.  display 0: waterfall (a = glyph, b = colour), 1: persistence (a = y).
+// extremes and the line of every frame from the resampled values.  display 0: waterfall (a = glyph, b = colour), 1: persistence (a = y), 2: gradient (a = glyph
+// index, b = colour).
 // Serves the lengths the register select serves (pss_post_sel_serves); d_vals: n_frames x disp_w doubles of scratch.
 bool pss_post_sel_serves(int n_fft, bool f64) { return n_fft >= 8 && post_sel_serves(n_fft, f64); }
 template <class TR>
@@ -1777,7 +1898,8 @@ static int chain_vals(pss_ctx *ctx, const TR *d_db, long n_frames, int n_fft, TR
     if (n_frames == 0) return PSS_OK;
     pss_time_begin(ctx);
     int r = post_sel_any<TR>(ctx, d_db, n_frames, n_fft, (TR *)nullptr, d_lo + n_halo, d_hi + n_halo, (TR *)nullptr, d_vals, disp_w);
-    if (!r) r = display ? display_rows<TR, 1>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const TR *)nullptr, d_vals)
+    if (!r) r = display == 2 ? display_rows<TR, 2>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const TR *)nullptr, d_vals)
+              : display ? display_rows<TR, 1>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const TR *)nullptr, d_vals)
                         : display_rows<TR, 0>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const TR *)nullptr, d_vals);
     pss_time_end(ctx);
     return r;
@@ -1817,7 +1939,8 @@ int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_ff
                        d_db64, tw, win, n_frames, d_lo + n_halo, d_hi + n_halo, d_vals, disp_w);
     pss_kernel_end(ctx);
     r = pss_hip_check(ctx, hipGetLastError(), "k_spectrum_post launch");
-    if (!r) r = display ? display_rows<double, 1>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const double *)nullptr, d_vals)
+    if (!r) r = display == 2 ? display_rows<double, 2>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const double *)nullptr, d_vals)
+              : display ? display_rows<double, 1>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const double *)nullptr, d_vals)
                         : display_rows<double, 0>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const double *)nullptr, d_vals);
     pss_time_end(ctx);
     return r;
@@ -1836,6 +1959,21 @@ extern "C" int pss_waterfall_rows_f64(pss_ctx *ctx, const double *d_post, long n
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     return display_rows<double, 0>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
+}
+// the gradient view's newest line per frame (draw_gradient_waterfall, pyspecsdr.py:1640-1716): pss_waterfall_rows' arguments, another quantiser
+extern "C" int pss_gradient_rows(pss_ctx *ctx, const float *d_post, long n_frames, int len, const float *d_row_lo,
+                                 const float *d_row_hi, int n_halo, int window, int disp_w, int8_t *d_glyph, int8_t *d_colour)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return display_rows<float, 2>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
+}
+extern "C" int pss_gradient_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
+                                     const double *d_row_hi, int n_halo, int window, int disp_w, int8_t *d_glyph, int8_t *d_colour)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return display_rows<double, 2>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
 }
 extern "C" int pss_persistence_rows(pss_ctx *ctx, const float *d_post, long n_frames, int len, const float *d_row_lo,
                                     const float *d_row_hi, int n_halo, int window, int disp_h, int disp_w, int8_t *d_y)
@@ -1908,6 +2046,107 @@ extern "C" int pss_spectrogram_cells_f64(pss_ctx *ctx, const double *d_rows, lon
                                          int8_t *d_glyph, int8_t *d_colour, double *d_range)
 {
     return launch_spectrogram<double>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_glyph, d_colour, d_range);
+}
+
+// ---- the spectrum display as bars (include/pss.h, "spectrum bars") ---------------------------------------------------------------------
+namespace {
+constexpr int BARS_REG_MAX_LEN = 4092;     // longest row of k_spectrum_bars (the post-processed row of a 4096-point frame); longer: k_spectrogram<T, true>
+
+template <class T, int EPL, int W>
+int launch_bars_reg(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range)
+{
+    constexpr int RPW = W == 1 ? 4 : 1;
+    const size_t lds = (size_t)RPW * 64 * W * EPL * sizeof(double);
+    auto kern = k_spectrum_bars<T, EPL, W>;
+    if (lds + 512 > 64 * 1024)
+        PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    long per_cu = (long)((160 * 1024) / (lds + 512));
+    per_cu = per_cu < 1 ? 1 : (per_cu > 6 ? 6 : per_cu);
+    const long groups = (n_rows + RPW - 1) / RPW, cap = 256L * per_cu;
+    pss_kernel_begin(ctx, "k_spectrum_bars");
+    hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(W == 1 ? 256 : 64 * W), lds, PSS_STREAM(ctx), d_rows, n_rows, len, disp_h,
+                       disp_w, d_height, d_level, d_range);
+    pss_kernel_end(ctx);
+    return PSS_OK;
+}
+
+template <class T>
+int spectrum_bars(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range)
+{
+    if (n_rows < 0 || len < 1 || disp_h < 1 || disp_h > 127 || disp_w < 1 || (n_rows > 0 && (!d_rows || !d_height || !d_level)))
+        return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_bars: bad argument (len >= 1, 1 <= disp_h <= 127, disp_w >= 1, non-null buffers)");
+    if (n_rows == 0) return PSS_OK;
+    pss_time_begin(ctx);
+    int r = PSS_OK;
+    if (len <= 256) r = launch_bars_reg<T, 4, 1>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+    else if (len <= 1024) r = launch_bars_reg<T, 16, 1>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+    else if (len <= 2048) r = launch_bars_reg<T, 32, 1>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+    else if (len <= BARS_REG_MAX_LEN) r = launch_bars_reg<T, 16, 4>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+    else {
+        pss_kernel_begin(ctx, "k_spectrum_bars");
+        hipLaunchKernelGGL((k_spectrogram<T, true>), dim3((unsigned)(n_rows < 4096 ? n_rows : 4096)), dim3(1024), 0, PSS_STREAM(ctx), d_rows, n_rows, len,
+                           disp_h, disp_w, d_height, d_level, d_range);
+        pss_kernel_end(ctx);
+    }
+    pss_time_end(ctx);
+    return r ? r : pss_hip_check(ctx, hipGetLastError(), "k_spectrum_bars launch");
+}
+
+// argument rules shared by the device and the host expansion
+bool bars_cells_args_ok(const int8_t *height, const int8_t *level, long n_rows, int disp_h, int disp_w, const int8_t *glyph, const int8_t *colour)
+{
+    return n_rows >= 0 && disp_h >= 1 && disp_h <= 127 && disp_w >= 1 && (n_rows == 0 || (height && level && glyph && colour));
+}
+}  // namespace
+
+extern "C" int pss_spectrum_bars(pss_ctx *ctx, const float *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level,
+                                 double *d_range)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return spectrum_bars<float>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+}
+extern "C" int pss_spectrum_bars_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level,
+                                     double *d_range)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return spectrum_bars<double>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
+}
+
+// The expansion reads the bars it is given: a height above disp_h cannot come from pss_spectrum_bars and is not checked on the device.
+extern "C" int pss_bars_cells(pss_ctx *ctx, const int8_t *d_height, const int8_t *d_level, long n_rows, int disp_h, int disp_w, int8_t *d_glyph,
+                              int8_t *d_colour)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (!bars_cells_args_ok(d_height, d_level, n_rows, disp_h, disp_w, d_glyph, d_colour))
+        return pss_fail(ctx, PSS_E_ARG, "pss_bars_cells: bad argument (1 <= disp_h <= 127, disp_w >= 1, non-null buffers)");
+    if (n_rows == 0) return PSS_OK;
+    const long total = n_rows * disp_h * disp_w, blocks = (total + 255) / 256;
+    pss_kernel_begin(ctx, "k_bars_cells");
+    hipLaunchKernelGGL(k_bars_cells, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, PSS_STREAM(ctx), d_height, d_level, n_rows, disp_h,
+                       disp_w, d_glyph, d_colour);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_bars_cells launch");
+}
+
+// The same expansion on the host: pure C, no context, no GPU.
+extern "C" int pss_h_bars_cells(const int8_t *height, const int8_t *level, long n_rows, int disp_h, int disp_w, int8_t *glyph, int8_t *colour)
+{
+    if (!bars_cells_args_ok(height, level, n_rows, disp_h, disp_w, glyph, colour)) return PSS_E_ARG;
+    const long cols = n_rows * disp_w;
+    for (long c = 0; c < cols; c++)
+        if (height[c] > disp_h) return PSS_E_ARG;
+    for (long f = 0; f < n_rows; f++)
+        for (int y = 0; y < disp_h; y++)
+            for (int x = 0; x < disp_w; x++) {
+                int g, c;
+                pss_bars::cell(height[f * disp_w + x], level[f * disp_w + x], disp_h, y, g, c);
+                glyph[(f * disp_h + y) * disp_w + x] = (int8_t)g;
+                colour[(f * disp_h + y) * disp_w + x] = (int8_t)c;
+            }
+    return PSS_OK;
 }
 
 // draw_vector_display (pyspecsdr.py:1718-1752): every IQ sample drops a '.' at (int(cx + i*scale), int(cy - q*scale)),

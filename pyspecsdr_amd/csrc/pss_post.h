@@ -930,9 +930,24 @@ struct PostFromDb {
 //           No zero-range guard (:1389), as in the reference.
 //   MODE 1  persistence (:1556-1563): y = int((1 - norm) * (disp_h - 1)) of the newest trace, -1 if not drawn (not finite or
 //           outside the grid); range 0 -> 1 (:1528-1530).
+//   MODE 2  gradient waterfall (:1657-1659, :1690-1712): a = int(norm * 8), the index into ' ._-=+*#@'; b = colour int(norm * 5); -1: not
+//           finite; range 0 -> 1 (this view has the guard the plain waterfall lacks).
 template <int MODE>
 __device__ __forceinline__ void quantise_cell(double v, double lo, double hi, int disp_h, int8_t &a, int8_t &b)
 {
+    if constexpr (MODE == 2) {
+        int8_t g = -1, ci = -1;
+        if (isfinite(v)) {
+            double range = hi - lo;
+            if (range == 0) range = 1;
+            const double nv = (v - lo) / range;
+            ci = (int8_t)(int)(nv * 5);
+            g = (int8_t)(int)(nv * 8);
+        }
+        a = g;
+        b = ci;
+        return;
+    }
     if (MODE == 0) {
         int8_t g = -1, ci = -1;
         if (isfinite(v)) {
@@ -978,7 +993,7 @@ __global__ __launch_bounds__(256) void k_disp_rows(const T *__restrict__ post, c
         int8_t a, b = 0;
         quantise_cell<MODE>(v, lo, hi, disp_h, a, b);
         out_a[c] = a;
-        if (MODE == 0) out_b[c] = b;
+        if (MODE != 1) out_b[c] = b;
     }
 }
 
@@ -1017,7 +1032,7 @@ __global__ __launch_bounds__(256) void k_disp_vals_win(const double *__restrict_
             int8_t a, b = 0;
             quantise_cell<MODE>(vals[c0 + c], s_lo[fr], s_hi[fr], disp_h, a, b);
             out_a[c0 + c] = a;
-            if (MODE == 0) out_b[c0 + c] = b;
+            if (MODE != 1) out_b[c0 + c] = b;
         }
         __syncthreads();
     }

@@ -29,6 +29,11 @@ def _ptr(x):
     return int(x)
 
 
+# the batched steps' `display` argument and the reference's history length of each view (pyspecsdr.py:130-131, :151-152, :1648)
+_DISPLAYS = {"waterfall": 0, "persistence": 1, "gradient": 2}
+_WINDOWS = (30, 10, 30)
+
+
 def h_squelch_gate(peak, squelch, every=3, phase=0, held_in=0.0, lib=None):
     """pss_h_squelch_gate: the reference loop's squelch gate (pyspecsdr.py:2261, :2288-2291) over a host array of per-frame peaks ->
     (open uint8 [n_frames], n_open, held_out).  Pure host code: needs the library, not a GPU."""
@@ -245,6 +250,11 @@ class Engine:
         self._dev(fn, _ptr(d_post), n_frames, length, _ptr(d_row_lo), _ptr(d_row_hi), n_halo, window, disp_h, disp_w,
                     _ptr(d_y))
 
+    def gradient_rows(self, d_post, n_frames, length, d_row_lo, d_row_hi, disp_w, d_glyph, d_colour, n_halo=0, window=30, f64=False):
+        """The gradient view's newest line of every frame (draw_gradient_waterfall): glyph = index into ' ._-=+*#@', colour 0..5."""
+        fn = self.lib.pss_gradient_rows_f64 if f64 else self.lib.pss_gradient_rows
+        self._dev(fn, _ptr(d_post), n_frames, length, _ptr(d_row_lo), _ptr(d_row_hi), n_halo, window, disp_w, _ptr(d_glyph), _ptr(d_colour))
+
     def spectrum_post_thresholds(self, d_db, n_frames, n_fft, d_row_thr, d_row_lo, d_row_hi):
         """The post-process without writing the rows: clamp threshold and finite extremes per row (inputs of *_rows_db)."""
         self._dev(self.lib.pss_spectrum_post_thresholds, _ptr(d_db), n_frames, n_fft, _ptr(d_row_thr), _ptr(d_row_lo), _ptr(d_row_hi))
@@ -324,11 +334,11 @@ class Engine:
 
     def frame_pipeline(self, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, disp_w, d_line_a, d_line_b, d_pcm,
                        n_halo=0, window=None, display="waterfall", disp_h=36):
-        """One main-loop iteration per read buffer in any demodulation mode (dispatcher semantics: WFM is IQ-corrected first) and for either
+        """One main-loop iteration per read buffer in any demodulation mode (dispatcher semantics: WFM is IQ-corrected first) and for any
         batched display accumulator: display "waterfall" -> (glyph, colour) lines, "persistence" -> the newest trace's row index (d_line_b
-        unused).  window defaults to the reference's history length (30 / 10)."""
-        disp = {"waterfall": 0, "persistence": 1}[display]
-        window = (30, 10)[disp] if window is None else int(window)
+        unused), "gradient" -> (glyph index into ' ._-=+*#@', colour) lines.  window defaults to the reference's history length (30 / 10 / 30)."""
+        disp = _DISPLAYS[display]
+        window = _WINDOWS[disp] if window is None else int(window)
         self._dev(self.lib.pss_frame_pipeline, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db), _ptr(d_post), _ptr(d_row_lo),
                                              _ptr(d_row_hi), n_halo, window, disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b), _ptr(d_pcm))
 
@@ -342,8 +352,8 @@ class Engine:
     def frame_pipeline_f64(self, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, disp_w, d_line_a, d_line_b, d_pcm,
                            n_halo=0, window=None, display="waterfall", disp_h=36):
         """frame_pipeline with float64 rows: any mode, waterfall line or persistence trace — the reference's cells."""
-        disp = {"waterfall": 0, "persistence": 1}[display]
-        window = (30, 10)[disp] if window is None else int(window)
+        disp = _DISPLAYS[display]
+        window = _WINDOWS[disp] if window is None else int(window)
         self._dev(self.lib.pss_frame_pipeline_f64, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db), _ptr(d_post), _ptr(d_row_lo),
                   _ptr(d_row_hi), n_halo, window, disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b), _ptr(d_pcm))
 
@@ -352,16 +362,16 @@ class Engine:
         """The cell-exact iteration (float64 from the IQ to the cells, frame_pipeline_f64's results) with the dB rows written as float32
         (d_db32: compute_fft's float64 value rounded once) and, if d_db64 is not None, as float64 too.  1024-point frames: the transform and
         the post-process are one kernel and the float64 rows never go through HBM unless d_db64 asks for them."""
-        disp = {"waterfall": 0, "persistence": 1}[display]
-        window = (30, 10)[disp] if window is None else int(window)
+        disp = _DISPLAYS[display]
+        window = _WINDOWS[disp] if window is None else int(window)
         self._dev(self.lib.pss_frame_pipeline_cells, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_row_lo),
                   _ptr(d_row_hi), n_halo, window, disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b), _ptr(d_pcm))
 
     def spectrum_cells(self, d_iq, n_frames, n, d_db32, d_db64, d_row_lo, d_row_hi, disp_w, d_line_a, d_line_b, n_halo=0, window=None,
                        display="waterfall", disp_h=36):
         """frame_pipeline_cells' display half alone: compute_fft -> post-process -> display line of every frame (no demodulator)."""
-        disp = {"waterfall": 0, "persistence": 1}[display]
-        window = (30, 10)[disp] if window is None else int(window)
+        disp = _DISPLAYS[display]
+        window = _WINDOWS[disp] if window is None else int(window)
         self._dev(self.lib.pss_spectrum_cells, _ptr(d_iq), n_frames, n, _ptr(d_db32), _ptr(d_db64), _ptr(d_row_lo), _ptr(d_row_hi), n_halo, window,
                   disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b))
 
@@ -388,8 +398,8 @@ class Engine:
                                disp_h=36):
         """frame_pipeline_cells with the squelch: its display results, every frame's Peak / Avg, the gate, and d_pcm [n_open][n_out][2] of
         the open frames only -> (n_open, held_out).  The next batch continues with held_in = held_out, phase = (phase + n_frames) % every."""
-        disp = {"waterfall": 0, "persistence": 1}[display]
-        window = (30, 10)[disp] if window is None else int(window)
+        disp = _DISPLAYS[display]
+        window = _WINDOWS[disp] if window is None else int(window)
         n_open, held = C.c_long(), C.c_double()
         self._dev(self.lib.pss_frame_pipeline_squelch, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_row_lo),
                   _ptr(d_row_hi), n_halo, window, disp, disp_h, disp_w, _ptr(d_line_a), _ptr(d_line_b), _ptr(d_pcm), float(squelch), int(every),
@@ -411,6 +421,23 @@ class Engine:
     def spectrogram_cells(self, d_rows, n_rows, length, disp_h, disp_w, d_glyph, d_colour, d_range=None, f64=False):
         fn = self.lib.pss_spectrogram_cells_f64 if f64 else self.lib.pss_spectrogram_cells
         self._dev(fn, _ptr(d_rows), n_rows, length, disp_h, disp_w, _ptr(d_glyph), _ptr(d_colour), _ptr(d_range))
+
+    def spectrum_bars(self, d_rows, n_rows, length, disp_h, disp_w, d_height, d_level, d_range=None, f64=False):
+        """draw_spectrogram per row in its compact form: bar height and level per column (int8 [n_rows][disp_w], -1 = not drawn) and the
+        scale's dB range [n_rows][2].  formats.bars_cells / bars_cells expand them to spectrogram_cells' grids."""
+        fn = self.lib.pss_spectrum_bars_f64 if f64 else self.lib.pss_spectrum_bars
+        self._dev(fn, _ptr(d_rows), n_rows, length, disp_h, disp_w, _ptr(d_height), _ptr(d_level), _ptr(d_range))
+
+    def bars_cells(self, d_height, d_level, n_rows, disp_h, disp_w, d_glyph, d_colour):
+        """spectrum_bars' bars expanded on the device to the glyph / colour grids [n_rows][disp_h][disp_w] spectrogram_cells writes."""
+        self._dev(self.lib.pss_bars_cells, _ptr(d_height), _ptr(d_level), n_rows, disp_h, disp_w, _ptr(d_glyph), _ptr(d_colour))
+
+    def frame_pipeline_bars(self, mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, disp_h, disp_w, d_height, d_level, d_range=None, d_pcm=None):
+        """One main-loop iteration per read buffer with the reference's default view: frame_pipeline_cells' dB rows, the demodulator's PCM
+        (d_pcm=None: the display half alone), the spectrum bars and scale range of every frame.  d_post (optional): the float64
+        post-processed rows [n_frames][n - 4], e.g. for row_meter -> squelch_gate -> demod_gated beside this view."""
+        self._dev(self.lib.pss_frame_pipeline_bars, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_post), disp_h,
+                  disp_w, _ptr(d_height), _ptr(d_level), _ptr(d_range), _ptr(d_pcm))
 
     def gradient_cells(self, d_rows, n_rows, length, disp_h, disp_w, d_glyph, d_colour, f64=False):
         fn = self.lib.pss_gradient_cells_f64 if f64 else self.lib.pss_gradient_cells

@@ -54,6 +54,35 @@ def header_strength_text(peak, avg):
     return f"Peak: {peak:.1f} dB Avg: {avg:.1f} dB"
 
 
+def spectrum_scale_labels(display_min, display_max, disp_h):
+    """draw_spectrogram's dB scale (pyspecsdr.py:430-435) for a row's range (spectrum_bars' d_range): the (line, text) pairs of every
+    third display line, line 0 at the top (the reference draws line i at screen row i + 2, column 0)."""
+    labels = []
+    for i in range(int(disp_h)):
+        db_value = display_max - (i * (display_max - display_min) / disp_h)
+        if i % 3 == 0:
+            labels.append((i, f"{db_value:4.0f}dB"))
+    return labels
+
+
+def bars_cells(height, level, disp_h, lib=None):
+    """pss_h_bars_cells: spectrum bars (int8 [..., disp_w] height and level, -1 = column not drawn) expanded to draw_spectrogram's
+    grids -> (glyph, colour) int8 [..., disp_h, disp_w]; glyph 0 '.', 1 '-', 2 '=', 3 '#', 4 ' ', colour = the curses pair (1 = cleared
+    cell).  Pure host code: needs the library, not a GPU."""
+    lib = lib or L.load()
+    height, level = np.ascontiguousarray(height, np.int8), np.ascontiguousarray(level, np.int8)
+    if height.shape != level.shape or height.ndim < 1:
+        raise ValueError("height and level must have the same shape [..., disp_w]")
+    disp_w = height.shape[-1]
+    n_rows = height.size // disp_w if disp_w else 0
+    shape = height.shape[:-1] + (int(disp_h), disp_w)
+    glyph, colour = np.empty(shape, np.int8), np.empty(shape, np.int8)
+    r = lib.pss_h_bars_cells(height.ctypes.data, level.ctypes.data, n_rows, int(disp_h), disp_w, glyph.ctypes.data, colour.ctypes.data)
+    if r != 0:
+        raise ValueError("pss_h_bars_cells: disp_h outside [1, 127], an empty line or a height above disp_h")
+    return glyph, colour
+
+
 def _squelch_args(squelch, meter_every, peak_power, frame_len, mode):
     """demodulate_recording's argument checks for the squelch path (host only: made before anything touches the GPU)."""
     if mode not in _MODES:
