@@ -244,12 +244,44 @@ static float var_c64(const float *z, long n, float *tmp)
     return pss_o_pairwise_sum_f32(tmp, n) / (float)n;
 }
 
+/* complex64 array / float32 scalar and complex64 array * float32 scalar as NumPy evaluates them: the scalar becomes the complex64
+ * (b + 0j) and the COMPLEX loop runs (loops.c.src, CFLOAT_divide: Smith's algorithm; CFLOAT_multiply: the four-product form).  On
+ * nonzero finite values both equal a per-component multiply by 1 / b or by b; the terms that vanish in value, a_i * 0 and a_r * 0,
+ * are still zeros WITH A SIGN, and adding them decides the sign of a zero result: (-0) + (+0) = +0 but (-0) + (-0) = -0. */
+static void cdiv_real_f32(float ar, float ai, float b, float *outr, float *outi)
+{
+    const float br = b, bi = 0.0f;
+    if (fabsf(br) >= fabsf(bi)) {
+        if (fabsf(br) == 0.0f && fabsf(bi) == 0.0f) { *outr = ar / fabsf(br); *outi = ai / fabsf(br); return; }   /* x / 0: inf or NaN */
+        const float rat = bi / br, scl = 1.0f / (br + bi * rat);
+        *outr = (ar + ai * rat) * scl;
+        *outi = (ai - ar * rat) * scl;
+    } else {                                                    /* only a NaN divisor comes here: every output is NaN */
+        const float rat = br / bi, scl = 1.0f / (bi + br * rat);
+        *outr = (ar * rat + ai) * scl;
+        *outi = (ai * rat - ar) * scl;
+    }
+}
+static void cmul_real_f32(float ar, float ai, float b, float *outr, float *outi)
+{
+    const float br = b, bi = 0.0f;
+    *outr = ar * br - ai * bi;
+    *outi = ar * bi + ai * br;
+}
+
 /* iq_correction — signal_processing.py:46-80, complex64 in, complex64 out, every step in float32 as NumPy 2.2
- * evaluates it (NEP 50: the Python scalars 2, 1, 1j are weak; complex64 / float32-scalar multiplies by the
- * reciprocal; complex64 * float32-scalar is a plain per-component multiply). */
+ * evaluates it (NEP 50: the Python scalars 2, 1, 1j are weak).  Values: complex64 / float32-scalar multiplies by the
+ * reciprocal, complex64 * float32-scalar is a per-component multiply.  Signs of zeros (a sample word that is -0: a
+ * buffer conjugated or negated upstream) follow the complex loops NumPy runs for those three statements:
+ *   :55 samples / q_amplitude            cdiv_real_f32: re = (a_r + a_i * 0) * scl, im = (a_i - a_r * 0) * scl
+ *   :71 (i_new + 1j * q_new)             (0 + 1j) * (q + 0j) = (0 * q - 1 * 0, 0 * 0 + 1 * q); + (i_new + 0j)
+ *   :71 (...) / cos_phi_est              cdiv_real_f32 again
+ *   :80 corrected * np.sqrt(...)         cmul_real_f32: re = a_r * g - a_i * 0, im = a_r * 0 + a_i * g
+ * np.angle(x[1:] * conj(x[:-1])) turns a zero of the wrong sign into pi, so the next stage sees these signs. */
 void pss_o_iq_correction(const float *iq, int n, float *out)
 {
     float *c = (float *)malloc(sizeof(float) * 2 * (size_t)n), *t = (float *)malloc(sizeof(float) * (size_t)n);
+    float *nm = (float *)malloc(sizeof(float) * 2 * (size_t)n);
     float sr, si;
     csum_f32(iq, n, &sr, &si);                                   /* :48 np.mean(samples) */
     const float mr = sr / (float)n, mi = si / (float)n;
@@ -257,25 +289,24 @@ void pss_o_iq_correction(const float *iq, int n, float *out)
     const float input_power = var_c64(c, n, t);                  /* :49 */
     for (int i = 0; i < n; i++) t[i] = iq[2 * i + 1] * iq[2 * i + 1];
     const float qa = sqrtf(2.0f * (pss_o_pairwise_sum_f32(t, n) / (float)n));   /* :52 */
-    const float scl = 1.0f / qa;                                 /* :55 samples / q_amplitude */
-    for (int i = 0; i < n; i++) { const float is = iq[2 * i] * scl; t[i] = is * is; }
+    for (int i = 0; i < n; i++) cdiv_real_f32(iq[2 * i], iq[2 * i + 1], qa, &nm[2 * i], &nm[2 * i + 1]);   /* :55 samples / q_amplitude */
+    for (int i = 0; i < n; i++) { const float is = nm[2 * i]; t[i] = is * is; }
     const float alpha = sqrtf(2.0f * (pss_o_pairwise_sum_f32(t, n) / (float)n)); /* :60 */
-    for (int i = 0; i < n; i++) t[i] = (iq[2 * i] * scl) * (iq[2 * i + 1] * scl);
+    for (int i = 0; i < n; i++) t[i] = nm[2 * i] * nm[2 * i + 1];
     const float sinphi = (2.0f / alpha) * (pss_o_pairwise_sum_f32(t, n) / (float)n); /* :61 */
     const float cosphi = sqrtf(1.0f - sinphi * sinphi);          /* :64 */
-    const float ia = 1.0f / alpha, qa2 = -sinphi / alpha, sc = 1.0f / cosphi;
+    const float ia = 1.0f / alpha, qa2 = -sinphi / alpha;
     for (int i = 0; i < n; i++) {                                /* :67-71 */
-        const float is = iq[2 * i] * scl, qs = iq[2 * i + 1] * scl;
+        const float is = nm[2 * i], qs = nm[2 * i + 1];
         const float i_new = ia * is, q_new = qa2 * is + qs;
-        /* i_new + 1j*q_new: (0+1j)*(q+0j) = (fma(0,q,-(1*0)), fma(0,0,1*q)); adding (i_new + 0j) normalises -0 */
+        /* i_new + 1j*q_new: (0+1j)*(q+0j) = (fma(0,q,-(1*0)), fma(0,0,1*q)); adding (i_new + 0j) */
         const float jr = fmaf(0.0f, q_new, -0.0f), ji = fmaf(0.0f, 0.0f, q_new);
-        c[2 * i] = (i_new + jr) * sc;
-        c[2 * i + 1] = (0.0f + ji) * sc;
+        cdiv_real_f32(i_new + jr, 0.0f + ji, cosphi, &c[2 * i], &c[2 * i + 1]);
     }
     const float v2 = var_c64(c, n, t);                           /* :80 */
     const float g = sqrtf(input_power / v2);
-    for (int i = 0; i < 2 * n; i++) out[i] = c[i] * g;
-    free(c); free(t);
+    for (int i = 0; i < n; i++) cmul_real_f32(c[2 * i], c[2 * i + 1], g, &out[2 * i], &out[2 * i + 1]);
+    free(c); free(t); free(nm);
 }
 
 /* ------------------------------------------------------------------------------------------------

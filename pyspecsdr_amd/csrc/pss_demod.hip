@@ -1299,20 +1299,35 @@ __global__ __launch_bounds__(256) void k_pairwise2(const float2 *__restrict__ iq
 // ia = 1 / alpha and qa2 = -sin(phi) / alpha (:67-68), sc = 1 / cos(phi) (:71), g = sqrt(input_power / var(corrected)) (:80).  Shared by
 // k_iqcorr (which also derives the scalars) and the fused WFM forward kernel, which applies the correction as it reads the raw IQ.
 struct IqcScal { float scl, ia, qa2, sc, g; };
+// Signs of zeros.  Three of the statements are complex64 (array) with a float32 scalar, for which NumPy runs its COMPLEX loops on
+// (scalar + 0j): :55 and :71 divide by Smith's algorithm, re = (a_r + a_i * 0) * (1 / b), im = (a_i - a_r * 0) * (1 / b); :80 multiplies
+// as re = a_r * g - a_i * 0, im = a_r * 0 + a_i * g.  The vanishing terms are zeros with a sign and decide the sign of a zero result
+// ((-0) + (+0) = +0, (-0) + (-0) = -0): an input word that is -0 (a buffer conjugated or negated upstream) comes out as the reference
+// leaves it, and np.angle(x[1:] * conj(x[:-1])) downstream turns the other sign into pi.  Each such term is one fused multiply-add
+// with the constant 0 (the product is exact, so the fma is the two-operation form bit for bit); values are untouched.  The divisors
+// are square roots (+0 or positive): with b = 0 NumPy divides the components by |b| directly, which (a + a' * 0) * inf equals for the
+// finite components an ADC delivers (oracle/pss_oracle.c restates the loops branch for branch; PARITY.md "iq_correction: signs of zeros").
+__device__ __forceinline__ float2 iqc_div_real(float2 a, float rcp)
+{
+    return make_float2(__fmul_rn(__fmaf_rn(a.y, 0.0f, a.x), rcp), __fmul_rn(__fmaf_rn(-a.x, 0.0f, a.y), rcp));
+}
 __device__ __forceinline__ float2 iqc_corrected(float2 v, float scl, float ia, float qa2, float sc)
 {
+    const float2 nm = iqc_div_real(v, scl);    // :55
     // :67-71 (the 1j*q_new complex multiply only touches the sign of zeros)
-    const float is = __fmul_rn(v.x, scl), qs = __fmul_rn(v.y, scl);
+    const float is = nm.x, qs = nm.y;
     const float i_new = __fmul_rn(ia, is), q_new = __fadd_rn(__fmul_rn(qa2, is), qs);
     const float jr = __fmaf_rn(0.0f, q_new, -0.0f), ji = __fmaf_rn(0.0f, 0.0f, q_new);
-    return make_float2(__fmul_rn(__fadd_rn(i_new, jr), sc), __fmul_rn(__fadd_rn(0.0f, ji), sc));
+    return iqc_div_real(make_float2(__fadd_rn(i_new, jr), __fadd_rn(0.0f, ji)), sc);
+}
+// :80 corrected * np.sqrt(input_power / np.var(corrected))
+__device__ __forceinline__ float2 iqc_scaled(float2 c, float g)
+{
+    return make_float2(__fmaf_rn(-c.y, 0.0f, __fmul_rn(c.x, g)), __fmaf_rn(c.x, 0.0f, __fmul_rn(c.y, g)));
 }
 __device__ __forceinline__ float2 iqc_apply(float2 v, const IqcScal &k)
 {
-    float2 c = iqc_corrected(v, k.scl, k.ia, k.qa2, k.sc);
-    c.x = __fmul_rn(c.x, k.g);
-    c.y = __fmul_rn(c.y, k.g);
-    return c;
+    return iqc_scaled(iqc_corrected(v, k.scl, k.ia, k.qa2, k.sc), k.g);
 }
 
 // STAGED: the frame is copied to LDS once and every pass reads it from there (frames up to 8192 samples).
@@ -1422,9 +1437,7 @@ __global__ __launch_bounds__(256) void k_iqcorr(const float2 *__restrict__ iq, i
         }
         if (out || raw) {
             for (int i = threadIdx.x; i < n; i += T) {
-                float2 c = corrected(i);
-                c.x = __fmul_rn(c.x, g);
-                c.y = __fmul_rn(c.y, g);
+                const float2 c = iqc_scaled(corrected(i), g);
                 if (out) out[(size_t)f * n + i] = c;
                 if (raw) raw[(size_t)f * n + i] = c.x;  // demodulate_signal(..., 'RAW'): np.real(samples) (:238)
             }
