@@ -18,12 +18,14 @@ BUILD = os.path.join(HERE, "_build")
 ARCH = "gfx950"
 COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # pss_demod.hip carries the bit-exactness contract: no implicit fused multiply-adds.
+DEMOD_FLAGS = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-instcombine-max-copied-from-constant-users=4000"]
 UNITS = [
     ("pss_fft.hip", ["-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the scanner rows use NumPy's float32 abs (IEEE sqrt / divide)
     # -instcombine-max-copied-from-constant-users: the FIR taps are a by-value kernel argument read at many (dynamic) offsets; past
     # LLVM's default of 300 users instcombine no longer forwards the reads to the kernarg segment and the whole table is copied to
     # scratch at kernel entry (measured: 412 spilled VGPRs in k_nfm_fwd instead of 3)
-    ("pss_demod.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-mllvm", "-instcombine-max-copied-from-constant-users=4000"]),
+    ("pss_demod.hip", DEMOD_FLAGS),
+    ("pss_pipeline.hip", DEMOD_FLAGS),   # the batched loop iterations around the demodulator: host code and one conversion kernel
     ("pss_squelch.hip", ["-ffp-contract=off"]),   # NumPy's summation tree and np.max, bit for bit: no fused multiply-adds either
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),
@@ -53,7 +55,7 @@ def build(force=False, verbose=False):
     headers.append(os.path.join(os.path.dirname(HERE), "include", "pss.h"))
     headers.append(os.path.abspath(__file__))
     objs, running = [], []
-    for src, extra in UNITS:   # the translation units compile side by side (the two .hip files take ~30 s each)
+    for src, extra in UNITS:   # the translation units compile side by side (the two large .hip files take ~30 s each)
         s = os.path.join(CSRC, src)
         o = os.path.join(BUILD, src.rsplit(".", 1)[0] + ".o")
         objs.append(o)

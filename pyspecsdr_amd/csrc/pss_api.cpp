@@ -77,6 +77,19 @@ void pss_time_end(pss_ctx *ctx)
     }
 }
 
+int pss_side_mark(pss_ctx *ctx) { PSS_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream)); return PSS_OK; }
+int pss_side_wait(pss_ctx *ctx) { return pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)"); }
+int pss_side_fork(pss_ctx *ctx)
+{
+    const int r = pss_hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
+    return r ? r : pss_side_wait(ctx);
+}
+int pss_side_join(pss_ctx *ctx)
+{
+    const int r = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
+    return r ? r : pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
+}
+
 extern "C" int pss_device_count(void)
 {
     int n = 0;

@@ -3,7 +3,6 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -34,22 +33,14 @@ struct pss_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipStream_t stream2 = nullptr;  // side stream: the spectrum kernel of pss_spectrum_nfm runs beside the demodulator
+    hipStream_t stream2 = nullptr;  // side stream: the spectrum / display chain runs beside the demodulator (pss_side_* below)
     hipStream_t cur = nullptr;      // stream the next launches go to (nullptr = `stream`)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;   // pss_side_* only
     hipEvent_t ev_in = nullptr, ev_out = nullptr;   // pss_order_after / pss_order_before (created on first use)
     int n_cus = 0;                                  // hipDeviceProp_t::multiProcessorCount
-    bool iq_c128 = false;           // set by pss_demod_ssb_c128 around pss_demod: d_iq points at complex128 frames (the SSB kernels' float64 loader)
     int fuse_post = 1;              // option "fuse_post" (float64-row pipelines, 1024-point frames): 1 = transform + post-process in ONE kernel (pss_spec_post.h), 0 = two kernels (A/B reference)
     double target_rate = 22050.0;   // demodulate_nfm / _wfm's target_rate (pss_set_target_rate): decimation factor int(fs / target_rate)
-    bool wfm_correct = false;       // pss_demod(WFM) is handed the frames AS READ and applies iq_correction itself (consumed there; set by pss_demod_signal / pss_frame_pipeline)
-    const float *wfm_scal = nullptr;   // ... the per-frame correction scalars for the fused forward kernel
     bool wfm_corr_copy = false;     // option "wfm_corr_copy": always materialise the corrected copy of the batch (the round-4 path; A/B reference)
-    float *power_out = nullptr;     // pss_demod_power -> pss_demod(AM): the power dB of the same frames from the mean pass (consumed there)
-    bool fork_after_fwd = false;
-    bool did_fork = false;
-    bool defer_bwd = false;              // the fused NFM path launches only its forward kernel and parks the backward launch here:
-    std::function<int()> pending_bwd;    // pss_frame_pipeline_nfm places it beside the post-process  // set by pss_demod when it recorded ev_fork (fused NFM path only)
     std::string err;
     std::map<int, double2 *> tw;       // exp(-2 pi i k / N), k < N
     std::map<int, double *> win;       // np.hamming(N)
@@ -160,11 +151,61 @@ int pss_ensure_scratch(pss_ctx *ctx, size_t bytes);
 int pss_ensure_buffer(pss_ctx *ctx, void **buf, size_t *cap, size_t bytes, const char *what);
 void pss_time_begin(pss_ctx *ctx);
 void pss_time_end(pss_ctx *ctx);
+// The timing bracket of a call (pss_last_kernel_ms): nested brackets are no-ops, the outermost one closes on every way out of its scope
+struct PssTimeScope {
+    pss_ctx *ctx;
+    explicit PssTimeScope(pss_ctx *c) : ctx(c) { pss_time_begin(c); }
+    ~PssTimeScope() { pss_time_end(ctx); }
+    PssTimeScope(const PssTimeScope &) = delete;
+    PssTimeScope &operator=(const PssTimeScope &) = delete;
+};
 // bracket ONE kernel launch with events on the context's stream (no-ops unless timing is enabled)
 void pss_kernel_begin(pss_ctx *ctx, const char *name);
 void pss_kernel_end(pss_ctx *ctx);
 
 #define PSS_STREAM(ctx) ((ctx)->cur ? (ctx)->cur : (ctx)->stream)
+
+// "Run this on stream2 beside the main stream" (pss_api.cpp).  pss_side_fork: stream2 waits for everything queued on the main stream so far
+// (pss_side_mark + pss_side_wait: the same in two steps, for a fork point inside the demodulator); pss_on_side: f's launches go to stream2;
+// pss_side_join: the main stream waits for stream2 — to be attempted whatever happened in between, the main stream must never run ahead of
+// the side stream.
+int pss_side_mark(pss_ctx *ctx);
+int pss_side_wait(pss_ctx *ctx);
+int pss_side_fork(pss_ctx *ctx);
+int pss_side_join(pss_ctx *ctx);
+template <class F>
+int pss_on_side(pss_ctx *ctx, F &&f)
+{
+    PssStreamScope side(ctx->cur, ctx->stream2);
+    return f();
+}
+
+// ---- the demodulator's internal call (pss_demod.hip): what the public entry points and the pipelines (pss_pipeline.hip) build -----------------
+struct PssIq {   // a batch of read buffers [n_frames][n]: complex64 (f32) or complex128 (f64, the SSB kernels' float64 loader), one of the two
+    const float *f32 = nullptr;
+    const double *f64 = nullptr;
+};
+// The backward launch of the fused NFM / WFM paths as data (k_nfm_bwd's arguments), for a caller that places it itself
+struct PssBwdLaunch {
+    const PssNfmFilt *flt = nullptr;   // the decimator (the context's cached design); NULL: nothing was handed back
+    bool stereo = false;               // WFM: both channels of a tile, joint normalisation
+    double *Yf = nullptr, *Af = nullptr;
+    int n = 0, q = 0, n_out = 0;
+    long n_frames = 0;
+    int16_t *d_pcm = nullptr; double *d_audio = nullptr;
+    int launch(pss_ctx *ctx) const;
+};
+enum PssAfterFwd { PSS_RUN_ALL = 0, PSS_FORK_AFTER_FWD, PSS_DEFER_BWD };
+struct PssDemodCall {   // in: correct, d_power, after_fwd; out: forked, bwd
+    bool correct = false;          // WFM: the frames are AS READ, iq_correction comes first (demodulate_signal's dispatcher)
+    float *d_power = nullptr;      // AM: the power dB of the same frames, out of the mean pass
+    PssAfterFwd after_fwd = PSS_RUN_ALL;   // fused NFM / WFM paths: PSS_FORK_AFTER_FWD marks the fork point behind the forward kernel (NFM),
+                                           // PSS_DEFER_BWD launches the forward kernel only and hands the backward launch back
+    bool forked = false;           // pss_side_mark was called: the caller owes pss_side_wait .. pss_side_join
+    PssBwdLaunch bwd;              // bwd.flt != NULL: the caller owes bwd.launch(ctx)
+};
+// Checks its arguments as pss_demod does; call == NULL: a default PssDemodCall
+int pss_demod_run(pss_ctx *ctx, int mode, PssIq iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, PssDemodCall *call);
 
 #define PSS_HIP(ctx, call)                                         \
     do {                                                           \

@@ -1,4 +1,5 @@
-// pss_demod.hip — demodulation kernels for gfx950 (NFM / AM / SSB), AGC power, int16 PCM.
+// pss_demod.hip — demodulation kernels for gfx950 (NFM / AM / SSB / WFM), AGC power, int16 PCM, and their host entry points: pss_demod_run
+// (pss_ctx.h) with one function per mode behind it; the batched pipelines that call it live in pss_pipeline.hip.
 //
 // Reference lines replaced: signal_processing.py:91-116 (demodulate_nfm), :179-195 (demodulate_am),
 // :198-217 (demodulate_ssb), :325-328 (measure_signal_power), :83-88 (mono_to_stereo),
@@ -2678,12 +2679,11 @@ static int iq_correction_launch(pss_ctx *ctx, const float *d_iq, long n_frames, 
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const RedPlan &a = rp, &b = cp;
     long g = n_frames < 8192 ? n_frames : 8192;  // several frames per workgroup: the plan tables are copied to LDS once (a grid capped at what the CUs hold at once — 2048 workgroups — measured 20 % slower: the dispatcher's backfill of finished workgroups is the better balance)
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_iqcorr");
     hipLaunchKernelGGL(kern, dim3((int)g), dim3(T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, a, b,
                        (int)part_slots, (int)val_slots, reinterpret_cast<float2 *>(d_out_iq), d_raw, d_scal);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_iqcorr launch");
 }
 
@@ -2693,9 +2693,8 @@ extern "C" int pss_power_db(pss_ctx *ctx, const float *d_iq, long n_frames, int 
     PSS_GUARD(ctx);
     if (n < 1 || n_frames < 0 || (n_frames > 0 && (!d_iq || !d_power))) return pss_fail(ctx, PSS_E_ARG, "bad power arguments");
     if (n_frames == 0) return PSS_OK;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     int r = launch_pairwise<0>(ctx, d_iq, n_frames, n, d_power);
-    pss_time_end(ctx);
     return r;
 }
 
@@ -2726,448 +2725,454 @@ static bool sections_b121(const double *sos)
     return true;
 }
 
-extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm,
-                         double *d_audio)
+static NfmCoef nfm_coef(const PssNfmFilt *flt)
 {
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (n_frames < 0 || n < 1 || (n_frames > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "bad demod arguments");
-    if (n_frames > 0 && !d_pcm && !d_audio) return pss_fail(ctx, PSS_E_ARG, "both outputs are null");
+    NfmCoef c;
+    sos_biquads(c.s, flt->sos, 4);
+    for (int i = 0; i < 8; i++) c.zi[i] = flt->zi[i];
+    return c;
+}
+
+int PssBwdLaunch::launch(pss_ctx *ctx) const
+{
+    const NfmCoef c = nfm_coef(flt);
     const long tiles = (n_frames + TILE - 1) / TILE;
-    if (mode == PSS_MODE_NFM) {
-        if (n - 1 <= EDGE)
-            return pss_fail(ctx, PSS_E_PADLEN, "The length of the input vector x must be greater than padlen, which is 27.");
-        PssNfmFilt *flt;
-        int r = nfm_filters(ctx, fs, &flt);
+    pss_kernel_begin(ctx, "k_nfm_bwd");
+    if (stereo)
+        hipLaunchKernelGGL((fused::k_nfm_bwd<true, true>), dim3((unsigned)tiles), dim3(2 * TILE), 0, PSS_STREAM(ctx), Yf, Af,
+                           n, q, n_out, n_frames, c, d_pcm, d_audio);      // both channels of a tile: joint normalisation + stereo PCM inside
+    else
+        hipLaunchKernelGGL(fused::k_nfm_bwd<true>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), Yf, Af, n, q,
+                           n_out, n_frames, c, d_pcm, d_audio);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), stereo ? "wfm fused launch (backward)" : "k_nfm_bwd launch");
+}
+
+// The kernel family of a call, decided once: it sizes the scratch, chooses the correction pre-pass (WFM) and the launches
+enum class NfmPath { Fused, SmallBatch, ThreeKernel };
+enum class WfmPath { SmallBatch, Fused, Plain, FactorOne };
+
+static int demod_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, PssDemodCall &call)
+{
+    if (n - 1 <= EDGE) return pss_fail(ctx, PSS_E_PADLEN, "The length of the input vector x must be greater than padlen, which is 27.");
+    PssNfmFilt *flt;
+    int r = nfm_filters(ctx, fs, &flt);
+    if (r) return r;
+    if (n_frames == 0) return PSS_OK;
+    const long tiles = (n_frames + TILE - 1) / TILE;
+    const int q = (int)(fs / ctx->target_rate);
+    const int n_out = (n - 1 + q - 1) / q;
+    const long L = (long)(n - 1) + 2 * EDGE;
+    const long Lp = (L + 1) & ~1L;  // even row stride -> 16-byte aligned rows of u
+    const size_t szU = align256((size_t)n_frames * Lp * sizeof(double));
+    const size_t szY = align256((size_t)tiles * L * TILE * sizeof(double));
+    const size_t szA = align256((size_t)tiles * n_out * TILE * sizeof(double));
+    const TapsArg targ = make_taps(flt->taps);
+    const NfmCoef c = nfm_coef(flt);
+    const float kscale = (float)(fs / (2.0 * M_PI));          // python float -> float32 scalar (:97)
+    const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;  // NumPy temporary elision threshold
+    const bool b121 = sections_b121(flt->sos);
+    // a handful of long frames (the interactive loop: one 32768-sample buffer per call) cannot fill lane-per-frame
+    // wavefronts: below this many frames the decimator runs as a 4-lane systolic array per frame instead
+    const bool small_batch = !ctx->no_small_batch && n_frames <= ctx->small_batch_max;
+    // (the fused kernels exist for decimator sections 1..3 with numerator exactly [1, 2, 1] — every cheby1 low-pass SOS; injected
+    // tables of another shape take the three-kernel path)
+    // (and for tiles of less than 2 GiB of IQ: the forward kernel addresses a tile of 64 frames through one buffer resource with 32-bit
+    // offsets — frames of 4 Mi samples and more take the three-kernel path)
+    const NfmPath path = (n - 1 >= 128 && !ctx->no_fused && !small_batch && b121 && (long)TILE * n * (long)sizeof(float2) < (1L << 31)) ? NfmPath::Fused
+                       : small_batch ? NfmPath::SmallBatch : NfmPath::ThreeKernel;
+    if (path == NfmPath::Fused) {
+        // fused path: u[] stays on chip; small L2-resident scratch for the irregular head / tail of u
+        const size_t szH = align256((size_t)tiles * fused::HEAD * TILE * sizeof(double));
+        const size_t szT = align256((size_t)tiles * (EDGE + 1) * TILE * sizeof(double));
+        r = pss_ensure_scratch(ctx, szY + szA + szH + szT);
         if (r) return r;
-        if (n_frames == 0) return PSS_OK;
-        const int q = (int)(fs / ctx->target_rate);
-        const int n_out = (n - 1 + q - 1) / q;
-        const long L = (long)(n - 1) + 2 * EDGE;
-        const long Lp = (L + 1) & ~1L;  // even row stride -> 16-byte aligned rows of u
-        const size_t szU = align256((size_t)n_frames * Lp * sizeof(double));
-        const size_t szY = align256((size_t)tiles * L * TILE * sizeof(double));
-        const size_t szA = align256((size_t)tiles * n_out * TILE * sizeof(double));
-        double *U = nullptr, *Y = nullptr, *A = nullptr;  // three-kernel path only; each path sizes the (grow-only) scratch itself
-        const TapsArg targ = make_taps(flt->taps);
-        NfmCoef c;
-        sos_biquads(c.s, flt->sos, 4);
-        for (int i = 0; i < 8; i++) c.zi[i] = flt->zi[i];
-        const float kscale = (float)(fs / (2.0 * M_PI));          // python float -> float32 scalar (:97)
-        const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;  // NumPy temporary elision threshold
-        const bool b121 = sections_b121(flt->sos);
-        // a handful of long frames (the interactive loop: one 32768-sample buffer per call) cannot fill lane-per-frame
-        // wavefronts: below this many frames the decimator runs as a 4-lane systolic array per frame instead
-        const bool small_batch = !ctx->no_small_batch && n_frames <= ctx->small_batch_max;
-        // (the fused kernels exist for decimator sections 1..3 with numerator exactly [1, 2, 1] — every cheby1 low-pass SOS; injected
-        // tables of another shape take the three-kernel path)
-        // (and for tiles of less than 2 GiB of IQ: the forward kernel addresses a tile of 64 frames through one buffer resource with 32-bit
-        // offsets — frames of 4 Mi samples and more take the three-kernel path)
-        if (n - 1 >= 128 && !ctx->no_fused && !small_batch && b121 && (long)TILE * n * (long)sizeof(float2) < (1L << 31)) {
-            // fused path: u[] stays on chip; small L2-resident scratch for the irregular head / tail of u
-            const size_t szH = align256((size_t)tiles * fused::HEAD * TILE * sizeof(double));
-            const size_t szT = align256((size_t)tiles * (EDGE + 1) * TILE * sizeof(double));
-            r = pss_ensure_scratch(ctx, szY + szA + szH + szT);
-            if (r) return r;
-            const double *d_rev = nullptr;
-            r = nfm_dev_taps(ctx, flt, &d_rev);
-            if (r) return r;
-            const unsigned ncu = ctx->n_cus > 0 ? (unsigned)ctx->n_cus : 256u;
-            if (!ctx->prog) {    // progress words of the forward kernel's workgroups (16 bytes per CU: up to four workgroups share one)
-                PSS_HIP(ctx, hipMalloc(&ctx->prog, 16 * (size_t)ncu));
-                PSS_HIP(ctx, hipMemsetAsync(ctx->prog, 0, 16 * (size_t)ncu, PSS_STREAM(ctx)));   // ordered before the first launch
-            }
-            ctx->prog_epoch = (ctx->prog_epoch + 1u) & 0xffffu;   // every launch ranks only against words of its own epoch (never reset)
-            if (ctx->prog_epoch == 0) ctx->prog_epoch = 1;
-            char *base = reinterpret_cast<char *>(ctx->scratch);
-            double *Yf = reinterpret_cast<double *>(base), *Af = reinterpret_cast<double *>(base + szY);
-            double *Uh = reinterpret_cast<double *>(base + szY + szA), *Ut = reinterpret_cast<double *>(base + szY + szA + szH);
-            pss_time_begin(ctx);
-            pss_kernel_begin(ctx, "k_nfm_fwd");
-            {
-                auto kf = swapped ? fused::k_nfm_fwd<true, true> : fused::k_nfm_fwd<true, false>;
-                hipLaunchKernelGGL(kf, dim3((unsigned)tiles), dim3(fused::WG), fused::LDS_BYTES, PSS_STREAM(ctx),
-                                   reinterpret_cast<const float2 *>(d_iq), Yf, Uh, Ut, n, n_frames, c, kscale, d_rev,
-                                   reinterpret_cast<unsigned *>(ctx->prog), ncu, ctx->prog_epoch, 0L);
-            }
-            pss_kernel_end(ctx);
-            auto launch_bwd = [=]() -> int {
-                pss_kernel_begin(ctx, "k_nfm_bwd");
-                hipLaunchKernelGGL(fused::k_nfm_bwd<true>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), Yf, Af, n, q,
-                                   n_out, n_frames, c, d_pcm, d_audio);
-                pss_kernel_end(ctx);
-                return pss_hip_check(ctx, hipGetLastError(), "k_nfm_bwd launch");
-            };
-            if (ctx->defer_bwd) {  // pss_frame_pipeline_nfm places the backward pass itself (beside the post-process)
-                ctx->pending_bwd = launch_bwd;
-                pss_time_end(ctx);
-                return pss_hip_check(ctx, hipGetLastError(), "nfm fused launch");
-            }
-            if (ctx->fork_after_fwd) {  // pss_spectrum_nfm overlaps the rest
-                PSS_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-                ctx->did_fork = true;
-            }
-            r = launch_bwd();
-            pss_time_end(ctx);
-            if (r) return r;
+        const double *d_rev = nullptr;
+        r = nfm_dev_taps(ctx, flt, &d_rev);
+        if (r) return r;
+        const unsigned ncu = ctx->n_cus > 0 ? (unsigned)ctx->n_cus : 256u;
+        if (!ctx->prog) {    // progress words of the forward kernel's workgroups (16 bytes per CU: up to four workgroups share one)
+            PSS_HIP(ctx, hipMalloc(&ctx->prog, 16 * (size_t)ncu));
+            PSS_HIP(ctx, hipMemsetAsync(ctx->prog, 0, 16 * (size_t)ncu, PSS_STREAM(ctx)));   // ordered before the first launch
+        }
+        ctx->prog_epoch = (ctx->prog_epoch + 1u) & 0xffffu;   // every launch ranks only against words of its own epoch (never reset)
+        if (ctx->prog_epoch == 0) ctx->prog_epoch = 1;
+        char *base = reinterpret_cast<char *>(ctx->scratch);
+        double *Yf = reinterpret_cast<double *>(base), *Af = reinterpret_cast<double *>(base + szY);
+        double *Uh = reinterpret_cast<double *>(base + szY + szA), *Ut = reinterpret_cast<double *>(base + szY + szA + szH);
+        PssTimeScope timed(ctx);
+        pss_kernel_begin(ctx, "k_nfm_fwd");
+        {
+            auto kf = swapped ? fused::k_nfm_fwd<true, true> : fused::k_nfm_fwd<true, false>;
+            hipLaunchKernelGGL(kf, dim3((unsigned)tiles), dim3(fused::WG), fused::LDS_BYTES, PSS_STREAM(ctx),
+                               reinterpret_cast<const float2 *>(d_iq), Yf, Uh, Ut, n, n_frames, c, kscale, d_rev,
+                               reinterpret_cast<unsigned *>(ctx->prog), ncu, ctx->prog_epoch, 0L);
+        }
+        pss_kernel_end(ctx);
+        const PssBwdLaunch bwd{flt, false, Yf, Af, n, q, n_out, n_frames, d_pcm, d_audio};
+        if (call.after_fwd == PSS_DEFER_BWD) {  // pss_frame_pipeline_nfm places the backward pass itself (beside the post-process)
+            call.bwd = bwd;
             return pss_hip_check(ctx, hipGetLastError(), "nfm fused launch");
         }
-        const int cpf = (n - 1 + FIR_CH - 1) / FIR_CH;
-        const long items = n_frames * cpf;
-        const long g1 = items < 256L * 64 ? items : 256L * 64;
-        if (!small_batch) {
-            r = pss_ensure_scratch(ctx, szU + szY + szA);
+        if (call.after_fwd == PSS_FORK_AFTER_FWD) {  // pss_spectrum_nfm overlaps the rest
+            r = pss_side_mark(ctx);
             if (r) return r;
-            U = reinterpret_cast<double *>(ctx->scratch);
-            Y = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->scratch) + szU);
-            A = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->scratch) + szU + szY);
+            call.forked = true;
         }
-        if (small_batch) {
-            const size_t szY2 = align256((size_t)n_frames * L * sizeof(double));
-            const size_t szA2 = align256((size_t)n_frames * n_out * sizeof(double));
-            r = pss_ensure_scratch(ctx, szU + szY2 + szA2 + align256((size_t)n_frames * sizeof(double)));
-            if (r) return r;
-            U = reinterpret_cast<double *>(ctx->scratch);
-        }
-        pss_time_begin(ctx);
-        pss_kernel_begin(ctx, "k_nfm_front");
-        hipLaunchKernelGGL(k_nfm_front, dim3((unsigned)g1), dim3(FIR_T), 0, PSS_STREAM(ctx),
-                           reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, cpf, Lp, kscale, swapped, targ);
-        pss_kernel_end(ctx);
-        pss_kernel_begin(ctx, "k_nfm_edge");
-        hipLaunchKernelGGL(k_nfm_edge, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
-                           reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, Lp, kscale, swapped, targ);
-        pss_kernel_end(ctx);
-        if (small_batch) {
-            // few frames: the four sections of a frame on four lanes (16 frames per wavefront), one launch per direction
-            char *b2 = reinterpret_cast<char *>(ctx->scratch);
-            const size_t szY2 = align256((size_t)n_frames * L * sizeof(double));
-            const size_t szA2 = align256((size_t)n_frames * n_out * sizeof(double));
-            double *Y2 = reinterpret_cast<double *>(b2 + szU), *A2 = reinterpret_cast<double *>(b2 + szU + szY2);
-            double *MX = reinterpret_cast<double *>(b2 + szU + szY2 + szA2);
-            const unsigned gs = (unsigned)((n_frames + IS_G - 1) / IS_G);
-            pss_kernel_begin(ctx, "k_iir4_sys");
-            hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), U, Lp, 0, L, L, c, Y2, L, q, n_out, nullptr, n_frames);
-            pss_kernel_end(ctx);
-            pss_kernel_begin(ctx, "k_iir4_sys");
-            hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), Y2, L, 1, L, L - EDGE, c, A2, (long)n_out, q, n_out, MX,
-                               n_frames);
-            pss_kernel_end(ctx);
-            size_t tot = (size_t)n_frames * n_out;
-            size_t g2 = (tot + TPB - 1) / TPB;
-            if (g2 > 16384) g2 = 16384;
-            pss_kernel_begin(ctx, "k_finalize");
-            hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A2, MX, n_out, n_frames, d_pcm, d_audio);
-            pss_kernel_end(ctx);
-            pss_time_end(ctx);
-            return pss_hip_check(ctx, hipGetLastError(), "nfm small-batch launch");
-        }
-        pss_kernel_begin(ctx, "k_nfm_iir");
-        if (b121)
-            hipLaunchKernelGGL(k_nfm_iir<true>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q, n_out,
-                               n_frames, Lp, c, d_pcm, d_audio);
-        else
-            hipLaunchKernelGGL(k_nfm_iir<false>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q, n_out,
-                               n_frames, Lp, c, d_pcm, d_audio);
-        pss_kernel_end(ctx);
-        pss_time_end(ctx);
-        return pss_hip_check(ctx, hipGetLastError(), "nfm launch");
+        r = bwd.launch(ctx);
+        return r ? r : pss_hip_check(ctx, hipGetLastError(), "nfm fused launch");
     }
-    if (mode == PSS_MODE_AM) {
-        if (n_frames == 0) return PSS_OK;
-        const size_t szY = align256((size_t)n_frames * n * sizeof(double));
-        const size_t szM = align256((size_t)n_frames * sizeof(double));
-        const size_t szMu = align256((size_t)n_frames * sizeof(float));
-        const size_t szE = align256((size_t)n_frames * n * sizeof(float));
-        int r = pss_ensure_scratch(ctx, szY + szM + szMu + szE);
-        if (r) return r;
-        char *base = reinterpret_cast<char *>(ctx->scratch);
-        double *Yf = reinterpret_cast<double *>(base);
-        double *mx = reinterpret_cast<double *>(base + szY);
-        float *mu = reinterpret_cast<float *>(base + szY + szM);
-        float *env = reinterpret_cast<float *>(base + szY + szM + szMu);  // |samples| float32, written once by the mean pass
-        double sos[30];
-        pss_am_bandpass_sos(sos);
-        AmCoef c;
-        sos_biquads(c.s, sos, 5);
-        pss_time_begin(ctx);
-        // (pss_demod_power: measure_signal_power of the same frames comes out of the same pass over the IQ)
-        r = ctx->power_out ? launch_pairwise2(ctx, d_iq, n_frames, n, ctx->power_out, mu, env) : launch_pairwise<1>(ctx, d_iq, n_frames, n, mu, env);
-        ctx->power_out = nullptr;
-        if (r) { pss_time_end(ctx); return r; }
-        pss_kernel_begin(ctx, "k_am_grp");
-        hipLaunchKernelGGL(k_am_grp, dim3((unsigned)((n_frames + GRP_G - 1) / GRP_G)), dim3(256), 0, PSS_STREAM(ctx), env, mu, Yf, mx, n, n_frames, c);
+    const int cpf = (n - 1 + FIR_CH - 1) / FIR_CH;
+    const long items = n_frames * cpf;
+    const long g1 = items < 256L * 64 ? items : 256L * 64;
+    // small batch: rows per frame, not per tile, and the frame peaks behind them
+    const size_t szY2 = align256((size_t)n_frames * L * sizeof(double));
+    const size_t szA2 = align256((size_t)n_frames * n_out * sizeof(double));
+    r = pss_ensure_scratch(ctx, path == NfmPath::SmallBatch ? szU + szY2 + szA2 + align256((size_t)n_frames * sizeof(double)) : szU + szY + szA);
+    if (r) return r;
+    char *base = reinterpret_cast<char *>(ctx->scratch);
+    double *U = reinterpret_cast<double *>(base);
+    PssTimeScope timed(ctx);
+    pss_kernel_begin(ctx, "k_nfm_front");
+    hipLaunchKernelGGL(k_nfm_front, dim3((unsigned)g1), dim3(FIR_T), 0, PSS_STREAM(ctx),
+                       reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, cpf, Lp, kscale, swapped, targ);
+    pss_kernel_end(ctx);
+    pss_kernel_begin(ctx, "k_nfm_edge");
+    hipLaunchKernelGGL(k_nfm_edge, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
+                       reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, Lp, kscale, swapped, targ);
+    pss_kernel_end(ctx);
+    if (path == NfmPath::SmallBatch) {
+        // few frames: the four sections of a frame on four lanes (16 frames per wavefront), one launch per direction
+        double *Y2 = reinterpret_cast<double *>(base + szU), *A2 = reinterpret_cast<double *>(base + szU + szY2);
+        double *MX = reinterpret_cast<double *>(base + szU + szY2 + szA2);
+        const unsigned gs = (unsigned)((n_frames + IS_G - 1) / IS_G);
+        pss_kernel_begin(ctx, "k_iir4_sys");
+        hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), U, Lp, 0, L, L, c, Y2, L, q, n_out, nullptr, n_frames);
         pss_kernel_end(ctx);
-        size_t total = (size_t)n_frames * n;
-        size_t g = (total + TPB - 1) / TPB;
-        if (g > 16384) g = 16384;
-        pss_kernel_begin(ctx, "k_finalize");
-        hipLaunchKernelGGL(k_finalize, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), Yf, mx, n, n_frames, d_pcm, d_audio);
+        pss_kernel_begin(ctx, "k_iir4_sys");
+        hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), Y2, L, 1, L, L - EDGE, c, A2, (long)n_out, q, n_out, MX,
+                           n_frames);
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
-        return pss_hip_check(ctx, hipGetLastError(), "am launch");
-    }
-    if (mode == PSS_MODE_USB || mode == PSS_MODE_LSB) {
-        double *taps;
-        int r = ssb_taps(ctx, fs, &taps);
-        if (r) return r;
-        if (n_frames == 0) return PSS_OK;
-        const size_t szY = align256((size_t)n_frames * n * sizeof(double));
-        const size_t szM = align256((size_t)n_frames * sizeof(double));
-        r = pss_ensure_scratch(ctx, szY + szM);
-        if (r) return r;
-        char *base = reinterpret_cast<char *>(ctx->scratch);
-        double *Yf = reinterpret_cast<double *>(base);
-        unsigned long long *mxb = reinterpret_cast<unsigned long long *>(base + szY);
-        const TapsArg targ = make_taps(taps);
-        pss_time_begin(ctx);
-        PSS_HIP(ctx, hipMemsetAsync(mxb, 0, (size_t)n_frames * sizeof(double), PSS_STREAM(ctx)));
-        if (ctx->ssb_hilbert && pss_ssb_fused_supported(n) && !ctx->hilbert_exact && !ctx->iq_c128) {
-            // frames of 8192 / 16 384 samples: FIR, hilbert() round trip, normalisation and PCM in ONE kernel (no float64 round trip of
-            // the FIR output through HBM)
-            r = pss_ssb_hilbert_fused(ctx, d_iq, n_frames, n, taps, d_audio, d_pcm);
-            pss_time_end(ctx);
-            return r ? r : pss_hip_check(ctx, hipGetLastError(), "ssb launch");
-        }
-        const int cpf = (n + 1023) / 1024;
-        long total = n_frames * cpf;
-        long g = total < 16384 ? total : 16384;
-        // (iq_c128: d_iq points at complex128 frames — pss_demod_ssb_c128; the same kernels behind a float64 loader)
-        pss_kernel_begin(ctx, "k_ssb_fir");
-        if (ctx->iq_c128)
-            hipLaunchKernelGGL(k_ssb_fir<double2>, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), reinterpret_cast<const double2 *>(d_iq),
-                               Yf, mxb, n, n_frames, cpf, targ);
-        else
-            hipLaunchKernelGGL(k_ssb_fir<float2>, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq),
-                               Yf, mxb, n, n_frames, cpf, targ);
-        pss_kernel_end(ctx);
-        pss_kernel_begin(ctx, "k_ssb_edge");
-        if (ctx->iq_c128)
-            hipLaunchKernelGGL(k_ssb_edge<double2>, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
-                               reinterpret_cast<const double2 *>(d_iq), Yf, mxb, n, n_frames, targ);
-        else
-            hipLaunchKernelGGL(k_ssb_edge<float2>, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
-                               reinterpret_cast<const float2 *>(d_iq), Yf, mxb, n, n_frames, targ);
-        pss_kernel_end(ctx);
-        // hilbert(np.real(analytical)) and np.real of it again (signal_processing.py:205-213): the FFT round trip of the
-        // reference, executed where a register transform exists for the frame length; numerically the identity on the
-        // real part up to the transforms' rounding (~1e-16), so skipping it (option "ssb_hilbert" = 0, and every other
-        // frame length) changes no int16 sample
-        if (ctx->ssb_hilbert && pss_hilbert_supported(n) && n <= 16384) {
-            // ... with the normalisation and the int16 conversion in the same kernel (the frame is in registers when the frame
-            // peak becomes known): no float64 round trip through HBM, no k_finalize pass
-            r = pss_hilbert_rows(ctx, Yf, n_frames, n, d_audio, 2, nullptr, d_pcm);
-            pss_time_end(ctx);
-            return r ? r : pss_hip_check(ctx, hipGetLastError(), "ssb launch");
-        }
-        if (ctx->ssb_hilbert && pss_hilbert_supported(n)) {
-            // longer read buffers (the reference's default is 32768 samples): the round trip goes through a spectrum in HBM, in
-            // place on Yf, and leaves the frame peak of its real part for k_finalize
-            PSS_HIP(ctx, hipMemsetAsync(mxb, 0, (size_t)n_frames * sizeof(double), PSS_STREAM(ctx)));
-            r = pss_hilbert_rows(ctx, Yf, n_frames, n, Yf, 1, mxb, nullptr);
-            if (r) { pss_time_end(ctx); return r; }
-        }
-        size_t tot = (size_t)n_frames * n;
+        size_t tot = (size_t)n_frames * n_out;
         size_t g2 = (tot + TPB - 1) / TPB;
         if (g2 > 16384) g2 = 16384;
         pss_kernel_begin(ctx, "k_finalize");
-        hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), Yf,
-                           reinterpret_cast<const double *>(mxb), n, n_frames, d_pcm, d_audio);
+        hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A2, MX, n_out, n_frames, d_pcm, d_audio);
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
-        return pss_hip_check(ctx, hipGetLastError(), "ssb launch");
+        return pss_hip_check(ctx, hipGetLastError(), "nfm small-batch launch");
     }
-    if (mode == PSS_MODE_WFM) {
-        const int q = (int)(fs / ctx->target_rate);
-        if (q < 1) return pss_fail(ctx, PSS_E_ARG, "WFM: sample rate below the target rate");
-        const bool q1 = q == 1;     // the reference skips its decimate() stage (:152-155): the plain kernels, normalisation of the de-emphasised rows
-        if (n - 1 <= EDGE)
-            return pss_fail(ctx, PSS_E_PADLEN, "The length of the input vector x must be greater than padlen, which is 27.");
-        PssWfmFilt *wf;
-        int r = wfm_filters(ctx, fs, &wf);
+    double *Y = reinterpret_cast<double *>(base + szU), *A = reinterpret_cast<double *>(base + szU + szY);
+    pss_kernel_begin(ctx, "k_nfm_iir");
+    if (b121)
+        hipLaunchKernelGGL(k_nfm_iir<true>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q, n_out,
+                           n_frames, Lp, c, d_pcm, d_audio);
+    else
+        hipLaunchKernelGGL(k_nfm_iir<false>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q, n_out,
+                           n_frames, Lp, c, d_pcm, d_audio);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "nfm launch");
+}
+
+// d_power (nullable; pss_demod_power): measure_signal_power of the same frames comes out of the same pass over the IQ
+static int demod_am(pss_ctx *ctx, const float *d_iq, long n_frames, int n, int16_t *d_pcm, double *d_audio, float *d_power)
+{
+    if (n_frames == 0) return PSS_OK;
+    const size_t szY = align256((size_t)n_frames * n * sizeof(double));
+    const size_t szM = align256((size_t)n_frames * sizeof(double));
+    const size_t szMu = align256((size_t)n_frames * sizeof(float));
+    const size_t szE = align256((size_t)n_frames * n * sizeof(float));
+    int r = pss_ensure_scratch(ctx, szY + szM + szMu + szE);
+    if (r) return r;
+    char *base = reinterpret_cast<char *>(ctx->scratch);
+    double *Yf = reinterpret_cast<double *>(base), *mx = reinterpret_cast<double *>(base + szY);
+    float *mu = reinterpret_cast<float *>(base + szY + szM);
+    float *env = reinterpret_cast<float *>(base + szY + szM + szMu);  // |samples| float32, written once by the mean pass
+    double sos[30];
+    pss_am_bandpass_sos(sos);
+    AmCoef c;
+    sos_biquads(c.s, sos, 5);
+    PssTimeScope timed(ctx);
+    r = d_power ? launch_pairwise2(ctx, d_iq, n_frames, n, d_power, mu, env) : launch_pairwise<1>(ctx, d_iq, n_frames, n, mu, env);
+    if (r) return r;
+    pss_kernel_begin(ctx, "k_am_grp");
+    hipLaunchKernelGGL(k_am_grp, dim3((unsigned)((n_frames + GRP_G - 1) / GRP_G)), dim3(256), 0, PSS_STREAM(ctx), env, mu, Yf, mx, n, n_frames, c);
+    pss_kernel_end(ctx);
+    size_t total = (size_t)n_frames * n;
+    size_t g = (total + TPB - 1) / TPB;
+    if (g > 16384) g = 16384;
+    pss_kernel_begin(ctx, "k_finalize");
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), Yf, mx, n, n_frames, d_pcm, d_audio);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "am launch");
+}
+
+// iq.f64: complex128 frames (pss_demod_ssb_c128) — the same kernels behind a float64 loader
+static int demod_ssb(pss_ctx *ctx, PssIq iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio)
+{
+    double *taps;
+    int r = ssb_taps(ctx, fs, &taps);
+    if (r) return r;
+    if (n_frames == 0) return PSS_OK;
+    const size_t szY = align256((size_t)n_frames * n * sizeof(double));
+    const size_t szM = align256((size_t)n_frames * sizeof(double));
+    r = pss_ensure_scratch(ctx, szY + szM);
+    if (r) return r;
+    char *base = reinterpret_cast<char *>(ctx->scratch);
+    double *Yf = reinterpret_cast<double *>(base);
+    unsigned long long *mxb = reinterpret_cast<unsigned long long *>(base + szY);
+    const TapsArg targ = make_taps(taps);
+    PssTimeScope timed(ctx);
+    PSS_HIP(ctx, hipMemsetAsync(mxb, 0, (size_t)n_frames * sizeof(double), PSS_STREAM(ctx)));
+    if (ctx->ssb_hilbert && pss_ssb_fused_supported(n) && !ctx->hilbert_exact && !iq.f64) {
+        // frames of 8192 / 16 384 samples: FIR, hilbert() round trip, normalisation and PCM in ONE kernel (no float64 round trip of
+        // the FIR output through HBM)
+        r = pss_ssb_hilbert_fused(ctx, iq.f32, n_frames, n, taps, d_audio, d_pcm);
+        return r ? r : pss_hip_check(ctx, hipGetLastError(), "ssb launch");
+    }
+    const int cpf = (n + 1023) / 1024;
+    long total = n_frames * cpf;
+    long g = total < 16384 ? total : 16384;
+    pss_kernel_begin(ctx, "k_ssb_fir");
+    if (iq.f64)
+        hipLaunchKernelGGL(k_ssb_fir<double2>, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), reinterpret_cast<const double2 *>(iq.f64),
+                           Yf, mxb, n, n_frames, cpf, targ);
+    else
+        hipLaunchKernelGGL(k_ssb_fir<float2>, dim3((unsigned)g), dim3(TPB), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(iq.f32),
+                           Yf, mxb, n, n_frames, cpf, targ);
+    pss_kernel_end(ctx);
+    pss_kernel_begin(ctx, "k_ssb_edge");
+    if (iq.f64)
+        hipLaunchKernelGGL(k_ssb_edge<double2>, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
+                           reinterpret_cast<const double2 *>(iq.f64), Yf, mxb, n, n_frames, targ);
+    else
+        hipLaunchKernelGGL(k_ssb_edge<float2>, dim3((unsigned)n_frames), dim3(128), 0, PSS_STREAM(ctx),
+                           reinterpret_cast<const float2 *>(iq.f32), Yf, mxb, n, n_frames, targ);
+    pss_kernel_end(ctx);
+    // hilbert(np.real(analytical)) and np.real of it again (signal_processing.py:205-213): the FFT round trip of the
+    // reference, executed where a register transform exists for the frame length; numerically the identity on the
+    // real part up to the transforms' rounding (~1e-16), so skipping it (option "ssb_hilbert" = 0, and every other
+    // frame length) changes no int16 sample
+    if (ctx->ssb_hilbert && pss_hilbert_supported(n) && n <= 16384) {
+        // ... with the normalisation and the int16 conversion in the same kernel (the frame is in registers when the frame
+        // peak becomes known): no float64 round trip through HBM, no k_finalize pass
+        r = pss_hilbert_rows(ctx, Yf, n_frames, n, d_audio, 2, nullptr, d_pcm);
+        return r ? r : pss_hip_check(ctx, hipGetLastError(), "ssb launch");
+    }
+    if (ctx->ssb_hilbert && pss_hilbert_supported(n)) {
+        // longer read buffers (the reference's default is 32768 samples): the round trip goes through a spectrum in HBM, in
+        // place on Yf, and leaves the frame peak of its real part for k_finalize
+        PSS_HIP(ctx, hipMemsetAsync(mxb, 0, (size_t)n_frames * sizeof(double), PSS_STREAM(ctx)));
+        r = pss_hilbert_rows(ctx, Yf, n_frames, n, Yf, 1, mxb, nullptr);
         if (r) return r;
-        PssNfmFilt *flt;  // the decimator (cheby1 + zi) is the NFM one
-        r = nfm_filters(ctx, fs, &flt);
+    }
+    size_t tot = (size_t)n_frames * n;
+    size_t g2 = (tot + TPB - 1) / TPB;
+    if (g2 > 16384) g2 = 16384;
+    pss_kernel_begin(ctx, "k_finalize");
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), Yf,
+                       reinterpret_cast<const double *>(mxb), n, n_frames, d_pcm, d_audio);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "ssb launch");
+}
+
+// The small-batch kernel's lanes: one per filter SECTION of a frame pair (k_wfm_mrg)
+static MrgArg wfm_mrg_lanes(const WfmCoef &wc, const NfmCoef &c)
+{
+    MrgArg am;
+    const Biquad idle{0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = 0; i < 27; i++) am.lane[i] = MrgLane{idle, 0, 1, 0, 1, -1, 0, 0.0, 0.0, -1};
+    // pass 1: a (rows D1 -> 2 -> 3 -> A ring), pilot band-pass (D1 -> 13..17) + 1-pole (17 -> Y), m (D1 -> 20..23 -> Mo ring)
+    for (int i = 0; i < 3; i++)
+        am.lane[i] = MrgLane{wc.lp[i], i == 0 ? WM_D1 : 1 + i, i == 0 ? 2 : 1, i == 2 ? WM_A : 2 + i, i == 2 ? 9 : 1, i, 0, 0.0, 0.0, -1};
+    for (int i = 0; i < 5; i++) am.lane[3 + i] = MrgLane{wc.pil[i], i == 0 ? WM_D1 : 12 + i, i == 0 ? 2 : 1, 13 + i, 1, i, 0, 0.0, 0.0, -1};
+    am.lane[8] = MrgLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 17, 1, WM_Y, 2, 5, 1, 0.0, 0.0, -1};            // lfilter([1],[1,-0.99]) -> y
+    for (int i = 0; i < 5; i++)
+        am.lane[9 + i] = MrgLane{wc.lmr[i], i == 0 ? WM_D1 : 19 + i, i == 0 ? 2 : 1, i == 4 ? WM_MO : 20 + i, i == 4 ? 3 : 1, i, 0, 0.0, 0.0, -1};
+    // pass 2: LP15k on m * 2p (D2 -> 29 -> 30 -> LP), de-emphasis per channel (DL -> UL, DR -> UR)
+    for (int i = 0; i < 3; i++)
+        am.lane[14 + i] = MrgLane{wc.lp[i], i == 0 ? WM_D2 : 28 + i, i == 0 ? 2 : 1, i == 2 ? WM_LP : 29 + i, i == 2 ? 2 : 1, 7 + i, 0, 0.0, 0.0, -1};
+    am.lane[17] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DL, 2, WM_UL, 3, 11, 1, 0.0, 0.0, -1};
+    am.lane[18] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DR, 2, WM_UR, 3, 11, 1, 0.0, 0.0, -1};
+    // forward half of the zero-phase decimator, per channel (EL -> 47 -> 48 -> 49 -> YL, ER -> 50 -> 51 -> 52 -> YR)
+    for (int ch = 0; ch < 2; ch++)
+        for (int i = 0; i < 4; i++)
+            am.lane[19 + 4 * ch + i] = MrgLane{c.s[i], i == 0 ? (ch ? WM_ER : WM_EL) : 46 + 3 * ch + i, i == 0 ? 2 : 1,
+                                               i == 3 ? (ch ? WM_YR : WM_YL) : 47 + 3 * ch + i, i == 3 ? 2 : 1, 13 + i, 0, c.zi[2 * i], c.zi[2 * i + 1], ch};
+    return am;
+}
+
+static int demod_wfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, PssDemodCall &call)
+{
+    const int q = (int)(fs / ctx->target_rate);
+    if (q < 1) return pss_fail(ctx, PSS_E_ARG, "WFM: sample rate below the target rate");
+    if (n - 1 <= EDGE) return pss_fail(ctx, PSS_E_PADLEN, "The length of the input vector x must be greater than padlen, which is 27.");
+    PssWfmFilt *wf;
+    int r = wfm_filters(ctx, fs, &wf);
+    if (r) return r;
+    PssNfmFilt *flt;  // the decimator (cheby1 + zi) is the NFM one
+    r = nfm_filters(ctx, fs, &flt);
+    if (r) return r;
+    if (n_frames == 0) return PSS_OK;
+    const long tiles = (n_frames + TILE - 1) / TILE;
+    const long rows = 2 * n_frames, tiles2 = (rows + TILE - 1) / TILE;
+    const int n_out = (n - 1 + q - 1) / q;
+    const long L = (long)(n - 1) + 2 * EDGE;
+    const long Lp = (L + 1) & ~1L;
+    const bool b121 = sections_b121(flt->sos);
+    // factor one: the reference skips its decimate() stage (:152-155): the plain kernels, normalisation of the de-emphasised rows;
+    // small batch: a handful of frames; fused: decimator sections 1..3 with numerator [1, 2, 1]
+    const WfmPath path = q == 1 ? WfmPath::FactorOne
+                       : (!ctx->no_small_batch && n_frames <= ctx->wfm_small_batch_max) ? WfmPath::SmallBatch
+                       : (!ctx->no_wfm_fused && b121) ? WfmPath::Fused : WfmPath::Plain;
+    const bool plain_front = path == WfmPath::Plain || path == WfmPath::FactorOne;   // k_wfm_front leaves u[] in memory
+    const size_t szU = plain_front ? align256((size_t)rows * Lp * sizeof(double)) : 0;
+    const long T2 = 2 * tiles;  // the fused path keeps the channels of a tile in two separate row blocks (T2 >= tiles2)
+    const size_t szY = align256((size_t)T2 * L * TILE * sizeof(double));
+    const size_t szA = align256((size_t)T2 * n_out * TILE * sizeof(double));
+    const size_t szM = align256((size_t)T2 * TILE * sizeof(double));
+    r = pss_ensure_scratch(ctx, szU + szY + szA + szM);   // (covers the small-batch path's per-row blocks: T2 * TILE >= rows)
+    if (r) return r;
+    char *base = reinterpret_cast<char *>(ctx->scratch);
+    WfmCoef wc;
+    sos_biquads(wc.lp, wf->lp, 3);
+    sos_biquads(wc.pil, wf->pilot, 5);
+    sos_biquads(wc.lmr, wf->lmr, 5);
+    wc.b0d = 1.0 - wf->alpha;
+    wc.a1d = -wf->alpha;
+    const NfmCoef c = nfm_coef(flt);
+    const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;
+    // SciPy's zero pairing gives every Butterworth SOS the same numerator shapes; anything else takes the generic steps
+    auto is_num = [](const double *row, double b0, double b1, double b2) { return row[0] == b0 && row[1] == b1 && row[2] == b2; };
+    bool spec = is_num(wf->lp + 6, 1, 2, 1) && is_num(wf->lp + 12, 1, 1, 0);
+    for (const double *bp : {wf->pilot, wf->lmr})
+        spec = spec && is_num(bp + 6, 1, 2, 1) && is_num(bp + 12, 1, 0, -1) && is_num(bp + 18, 1, -2, 1) && is_num(bp + 24, 1, -2, 1);
+    PssTimeScope timed(ctx);
+    // demodulate_signal's dispatcher (call.correct: pss_demod_signal, pss_frame_pipeline): d_iq holds the frames as read and iq_correction comes
+    // first (signal_processing.py:222-225).  The fused forward kernel corrects the samples as it loads them, from a pre-pass that leaves five
+    // scalars per frame (no corrected copy of the batch: 8 bytes per sample neither written nor read back); the other kernel families
+    // read a corrected copy from the context's scratch.
+    const float *scal = nullptr;
+    if (call.correct) {
+        if (path == WfmPath::Fused && !ctx->wfm_corr_copy) {
+            r = pss_ensure_buffer(ctx, &ctx->scratch_iqc, &ctx->scratch_iqc_bytes, (size_t)n_frames * 8 * sizeof(float), "iq_correction scalars");
+            if (!r) r = iq_correction_launch(ctx, d_iq, n_frames, n, nullptr, nullptr, reinterpret_cast<float *>(ctx->scratch_iqc));
+            scal = reinterpret_cast<const float *>(ctx->scratch_iqc);
+        } else {
+            r = pss_ensure_buffer(ctx, &ctx->scratch_iqc, &ctx->scratch_iqc_bytes, (size_t)n_frames * n * sizeof(float2), "iq_correction scratch");
+            if (!r) r = iq_correction_launch(ctx, d_iq, n_frames, n, reinterpret_cast<float *>(ctx->scratch_iqc), nullptr, nullptr);
+            d_iq = reinterpret_cast<const float *>(ctx->scratch_iqc);
+        }
         if (r) return r;
-        if (n_frames == 0) return PSS_OK;
-        const long rows = 2 * n_frames, tiles2 = (rows + TILE - 1) / TILE;
-        const int n_out = (n - 1 + q - 1) / q;
-        const long L = (long)(n - 1) + 2 * EDGE;
-        const long Lp = (L + 1) & ~1L;
-        const size_t szU = align256((size_t)rows * Lp * sizeof(double));
-        const long T2 = 2 * tiles;  // the fused path keeps the channels of a tile in two separate row blocks (T2 >= tiles2)
-        const size_t szY = align256((size_t)T2 * L * TILE * sizeof(double));
-        const size_t szA = align256((size_t)T2 * n_out * TILE * sizeof(double));
-        const size_t szM = align256((size_t)T2 * TILE * sizeof(double));
-        const bool b121 = sections_b121(flt->sos);
-        r = pss_ensure_scratch(ctx, ((ctx->no_wfm_fused || !b121 || q1) ? szU : 0) + szY + szA + szM);
-        if (r) return r;
-        char *base = reinterpret_cast<char *>(ctx->scratch);
-        double *U = reinterpret_cast<double *>(base), *Y = reinterpret_cast<double *>(base + szU);
-        double *A = reinterpret_cast<double *>(base + szU + szY), *MX = reinterpret_cast<double *>(base + szU + szY + szA);
-        WfmCoef wc;
-        sos_biquads(wc.lp, wf->lp, 3);
-        sos_biquads(wc.pil, wf->pilot, 5);
-        sos_biquads(wc.lmr, wf->lmr, 5);
-        wc.b0d = 1.0 - wf->alpha;
-        wc.a1d = -wf->alpha;
-        NfmCoef c;
-        sos_biquads(c.s, flt->sos, 4);
-        for (int i = 0; i < 8; i++) c.zi[i] = flt->zi[i];
-        const int swapped = ((long)(n - 1) * 8 >= 262144) ? 1 : 0;
-        // SciPy's zero pairing gives every Butterworth SOS the same numerator shapes; anything else takes the generic steps
-        auto is_num = [](const double *row, double b0, double b1, double b2) { return row[0] == b0 && row[1] == b1 && row[2] == b2; };
-        bool spec = is_num(wf->lp + 6, 1, 2, 1) && is_num(wf->lp + 12, 1, 1, 0);
-        for (const double *bp : {wf->pilot, wf->lmr})
-            spec = spec && is_num(bp + 6, 1, 2, 1) && is_num(bp + 12, 1, 0, -1) && is_num(bp + 18, 1, -2, 1) && is_num(bp + 24, 1, -2, 1);
-        pss_time_begin(ctx);
-        // demodulate_signal's dispatcher (pss_demod_signal, pss_frame_pipeline): d_iq holds the frames as read and iq_correction comes first
-        // (signal_processing.py:222-225).  The fused forward kernel corrects the samples as it loads them, from a pre-pass that leaves five
-        // scalars per frame (no corrected copy of the batch: 8 bytes per sample neither written nor read back); the other kernel families
-        // read a corrected copy from the context's scratch.
-        const bool correct = ctx->wfm_correct;
-        ctx->wfm_correct = false;
-        ctx->wfm_scal = nullptr;
-        if (correct) {
-            const bool fused_path = !(!ctx->no_small_batch && n_frames <= ctx->wfm_small_batch_max) && !ctx->no_wfm_fused && b121 && !ctx->wfm_corr_copy && !q1;
-            if (fused_path) {
-                r = pss_ensure_buffer(ctx, &ctx->scratch_iqc, &ctx->scratch_iqc_bytes, (size_t)n_frames * 8 * sizeof(float), "iq_correction scalars");
-                if (!r) r = iq_correction_launch(ctx, d_iq, n_frames, n, nullptr, nullptr, reinterpret_cast<float *>(ctx->scratch_iqc));
-                ctx->wfm_scal = reinterpret_cast<const float *>(ctx->scratch_iqc);
-            } else {
-                r = pss_ensure_buffer(ctx, &ctx->scratch_iqc, &ctx->scratch_iqc_bytes, (size_t)n_frames * n * sizeof(float2), "iq_correction scratch");
-                if (!r) r = iq_correction_launch(ctx, d_iq, n_frames, n, reinterpret_cast<float *>(ctx->scratch_iqc), nullptr, nullptr);
-                d_iq = reinterpret_cast<const float *>(ctx->scratch_iqc);
-            }
-            if (r) { pss_time_end(ctx); return r; }
-        }
-        if (!q1 && !ctx->no_small_batch && n_frames <= ctx->wfm_small_batch_max) {
-            // a handful of frames: one lane per filter SECTION instead of one lane per frame (k_wfm_mrg up to the forward half of the
-            // decimator, then its backward half in k_iir4_sys)
-            const size_t szY2 = align256((size_t)rows * L * sizeof(double));
-            const size_t szA2 = align256((size_t)rows * n_out * sizeof(double));
-            r = pss_ensure_scratch(ctx, szY2 + szA2 + align256((size_t)rows * sizeof(double)));
-            if (r) return r;
-            char *b2 = reinterpret_cast<char *>(ctx->scratch);
-            double *Y2 = reinterpret_cast<double *>(b2), *A2 = reinterpret_cast<double *>(b2 + szY2), *MX2 = reinterpret_cast<double *>(b2 + szY2 + szA2);
-            MrgArg am;
-            const Biquad idle{0.0, 0.0, 0.0, 0.0, 0.0};
-            for (int i = 0; i < 27; i++) am.lane[i] = MrgLane{idle, 0, 1, 0, 1, -1, 0, 0.0, 0.0, -1};
-            // pass 1: a (rows D1 -> 2 -> 3 -> A ring), pilot band-pass (D1 -> 13..17) + 1-pole (17 -> Y), m (D1 -> 20..23 -> Mo ring)
-            for (int i = 0; i < 3; i++)
-                am.lane[i] = MrgLane{wc.lp[i], i == 0 ? WM_D1 : 1 + i, i == 0 ? 2 : 1, i == 2 ? WM_A : 2 + i, i == 2 ? 9 : 1, i, 0, 0.0, 0.0, -1};
-            for (int i = 0; i < 5; i++) am.lane[3 + i] = MrgLane{wc.pil[i], i == 0 ? WM_D1 : 12 + i, i == 0 ? 2 : 1, 13 + i, 1, i, 0, 0.0, 0.0, -1};
-            am.lane[8] = MrgLane{Biquad{1.0, 0.0, 0.0, -0.99, 0.0}, 17, 1, WM_Y, 2, 5, 1, 0.0, 0.0, -1};            // lfilter([1],[1,-0.99]) -> y
-            for (int i = 0; i < 5; i++)
-                am.lane[9 + i] = MrgLane{wc.lmr[i], i == 0 ? WM_D1 : 19 + i, i == 0 ? 2 : 1, i == 4 ? WM_MO : 20 + i, i == 4 ? 3 : 1, i, 0, 0.0, 0.0, -1};
-            // pass 2: LP15k on m * 2p (D2 -> 29 -> 30 -> LP), de-emphasis per channel (DL -> UL, DR -> UR)
-            for (int i = 0; i < 3; i++)
-                am.lane[14 + i] = MrgLane{wc.lp[i], i == 0 ? WM_D2 : 28 + i, i == 0 ? 2 : 1, i == 2 ? WM_LP : 29 + i, i == 2 ? 2 : 1, 7 + i, 0, 0.0, 0.0, -1};
-            am.lane[17] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DL, 2, WM_UL, 3, 11, 1, 0.0, 0.0, -1};
-            am.lane[18] = MrgLane{Biquad{wc.b0d, 0.0, 0.0, wc.a1d, 0.0}, WM_DR, 2, WM_UR, 3, 11, 1, 0.0, 0.0, -1};
-            // forward half of the zero-phase decimator, per channel (EL -> 47 -> 48 -> 49 -> YL, ER -> 50 -> 51 -> 52 -> YR)
-            for (int ch = 0; ch < 2; ch++)
-                for (int i = 0; i < 4; i++)
-                    am.lane[19 + 4 * ch + i] = MrgLane{c.s[i], i == 0 ? (ch ? WM_ER : WM_EL) : 46 + 3 * ch + i, i == 0 ? 2 : 1,
-                                                       i == 3 ? (ch ? WM_YR : WM_YL) : 47 + 3 * ch + i, i == 3 ? 2 : 1, 13 + i, 0, c.zi[2 * i], c.zi[2 * i + 1], ch};
-            const unsigned gm = (unsigned)((n_frames + 1) / 2);
-            pss_kernel_begin(ctx, "k_wfm_casc");
-            hipLaunchKernelGGL(k_wfm_mrg, dim3(gm), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Y2, n, n_frames, L,
-                               swapped, am);
-            pss_kernel_end(ctx);
-            const unsigned gs = (unsigned)((rows + IS_G - 1) / IS_G);
-            pss_kernel_begin(ctx, "k_iir4_sys");
-            hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), Y2, L, 1, L, L - EDGE, c, A2, (long)n_out, q, n_out, MX2, rows);
-            pss_kernel_end(ctx);
-            size_t tot = (size_t)n_frames * n_out;
-            size_t g2 = (tot + TPB - 1) / TPB;
-            if (g2 > 16384) g2 = 16384;
-            pss_kernel_begin(ctx, "k_wfm_finalize");
-            hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A2, MX2, n_out, n_frames, 2, d_pcm, d_audio);
-            pss_kernel_end(ctx);
-            pss_time_end(ctx);
-            return pss_hip_check(ctx, hipGetLastError(), "wfm small-batch launch");
-        }
-        if (!q1 && !ctx->no_wfm_fused && b121) {
-            // fused path (decimator sections 1..3 with numerator [1, 2, 1]): forward decimator pass inside the front kernel, y_fwd planar-transposed, u[] never stored
-            double *Yf = reinterpret_cast<double *>(base), *Af = reinterpret_cast<double *>(base + szY);
-            double *MXf = reinterpret_cast<double *>(base + szY + szA);
-            // ctx->wfm_scal (pss_demod_signal / pss_frame_pipeline, WFM): d_iq holds the frames as read, corrected on the fly by the kernel
-            const float *scal = ctx->wfm_scal;
-            ctx->wfm_scal = nullptr;
-            auto kf = scal ? (spec ? wfmf::k_wfm_fwd<true, true, true> : wfmf::k_wfm_fwd<false, true, true>)
-                           : (spec ? wfmf::k_wfm_fwd<true, true> : wfmf::k_wfm_fwd<false, true>);
-            pss_kernel_begin(ctx, "k_wfm_fwd");
-            hipLaunchKernelGGL(kf, dim3((unsigned)tiles), dim3(TILE), wfmf::LDS_BYTES, PSS_STREAM(ctx),
-                               reinterpret_cast<const float2 *>(d_iq), Yf, n, n_frames, swapped, wc, c, scal);
-            pss_kernel_end(ctx);
-            auto launch_bwd = [=]() -> int {
-                pss_kernel_begin(ctx, "k_nfm_bwd");
-                hipLaunchKernelGGL((fused::k_nfm_bwd<true, true>), dim3((unsigned)tiles), dim3(2 * TILE), 0, PSS_STREAM(ctx), Yf, Af,
-                                   n, q, n_out, n_frames, c, d_pcm, d_audio);      // both channels of a tile: joint normalisation + stereo PCM inside
-                pss_kernel_end(ctx);
-                return pss_hip_check(ctx, hipGetLastError(), "wfm fused launch (backward)");
-            };
-            if (ctx->defer_bwd) {  // pss_frame_pipeline places the backward pass + the L / R normalisation itself (beside the display chain)
-                ctx->pending_bwd = launch_bwd;
-                pss_time_end(ctx);
-                return pss_hip_check(ctx, hipGetLastError(), "wfm fused launch");
-            }
-            const int rb = launch_bwd();
-            pss_time_end(ctx);
-            return rb;
-        }
-        pss_kernel_begin(ctx, "k_wfm_front");
-        hipLaunchKernelGGL(spec ? k_wfm_front<true> : k_wfm_front<false>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx),
-                           reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, Lp, swapped, wc);
+    }
+    if (path == WfmPath::SmallBatch) {
+        // a handful of frames: one lane per filter SECTION instead of one lane per frame (k_wfm_mrg up to the forward half of the
+        // decimator, then its backward half in k_iir4_sys)
+        const size_t szY2 = align256((size_t)rows * L * sizeof(double));
+        const size_t szA2 = align256((size_t)rows * n_out * sizeof(double));
+        double *Y2 = reinterpret_cast<double *>(base), *A2 = reinterpret_cast<double *>(base + szY2), *MX2 = reinterpret_cast<double *>(base + szY2 + szA2);
+        const MrgArg am = wfm_mrg_lanes(wc, c);
+        const unsigned gm = (unsigned)((n_frames + 1) / 2);
+        pss_kernel_begin(ctx, "k_wfm_casc");
+        hipLaunchKernelGGL(k_wfm_mrg, dim3(gm), dim3(128), 0, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), Y2, n, n_frames, L,
+                           swapped, am);
         pss_kernel_end(ctx);
-        if (q1) {
-            // no decimate() stage: the de-emphasised channels are normalised as they are (n_out = n - 1 samples per channel)
-            pss_kernel_begin(ctx, "k_wfm_rows_q1");
-            hipLaunchKernelGGL(k_wfm_rows_q1, dim3((unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192)), dim3(256), 0, PSS_STREAM(ctx), U, Lp, n - 1, rows, A, MX);
-            pss_kernel_end(ctx);
-            size_t tot1 = (size_t)n_frames * n_out;
-            size_t g1 = (tot1 + TPB - 1) / TPB;
-            if (g1 > 16384) g1 = 16384;
-            pss_kernel_begin(ctx, "k_wfm_finalize");
-            hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g1), dim3(TPB), 0, PSS_STREAM(ctx), A, MX, n_out, n_frames, 2, d_pcm, d_audio);
-            pss_kernel_end(ctx);
-            pss_time_end(ctx);
-            return pss_hip_check(ctx, hipGetLastError(), "wfm (decimation factor 1) launch");
-        }
-        pss_kernel_begin(ctx, "k_nfm_iir");
-        if (b121)
-            hipLaunchKernelGGL((k_nfm_iir<true, true>), dim3((unsigned)tiles2), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q,
-                               n_out, rows, Lp, c, nullptr, MX);
-        else
-            hipLaunchKernelGGL((k_nfm_iir<false, true>), dim3((unsigned)tiles2), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q,
-                               n_out, rows, Lp, c, nullptr, MX);
+        const unsigned gs = (unsigned)((rows + IS_G - 1) / IS_G);
+        pss_kernel_begin(ctx, "k_iir4_sys");
+        hipLaunchKernelGGL(k_iir4_sys, dim3(gs), dim3(128), 0, PSS_STREAM(ctx), Y2, L, 1, L, L - EDGE, c, A2, (long)n_out, q, n_out, MX2, rows);
         pss_kernel_end(ctx);
         size_t tot = (size_t)n_frames * n_out;
         size_t g2 = (tot + TPB - 1) / TPB;
         if (g2 > 16384) g2 = 16384;
         pss_kernel_begin(ctx, "k_wfm_finalize");
-        hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A, MX, n_out, n_frames, 0, d_pcm,
-                           d_audio);
+        hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A2, MX2, n_out, n_frames, 2, d_pcm, d_audio);
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
-        return pss_hip_check(ctx, hipGetLastError(), "wfm launch");
+        return pss_hip_check(ctx, hipGetLastError(), "wfm small-batch launch");
     }
+    if (path == WfmPath::Fused) {
+        // forward decimator pass inside the front kernel, y_fwd planar-transposed, u[] never stored
+        double *Yf = reinterpret_cast<double *>(base), *Af = reinterpret_cast<double *>(base + szY);
+        // scal (pss_demod_signal / pss_frame_pipeline, WFM): d_iq holds the frames as read, corrected on the fly by the kernel
+        auto kf = scal ? (spec ? wfmf::k_wfm_fwd<true, true, true> : wfmf::k_wfm_fwd<false, true, true>)
+                       : (spec ? wfmf::k_wfm_fwd<true, true> : wfmf::k_wfm_fwd<false, true>);
+        pss_kernel_begin(ctx, "k_wfm_fwd");
+        hipLaunchKernelGGL(kf, dim3((unsigned)tiles), dim3(TILE), wfmf::LDS_BYTES, PSS_STREAM(ctx),
+                           reinterpret_cast<const float2 *>(d_iq), Yf, n, n_frames, swapped, wc, c, scal);
+        pss_kernel_end(ctx);
+        const PssBwdLaunch bwd{flt, true, Yf, Af, n, q, n_out, n_frames, d_pcm, d_audio};
+        if (call.after_fwd == PSS_DEFER_BWD) {  // pss_frame_pipeline places the backward pass + the L / R normalisation itself (beside the display chain)
+            call.bwd = bwd;
+            return pss_hip_check(ctx, hipGetLastError(), "wfm fused launch");
+        }
+        return bwd.launch(ctx);
+    }
+    double *U = reinterpret_cast<double *>(base), *Y = reinterpret_cast<double *>(base + szU);
+    double *A = reinterpret_cast<double *>(base + szU + szY), *MX = reinterpret_cast<double *>(base + szU + szY + szA);
+    pss_kernel_begin(ctx, "k_wfm_front");
+    hipLaunchKernelGGL(spec ? k_wfm_front<true> : k_wfm_front<false>, dim3((unsigned)tiles), dim3(TILE), 0, PSS_STREAM(ctx),
+                       reinterpret_cast<const float2 *>(d_iq), U, n, n_frames, Lp, swapped, wc);
+    pss_kernel_end(ctx);
+    if (path == WfmPath::FactorOne) {
+        // no decimate() stage: the de-emphasised channels are normalised as they are (n_out = n - 1 samples per channel)
+        pss_kernel_begin(ctx, "k_wfm_rows_q1");
+        hipLaunchKernelGGL(k_wfm_rows_q1, dim3((unsigned)((rows + 3) / 4 < 8192 ? (rows + 3) / 4 : 8192)), dim3(256), 0, PSS_STREAM(ctx), U, Lp, n - 1, rows, A, MX);
+        pss_kernel_end(ctx);
+        size_t tot1 = (size_t)n_frames * n_out;
+        size_t g1 = (tot1 + TPB - 1) / TPB;
+        if (g1 > 16384) g1 = 16384;
+        pss_kernel_begin(ctx, "k_wfm_finalize");
+        hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g1), dim3(TPB), 0, PSS_STREAM(ctx), A, MX, n_out, n_frames, 2, d_pcm, d_audio);
+        pss_kernel_end(ctx);
+        return pss_hip_check(ctx, hipGetLastError(), "wfm (decimation factor 1) launch");
+    }
+    pss_kernel_begin(ctx, "k_nfm_iir");
+    if (b121)
+        hipLaunchKernelGGL((k_nfm_iir<true, true>), dim3((unsigned)tiles2), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q,
+                           n_out, rows, Lp, c, nullptr, MX);
+    else
+        hipLaunchKernelGGL((k_nfm_iir<false, true>), dim3((unsigned)tiles2), dim3(TILE), 0, PSS_STREAM(ctx), U, Y, A, n, q,
+                           n_out, rows, Lp, c, nullptr, MX);
+    pss_kernel_end(ctx);
+    size_t tot = (size_t)n_frames * n_out;
+    size_t g2 = (tot + TPB - 1) / TPB;
+    if (g2 > 16384) g2 = 16384;
+    pss_kernel_begin(ctx, "k_wfm_finalize");
+    hipLaunchKernelGGL(k_wfm_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), A, MX, n_out, n_frames, 0, d_pcm,
+                       d_audio);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "wfm launch");
+}
+
+int pss_demod_run(pss_ctx *ctx, int mode, PssIq iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, PssDemodCall *call)
+{
+    if (n_frames < 0 || n < 1 || (n_frames > 0 && !iq.f32 && !iq.f64)) return pss_fail(ctx, PSS_E_ARG, "bad demod arguments");
+    if (n_frames > 0 && !d_pcm && !d_audio) return pss_fail(ctx, PSS_E_ARG, "both outputs are null");
+    PssDemodCall plain;
+    if (!call) call = &plain;
+    const bool ssb = mode == PSS_MODE_USB || mode == PSS_MODE_LSB;
+    if (iq.f64 && !ssb) return pss_fail(ctx, PSS_E_ARG, "complex128 frames: SSB only");
+    if (mode == PSS_MODE_NFM) return demod_nfm(ctx, iq.f32, n_frames, n, fs, d_pcm, d_audio, *call);
+    if (mode == PSS_MODE_AM) return demod_am(ctx, iq.f32, n_frames, n, d_pcm, d_audio, call->d_power);
+    if (ssb) return demod_ssb(ctx, iq, n_frames, n, fs, d_pcm, d_audio);
+    if (mode == PSS_MODE_WFM) return demod_wfm(ctx, iq.f32, n_frames, n, fs, d_pcm, d_audio, *call);
     return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
 }
 
-// demodulate_signal (signal_processing.py:220-240): the voice modes go straight to their demodulator, every other mode
-// is IQ-corrected first (:222-225).
-extern "C" int pss_demod_signal(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm,
-                                double *d_audio)
+extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio)
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
-    if (mode != PSS_MODE_WFM) return pss_demod(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);
-    if (n_frames < 0 || n < 1 || (n_frames > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "bad demod arguments");
-    if (n_frames == 0) return pss_demod(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);
-    PssFlagScope corr(ctx->wfm_correct, true);    // the WFM branch of pss_demod runs iq_correction itself (scalars pre-pass or a corrected copy)
-    return pss_demod(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);
+    return pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, nullptr);
+}
+
+// demodulate_signal (signal_processing.py:220-240): the voice modes go straight to their demodulator, every other mode
+// is IQ-corrected first (:222-225): the WFM demodulator runs iq_correction itself (scalars pre-pass or a corrected copy).
+extern "C" int pss_demod_signal(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    PssDemodCall call;
+    call.correct = mode == PSS_MODE_WFM && n_frames > 0;
+    return pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, &call);
 }
 
 // measure_signal_power + demodulate of the same read buffers, as the main loop runs them back to back (pyspecsdr.py:2251, :2262): d_power
@@ -3179,14 +3184,14 @@ extern "C" int pss_demod_power(pss_ctx *ctx, int mode, const float *d_iq, long n
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_power && n_frames > 0) return pss_fail(ctx, PSS_E_ARG, "pss_demod_power: d_power is null");
+    PssDemodCall call;
     if (mode == PSS_MODE_AM && n_frames > 0 && n >= 1 && d_iq) {
-        PssScoped<float *> want(ctx->power_out, d_power);
-        return pss_demod(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);
+        call.d_power = d_power;
+        return pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, &call);
     }
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     int r = pss_power_db(ctx, d_iq, n_frames, n, d_power);
-    if (!r) r = pss_demod(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);
-    pss_time_end(ctx);
+    if (!r) r = pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, &call);
     return r;
 }
 
@@ -3199,11 +3204,10 @@ extern "C" int pss_sosfilt(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     SosArg a;
     a.nsec = nsec;
     for (int s2 = 0; s2 < 8; s2++) a.s[s2] = sos_biquad(sos + 6 * (s2 < nsec ? s2 : 0));
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_sosfilt");
     hipLaunchKernelGGL(k_sosfilt, dim3((unsigned)((n_rows + TILE - 1) / TILE)), dim3(TILE), 0, PSS_STREAM(ctx), d_x, d_y, n, n_rows, a);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_sosfilt launch");
 }
 
@@ -3360,7 +3364,7 @@ extern "C" int pss_demod_am_c128(pss_ctx *ctx, const double *d_iq, long n_frames
     double *X = reinterpret_cast<double *>(ctx->scratch), *Y = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->scratch) + rows);
     double sos[30];
     pss_am_bandpass_sos(sos);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_am_env_c128");
     hipLaunchKernelGGL(k_am_env_c128, dim3((unsigned)(n_frames < 4096 ? n_frames : 4096)), dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const double2 *>(d_iq), n,
                        n_frames, X);
@@ -3373,7 +3377,6 @@ extern "C" int pss_demod_am_c128(pss_ctx *ctx, const double *d_iq, long n_frames
         pss_kernel_end(ctx);
         r = pss_hip_check(ctx, hipGetLastError(), "k_norm_rows_f64 launch");
     }
-    pss_time_end(ctx);
     return r;
 }
 
@@ -3385,8 +3388,7 @@ extern "C" int pss_demod_ssb_c128(pss_ctx *ctx, int lower, const double *d_iq, l
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || (n_frames > 0 && (!d_iq || (!d_pcm && !d_audio)))) return pss_fail(ctx, PSS_E_ARG, "pss_demod_ssb_c128: bad argument");
-    PssFlagScope wide(ctx->iq_c128, true);
-    return pss_demod(ctx, lower ? PSS_MODE_LSB : PSS_MODE_USB, reinterpret_cast<const float *>(d_iq), n_frames, n, fs, d_pcm, d_audio);
+    return pss_demod_run(ctx, lower ? PSS_MODE_LSB : PSS_MODE_USB, PssIq{nullptr, d_iq}, n_frames, n, fs, d_pcm, d_audio, nullptr);
 }
 
 // measure_signal_power (signal_processing.py:325-328) of complex128 frames, the array part: d_power[f] = np.mean(np.abs(x) ** 2) in float64 as the
@@ -3504,7 +3506,7 @@ extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int 
     const int partc = 4 * lc;
     const size_t lds2 = sizeof(double2) * (CLS_NP + CLS_NP / 2) + sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);
     const long g = n_frames < 16384 ? n_frames : 16384;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_cls_modidx");
     hipLaunchKernelGGL(k_cls_modidx, dim3((unsigned)g), dim3(256), lds1, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n,
                        n_frames, rn, rm, part1, val1, up, mi);
@@ -3520,7 +3522,6 @@ extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int 
                            n, n_frames, fs, cp, partc, vc, d_win, scale, mi, d_label, d_bw, d_flat, d_psd);
     }
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "classify launch");
 }
 
@@ -3545,16 +3546,15 @@ extern "C" int pss_afsk_bits(pss_ctx *ctx, const double *d_audio, long n_rows, i
     int r = pss_ensure_scratch(ctx, 2 * szF);
     if (r) return r;
     double *f1 = reinterpret_cast<double *>(ctx->scratch), *f2 = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->scratch) + szF);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     r = pss_sosfilt(ctx, d_audio, n_rows, n, sos1200, nsec, f1);
     if (!r) r = pss_sosfilt(ctx, d_audio, n_rows, n, sos2200, nsec, f2);
-    if (r) { pss_time_end(ctx); return r; }
+    if (r) return r;
     const long total = n_rows * n_bits;
     pss_kernel_begin(ctx, "k_afsk_bits");
     hipLaunchKernelGGL(k_afsk_bits, dim3((unsigned)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096)), dim3(256), 0,
                        PSS_STREAM(ctx), f1, f2, n, (int)(fs / 1200.0), n_bits, n_rows, d_bits);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_afsk_bits launch");
 }
 
@@ -3656,357 +3656,6 @@ extern "C" int pss_get_wfm_filters(pss_ctx *ctx, double fs, double *lp3x6, doubl
     return PSS_OK;
 }
 
-
-extern "C" int pss_spectrum_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db,
-                                int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    // The backward IIR pass runs one wavefront per SIMD and is latency-bound; the spectrum kernel (HBM-bound, high
-    // occupancy) is launched on a side stream right behind the forward kernel so that the two share the machine
-    // (fork / join with events).  Only the fused large-batch NFM path honours fork_after_fwd, and reports it in did_fork.
-    pss_time_begin(ctx);  // nested begin/end pairs inside the two calls are no-ops
-    int r2;
-    {
-        PssFlagScope fork(ctx->fork_after_fwd, true);
-        ctx->did_fork = false;
-        r2 = pss_demod(ctx, PSS_MODE_NFM, d_iq, n_frames, n, fs, d_pcm, nullptr);
-    }
-    int r;
-    if (ctx->did_fork) {
-        ctx->did_fork = false;
-        r = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        if (!r && !r2) {
-            PssStreamScope side(ctx->cur, ctx->stream2);
-            r = pss_spectrum_db(ctx, d_iq, n_frames, n, d_db);
-        }
-        // the join is attempted whatever happened above: the main stream must never run ahead of the side stream
-        int rj = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
-        if (!rj) rj = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
-        if (!r) r = rj;
-    } else {
-        r = r2 ? r2 : pss_spectrum_db(ctx, d_iq, n_frames, n, d_db);
-    }
-    pss_time_end(ctx);
-    return r2 ? r2 : r;
-}
-
-// One iteration of the reference's main loop for a whole batch of read buffers (pyspecsdr.py:2262-2283 + the display call):
-// demodulate_signal(samples, fs, mode) -> int16; compute_fft -> dB row; smoothing + median clamp; display accumulator line.
-// Rows of either type through the SAME schedule: TR = float (pss_frame_pipeline[_nfm]: float32 dB rows, the contract of the spectrum
-// output) or TR = double (pss_frame_pipeline_nfm_f64: the reference's own row type from IQ to cells — compute_fft returns float64 and the
-// caller smooths, clamps and draws float64: these are the reference's cells).
-namespace {
-inline int pipe_spectrum(pss_ctx *ctx, const float *d_iq, long nf, int n, float *d_db) { return pss_spectrum_db(ctx, d_iq, nf, n, d_db); }
-inline int pipe_spectrum(pss_ctx *ctx, const float *d_iq, long nf, int n, double *d_db) { return pss_spectrum_db_f64(ctx, d_iq, nf, n, d_db); }
-inline int pipe_post(pss_ctx *ctx, const float *d_db, long nf, int n, float *d_post, float *lo, float *hi) { return pss_spectrum_post_extremes(ctx, d_db, nf, n, d_post, lo, hi); }
-inline int pipe_post(pss_ctx *ctx, const double *d_db, long nf, int n, double *d_post, double *lo, double *hi) { return pss_spectrum_post_f64(ctx, d_db, nf, n, d_post, lo, hi); }
-inline int pipe_lines(pss_ctx *ctx, int display, const float *d_post, long nf, int len, const float *lo, const float *hi, int n_halo, int window, int disp_h,
-                      int disp_w, int8_t *a, int8_t *b)
-{
-    return display == 2 ? pss_gradient_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
-         : display ? pss_persistence_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
-                   : pss_waterfall_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
-}
-inline int pipe_lines(pss_ctx *ctx, int display, const double *d_post, long nf, int len, const double *lo, const double *hi, int n_halo, int window, int disp_h,
-                      int disp_w, int8_t *a, int8_t *b)
-{
-    return display == 2 ? pss_gradient_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
-         : display ? pss_persistence_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
-                   : pss_waterfall_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
-}
-inline int pipe_chain_vals(pss_ctx *ctx, const float *d_db, long nf, int n, float *lo, float *hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                           int8_t *a, int8_t *b, double *vals)
-{
-    return pss_chain_vals_f32(ctx, d_db, nf, n, lo, hi, n_halo, window, display, disp_h, disp_w, a, b, vals);
-}
-inline int pipe_chain_vals(pss_ctx *ctx, const double *d_db, long nf, int n, double *lo, double *hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                           int8_t *a, int8_t *b, double *vals)
-{
-    return pss_chain_vals_f64(ctx, d_db, nf, n, lo, hi, n_halo, window, display, disp_h, disp_w, a, b, vals);
-}
-}  // namespace
-
-// display: 0 = the waterfall accumulator's newest line (d_glyph, d_colour), 1 = the persistence accumulator's newest trace (d_glyph = row
-// index per column, d_colour unused), 2 = the gradient view's newest line (d_glyph = index into ' ._-=+*#@', d_colour).
-// d_post == NULL: the post-processed rows are not materialised.  Rows the register select serves (a multiple of 4 points, up to 32 772 /
-// float64: 16 388): ONE pass over the dB rows leaves per row the extremes and the row resampled to the display width (disp_w float64
-// values: what the accumulators normalise and quantise), and the lines are quantised from those — the same bytes as from materialised rows.
-// Other lengths go through a context-owned scratch copy of the rows.
-template <class TR>
-static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, TR *d_db, TR *d_post,
-                               TR *d_row_lo, TR *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                               int8_t *d_glyph, int8_t *d_colour, int16_t *d_pcm, float *d_db32, bool demodulate);
-// d_db32 (float64 rows only; NULL otherwise): the dB rows ALSO (or, with d_db == NULL, ONLY) as float32 — compute_fft's float64 value rounded once
-// demodulate = false: the display half alone (pss_spectrum_cells): no demodulator, d_pcm unused
-template <class TR>
-static int frame_pipeline(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, TR *d_db, TR *d_post,
-                          TR *d_row_lo, TR *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                          int8_t *d_glyph, int8_t *d_colour, int16_t *d_pcm, float *d_db32 = nullptr, bool demodulate = true)
-{
-    pss_time_begin(ctx);     // one bracket around the whole call (the nested pairs inside are no-ops)
-    const int r = frame_pipeline_impl<TR>(ctx, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w,
-                                          d_glyph, d_colour, d_pcm, d_db32, demodulate);
-    pss_time_end(ctx);
-    return r;
-}
-
-__global__ __launch_bounds__(256) void k_rows_f64_to_f32(const double *__restrict__ src, float *__restrict__ dst, long count)
-{
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long)gridDim.x * blockDim.x) dst[i] = (float)src[i];
-}
-
-template <class TR>
-static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, TR *d_db, TR *d_post,
-                               TR *d_row_lo, TR *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                               int8_t *d_glyph, int8_t *d_colour, int16_t *d_pcm, float *d_db32, bool demodulate)
-{
-    constexpr bool F64 = sizeof(TR) == 8;
-    if (n_frames < 0 || n_halo < 0 || window < 1 || disp_w < 1 || display < 0 || display > 2 || (display == 1 && (disp_h < 1 || disp_h > 127)))
-        return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: bad frame count, halo, window or display geometry");
-    if (n < 8) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: frames of fewer than 8 samples have no post-processed row to draw");
-    if (n_frames > 0 && (!d_iq || (!d_db && !d_db32) || !d_row_lo || !d_row_hi || !d_glyph || (!d_colour && display != 1) || (!d_pcm && demodulate)))
-        return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline: null buffer");
-    double *d_vals = nullptr;
-    if (n_frames > 0 && !d_post) {
-        const bool direct = pss_post_sel_serves(n, F64) && !(F64 && ctx->f64_plain);
-        const size_t need = direct ? (size_t)n_frames * disp_w * sizeof(double) : (size_t)n_frames * (n - 4) * sizeof(TR);
-        int rq = pss_ensure_buffer(ctx, &ctx->scratch_post, &ctx->scratch_post_bytes, need, "post-process scratch");
-        if (rq) return rq;
-        if (direct) d_vals = reinterpret_cast<double *>(ctx->scratch_post);
-        else d_post = reinterpret_cast<TR *>(ctx->scratch_post);
-    }
-    // 1024-point frames, float64 rows, rows not materialised: the transform and the post-process are ONE kernel (pss_spec_post.h; option
-    // "fuse_post" = 0: the two kernels) — the float64 rows never go through HBM unless the caller asks for them (d_db)
-    bool fused = false;
-    if constexpr (F64) fused = ctx->fuse_post && d_vals && pss_spec_post_serves(ctx, n);
-    if (n_frames > 0 && !d_db && !fused) {     // float32 rows only, but this path needs the float64 rows in memory: the context's scratch
-        int rq = pss_ensure_buffer(ctx, &ctx->scratch_db64, &ctx->scratch_db64_bytes, (size_t)n_frames * n * sizeof(TR), "float64 dB rows");
-        if (rq) return rq;
-        d_db = reinterpret_cast<TR *>(ctx->scratch_db64);
-    }
-    // compute_fft of every frame and the display chain behind it, on whichever stream it is queued
-    auto spectrum_and_chain = [&]() -> int {
-        if constexpr (F64) {
-            if (fused)
-                return pss_spec_post_chain(ctx, d_iq, n_frames, n, d_db32, d_db, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph,
-                                           d_colour, d_vals);
-        }
-        int q = pipe_spectrum(ctx, d_iq, n_frames, n, d_db);     // compute_fft sees the samples as read (pyspecsdr.py:2275), not the corrected ones
-        if (q) return q;
-        if (d_db32 && n_frames > 0) {
-            const long count = n_frames * (long)n;
-            pss_kernel_begin(ctx, "k_rows_f64_to_f32");
-            hipLaunchKernelGGL(k_rows_f64_to_f32, dim3((unsigned)((count + 255) / 256 < 16384 ? (count + 255) / 256 : 16384)), dim3(256), 0, PSS_STREAM(ctx),
-                               reinterpret_cast<const double *>(d_db), d_db32, count);
-            pss_kernel_end(ctx);
-            q = pss_hip_check(ctx, hipGetLastError(), "k_rows_f64_to_f32 launch");
-            if (q) return q;
-        }
-        if (d_vals) return pipe_chain_vals(ctx, d_db, n_frames, n, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph, d_colour, d_vals);
-        q = pipe_post(ctx, d_db, n_frames, n, d_post, d_row_lo + n_halo, d_row_hi + n_halo);
-        if (!q) q = pipe_lines(ctx, display, d_post, n_frames, n - 4, d_row_lo, d_row_hi, n_halo, window, disp_h, disp_w, d_glyph, d_colour);
-        return q;
-    };
-    if (!demodulate) return spectrum_and_chain();
-    // WFM: demodulate_signal's dispatcher semantics — the frames are IQ-corrected first (signal_processing.py:222-225); pss_demod's WFM
-    // branch does it (wfm_correct): a scalars pre-pass in front of the forward kernel, alone on the machine
-    const float *d_in = d_iq;
-    PssFlagScope corr(ctx->wfm_correct, mode == PSS_MODE_WFM && n_frames > 0);
-    if (mode != PSS_MODE_NFM && mode != PSS_MODE_WFM) {
-        // AM / USB / LSB: neither demodulator has the two-phase shape of the FM paths, so the display chain simply runs on the side stream
-        // beside the whole demodulator (AM's recurrence kernel keeps two thirds of the SIMDs busy with one wavefront each — the HBM-bound
-        // chain fits in beside it).
-        pss_time_begin(ctx);
-        int r = pss_hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
-        if (!r) r = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        if (r) { pss_time_end(ctx); return r; }
-        const int rd = pss_demod(ctx, mode, d_in, n_frames, n, fs, d_pcm, nullptr);   // main stream
-        int rc;
-        {
-            PssStreamScope side(ctx->cur, ctx->stream2);
-            rc = spectrum_and_chain();
-        }
-        int rj = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
-        if (!rj) rj = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
-        pss_time_end(ctx);
-        return rd ? rd : (rc ? rc : rj);
-    }
-    pss_time_begin(ctx);
-    // NFM and WFM.  Schedule: forward kernel (VALU-bound, fills the machine) ->
-    //   { backward pass (latency-bound, one wavefront per SIMD)  ||  spectrum -> post-process -> display lines }.
-    // (WFM until round 4: the chain beside the whole demodulator.  k_wfm_fwd's four workgroups per CU hold 150 of a CU's 160 KB of LDS, so the
-    // spectrum kernel's 70 KB workgroups only ran as forward workgroups retired: 1.2 ms for a 0.17 ms kernel, and the chain was the critical path.)
-    // Measured alternatives (rounds 2 - 4, NOTEBOOK.md R4-08 and A5; the code of those experiments left the tree in round 5): the spectrum in
-    // front of the fork (+2 %); the whole display chain on the side stream from the start (-5 % when the forward kernel reaches the dispatcher
-    // first, +8 % when it does not); the two streams on disjoint CU masks (hipExtStreamCreateWithCUMask, 128..240 of 256 CUs for the forward
-    // kernel: +5 % at best — both halves of the step scale with the CUs they get); the spectrum kernel handing discriminator rows to the
-    // forward kernel (+2 %); everything in order on one stream; forward -> spectrum -> { backward || post-process -> lines }.
-    int r2;
-    ctx->pending_bwd = nullptr;
-    {
-        PssFlagScope defer(ctx->defer_bwd, true);
-        r2 = pss_demod(ctx, mode, d_in, n_frames, n, fs, d_pcm, nullptr);
-    }
-    int r = r2;
-    if (ctx->pending_bwd) {
-        auto bwd = ctx->pending_bwd;
-        ctx->pending_bwd = nullptr;
-        // the side stream ALWAYS waits for the main stream here: the chain reads d_iq and writes d_db / the scratch, all ordered on ctx->stream
-        if (!r) r = pss_hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
-        if (!r) r = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        if (!r) {
-            PssStreamScope side(ctx->cur, ctx->stream2);
-            r = spectrum_and_chain();
-        }
-        const int rb = bwd();                      // main stream; launched whatever happened above (the PCM must be produced)
-        int rj = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
-        if (!rj) rj = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
-        if (!r) r = rb ? rb : rj;
-    } else if (!r) {
-        r = spectrum_and_chain();                  // the demodulator took a path without a separate backward kernel
-    }
-    pss_time_end(ctx);
-    return r;
-}
-
-// The iteration with the reference's own row type: float64 dB rows, float64 post-processed rows (d_post may be NULL: not materialised) and
-// extremes, the waterfall line quantised from those — the cells the reference draws from this IQ, not those of the float32 rows.  The same
-// schedule and the same kernel families as the float32 call (register transform with a float64 dB evaluation and 8-byte stores, register
-// select on 64-bit keys); option "f64_plain" = 1: the plain round-3 kernels.  n: a power of two in [16, 65536].
-extern "C" int pss_frame_pipeline_nfm_f64(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, double *d_db, double *d_post,
-                                          double *d_row_lo, double *d_row_hi, int n_halo, int window, int disp_w, int8_t *d_glyph,
-                                          int8_t *d_colour, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_nfm_f64: n must be a power of two in [16, 65536]");
-    return frame_pipeline<double>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, 0, 0, disp_w, d_glyph,
-                                  d_colour, d_pcm);
-}
-
-// ... in ANY demodulation mode and for either batched display accumulator (pss_frame_pipeline's arguments, float64 rows)
-extern "C" int pss_frame_pipeline_f64(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, double *d_db, double *d_post,
-                                      double *d_row_lo, double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                                      int8_t *d_line_a, int8_t *d_line_b, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_f64: n must be a power of two in [16, 65536]");
-    return frame_pipeline<double>(ctx, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
-                                  d_line_b, d_pcm);
-}
-
-// The cell-exact iteration with the dB rows materialised as float32 (compute_fft's float64 value rounded once: the spectrum output's own contract),
-// and as float64 too if d_db64 != NULL; float64 from the IQ to the cells either way.
-extern "C" int pss_frame_pipeline_cells(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
-                                        double *d_row_lo, double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_line_a,
-                                        int8_t *d_line_b, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_cells: n must be a power of two in [16, 65536]");
-    if (n_frames > 0 && !d_db32) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_cells: d_db32 is null");
-    return frame_pipeline<double>(ctx, mode, d_iq, n_frames, n, fs, d_db64, nullptr, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
-                                  d_line_b, d_pcm, d_db32);
-}
-
-// ... and its display half alone: compute_fft -> post-process -> display line of every frame, no demodulator
-extern "C" int pss_spectrum_cells(pss_ctx *ctx, const float *d_iq, long n_frames, int n, float *d_db32, double *d_db64, double *d_row_lo,
-                                  double *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_line_a, int8_t *d_line_b)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_cells: n must be a power of two in [16, 65536]");
-    if (n_frames > 0 && !d_db32 && !d_db64) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_cells: no row buffer");
-    return frame_pipeline<double>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, 0.0, d_db64, nullptr, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w,
-                                  d_line_a, d_line_b, nullptr, d_db32, false);
-}
-
-// One loop iteration per read buffer with the reference's DEFAULT view (draw_spectrogram): pss_frame_pipeline_cells' dB rows, the demodulator's
-// PCM (d_pcm NULL: the display half alone) and per frame the bars and the scale's range of the post-processed float64 row.  The view has no
-// history: no halo, no window, no extremes.  Schedule: the demodulator on the main stream, compute_fft -> float32 rows -> post-process ->
-// k_spectrum_bars on the side stream (the AM branch of frame_pipeline_impl).  The float64 rows go through memory here (d_db64 / d_post, or the
-// context's scratch): the bars need the whole post-processed row for their percentile.
-extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
-                                       double *d_post, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: n must be a power of two in [16, 65536]");
-    if (n_frames < 0 || disp_h < 1 || disp_h > 127 || disp_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: bad frame count or display geometry");
-    if (n_frames > 0 && (!d_iq || !d_db32 || !d_height || !d_level)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: null buffer");
-    if (n_frames == 0) return PSS_OK;
-    if (!d_db64) {
-        int rq = pss_ensure_buffer(ctx, &ctx->scratch_db64, &ctx->scratch_db64_bytes, (size_t)n_frames * n * sizeof(double), "float64 dB rows");
-        if (rq) return rq;
-        d_db64 = reinterpret_cast<double *>(ctx->scratch_db64);
-    }
-    if (!d_post) {
-        int rq = pss_ensure_buffer(ctx, &ctx->scratch_post, &ctx->scratch_post_bytes, (size_t)n_frames * (n - 4) * sizeof(double), "post-process scratch");
-        if (rq) return rq;
-        d_post = reinterpret_cast<double *>(ctx->scratch_post);
-    }
-    auto display_chain = [&]() -> int {
-        int q = pss_spectrum_db_f64(ctx, d_iq, n_frames, n, d_db64);
-        if (q) return q;
-        const long count = n_frames * (long)n;
-        pss_kernel_begin(ctx, "k_rows_f64_to_f32");
-        hipLaunchKernelGGL(k_rows_f64_to_f32, dim3((unsigned)((count + 255) / 256 < 16384 ? (count + 255) / 256 : 16384)), dim3(256), 0, PSS_STREAM(ctx),
-                           d_db64, d_db32, count);
-        pss_kernel_end(ctx);
-        q = pss_hip_check(ctx, hipGetLastError(), "k_rows_f64_to_f32 launch");
-        if (!q) q = pss_spectrum_post_f64(ctx, d_db64, n_frames, n, d_post, nullptr, nullptr);
-        if (!q) q = pss_spectrum_bars_f64(ctx, d_post, n_frames, n - 4, disp_h, disp_w, d_height, d_level, d_range);
-        return q;
-    };
-    pss_time_begin(ctx);
-    int r;
-    if (!d_pcm) {
-        r = display_chain();
-    } else {
-        r = pss_hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "hipEventRecord(fork)");
-        if (!r) r = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0), "hipStreamWaitEvent(fork)");
-        if (!r) {
-            const int rd = pss_demod_signal(ctx, mode, d_iq, n_frames, n, fs, d_pcm, nullptr);   // main stream
-            int rc;
-            {
-                PssStreamScope side(ctx->cur, ctx->stream2);
-                rc = display_chain();
-            }
-            // the join is attempted whatever happened above: the main stream must never run ahead of the side stream
-            int rj = pss_hip_check(ctx, hipEventRecord(ctx->ev_join, ctx->stream2), "hipEventRecord(join)");
-            if (!rj) rj = pss_hip_check(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0), "hipStreamWaitEvent(join)");
-            r = rd ? rd : (rc ? rc : rj);
-        }
-    }
-    pss_time_end(ctx);
-    return r;
-}
-
-extern "C" int pss_frame_pipeline_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db, float *d_post,
-                                      float *d_row_lo, float *d_row_hi, int n_halo, int window, int disp_w, int8_t *d_glyph,
-                                      int8_t *d_colour, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    return frame_pipeline<float>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, 0, 0, disp_w, d_glyph,
-                                 d_colour, d_pcm);
-}
-
-extern "C" int pss_frame_pipeline(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db, float *d_post,
-                                  float *d_row_lo, float *d_row_hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                                  int8_t *d_line_a, int8_t *d_line_b, int16_t *d_pcm)
-{
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
-    return frame_pipeline<float>(ctx, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
-                                 d_line_b, d_pcm);
-}
 
 extern "C" int pss_set_nfm_filters(pss_ctx *ctx, double fs, const double *taps65, const double *sos4x6, const double *zi4x2)
 {

@@ -785,12 +785,11 @@ int launch_r16(pss_ctx *ctx, const float *d_iq, long n_frames, float *d_db, cons
     if (per_cu < 1) per_cu = 1;
     const long cap = 256L * per_cu * 2;
     const int grid = (int)(groups < cap ? groups : cap);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(wg_threads), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db, tw,
                        win, n_frames, d_peak, d_bw, d_count, bin_hz, spec_flags(ctx));
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_r16 launch");
 }
 
@@ -813,12 +812,11 @@ int launch_r16_f64(pss_ctx *ctx, const float *d_iq, long n_frames, double *d_db,
     if (per_cu > vgpr_cap) per_cu = vgpr_cap;
     if (per_cu < 1) per_cu = 1;
     const long cap = 256L * per_cu * 2;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum");
     hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(wg_threads), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq),
                        reinterpret_cast<float *>(d_db), tw, win, n_frames, (float *)nullptr, (double *)nullptr, (int *)nullptr, 0.0, spec_flags(ctx));
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_r16 (float64 rows) launch");
 }
 
@@ -855,12 +853,11 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
         auto go = [&](auto kern, size_t lds, int threads, int per_cu) -> int {
             PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             const long cap = 256L * per_cu;
-            pss_time_begin(ctx);
+            PssTimeScope timed(ctx);
             pss_kernel_begin(ctx, "k_spectrum");
             hipLaunchKernelGGL(kern, dim3((unsigned)(n_frames < cap ? n_frames : cap)), dim3(threads), lds, PSS_STREAM(ctx),
                                reinterpret_cast<const float2 *>(d_iq), d_db, tw, win, n_frames, d_peak, d_bw, d_count, bin_hz, spec_flags(ctx));
             pss_kernel_end(ctx);
-            pss_time_end(ctx);
             return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_xl launch");
         };
         if (!SCAN && ctx->db_exact) {
@@ -883,12 +880,11 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
         auto kern = n_fft == 32768 ? pss_r16::k_spectrum_r16_big<3, true> : pss_r16::k_spectrum_r16_big<4, true>;
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                          (int)C::LDS));
-        pss_time_begin(ctx);
+        PssTimeScope timed(ctx);
         pss_kernel_begin(ctx, "k_spectrum");
         hipLaunchKernelGGL(kern, dim3(grid), dim3(256), C::LDS, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db,
                            tw, win, n_frames, scr, spec_flags(ctx));
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
         return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_r16_big launch");
     }
     if (!SCAN && n_fft >= (1 << 17)) {
@@ -903,7 +899,7 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(pss_r16::k_huge_p1),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
         const long total1 = n_frames * (NS / 16);
-        pss_time_begin(ctx);
+        PssTimeScope timed(ctx);
         pss_kernel_begin(ctx, "k_spectrum_p1");
         hipLaunchKernelGGL(pss_r16::k_huge_p1, dim3((unsigned)(total1 < 8192 ? total1 : 8192)), dim3(256), lds1, PSS_STREAM(ctx),
                            reinterpret_cast<const float2 *>(d_iq), tw, win, Y, NS, n_frames);
@@ -922,7 +918,6 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
         default: launch2(pss_r16::k_huge_p2<4>, pss_r16::Cfg<4>::LDS, pss_r16::Cfg<4>::FPW); break;
         }
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
         return pss_hip_check(ctx, hipGetLastError(), "k_huge launch");
     }
     int logn = ilog2(n_fft);
@@ -939,12 +934,11 @@ int launch_spectrum(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, f
     if (per_cu > 8) per_cu = 8;
     if (per_cu < 1) per_cu = 1;
     int grid = grid_for(n_frames, per_cu);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum_generic");
     hipLaunchKernelGGL(kern, dim3(grid), dim3(TPB), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db, tw,
                        win, n_fft, logNsub, R, n_frames, staged, d_peak, d_bw, d_count, bin_hz, spec_flags(ctx));
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_spectrum launch");
 }
 
@@ -1123,7 +1117,7 @@ int bluestein_db(pss_ctx *ctx, const float *d_iq, long n_frames, int n, bool win
     if (r) return r;
     double2 *Y = reinterpret_cast<double2 *>(ctx->scratch_fft), *A = Y + (size_t)chunk * M;
     const int NS = p->M >> 8;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     for (long f0 = 0; f0 < n_frames && !r; f0 += chunk) {
         const long nf = (n_frames - f0) < chunk ? (n_frames - f0) : chunk;
         const float2 *x = reinterpret_cast<const float2 *>(d_iq) + (size_t)f0 * n;
@@ -1140,7 +1134,6 @@ int bluestein_db(pss_ctx *ctx, const float *d_iq, long n_frames, int n, bool win
         if (!r) r = bs_pass2(ctx, Y, BsStoreDb{d_db + (size_t)f0 * n, p->d_chirp, n, n / 2, 1.0 / (double)M, !window && ctx->scan_exact, spec_flags(ctx)}, tw, NS, nf);
         pss_kernel_end(ctx);
     }
-    pss_time_end(ctx);
     if (r) return r;
     return pss_hip_check(ctx, hipGetLastError(), "bluestein launch");
 }
@@ -1476,9 +1469,8 @@ extern "C" int pss_hilbert(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || (n_rows > 0 && (!d_x || !d_analytic))) return pss_fail(ctx, PSS_E_ARG, "pss_hilbert: bad argument");
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     const int r = pss_hilbert_rows(ctx, d_x, n_rows, n, d_analytic, 0, nullptr, nullptr);
-    pss_time_end(ctx);
     return r;
 }
 
@@ -1499,12 +1491,11 @@ extern "C" int pss_spectrum_db(pss_ctx *ctx, const float *d_iq, long n_frames, i
     if (n_fft == 1) {
         if (n_frames < 0 || (n_frames > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "null iq / negative n_frames");
         if (n_frames == 0) return PSS_OK;
-        pss_time_begin(ctx);
+        PssTimeScope timed(ctx);
         pss_kernel_begin(ctx, "k_spectrum_one");
         hipLaunchKernelGGL(k_spectrum_one, dim3((unsigned)((n_frames + 255) / 256 < 1024 ? (n_frames + 255) / 256 : 1024)), dim3(256), 0, PSS_STREAM(ctx),
                            reinterpret_cast<const float2 *>(d_iq), d_db, n_frames, spec_flags(ctx));
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
         return pss_hip_check(ctx, hipGetLastError(), "k_spectrum_one launch");
     }
     if (n_frames > 0 && d_iq && n_fft >= 2 && !(is_pow2(n_fft) && n_fft >= 16)) return bluestein_db(ctx, d_iq, n_frames, n_fft, true, d_db);
@@ -1543,12 +1534,11 @@ extern "C" int pss_spectrum_db_f64(pss_ctx *ctx, const float *d_iq, long n_frame
     if (lds > 64 * 1024) PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((160 * 1024) / (lds + 64));
     per_cu = per_cu > 8 ? 8 : per_cu;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum_f64");
     hipLaunchKernelGGL(kern, dim3(grid_for(n_frames, per_cu)), dim3(TPB), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq),
                        reinterpret_cast<float *>(d_db), tw, win, n_fft, logNsub, n_fft >> logNsub, n_frames, 0, nullptr, nullptr, nullptr, 0.0, 0);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_spectrum (float64 rows) launch");
 }
 
@@ -1573,12 +1563,11 @@ extern "C" int pss_spectrum_db_c128(pss_ctx *ctx, const double *d_iq, long n_fra
     if (lds > 64 * 1024) PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per_cu = (int)((160 * 1024) / (lds + 64));
     per_cu = per_cu > 8 ? 8 : per_cu;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum_c128");
     hipLaunchKernelGGL(kern, dim3(grid_for(n_frames, per_cu)), dim3(TPB), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq),
                        reinterpret_cast<float *>(d_db), tw, win, n_fft, logNsub, n_fft >> logNsub, n_frames, 0, nullptr, nullptr, nullptr, 0.0, 0);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_spectrum (complex128 frames) launch");
 }
 
@@ -1691,7 +1680,7 @@ int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, flo
     if (n_frames == 0) return PSS_OK;
     const int m = n_fft - 4;
     int r = PSS_OK;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     if (post_sel_serves(n_fft)) {
         // register-resident binary-search select: one wavefront per row up to 2048 points, 4 / 16 wavefronts above
         r = post_sel_any<float>(ctx, d_db, n_frames, n_fft, d_post, d_lo, d_hi, d_thr, d_vals, disp_w);
@@ -1727,7 +1716,6 @@ int spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, flo
         pss_kernel_end(ctx);
         r = pss_hip_check(ctx, hipGetLastError(), "k_row_extremes launch");
     }
-    pss_time_end(ctx);
     return r;
 }
 
@@ -1754,7 +1742,7 @@ int display_rows(pss_ctx *ctx, const T *d_post, long n_frames, int len, const T 
         (n_frames > 0 && ((!d_post && !d_vals) || !d_lo || !d_hi || !d_a || (MODE != 1 && !d_b))))
         return pss_fail(ctx, PSS_E_ARG, "bad display-rows arguments");
     if (n_frames == 0) return PSS_OK;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     if (d_vals) {
         // the batched steps: window extremes and the lines from the resampled rows in ONE launch
         constexpr int RPB = 32;
@@ -1763,11 +1751,10 @@ int display_rows(pss_ctx *ctx, const T *d_post, long n_frames, int len, const T 
         hipLaunchKernelGGL((pss_post::k_disp_vals_win<MODE, T, RPB>), dim3((unsigned)(groups < 8192 ? groups : 8192)), dim3(256), 0, PSS_STREAM(ctx),
                            d_vals, d_lo, d_hi, n_frames, n_halo, window, disp_w, disp_h, d_a, d_b);
         pss_kernel_end(ctx);
-        pss_time_end(ctx);
         return pss_hip_check(ctx, hipGetLastError(), "k_disp_vals_win launch");
     }
     int r = pss_ensure_buffer(ctx, &ctx->scratch_win, &ctx->scratch_win_bytes, (size_t)n_frames * 2 * sizeof(double), "window extremes");
-    if (r) { pss_time_end(ctx); return r; }
+    if (r) return r;
     double *wlo = reinterpret_cast<double *>(ctx->scratch_win), *whi = wlo + n_frames;
     pss_kernel_begin(ctx, "k_slide_extremes");
     hipLaunchKernelGGL(pss_post::k_slide_extremes<T>, dim3((unsigned)((n_frames + 255) / 256 < 4096 ? (n_frames + 255) / 256 : 4096)),
@@ -1783,7 +1770,6 @@ int display_rows(pss_ctx *ctx, const T *d_post, long n_frames, int len, const T 
         hipLaunchKernelGGL((pss_post::k_disp_rows<T, MODE>), dgrid, dim3(256), 0, PSS_STREAM(ctx), d_post, wlo, whi, n_frames, len, disp_w,
                            disp_h, d_a, d_b, (const T *)nullptr);
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_disp_rows launch");
 }
 
@@ -1843,18 +1829,16 @@ extern "C" int pss_spectrum_post_f64(pss_ctx *ctx, const double *d_db, long n_fr
     if ((d_row_lo == nullptr) != (d_row_hi == nullptr)) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_f64: row_lo and row_hi go together");
     if (n_frames == 0) return PSS_OK;
     if (!ctx->f64_plain && n_fft >= 8 && post_sel_serves(n_fft, true)) {   // the register select on 64-bit keys (option "f64_plain" = 1: the radix-select kernel below)
-        pss_time_begin(ctx);
+        PssTimeScope timed(ctx);
         const int rq = post_sel_any<double>(ctx, d_db, n_frames, n_fft, d_post, d_row_lo, d_row_hi, nullptr, nullptr, 0);
-        pss_time_end(ctx);
         return rq;
     }
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_post_f64");
     hipLaunchKernelGGL(k_post_f64, dim3((unsigned)(n_frames < 2048 ? n_frames : 2048)), dim3(256), 0, PSS_STREAM(ctx), d_db, d_post, n_fft, n_frames);
     pss_kernel_end(ctx);
     int r = pss_hip_check(ctx, hipGetLastError(), "k_post_f64 launch");
     if (!r && d_row_lo) r = row_extremes<double>(ctx, d_post, n_frames, n_fft - 4, d_row_lo, d_row_hi);
-    pss_time_end(ctx);
     return r;
 }
 
@@ -1896,12 +1880,11 @@ static int chain_vals(pss_ctx *ctx, const TR *d_db, long n_frames, int n_fft, TR
                       int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals)
 {
     if (n_frames == 0) return PSS_OK;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     int r = post_sel_any<TR>(ctx, d_db, n_frames, n_fft, (TR *)nullptr, d_lo + n_halo, d_hi + n_halo, (TR *)nullptr, d_vals, disp_w);
     if (!r) r = display == 2 ? display_rows<TR, 2>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const TR *)nullptr, d_vals)
               : display ? display_rows<TR, 1>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const TR *)nullptr, d_vals)
                         : display_rows<TR, 0>(ctx, (const TR *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const TR *)nullptr, d_vals);
-    pss_time_end(ctx);
     return r;
 }
 int pss_chain_vals_f32(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, float *d_lo, float *d_hi, int n_halo, int window, int display,
@@ -1933,7 +1916,7 @@ int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_ff
     const long cap = 256L * 2 * 2;       // two 256-thread workgroups per CU (LDS, registers), two rounds
     if (lds > 64 * 1024) PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long groups = (n_frames + C::FPW - 1) / C::FPW;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum_post");
     hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(256), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db32,
                        d_db64, tw, win, n_frames, d_lo + n_halo, d_hi + n_halo, d_vals, disp_w);
@@ -1942,7 +1925,6 @@ int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_ff
     if (!r) r = display == 2 ? display_rows<double, 2>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const double *)nullptr, d_vals)
               : display ? display_rows<double, 1>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, disp_h, disp_w, d_a, nullptr, (const double *)nullptr, d_vals)
                         : display_rows<double, 0>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const double *)nullptr, d_vals);
-    pss_time_end(ctx);
     return r;
 }
 
@@ -2076,7 +2058,7 @@ int spectrum_bars(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_
     if (n_rows < 0 || len < 1 || disp_h < 1 || disp_h > 127 || disp_w < 1 || (n_rows > 0 && (!d_rows || !d_height || !d_level)))
         return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_bars: bad argument (len >= 1, 1 <= disp_h <= 127, disp_w >= 1, non-null buffers)");
     if (n_rows == 0) return PSS_OK;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     int r = PSS_OK;
     if (len <= 256) r = launch_bars_reg<T, 4, 1>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
     else if (len <= 1024) r = launch_bars_reg<T, 16, 1>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
@@ -2088,7 +2070,6 @@ int spectrum_bars(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_
                            disp_h, disp_w, d_height, d_level, d_range);
         pss_kernel_end(ctx);
     }
-    pss_time_end(ctx);
     return r ? r : pss_hip_check(ctx, hipGetLastError(), "k_spectrum_bars launch");
 }
 

@@ -39,7 +39,7 @@ extern "C" int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows
     pl.n_chunks = pl.n_full + (rem > 0 ? 1 : 0);
     if (pl.n_full) build_plan(CHUNK, pl.full);
     if (rem > 0) build_plan(rem, pl.tail);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_row_meter");
     if (len <= METER_WAVE_MAX_LEN) {
         const long groups = (n_rows + 3) / 4;
@@ -48,7 +48,6 @@ extern "C" int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows
         hipLaunchKernelGGL(k_row_meter<256>, dim3((unsigned)(n_rows < 4096 ? n_rows : 4096)), dim3(256), 0, PSS_STREAM(ctx), d_rows, n_rows, len, pl, d_peak, d_avg);
     }
     pss_kernel_end(ctx);
-    pss_time_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_row_meter launch");
 }
 
@@ -91,19 +90,20 @@ extern "C" int pss_squelch_gate(pss_ctx *ctx, const double *d_peak, long n_frame
     GateResult *d_res = reinterpret_cast<GateResult *>(buf);
     int *tiles = reinterpret_cast<int *>(d_res + 1);
     const dim3 grid((unsigned)(n_tiles < 4096 ? n_tiles : 4096));
-    pss_time_begin(ctx);
-    pss_kernel_begin(ctx, "k_gate_flags");
-    hipLaunchKernelGGL(k_gate_flags, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, d_open, tiles, n_tiles);
-    pss_kernel_end(ctx);
-    pss_kernel_begin(ctx, "k_gate_scan");
-    hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(256), 0, PSS_STREAM(ctx), tiles, n_tiles, d_peak, n_frames, every, (long)phase, held_in, d_res);
-    pss_kernel_end(ctx);
-    if (d_open_idx) {
-        pss_kernel_begin(ctx, "k_gate_index");
-        hipLaunchKernelGGL(k_gate_index, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, tiles, n_tiles, d_open_idx);
+    {
+        PssTimeScope timed(ctx);
+        pss_kernel_begin(ctx, "k_gate_flags");
+        hipLaunchKernelGGL(k_gate_flags, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, d_open, tiles, n_tiles);
         pss_kernel_end(ctx);
+        pss_kernel_begin(ctx, "k_gate_scan");
+        hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(256), 0, PSS_STREAM(ctx), tiles, n_tiles, d_peak, n_frames, every, (long)phase, held_in, d_res);
+        pss_kernel_end(ctx);
+        if (d_open_idx) {
+            pss_kernel_begin(ctx, "k_gate_index");
+            hipLaunchKernelGGL(k_gate_index, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, n_frames, squelch, every, (long)phase, held_in, tiles, n_tiles, d_open_idx);
+            pss_kernel_end(ctx);
+        }
     }
-    pss_time_end(ctx);
     r = pss_hip_check(ctx, hipGetLastError(), "squelch gate launch");
     if (r) return r;
     // the one place where the count reaches the host: 16 bytes into pinned memory, one stream synchronisation
@@ -131,7 +131,7 @@ extern "C" int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n
     void *gathered;
     int r = sq_buffer(ctx, 1, (size_t)n_open * n * 2 * sizeof(float), "open frames", &gathered);
     if (r) return r;
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     const dim3 grid((unsigned)(n_open < 2048 ? n_open : 2048));
     pss_kernel_begin(ctx, "k_gather_frames");
     if (n % 2 == 0 && a % 16 == 0)
@@ -143,7 +143,6 @@ extern "C" int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n
     pss_kernel_end(ctx);
     r = pss_hip_check(ctx, hipGetLastError(), "k_gather_frames launch");
     if (!r) r = pss_demod_signal(ctx, mode, reinterpret_cast<const float *>(gathered), n_open, n, fs, d_pcm, d_audio);
-    pss_time_end(ctx);
     return r;
 }
 
@@ -175,14 +174,13 @@ extern "C" int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d
     double *db64 = d_db64 ? d_db64 : reinterpret_cast<double *>(b);
     double *post = reinterpret_cast<double *>(b + (d_db64 ? 0 : row_bytes));
     int32_t *open_idx = reinterpret_cast<int32_t *>(b + (d_db64 ? 0 : row_bytes) + post_bytes);
-    pss_time_begin(ctx);
+    PssTimeScope timed(ctx);
     r = pss_spectrum_cells(ctx, d_iq, n_frames, n, d_db32, db64, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a, d_line_b);
     if (!r) r = pss_spectrum_post_f64(ctx, db64, n_frames, n, post, nullptr, nullptr);
     if (!r) r = pss_row_meter_f64(ctx, post, n_frames, n - 4, d_peak, d_avg);
     long count = 0;
     if (!r) r = pss_squelch_gate(ctx, d_peak, n_frames, squelch, every, phase, held_in, d_open, open_idx, &count, held_out);
     if (!r) r = pss_demod_gated(ctx, mode, d_iq, n_frames, n, fs, open_idx, count, d_pcm, nullptr);
-    pss_time_end(ctx);
     if (!r && n_open) *n_open = count;
     return r;
 }

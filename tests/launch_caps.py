@@ -82,14 +82,14 @@ CAPS = {
         "pss_classify (n >= 1024)", "k_cls_modidx, k_cls_welch", "frames", lambda n, o=None: 16384,
         {"pss_demod.hip": [
             "const int np = n < CLS_NP ? n : CLS_NP;",
-            "const long g = n_frames < 16384 ? n_frames : 16384;\n    pss_time_begin(ctx);\n    pss_kernel_begin(ctx, \"k_cls_modidx\");",
+            "const long g = n_frames < 16384 ? n_frames : 16384;\n    PssTimeScope timed(ctx);\n    pss_kernel_begin(ctx, \"k_cls_modidx\");",
             "hipLaunchKernelGGL(k_cls_modidx, dim3((unsigned)g), dim3(256), lds1,",
             "hipLaunchKernelGGL(k_cls_welch, dim3((unsigned)g), dim3(256), lds2,",
         ]}),
     "classify_short": Cap(
         "pss_classify (n < 1024)", "k_cls_modidx, k_cls_welch_short", "frames", lambda n, o=None: 16384,
         {"pss_demod.hip": [
-            "const long g = n_frames < 16384 ? n_frames : 16384;\n    pss_time_begin(ctx);\n    pss_kernel_begin(ctx, \"k_cls_modidx\");",
+            "const long g = n_frames < 16384 ? n_frames : 16384;\n    PssTimeScope timed(ctx);\n    pss_kernel_begin(ctx, \"k_cls_modidx\");",
             "hipLaunchKernelGGL(k_cls_welch_short, dim3((unsigned)g), dim3(256), lds3,",
         ]}),
     "morse": Cap(
@@ -126,10 +126,10 @@ CAPS = {
         "pss_demod_ssb_c128 (n not a power of two)", "k_ssb_fir<double2>, k_finalize", "frames",
         lambda n, o=None: max(16384 // ((n + 1023) // 1024), 16384 * 256 // n),
         {"pss_demod.hip": [
-            "const int cpf = (n + 1023) / 1024;\n        long total = n_frames * cpf;\n        long g = total < 16384 ? total : 16384;",
+            "const int cpf = (n + 1023) / 1024;\n    long total = n_frames * cpf;\n    long g = total < 16384 ? total : 16384;",
             "hipLaunchKernelGGL(k_ssb_fir<double2>, dim3((unsigned)g), dim3(TPB), 0,",
-            "size_t tot = (size_t)n_frames * n;\n        size_t g2 = (tot + TPB - 1) / TPB;\n        if (g2 > 16384) g2 = 16384;\n"
-            "        pss_kernel_begin(ctx, \"k_finalize\");\n        hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), Yf,",
+            "size_t tot = (size_t)n_frames * n;\n    size_t g2 = (tot + TPB - 1) / TPB;\n    if (g2 > 16384) g2 = 16384;\n"
+            "    pss_kernel_begin(ctx, \"k_finalize\");\n    hipLaunchKernelGGL(k_finalize, dim3((unsigned)g2), dim3(TPB), 0, PSS_STREAM(ctx), Yf,",
             "constexpr int TPB = 256;",
         ]}),
     "np_f32": Cap(
@@ -201,7 +201,7 @@ CAPS = {
             "    const long groups = (n_frames + fpw - 1) / fpw;\n    const int wg_threads = fpw * C::T;\n"
             "    int per_cu = (int)((160 * 1024) / (lds + 256));\n    const int vgpr_cap = (split ? 4 : 2) * 256 / wg_threads;\n"
             "    if (per_cu > vgpr_cap) per_cu = vgpr_cap;\n    if (per_cu < 1) per_cu = 1;\n    const long cap = 256L * per_cu * 2;\n"
-            "    pss_time_begin(ctx);\n    pss_kernel_begin(ctx, \"k_spectrum\");\n"
+            "    PssTimeScope timed(ctx);\n    pss_kernel_begin(ctx, \"k_spectrum\");\n"
             "    hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(wg_threads), lds,",
         ]})),
     # float64 rows of the other lengths (or option f64_plain = 1) and complex128 frames: the plain LDS transform, one frame per workgroup
@@ -213,7 +213,7 @@ CAPS = {
             "long cap = 256L * per_cu * 4;",
             "const int logn = ilog2(n_fft), logNsub = logn < LOG_NSUB_MAX ? logn : LOG_NSUB_MAX;\n"
             "    const size_t lds = ((size_t)1 << logNsub) * sizeof(double2);\n    auto kern = k_spectrum<false, false, true>;",
-            "    int per_cu = (int)((160 * 1024) / (lds + 64));\n    per_cu = per_cu > 8 ? 8 : per_cu;\n    pss_time_begin(ctx);\n"
+            "    int per_cu = (int)((160 * 1024) / (lds + 64));\n    per_cu = per_cu > 8 ? 8 : per_cu;\n    PssTimeScope timed(ctx);\n"
             "    pss_kernel_begin(ctx, \"k_spectrum_f64\");\n    hipLaunchKernelGGL(kern, dim3(grid_for(n_frames, per_cu)), dim3(TPB), lds,",
         ]}),
     "spectrum_c128": Cap(
@@ -223,7 +223,7 @@ CAPS = {
             "long cap = 256L * per_cu * 4;",
             "const int logn = ilog2(n_fft), logNsub = logn < LOG_NSUB_MAX ? logn : LOG_NSUB_MAX;\n"
             "    const size_t lds = ((size_t)1 << logNsub) * sizeof(double2);\n    auto kern = k_spectrum<false, false, true, true>;",
-            "    int per_cu = (int)((160 * 1024) / (lds + 64));\n    per_cu = per_cu > 8 ? 8 : per_cu;\n    pss_time_begin(ctx);\n"
+            "    int per_cu = (int)((160 * 1024) / (lds + 64));\n    per_cu = per_cu > 8 ? 8 : per_cu;\n    PssTimeScope timed(ctx);\n"
             "    pss_kernel_begin(ctx, \"k_spectrum_c128\");\n    hipLaunchKernelGGL(kern, dim3(grid_for(n_frames, per_cu)), dim3(TPB), lds,",
         ]}),
     # option f64_plain = 1, or a length the register select does not serve

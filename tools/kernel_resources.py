@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Register / LDS / scratch use of every kernel of libpss.so, read from the CODE OBJECT's metadata (hipcc --offload-device-only -S of
-the two kernel units with the product build's flags), not from a profiler's dispatch record (rocprofv3's VGPR / LDS columns were wrong
+every .hip unit of pyspecsdr_amd.build.UNITS with the product build's flags; the device assembly stays under _build/asm/), not from a profiler's dispatch record (rocprofv3's VGPR / LDS columns were wrong
 for these kernels in round 2: 64 VGPRs / 0 bytes reported for k_nfm_fwd, the compiler says 128 / static 0 + 39 KB dynamic).
 
     python tools/kernel_resources.py  ->  profiles/kernel_resources.json  {src_hash, kernels: {mangled name: {short, vgpr, agpr, sgpr,
