@@ -409,6 +409,61 @@ int pss_surface_cells_f64(pss_ctx *ctx, const double *d_row, int len, int max_h,
  * one of the n IQ samples lands (float32 arithmetic as in the reference). */
 int pss_vector_cells(pss_ctx *ctx, const float *d_iq, int n, int max_h, int max_w, int8_t *d_grid);
 
+/* The surface plot in its compact per-column form ("surface magnitudes") — draw_surface_plot (pyspecsdr.py:1567-1616) for BATCHES of rows.  Every
+ * '#' the reference draws from a column follows from magnitude = int(value * 20) (:1593) and the screen size, so that is what a batch returns
+ * per row instead of pss_surface_cells' max_h x max_w grid (disp_w + 16 bytes per row; disp_w = max_w - 8, :1571):
+ *   d_mag    int8 [n_rows][disp_w]  int(value * 20), 0 .. 20; -1: the resampled value is not finite, column not drawn (:1592)
+ *   d_range  double [n_rows][2]     the row's finite (min_val, max_val) (:1575-1576), bit-equal to pss_row_extremes[_f64]'s pair (float32 rows:
+ *                                   widened); nullable.  The scale labels follow from it (formats.surface_scale_labels).
+ * `value` is pss_surface_cells' own: both kernels call one __device__ function for the normaliser ((row - min_val) / db_range per sample in
+ * float64, db_range == 0 -> 1, THEN np.interp) and the magnitude, so the magnitudes ARE that kernel's, column by column.
+ *   pss_surface_mags[_f64]   rows [n_rows][len].  The row's extremes and its columns come out of one kernel, many rows per launch: one wavefront per
+ *                            row up to 1024 values, four up to 4092, the row parked in LDS (one read from HBM); longer rows are read twice.  No
+ *                            atomics; the output does not depend on the schedule.  A row without a finite value (the reference raises ValueError
+ *                            there): range (+inf, -inf), every column -1, as pss_surface_cells draws nothing.  PSS_E_ARG: len < 2, disp_w < 2
+ *                            (max_w >= 10), n_rows < 0, null d_rows / d_mag.
+ *   pss_mags_cells           the expansion to pss_surface_cells' grids, d_colour int8 [n_rows][max_h][max_w] (disp_w = max_w - 8 magnitudes per row):
+ *                            cell (sy, sx) holds 1 + y % 5 of the LAST (x, y), x = 0 .. disp_w - 1 outer, y = 0 .. mag[x] - 1 inner (:1591-1601),
+ *                            with sx = int(x - y cos45) + 8 and sy = int(max_h - 2 - y sin45), 0 <= sx < max_w, 2 <= sy < max_h - 1; 0 where none
+ *                            hits.  Every cell finds its own winner (at most two y map to one sy): no atomics.  PSS_E_ARG: max_h < 4, max_w < 10,
+ *                            n_rows < 0, null buffers.  A magnitude below -1 cannot come from pss_surface_mags and is not checked on the device.
+ *   pss_h_mags_cells         the same on host arrays, pure C, no context and no GPU.  PSS_E_ARG also for a magnitude outside [-1, 127].
+ *   pss_frame_pipeline_surface  one loop iteration per read buffer with this view (current_display_mode SURFACE): pss_frame_pipeline_bars' rows
+ *                            (d_db32 [n_frames][n]; d_db64, d_post nullable: context scratch) and PCM (d_pcm NULL: the display half alone), with
+ *                            pss_surface_mags_f64 of the post-processed rows (len n - 4) as the chain's last link.  n: a power of two in
+ *                            [16, 65536], any of the five modes.  PSS_E_ARG: unknown mode, n, disp_w < 2, n_frames < 0, null d_iq / d_db32 / d_mag. */
+int pss_surface_mags(pss_ctx *ctx, const float *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range);
+int pss_surface_mags_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range);
+int pss_mags_cells(pss_ctx *ctx, const int8_t *d_mag, long n_rows, int max_h, int max_w, int8_t *d_colour);
+int pss_h_mags_cells(const int8_t *mag, long n_rows, int max_h, int max_w, int8_t *colour);
+int pss_frame_pipeline_surface(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                               double *d_post, int disp_w, int8_t *d_mag, double *d_range, int16_t *d_pcm);
+
+/* The constellation in its compact form ("constellation masks") — draw_vector_display (pyspecsdr.py:1719-1752) for BATCHES of read buffers: one
+ * bit per screen cell instead of pss_vector_cells' byte grid.
+ *   d_mask   uint32 [n_frames][max_h][words], words = (max_w + 31) / 32: bit (x & 31) of word (x >> 5) of line y is set where a '.' lands at
+ *            (y, x); the unused bits of a line's last word are 0.
+ *   pss_vector_masks         d_iq complex64 [n_frames][n].  Per sample pss_vector_cells' arithmetic (one shared __device__ function: float32
+ *                            products and sums, truncation toward zero; a coordinate that is not finite draws nothing — the reference raises
+ *                            there and abandons the rest of the buffer).  The frame's mask is built in LDS (LDS atomic OR) and stored once:
+ *                            one wavefront per frame up to 4096 samples where four masks fit in 64 KB, else one 512-thread workgroup per frame; no
+ *                            global atomics, no per-frame memset.  n = 0: empty masks.  LIMIT: max_h * words <= 16384 (the mask in 64 KB of
+ *                            LDS; 130 x 1100 takes 4550 words, 6 x 32 767 takes 6144).  PSS_E_ARG: max_h < 1, max_w < 1, a screen above that
+ *                            limit, n < 0, n_frames < 0, null buffers.
+ *   pss_masks_cells          the expansion to pss_vector_cells' grids, d_grid int8 [n_frames][max_h][max_w] (1 = '.').  PSS_E_ARG: max_h < 1,
+ *                            max_w < 1, n_frames < 0, null buffers.
+ *   pss_h_masks_cells        the same on host arrays, pure C, no context and no GPU.
+ *   pss_frame_pipeline_vector  one loop iteration per read buffer with this view (current_display_mode VECTOR): pss_frame_pipeline_bars' rows and
+ *                            PCM — the header's meter needs the rows in this view too — and the masks of the read buffers AS READ (the reference
+ *                            hands `samples` to the view, not the corrected copy).  PSS_E_ARG: unknown mode, n, the screen rules above,
+ *                            n_frames < 0, null d_iq / d_db32 / d_mask.
+ * Not reproduced: the axes ('-' / '|', drawn before the dots) and draw_frequency_labels, which are host text. */
+int pss_vector_masks(pss_ctx *ctx, const float *d_iq, long n_frames, int n, int max_h, int max_w, uint32_t *d_mask);
+int pss_masks_cells(pss_ctx *ctx, const uint32_t *d_mask, long n_frames, int max_h, int max_w, int8_t *d_grid);
+int pss_h_masks_cells(const uint32_t *mask, long n_frames, int max_h, int max_w, int8_t *grid);
+int pss_frame_pipeline_vector(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                              double *d_post, int max_h, int max_w, uint32_t *d_mask, int16_t *d_pcm);
+
 /* decode_morse, front half (decoders.py:149-165): envelope = |x| / max|x| in float32, 20 log10(envelope + 1e-10) > threshold,
  * and the indices of the rising / falling transitions of that mask (np.diff + np.where), i.e. the arrays rise_times /
  * fall_times the timing logic of decode_morse (:167 ff., stays in the reference's own decoders.py) starts from.

@@ -103,6 +103,15 @@ _SIGS = {
     "pss_surface_cells": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p]),
     "pss_surface_cells_f64": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p]),
     "pss_vector_cells": (C.c_int, [_p, _p, C.c_int, C.c_int, C.c_int, _p]),
+    "pss_surface_mags": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, _p, _p]),
+    "pss_surface_mags_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, _p, _p]),
+    "pss_mags_cells": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, _p]),
+    "pss_h_mags_cells": (C.c_int, [_p, C.c_long, C.c_int, C.c_int, _p]),
+    "pss_frame_pipeline_surface": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, C.c_int, _p, _p, _p]),
+    "pss_vector_masks": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, C.c_int, _p]),
+    "pss_masks_cells": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_int, _p]),
+    "pss_h_masks_cells": (C.c_int, [_p, C.c_long, C.c_int, C.c_int, _p]),
+    "pss_frame_pipeline_vector": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, C.c_int, C.c_int, _p, _p]),
     "pss_morse_edges": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, C.c_int, _p, _p, _p]),
     "pss_h_morse_edges": (C.c_int, [_p, _p, C.c_int, C.c_double, C.c_int, _p, _p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pss_h_morse_decode": (C.c_int, [_p, C.c_long, _p, C.c_long, C.c_double, _p, C.c_long, _p]),

@@ -23,6 +23,7 @@
 #include "pss_fft_xl.h"
 #include "pss_post.h"
 #include "pss_bars.h"
+#include "pss_views.h"
 #include "pss_spec_post.h"
 #include "pss_hilbert.h"
 #include "pss_hilbert_pf.h"
@@ -699,7 +700,6 @@ __global__ __launch_bounds__(1024) void k_cells(const T *__restrict__ rows, int 
     } else if (MODE == 3) {
         // '#' cells march up-left at 45 degrees from every column; later (x, y) overwrite earlier ones, so each cell keeps
         // the LARGEST (x, y) key that hits it (atomicMax on an int grid in global memory, then decoded to the colour pair)
-        const double COS45 = 0x1.6a09e667f3bcdp-1, SIN45 = 0x1.6a09e667f3bccp-1;  // np.cos / np.sin(np.radians(45))
         double range = hi - lo;
         if (range == 0) range = 1;
         int *keys = reinterpret_cast<int *>(glyph);  // scratch: [disp_h][disp_w] ints supplied by the host wrapper
@@ -707,16 +707,12 @@ __global__ __launch_bounds__(1024) void k_cells(const T *__restrict__ rows, int 
         __syncthreads();
         const int w = disp_w - 8;
         const T *row = rowp(0);
-        const auto normalised = [&](int j) { return ((double)row[j] - lo) / range; };
         for (int x = tid; x < w; x += CT) {
-            // np.interp over the NORMALISED row: normalisation is affine and applied per sample before interpolating
-            const double value = pss_post::interp_at(pss_post::fn_row(normalised), len, w, x);
-            if (!isfinite(value)) continue;
-            const int mag = (int)(value * 20);
+            // np.interp over the NORMALISED row, int(value * 20): pss_views::surface_mag, shared with k_surface_mags (-1: not finite, no step)
+            const int mag = pss_views::surface_mag(row, len, w, x, lo, range);
             for (int y = 0; y < mag; y++) {
-                const int sx = (int)((double)x - (double)y * COS45) + 8;
-                const int sy = (int)((double)(disp_h - 2) - (double)y * SIN45);
-                if (sx >= 0 && sx < disp_w && sy >= 2 && sy < disp_h - 1) atomicMax(&keys[sy * disp_w + sx], x * 32 + y);
+                int sx, sy;
+                if (pss_views::surface_hit(x, y, disp_h, disp_w, sx, sy)) atomicMax(&keys[sy * disp_w + sx], x * 32 + y);
             }
         }
         __syncthreads();
@@ -2136,11 +2132,8 @@ __global__ __launch_bounds__(256) void k_vector(const float2 *__restrict__ iq, i
 {
     const int cx = max_w / 2, cy = max_h / 2, scale = (max_w < max_h ? max_w : max_h) / 4;
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += gridDim.x * blockDim.x) {
-        const float2 v = iq[k];
-        const float fx = __fadd_rn((float)cx, __fmul_rn(v.x, (float)scale)), fy = __fsub_rn((float)cy, __fmul_rn(v.y, (float)scale));
-        if (!isfinite(fx) || !isfinite(fy)) continue;
-        const int x = (int)fx, y = (int)fy;
-        if (x >= 0 && x < max_w && y >= 0 && y < max_h) grid[y * max_w + x] = 1;
+        int x, y;
+        if (pss_views::vector_cell(iq[k], cx, cy, scale, max_h, max_w, x, y)) grid[y * max_w + x] = 1;
     }
 }
 
@@ -2205,6 +2198,147 @@ extern "C" int pss_surface_cells(pss_ctx *ctx, const float *d_row, int len, int 
 extern "C" int pss_surface_cells_f64(pss_ctx *ctx, const double *d_row, int len, int max_h, int max_w, int8_t *d_colour)
 {
     return launch_surface<double>(ctx, d_row, len, max_h, max_w, d_colour);
+}
+
+// ---- the surface plot and the constellation in their compact forms, for batches (include/pss.h; kernels in pss_views.h) ------------------
+namespace {
+constexpr int MAGS_WAVE_MAX_LEN = 1024;    // one wavefront per row, four rows per workgroup (32 KB of LDS for float64 rows)
+constexpr int MAGS_LDS_MAX_LEN = 4092;     // four wavefronts per row, the row in LDS (k_spectrum_bars' limit); longer rows are read twice
+constexpr long MAGS_MAX_GROUPS = 2048;     // workgroups per launch (grid-stride beyond)
+constexpr int MASK_MAX_WORDS = 16384;      // max_h * ((max_w + 31) / 32) <= 16384: the frame's mask in 64 KB of LDS (130 x 1100: 4550 words)
+constexpr int MASK_WAVE_MAX_N = 4096;      // frames up to here: one wavefront each (if four masks fit in LDS); longer: eight wavefronts
+constexpr long MASK_MAX_GROUPS = 2048;
+
+template <class T, int W, bool STAGED>
+void launch_surface_mags(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range)
+{
+    constexpr int RPW = W == 1 ? 4 : 1;
+    const size_t lds = STAGED ? (size_t)RPW * len * sizeof(T) : 0;
+    const long groups = (n_rows + RPW - 1) / RPW;
+    hipLaunchKernelGGL((pss_views::k_surface_mags<T, W, STAGED>), dim3((unsigned)(groups < MAGS_MAX_GROUPS ? groups : MAGS_MAX_GROUPS)),
+                       dim3(W == 1 ? 256 : 64 * W), lds, PSS_STREAM(ctx), d_rows, n_rows, len, disp_w, d_mag, d_range);
+}
+
+template <class T>
+int surface_mags(pss_ctx *ctx, const T *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range)
+{
+    if (n_rows < 0 || len < 2 || disp_w < 2 || (n_rows > 0 && (!d_rows || !d_mag)))
+        return pss_fail(ctx, PSS_E_ARG, "pss_surface_mags: bad argument (len >= 2, disp_w >= 2, n_rows >= 0, non-null buffers)");
+    if (n_rows == 0) return PSS_OK;
+    PssTimeScope timed(ctx);
+    pss_kernel_begin(ctx, "k_surface_mags");
+    if (len <= MAGS_WAVE_MAX_LEN) launch_surface_mags<T, 1, true>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
+    else if (len <= MAGS_LDS_MAX_LEN) launch_surface_mags<T, 4, true>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
+    else launch_surface_mags<T, 4, false>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_surface_mags launch");
+}
+
+// argument rules shared by the device and the host expansions
+bool mags_cells_args_ok(const int8_t *mag, long n_rows, int max_h, int max_w, const int8_t *colour)
+{
+    return n_rows >= 0 && max_h >= 4 && max_w >= 10 && (n_rows == 0 || (mag && colour));
+}
+bool masks_cells_args_ok(const uint32_t *mask, long n_frames, int max_h, int max_w, const int8_t *grid)
+{
+    return n_frames >= 0 && max_h >= 1 && max_w >= 1 && (n_frames == 0 || (mask && grid));
+}
+}  // namespace
+
+extern "C" int pss_surface_mags(pss_ctx *ctx, const float *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return surface_mags<float>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
+}
+extern "C" int pss_surface_mags_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    return surface_mags<double>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
+}
+
+// The expansion reads the magnitudes it is given: a value below -1 cannot come from pss_surface_mags, is not checked on the device and draws
+// nothing there.
+extern "C" int pss_mags_cells(pss_ctx *ctx, const int8_t *d_mag, long n_rows, int max_h, int max_w, int8_t *d_colour)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (!mags_cells_args_ok(d_mag, n_rows, max_h, max_w, d_colour))
+        return pss_fail(ctx, PSS_E_ARG, "pss_mags_cells: bad argument (max_h >= 4, max_w >= 10, n_rows >= 0, non-null buffers)");
+    if (n_rows == 0) return PSS_OK;
+    const long total = n_rows * max_h * max_w, blocks = (total + 255) / 256;
+    pss_kernel_begin(ctx, "k_mags_cells");
+    hipLaunchKernelGGL(pss_views::k_mags_cells, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, PSS_STREAM(ctx), d_mag, n_rows, max_h,
+                       max_w, d_colour);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_mags_cells launch");
+}
+
+// The same expansion on the host, in the reference's own loop order (later steps overwrite): pure C, no context, no GPU.
+extern "C" int pss_h_mags_cells(const int8_t *mag, long n_rows, int max_h, int max_w, int8_t *colour)
+{
+    if (!mags_cells_args_ok(mag, n_rows, max_h, max_w, colour)) return PSS_E_ARG;
+    const int w = max_w - 8;
+    for (long c = 0; c < n_rows * w; c++)
+        if (mag[c] < -1) return PSS_E_ARG;
+    for (long f = 0; f < n_rows; f++) {
+        int8_t *co = colour + f * max_h * max_w;
+        for (long c = 0; c < (long)max_h * max_w; c++) co[c] = 0;
+        for (int x = 0; x < w; x++)
+            for (int y = 0; y < mag[f * w + x]; y++) {
+                int sx, sy;
+                if (pss_views::surface_hit(x, y, max_h, max_w, sx, sy)) co[sy * max_w + sx] = (int8_t)(1 + y % 5);
+            }
+    }
+    return PSS_OK;
+}
+
+extern "C" int pss_vector_masks(pss_ctx *ctx, const float *d_iq, long n_frames, int n, int max_h, int max_w, uint32_t *d_mask)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    const long words = ((long)max_w + 31) / 32;
+    if (n_frames < 0 || n < 0 || max_h < 1 || max_w < 1 || (long)max_h * words > MASK_MAX_WORDS || (n_frames > 0 && (!d_iq || !d_mask)))
+        return pss_fail(ctx, PSS_E_ARG, "pss_vector_masks: bad argument (counts >= 0, max_h >= 1, max_w >= 1, max_h * ((max_w + 31) / 32) <= 16384, non-null buffers)");
+    if (n_frames == 0) return PSS_OK;
+    const size_t mask_bytes = (size_t)max_h * words * sizeof(uint32_t);
+    PssTimeScope timed(ctx);
+    pss_kernel_begin(ctx, "k_vector_masks");
+    if (n <= MASK_WAVE_MAX_N && 4 * mask_bytes <= 64 * 1024) {
+        const long groups = (n_frames + 3) / 4;
+        hipLaunchKernelGGL(pss_views::k_vector_masks<1>, dim3((unsigned)(groups < MASK_MAX_GROUPS ? groups : MASK_MAX_GROUPS)), dim3(256), 4 * mask_bytes,
+                           PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n_frames, n, max_h, max_w, d_mask);
+    } else {
+        hipLaunchKernelGGL(pss_views::k_vector_masks<8>, dim3((unsigned)(n_frames < MASK_MAX_GROUPS ? n_frames : MASK_MAX_GROUPS)), dim3(512), mask_bytes,
+                           PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n_frames, n, max_h, max_w, d_mask);
+    }
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_vector_masks launch");
+}
+
+extern "C" int pss_masks_cells(pss_ctx *ctx, const uint32_t *d_mask, long n_frames, int max_h, int max_w, int8_t *d_grid)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (!masks_cells_args_ok(d_mask, n_frames, max_h, max_w, d_grid))
+        return pss_fail(ctx, PSS_E_ARG, "pss_masks_cells: bad argument (max_h >= 1, max_w >= 1, n_frames >= 0, non-null buffers)");
+    if (n_frames == 0) return PSS_OK;
+    const long total = n_frames * max_h * max_w, blocks = (total + 255) / 256;
+    pss_kernel_begin(ctx, "k_masks_cells");
+    hipLaunchKernelGGL(pss_views::k_masks_cells, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, PSS_STREAM(ctx), d_mask, n_frames, max_h,
+                       max_w, d_grid);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_masks_cells launch");
+}
+
+extern "C" int pss_h_masks_cells(const uint32_t *mask, long n_frames, int max_h, int max_w, int8_t *grid)
+{
+    if (!masks_cells_args_ok(mask, n_frames, max_h, max_w, grid)) return PSS_E_ARG;
+    const long words = ((long)max_w + 31) / 32, lines = n_frames * max_h;
+    for (long q = 0; q < lines; q++)
+        for (int x = 0; x < max_w; x++) grid[q * max_w + x] = (int8_t)((mask[q * words + (x >> 5)] >> (x & 31)) & 1u);
+    return PSS_OK;
 }
 
 extern "C" int pss_waterfall_cells_f64(pss_ctx *ctx, const double *d_rows, int n_rows, int len, int disp_h, int disp_w,

@@ -3,6 +3,8 @@
 // pss_demod.hip's flags.
 #include <hip/hip_runtime.h>
 
+#include <string>
+
 #include "pss_ctx.h"
 
 extern "C" int pss_spectrum_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db,
@@ -240,20 +242,18 @@ extern "C" int pss_spectrum_cells(pss_ctx *ctx, const float *d_iq, long n_frames
                                   d_line_a, d_line_b, nullptr, d_db32, false);
 }
 
-// One loop iteration per read buffer with the reference's DEFAULT view (draw_spectrogram): pss_frame_pipeline_cells' dB rows, the demodulator's
-// PCM (d_pcm NULL: the display half alone) and per frame the bars and the scale's range of the post-processed float64 row.  The view has no
-// history: no halo, no window, no extremes.  Schedule: the demodulator on the main stream, compute_fft -> float32 rows -> post-process ->
-// k_spectrum_bars on the side stream (the AM branch of frame_pipeline_impl).  The float64 rows go through memory here (d_db64 / d_post, or the
-// context's scratch): the bars need the whole post-processed row for their percentile.
-extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
-                                       double *d_post, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range, int16_t *d_pcm)
+// One loop iteration per read buffer with a view that has no history (no halo, no window, no extremes): pss_frame_pipeline_cells' dB rows, the
+// demodulator's PCM (d_pcm NULL: the display half alone) and what `view` queues behind the post-processed float64 rows.  Schedule: the
+// demodulator on the main stream, compute_fft -> float32 rows -> post-process -> view on the side stream (the AM branch of
+// frame_pipeline_impl).  The float64 rows go through memory here (d_db64 / d_post, or the context's scratch): these views need the whole
+// post-processed row (the bars' percentile, the surface's extremes), and the header's meter reads it in every view.
+template <class View>
+static int view_pipeline(pss_ctx *ctx, const char *who, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                         double *d_post, int16_t *d_pcm, View view)
 {
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
     if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
-    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: n must be a power of two in [16, 65536]");
-    if (n_frames < 0 || disp_h < 1 || disp_h > 127 || disp_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: bad frame count or display geometry");
-    if (n_frames > 0 && (!d_iq || !d_db32 || !d_height || !d_level)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: null buffer");
+    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, std::string(who) + ": n must be a power of two in [16, 65536]");
+    if (n_frames > 0 && (!d_iq || !d_db32)) return pss_fail(ctx, PSS_E_ARG, std::string(who) + ": null buffer");
     if (n_frames == 0) return PSS_OK;
     if (!d_db64) {
         int rq = pss_ensure_buffer(ctx, &ctx->scratch_db64, &ctx->scratch_db64_bytes, (size_t)n_frames * n * sizeof(double), "float64 dB rows");
@@ -275,7 +275,7 @@ extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq
         pss_kernel_end(ctx);
         q = pss_hip_check(ctx, hipGetLastError(), "k_rows_f64_to_f32 launch");
         if (!q) q = pss_spectrum_post_f64(ctx, d_db64, n_frames, n, d_post, nullptr, nullptr);
-        if (!q) q = pss_spectrum_bars_f64(ctx, d_post, n_frames, n - 4, disp_h, disp_w, d_height, d_level, d_range);
+        if (!q) q = view(d_post);
         return q;
     };
     PssTimeScope timed(ctx);
@@ -286,6 +286,48 @@ extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq
     const int rc = pss_on_side(ctx, display_chain);
     const int rj = pss_side_join(ctx);
     return rd ? rd : (rc ? rc : rj);
+}
+
+// ... with the reference's DEFAULT view (draw_spectrogram): per frame the bars and the scale's range of the post-processed float64 row
+// (k_spectrum_bars).
+extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                                       double *d_post, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level, double *d_range, int16_t *d_pcm)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_frames < 0 || disp_h < 1 || disp_h > 127 || disp_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: bad frame count or display geometry");
+    if (n_frames > 0 && (!d_height || !d_level)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: null buffer");
+    return view_pipeline(ctx, "pss_frame_pipeline_bars", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *post) {
+        return pss_spectrum_bars_f64(ctx, post, n_frames, n - 4, disp_h, disp_w, d_height, d_level, d_range);
+    });
+}
+
+// ... with the surface plot (draw_surface_plot): per frame the magnitudes and the finite extremes of the post-processed float64 row
+// (k_surface_mags).
+extern "C" int pss_frame_pipeline_surface(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                                          double *d_post, int disp_w, int8_t *d_mag, double *d_range, int16_t *d_pcm)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_frames < 0 || disp_w < 2) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_surface: bad frame count or display width");
+    if (n_frames > 0 && !d_mag) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_surface: null buffer");
+    return view_pipeline(ctx, "pss_frame_pipeline_surface", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *post) {
+        return pss_surface_mags_f64(ctx, post, n_frames, n - 4, disp_w, d_mag, d_range);
+    });
+}
+
+// ... with the constellation (draw_vector_display): the masks of the read buffers AS READ (the reference hands `samples` to the view, not the
+// corrected copy the WFM demodulator works on), and the rows all the same: the header's meter reads them in this view too.
+extern "C" int pss_frame_pipeline_vector(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, float *d_db32, double *d_db64,
+                                         double *d_post, int max_h, int max_w, uint32_t *d_mask, int16_t *d_pcm)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_frames < 0 || max_h < 1 || max_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_vector: bad frame count or screen size");
+    if (n_frames > 0 && !d_mask) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_vector: null buffer");
+    return view_pipeline(ctx, "pss_frame_pipeline_vector", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *) {
+        return pss_vector_masks(ctx, d_iq, n_frames, n, max_h, max_w, d_mask);
+    });
 }
 
 extern "C" int pss_frame_pipeline_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db, float *d_post,

@@ -450,6 +450,37 @@ class Engine:
     def vector_cells(self, d_iq, n, max_h, max_w, d_grid):
         self._dev(self.lib.pss_vector_cells, _ptr(d_iq), n, max_h, max_w, _ptr(d_grid))
 
+    def surface_mags(self, d_rows, n_rows, length, disp_w, d_mag, d_range=None, f64=False):
+        """draw_surface_plot per row in its compact form: int(value * 20) per column (int8 [n_rows][disp_w], disp_w = max_w - 8, -1 = not
+        drawn) and the row's finite (min_val, max_val) [n_rows][2].  formats.surface_cells / mags_cells expand them to surface_cells' grids."""
+        fn = self.lib.pss_surface_mags_f64 if f64 else self.lib.pss_surface_mags
+        self._dev(fn, _ptr(d_rows), n_rows, length, disp_w, _ptr(d_mag), _ptr(d_range))
+
+    def mags_cells(self, d_mag, n_rows, max_h, max_w, d_colour):
+        """surface_mags' magnitudes expanded on the device to the colour grids [n_rows][max_h][max_w] surface_cells writes."""
+        self._dev(self.lib.pss_mags_cells, _ptr(d_mag), n_rows, max_h, max_w, _ptr(d_colour))
+
+    def vector_masks(self, d_iq, n_frames, n, max_h, max_w, d_mask):
+        """draw_vector_display per read buffer in its compact form: one bit per screen cell, uint32 [n_frames][max_h][(max_w + 31) // 32]
+        (int32 tensors serve).  formats.vector_cells / masks_cells expand them to vector_cells' grids."""
+        self._dev(self.lib.pss_vector_masks, _ptr(d_iq), n_frames, n, max_h, max_w, _ptr(d_mask))
+
+    def masks_cells(self, d_mask, n_frames, max_h, max_w, d_grid):
+        """vector_masks' masks expanded on the device to the int8 grids [n_frames][max_h][max_w] vector_cells writes."""
+        self._dev(self.lib.pss_masks_cells, _ptr(d_mask), n_frames, max_h, max_w, _ptr(d_grid))
+
+    def frame_pipeline_surface(self, mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, disp_w, d_mag, d_range=None, d_pcm=None):
+        """One main-loop iteration per read buffer with the SURFACE view: frame_pipeline_bars' rows and PCM (d_pcm=None: the display half
+        alone), the surface magnitudes and finite extremes of every frame's post-processed row."""
+        self._dev(self.lib.pss_frame_pipeline_surface, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_post), disp_w,
+                  _ptr(d_mag), _ptr(d_range), _ptr(d_pcm))
+
+    def frame_pipeline_vector(self, mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, max_h, max_w, d_mask, d_pcm=None):
+        """One main-loop iteration per read buffer with the VECTOR view: frame_pipeline_bars' rows and PCM (d_pcm=None: the display half
+        alone) and the constellation masks of the read buffers as read."""
+        self._dev(self.lib.pss_frame_pipeline_vector, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_post), max_h,
+                  max_w, _ptr(d_mask), _ptr(d_pcm))
+
     def morse_edges(self, d_iq, n_frames, n, cap, d_rise, d_fall, d_counts, threshold_db=-20.0):
         self._dev(self.lib.pss_morse_edges, _ptr(d_iq), n_frames, n, float(threshold_db), cap, _ptr(d_rise), _ptr(d_fall),
                                           _ptr(d_counts))

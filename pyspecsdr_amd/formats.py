@@ -83,6 +83,53 @@ def bars_cells(height, level, disp_h, lib=None):
     return glyph, colour
 
 
+def surface_cells(mag, max_h, max_w, lib=None):
+    """pss_h_mags_cells: surface magnitudes (int8 [..., max_w - 8], -1 = column not drawn) expanded to draw_surface_plot's grid -> colour
+    int8 [..., max_h, max_w]: 0 = empty, else the curses pair 1..5 of the '#' drawn there.  Pure host code: needs the library, not a GPU."""
+    lib = lib or L.load()
+    mag = np.ascontiguousarray(mag, np.int8)
+    max_h, max_w = int(max_h), int(max_w)
+    if mag.ndim < 1 or mag.shape[-1] != max_w - 8:
+        raise ValueError("mag must have the shape [..., max_w - 8]")
+    n_rows = mag.size // mag.shape[-1] if mag.shape[-1] > 0 else 0
+    colour = np.empty(mag.shape[:-1] + (max(max_h, 0), max(max_w, 0)), np.int8)
+    if lib.pss_h_mags_cells(mag.ctypes.data, n_rows, max_h, max_w, colour.ctypes.data) != 0:
+        raise ValueError("pss_h_mags_cells: max_h < 4, max_w < 10 or a magnitude below -1")
+    return colour
+
+
+def vector_cells(mask, max_h, max_w, lib=None):
+    """pss_h_masks_cells: constellation masks (uint32 [..., max_h, (max_w + 31) // 32], bit x & 31 of word x >> 5) expanded to
+    draw_vector_display's grid -> int8 [..., max_h, max_w], 1 where a '.' lands.  Pure host code: needs the library, not a GPU."""
+    lib = lib or L.load()
+    mask = np.ascontiguousarray(mask)
+    if mask.dtype != np.uint32:
+        mask = mask.view(np.uint32) if mask.dtype == np.int32 else mask.astype(np.uint32)
+    max_h, max_w = int(max_h), int(max_w)
+    if max_h < 1 or max_w < 1 or mask.ndim < 2 or mask.shape[-2:] != (max_h, (max_w + 31) // 32):
+        raise ValueError("mask must have the shape [..., max_h, (max_w + 31) // 32] with max_h, max_w >= 1")
+    n_frames = mask.size // (max_h * mask.shape[-1])
+    grid = np.empty(mask.shape[:-2] + (max_h, max_w), np.int8)
+    if lib.pss_h_masks_cells(mask.ctypes.data, n_frames, max_h, max_w, grid.ctypes.data) != 0:
+        raise ValueError("pss_h_masks_cells: bad argument")
+    return grid
+
+
+def surface_scale_labels(min_val, max_val, disp_h):
+    """draw_surface_plot's amplitude scale (pyspecsdr.py:1609-1612) for a row's finite extremes (surface_mags' d_range): the (line, text)
+    pairs of every third display line (disp_h = max_h - 4; the reference draws line i at screen row i + 2, column 0).  db_range carries
+    the zero guard of :1578-1579: a constant row's labels step by 1 / disp_h."""
+    db_range = max_val - min_val
+    if db_range == 0:
+        db_range = 1
+    labels = []
+    for i in range(int(disp_h)):
+        db_value = max_val - (i * db_range / disp_h)
+        if i % 3 == 0:
+            labels.append((i, f"{db_value:4.0f}dB"))
+    return labels
+
+
 def _squelch_args(squelch, meter_every, peak_power, frame_len, mode):
     """demodulate_recording's argument checks for the squelch path (host only: made before anything touches the GPU)."""
     if mode not in _MODES:
