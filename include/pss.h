@@ -656,6 +656,43 @@ int pss_h_stream_display_nfm_f64(pss_ctx *ctx, const float *h_iq, long n_frames,
                                  int8_t *h_line_a, int8_t *h_line_b, int16_t *h_pcm, double *h_db, double *h_row_lo, double *h_row_hi,
                                  int8_t *h_grid_a, int8_t *h_grid_b);
 
+/* ---- ADC codes: read buffers as the radio delivers them ---------------------------------------------
+ * Every entry point above takes complex64 (SoapySDR CF32: the driver's widening of the converter's integer codes).  These take the
+ * codes: interleaved I,Q pairs in an 8-bit or int16 container, uploaded as they are (2 or 4 bytes per sample over the link instead
+ * of 8) and widened on the device into the complex64 buffer the driver would have produced, bit for bit.  Drivers differ in that
+ * widening, so it is not hard-wired:
+ *   8-bit containers   iq_word = table256[index], index = the byte (PSS_IQ_U8) or code + 128 (PSS_IQ_S8); whatever the table holds
+ *                      comes out unchanged (NaN, -0 included).  pss_h_iq_table fills it for a (scale, offset) grid.
+ *   PSS_IQ_S16         iq_word = (float)code / (float)scale: one correctly rounded float32 division (NumPy's
+ *                      codes.astype(float32) / float32(scale)); scale 2048 for 12-bit codes, 32768 for 16-bit ones.
+ * table256 / h_table256 are HOST pointers, read during the call and not retained: required for the 8-bit containers, NULL for
+ * PSS_IQ_S16.  scale: finite and > 0 for PSS_IQ_S16, ignored otherwise.  Violations: PSS_E_ARG (pss_last_error; with NULL for the
+ * calls without a context). */
+#define PSS_IQ_U8 0   /* uint8 I,Q pairs   (.cu8) */
+#define PSS_IQ_S8 1   /* int8 I,Q pairs    (.cs8) */
+#define PSS_IQ_S16 2  /* int16 LE I,Q pairs (.cs16; 12-bit codes use scale 2048) */
+int pss_iq_code_bytes(int container);   /* bytes per complex sample: 2, 2, 4; < 0: unknown container */
+/* table256[i] = (float)(((double)code_i - offset) / scale), rounded once; code_i = i (PSS_IQ_U8) or i - 128 (PSS_IQ_S8). */
+int pss_h_iq_table(int container, double scale, double offset, float *table256);
+/* The widening restated on the host: codes (any address) -> iq, 2 * n_samples float32 words. */
+int pss_h_unpack_iq(int container, const void *codes, long n_samples, double scale, const float *table256, float *iq);
+/* The same on the device, queued on the context's stream (no allocation, no host wait).  d_codes: any address with the container's
+ * natural alignment (1 byte; 2 for int16); d_iq: 8-byte aligned, 2 * n_samples float32 words.  n_samples == 0: PSS_OK. */
+int pss_unpack_iq(pss_ctx *ctx, int container, const void *d_codes, long n_samples, double scale, const float *h_table256, float *d_iq);
+/* pss_h_demodulate_batch on a recording of codes (h_codes: n_frames x n samples): the codes go up, are unpacked on the device. */
+int pss_h_demodulate_batch_codes(pss_ctx *ctx, int container, double scale, const float *h_table256, int mode, const void *h_codes,
+                                 long n_frames, int n, double fs, long chunk_frames, int16_t *h_pcm);
+/* pss_h_stream_display_nfm / _f64 on a capture of codes: per chunk the codes are uploaded on the copy stream and unpacked on the compute
+ * stream in front of the chunk's kernels.  Every result is that of the complex64 call on the unpacked capture. */
+int pss_h_stream_display_nfm_codes(pss_ctx *ctx, int container, double scale, const float *h_table256, const void *h_codes, long n_frames,
+                                   int n, double fs, long chunk_frames, int mode, int window, int disp_h, int disp_w, const float *h_halo_lo,
+                                   const float *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b, int16_t *h_pcm, float *h_db,
+                                   float *h_row_lo, float *h_row_hi);
+int pss_h_stream_display_nfm_codes_f64(pss_ctx *ctx, int container, double scale, const float *h_table256, const void *h_codes, long n_frames,
+                                       int n, double fs, long chunk_frames, int mode, int window, int disp_h, int disp_w,
+                                       const double *h_halo_lo, const double *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b,
+                                       int16_t *h_pcm, double *h_db, double *h_row_lo, double *h_row_hi, int8_t *h_grid_a, int8_t *h_grid_b);
+
 /* ---- Multi-GPU: the path's exchange steps (one process per GPU, RCCL over xGMI) ----------------------------------------------------------
  * The path shards by contiguous blocks of independent frames / scanner slices (the sweep of pyspecsdr.py:2514-2590; every read buffer of
  * the loop :2236-2283 is processed on its own): every rank runs the single-GPU entry points above on its block, with NO collective in

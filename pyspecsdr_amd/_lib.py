@@ -13,6 +13,7 @@ PSS_OK, PSS_E_ARG, PSS_E_HIP, PSS_E_PADLEN, PSS_E_CUTOFF, PSS_E_NOMEM, PSS_E_COM
 COMM_ID_BYTES = 128
 MODE_NFM, MODE_AM, MODE_USB, MODE_LSB, MODE_WFM = 0, 1, 2, 3, 4
 NP_ARCTAN2, NP_LOG10, NP_ABS = 0, 1, 2          # pss_np_f32 operations
+IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2                  # ADC code containers (PSS_IQ_*)
 
 _p = C.c_void_p
 _SIGS = {
@@ -152,6 +153,15 @@ _SIGS = {
                                                  _p, _p, _p, _p, _p]),
     "pss_h_stream_display_nfm_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p,
                                                C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pss_iq_code_bytes": (C.c_int, [C.c_int]),
+    "pss_h_iq_table": (C.c_int, [C.c_int, C.c_double, C.c_double, _p]),
+    "pss_h_unpack_iq": (C.c_int, [C.c_int, _p, C.c_long, C.c_double, _p, _p]),
+    "pss_unpack_iq": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_double, _p, _p]),
+    "pss_h_demodulate_batch_codes": (C.c_int, [_p, C.c_int, C.c_double, _p, C.c_int, _p, C.c_long, C.c_int, C.c_double, C.c_long, _p]),
+    "pss_h_stream_display_nfm_codes": (C.c_int, [_p, C.c_int, C.c_double, _p, _p, C.c_long, C.c_int, C.c_double, C.c_long, C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p]),
+    "pss_h_stream_display_nfm_codes_f64": (C.c_int, [_p, C.c_int, C.c_double, _p, _p, C.c_long, C.c_int, C.c_double, C.c_long, C.c_int, C.c_int,
+                                                     C.c_int, C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pss_shard_range": (C.c_int, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pss_comm_id": (C.c_int, [_p]),
     "pss_comm_init": (C.c_int, [_p, _p, C.c_int, C.c_int]),

@@ -455,25 +455,37 @@ extern "C" int pss_h_demodulate_signal(pss_ctx *ctx, int mode, const float *h_iq
 // demodulate_signal over a batch of frames in HOST memory (a recording cut into read buffers, pyspecsdr.py:814-824 /
 // :2236): chunks of frames go up, through pss_demod_signal, and the int16 PCM comes back — the byte stream
 // audio_processing.write_audio_samples / io_manager.write_to_pipe would have produced buffer by buffer.
-extern "C" int pss_h_demodulate_batch(pss_ctx *ctx, int mode, const float *h_iq, long n_frames, int n, double fs,
-                                      long chunk_frames, int16_t *h_pcm)
+// fmt: the recording's sample format; ADC codes are uploaded as they are and unpacked in front of the demodulator (pss_ingest.hip)
+static int h_demod_batch_impl(pss_ctx *ctx, int mode, const void *h_in, const PssIqFmt &fmt, long n_frames, int n, double fs,
+                              long chunk_frames, int16_t *h_pcm)
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
-    if (!h_iq || !h_pcm || n_frames < 0 || n < 1 || chunk_frames < 1) return pss_fail(ctx, PSS_E_ARG, "bad arguments");
+    if (fmt.codes) {
+        const int rf = pss_iq_check(ctx, fmt.container, fmt.scale, fmt.h_table256);
+        if (rf) return rf;
+    }
+    if (!h_in || !h_pcm || n_frames < 0 || n < 1 || chunk_frames < 1) return pss_fail(ctx, PSS_E_ARG, "bad arguments");
+    const char *h_bytes = static_cast<const char *>(h_in);
+    const size_t sample_b = fmt.sample_bytes();
     const int n_out = pss_demod_out_len_ctx(ctx, mode, n, fs);
     if (n_out < 0) return pss_fail(ctx, PSS_E_ARG, "unknown mode or sample rate below the target rate");
     if (chunk_frames > n_frames) chunk_frames = n_frames;
     if (n_frames == 0) return PSS_OK;
     const size_t iq_b = up256((size_t)chunk_frames * n * 2 * sizeof(float));
     const size_t pcm_b = up256((size_t)chunk_frames * n_out * 2 * sizeof(int16_t));
-    int r = pss_ensure_buffer(ctx, &ctx->stage, &ctx->stage_bytes, iq_b + pcm_b, "staging");
+    const size_t codes_b = fmt.codes ? up256((size_t)chunk_frames * n * sample_b) : 0;
+    int r = pss_ensure_buffer(ctx, &ctx->stage, &ctx->stage_bytes, iq_b + pcm_b + codes_b, "staging");
     if (r) return r;
     char *base = reinterpret_cast<char *>(ctx->stage);
+    char *d_in = fmt.codes ? base + iq_b + pcm_b : base;
     for (long f0 = 0; f0 < n_frames; f0 += chunk_frames) {
         const long cnt = (n_frames - f0) < chunk_frames ? (n_frames - f0) : chunk_frames;
-        PSS_HIP(ctx, hipMemcpyAsync(base, h_iq + (size_t)f0 * n * 2, (size_t)cnt * n * 2 * sizeof(float), hipMemcpyHostToDevice,
-                                    ctx->stream));
+        PSS_HIP(ctx, hipMemcpyAsync(d_in, h_bytes + (size_t)f0 * n * sample_b, (size_t)cnt * n * sample_b, hipMemcpyHostToDevice, ctx->stream));
+        if (fmt.codes) {
+            r = pss_unpack_iq(ctx, fmt.container, d_in, cnt * (long)n, fmt.scale, fmt.h_table256, reinterpret_cast<float *>(base));
+            if (r) return r;
+        }
         r = pss_demod_signal(ctx, mode, reinterpret_cast<const float *>(base), cnt, n, fs, reinterpret_cast<int16_t *>(base + iq_b),
                              nullptr);
         if (r) return r;
@@ -482,6 +494,18 @@ extern "C" int pss_h_demodulate_batch(pss_ctx *ctx, int mode, const float *h_iq,
         PSS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return PSS_OK;
+}
+
+extern "C" int pss_h_demodulate_batch(pss_ctx *ctx, int mode, const float *h_iq, long n_frames, int n, double fs,
+                                      long chunk_frames, int16_t *h_pcm)
+{
+    return h_demod_batch_impl(ctx, mode, h_iq, PssIqFmt{}, n_frames, n, fs, chunk_frames, h_pcm);
+}
+
+extern "C" int pss_h_demodulate_batch_codes(pss_ctx *ctx, int container, double scale, const float *h_table256, int mode, const void *h_codes,
+                                            long n_frames, int n, double fs, long chunk_frames, int16_t *h_pcm)
+{
+    return h_demod_batch_impl(ctx, mode, h_codes, PssIqFmt::of_codes(container, scale, h_table256), n_frames, n, fs, chunk_frames, h_pcm);
 }
 
 extern "C" int pss_h_measure_power(pss_ctx *ctx, const float *h_iq, int n, float *h_power)
@@ -731,7 +755,7 @@ inline int sd_ps_cells(pss_ctx *c, const float *r, int nr, int m, int dh, int dw
 inline int sd_ps_cells(pss_ctx *c, const double *r, int nr, int m, int dh, int dw, int8_t *a) { return pss_persistence_cells_f64(c, r, nr, m, dh, dw, a); }
 }  // namespace
 template <class TR>
-static int stream_display(pss_ctx *ctx, const float *h_iq, long n_frames, int n, double fs, long chunk_frames,
+static int stream_display(pss_ctx *ctx, const void *h_in, const PssIqFmt &fmt, long n_frames, int n, double fs, long chunk_frames,
                           int mode, int window, int disp_h, int disp_w, const TR *h_halo_lo,
                           const TR *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b, int16_t *h_pcm,
                           TR *h_db, TR *h_row_lo, TR *h_row_hi, int8_t *h_grid_a, int8_t *h_grid_b)
@@ -740,7 +764,11 @@ static int stream_display(pss_ctx *ctx, const float *h_iq, long n_frames, int n,
     PSS_GUARD(ctx);
     if (h_grid_a && (window > 64 || (mode == 0 && !h_grid_b)))
         return pss_fail(ctx, PSS_E_ARG, "stream display grids: window <= 64, and both planes for the waterfall");
-    if (!h_iq || !h_pcm || !h_line_a || n_frames < 0 || n < 8 || chunk_frames < 1 || window < 1 || disp_w < 1 || disp_h < 1 ||
+    if (fmt.codes) {
+        const int rf = pss_iq_check(ctx, fmt.container, fmt.scale, fmt.h_table256);
+        if (rf) return rf;
+    }
+    if (!h_in || !h_pcm || !h_line_a || n_frames < 0 || n < 8 || chunk_frames < 1 || window < 1 || disp_w < 1 || disp_h < 1 ||
         disp_h > 127 || n_halo < 0 || (mode != 0 && mode != 1) || (mode == 0 && !h_line_b) || (n_halo > 0 && (!h_halo_lo || !h_halo_hi)))
         return pss_fail(ctx, PSS_E_ARG, "bad stream-display arguments");
     const int n_out = pss_demod_out_len_ctx(ctx, PSS_MODE_NFM, n, fs);
@@ -751,6 +779,10 @@ static int stream_display(pss_ctx *ctx, const float *h_iq, long n_frames, int n,
     const size_t iq_b = (size_t)chunk_frames * n * 2 * sizeof(float), db_b = (size_t)chunk_frames * n * sizeof(TR),
                  post_b = (size_t)chunk_frames * m * sizeof(TR), pcm_b = (size_t)chunk_frames * n_out * 2 * sizeof(int16_t),
                  line_b = (size_t)chunk_frames * disp_w;
+    // ADC codes: the chunk goes up as codes into a buffer pair of its own and is unpacked into d_iq[b] on the compute stream
+    const char *h_bytes = static_cast<const char *>(h_in);
+    const size_t sample_b = fmt.sample_bytes();
+    void *d_codes[2] = {nullptr, nullptr};
     int rc = stream_res(ctx);
     if (rc) return rc;
     hipStream_t s_up = ctx->st_up, s_dn = ctx->st_dn;
@@ -764,6 +796,7 @@ static int stream_display(pss_ctx *ctx, const float *h_iq, long n_frames, int n,
         if (!rc) rc = stream_buf(ctx, 4 + i, pcm_b, &d_pcm[i]);
         if (!rc) rc = stream_buf(ctx, 6 + i, line_b, &d_la[i]);
         if (!rc && mode == 0) rc = stream_buf(ctx, 8 + i, line_b, &d_lb[i]);
+        if (!rc && fmt.codes) rc = stream_buf(ctx, 18 + i, (size_t)chunk_frames * n * sample_b, &d_codes[i]);
     }
     if (!rc) rc = stream_buf(ctx, 10, post_b, &d_post);
     if (!rc) rc = stream_buf(ctx, 11, 2 * n_ext * sizeof(TR), &d_ext);
@@ -803,10 +836,15 @@ static int stream_display(pss_ctx *ctx, const float *h_iq, long n_frames, int n,
         // whichever hardware queue the upload stream shares (the runtime multiplexes streams over a few queues), and sat behind chunk k-1's
         // kernels there — uploads and compute alternated instead of overlapping (21.4 ms per cfg 5 capture; 15 ms with the host-side wait)
         if (k >= 2) STREAM_HIP(hipEventSynchronize(dn_done[b]));
-        STREAM_HIP(hipMemcpyAsync(d_iq[b], h_iq + (size_t)f0 * n * 2, (size_t)cnt * n * 2 * sizeof(float), hipMemcpyHostToDevice, s_up));
+        STREAM_HIP(hipMemcpyAsync(fmt.codes ? d_codes[b] : d_iq[b], h_bytes + (size_t)f0 * n * sample_b, (size_t)cnt * n * sample_b,
+                                  hipMemcpyHostToDevice, s_up));
         STREAM_HIP(hipEventRecord(up_done[b], s_up));
         STREAM_HIP(hipStreamWaitEvent(ctx->stream, up_done[b], 0));
         if (k >= 2) STREAM_HIP(hipStreamWaitEvent(ctx->stream, dn_done[b], 0));
+        if (fmt.codes) {
+            rc = pss_unpack_iq(ctx, fmt.container, d_codes[b], cnt * (long)n, fmt.scale, fmt.h_table256, (float *)d_iq[b]);
+            if (rc) { cleanup(); return rc; }
+        }
         {
             PssFlagScope keep(ctx->no_small_batch, true);   // chunks of a stream are throughput work: fused large-batch kernels
             rc = sd_spectrum_nfm(ctx, (const float *)d_iq[b], cnt, n, fs, (TR *)d_db[b], (int16_t *)d_pcm[b]);
@@ -862,7 +900,7 @@ extern "C" int pss_h_stream_display_nfm(pss_ctx *ctx, const float *h_iq, long n_
                                         const float *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b, int16_t *h_pcm,
                                         float *h_db, float *h_row_lo, float *h_row_hi)
 {
-    return stream_display<float>(ctx, h_iq, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, h_halo_lo, h_halo_hi, n_halo, h_line_a,
+    return stream_display<float>(ctx, h_iq, PssIqFmt{}, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, h_halo_lo, h_halo_hi, n_halo, h_line_a,
                                  h_line_b, h_pcm, h_db, h_row_lo, h_row_hi, nullptr, nullptr);
 }
 
@@ -874,7 +912,7 @@ extern "C" int pss_h_stream_display_nfm_f64(pss_ctx *ctx, const float *h_iq, lon
 {
     if (ctx && (n < 16 || n > 65536 || (n & (n - 1)))) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_f64: n must be a power of two in [16, 65536]");
     if (ctx && h_grid_a && n_halo > 0) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_f64: grids need a fresh history (no halo)");
-    return stream_display<double>(ctx, h_iq, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, h_halo_lo, h_halo_hi, n_halo, h_line_a,
+    return stream_display<double>(ctx, h_iq, PssIqFmt{}, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, h_halo_lo, h_halo_hi, n_halo, h_line_a,
                                   h_line_b, h_pcm, h_db, h_row_lo, h_row_hi, h_grid_a, h_grid_b);
 }
 
@@ -883,6 +921,28 @@ extern "C" int pss_h_stream_display_nfm_grids(pss_ctx *ctx, const float *h_iq, l
                                               int16_t *h_pcm, float *h_row_lo, float *h_row_hi, int8_t *h_grid_a, int8_t *h_grid_b)
 {
     if (ctx && !h_grid_a) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_grids: h_grid_a is null");
-    return stream_display<float>(ctx, h_iq, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, nullptr, nullptr, 0, h_line_a, h_line_b,
+    return stream_display<float>(ctx, h_iq, PssIqFmt{}, n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w, nullptr, nullptr, 0, h_line_a, h_line_b,
                                  h_pcm, nullptr, h_row_lo, h_row_hi, h_grid_a, h_grid_b);
+}
+
+// ... and on captures of ADC codes (include/pss.h "ADC codes"): the same template, the codes uploaded and unpacked chunk by chunk
+extern "C" int pss_h_stream_display_nfm_codes(pss_ctx *ctx, int container, double scale, const float *h_table256, const void *h_codes,
+                                              long n_frames, int n, double fs, long chunk_frames, int mode, int window, int disp_h, int disp_w,
+                                              const float *h_halo_lo, const float *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b,
+                                              int16_t *h_pcm, float *h_db, float *h_row_lo, float *h_row_hi)
+{
+    return stream_display<float>(ctx, h_codes, PssIqFmt::of_codes(container, scale, h_table256), n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w,
+                                 h_halo_lo, h_halo_hi, n_halo, h_line_a, h_line_b, h_pcm, h_db, h_row_lo, h_row_hi, nullptr, nullptr);
+}
+
+extern "C" int pss_h_stream_display_nfm_codes_f64(pss_ctx *ctx, int container, double scale, const float *h_table256, const void *h_codes,
+                                                  long n_frames, int n, double fs, long chunk_frames, int mode, int window, int disp_h,
+                                                  int disp_w, const double *h_halo_lo, const double *h_halo_hi, int n_halo, int8_t *h_line_a,
+                                                  int8_t *h_line_b, int16_t *h_pcm, double *h_db, double *h_row_lo, double *h_row_hi,
+                                                  int8_t *h_grid_a, int8_t *h_grid_b)
+{
+    if (ctx && (n < 16 || n > 65536 || (n & (n - 1)))) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_codes_f64: n must be a power of two in [16, 65536]");
+    if (ctx && h_grid_a && n_halo > 0) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_codes_f64: grids need a fresh history (no halo)");
+    return stream_display<double>(ctx, h_codes, PssIqFmt::of_codes(container, scale, h_table256), n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w,
+                                  h_halo_lo, h_halo_hi, n_halo, h_line_a, h_line_b, h_pcm, h_db, h_row_lo, h_row_hi, h_grid_a, h_grid_b);
 }

@@ -72,8 +72,8 @@ struct pss_ctx {
     // (creating and freeing them per capture cost ~2 ms of a 17 ms capture)
     hipStream_t st_up = nullptr, st_dn = nullptr;
     hipEvent_t st_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // up_done[2], cmp_done[2], dn_done[2]
-    void *st_buf[18] = {};         // [0..11]: the chunk buffer sets; [12..15]: per-chunk display grids (two sets x two planes); [16..17]: the last `window` post-processed rows (ping-pong)
-    size_t st_cap[18] = {};
+    void *st_buf[20] = {};         // [0..11]: the chunk buffer sets; [12..15]: per-chunk display grids (two sets x two planes); [16..17]: the last `window` post-processed rows (ping-pong); [18..19]: the chunk's ADC codes as uploaded (the *_codes calls, pss_ingest.hip)
+    size_t st_cap[20] = {};
     float *d_hann_short = nullptr;  // the same for reads shorter than 1024 samples (window length = read length hann_short_n)
     float hann_short_sum = 0.0f;
     int hann_short_n = 0;
@@ -212,6 +212,24 @@ int pss_demod_run(pss_ctx *ctx, int mode, PssIq iq, long n_frames, int n, double
         int _r = pss_hip_check((ctx), (call), #call);              \
         if (_r) return _r;                                         \
     } while (0)
+
+// implemented in pss_ingest.hip: the argument rules every *_codes entry point shares (container, scale, table); ctx may be NULL
+int pss_iq_check(pss_ctx *ctx, int container, double scale, const float *h_table256);
+// A host capture's sample format: complex64 as it is (the default), or ADC codes that are unpacked on the device.  `codes` is set by
+// of_codes alone, never derived from the caller's container, so no container value can select the complex64 path.
+struct PssIqFmt {
+    bool codes = false;
+    int container = 0;
+    double scale = 0.0;
+    const float *h_table256 = nullptr;
+    static PssIqFmt of_codes(int container, double scale, const float *h_table256)
+    {
+        PssIqFmt f;
+        f.codes = true, f.container = container, f.scale = scale, f.h_table256 = h_table256;
+        return f;
+    }
+    size_t sample_bytes() const { return codes ? (size_t)pss_iq_code_bytes(container) : 2 * sizeof(float); }   // behind pss_iq_check
+};
 
 // implemented in pss_fft.hip
 bool pss_hilbert_supported(int n);

@@ -34,6 +34,58 @@ _DISPLAYS = {"waterfall": 0, "persistence": 1, "gradient": 2}
 _WINDOWS = (30, 10, 30)
 
 
+# Read buffers as ADC codes (include/pss.h "ADC codes"): name -> (container, scale, offset), the four grids of tests/adc_cases.GRIDS.
+# cu8: rtl_sdr's files (offset binary; 127.4 is SoapyRTLSDR's zero), cs8: hackrf_transfer's, cs12 / cs16: int16 containers (airspy_rx, ...)
+IQ_FORMATS = {"cu8": (L.IQ_U8, 128.0, 127.4), "cs8": (L.IQ_S8, 128.0, 0.0), "cs12": (L.IQ_S16, 2048.0, 0.0), "cs16": (L.IQ_S16, 32768.0, 0.0)}
+_IQ_DTYPES = {L.IQ_U8: np.uint8, L.IQ_S8: np.int8, L.IQ_S16: np.int16}
+
+
+def iq_table(fmt, lib=None):
+    """pss_h_iq_table: the 256 float32 values an 8-bit format's codes widen to, table[i] = float32((code_i - offset) / scale) with
+    code_i = i (cu8) or i - 128 (cs8).  fmt: a name of IQ_FORMATS or (container, scale, offset).  Host code: no GPU needed."""
+    container, scale, offset = IQ_FORMATS[fmt] if isinstance(fmt, str) else fmt
+    table = np.empty(256, np.float32)
+    if (lib or L.load()).pss_h_iq_table(int(container), float(scale), float(offset), _ptr(table)) != 0:
+        raise ValueError("iq_table: an 8-bit format with a finite scale > 0 and a finite offset")
+    return table
+
+
+def _iq_args(fmt, table):
+    """(container, scale, table or None) of a code format for the C ABI: an 8-bit format's own table unless the caller brings one (the
+    driver's: SoapyRTLSDR's float32 formula, pyrtlsdr's c / 127.5 - 1, ...); int16 formats take no table."""
+    container, scale, _ = IQ_FORMATS[fmt] if isinstance(fmt, str) else fmt
+    if container == L.IQ_S16:
+        if table is not None:
+            raise ValueError("int16 code formats take a scale, not a table")
+        return int(container), float(scale), None
+    if table is None:
+        table = iq_table(fmt)
+    table = np.ascontiguousarray(table, np.float32)
+    if table.shape != (256,):
+        raise ValueError("table: 256 float32 values")
+    return int(container), float(scale), table
+
+
+def _iq_codes(codes, container):
+    """A code array [..., 2] of the container's integer type, C-contiguous (no conversion: another type is an error, not a cast)."""
+    dt = _IQ_DTYPES.get(container)
+    if dt is None:
+        raise ValueError("unknown IQ code container")
+    if not isinstance(codes, np.ndarray) or codes.dtype != dt or codes.ndim < 1 or codes.shape[-1] != 2:
+        raise ValueError(f"codes: a {np.dtype(dt).name} array [..., 2] (I, Q)")
+    return np.ascontiguousarray(codes)
+
+
+def h_unpack_iq(codes, fmt, table=None, lib=None):
+    """pss_h_unpack_iq: codes [..., 2] -> the complex64 array [...] the driver would have delivered.  Host code: no GPU needed."""
+    container, scale, table = _iq_args(fmt, table)
+    codes = _iq_codes(codes, container)
+    out = np.empty(codes.shape[:-1], np.complex64)
+    if (lib or L.load()).pss_h_unpack_iq(container, _ptr(codes), out.size, scale, _ptr(table), _ptr(out)) != 0:
+        raise ValueError("pss_h_unpack_iq: bad arguments")
+    return out
+
+
 def h_squelch_gate(peak, squelch, every=3, phase=0, held_in=0.0, lib=None):
     """pss_h_squelch_gate: the reference loop's squelch gate (pyspecsdr.py:2261, :2288-2291) over a host array of per-frame peaks ->
     (open uint8 [n_frames], n_open, held_out).  Pure host code: needs the library, not a GPU."""
@@ -481,6 +533,13 @@ class Engine:
         self._dev(self.lib.pss_frame_pipeline_vector, int(mode), _ptr(d_iq), n_frames, n, float(fs), _ptr(d_db32), _ptr(d_db64), _ptr(d_post), max_h,
                   max_w, _ptr(d_mask), _ptr(d_pcm))
 
+    def unpack_iq(self, d_codes, n_samples, d_iq, fmt, table=None):
+        """ADC codes on the device -> complex64 (pss_unpack_iq): d_codes any address with the container's alignment, d_iq 8-byte aligned,
+        n_samples complex samples.  fmt: a name of IQ_FORMATS or (container, scale, offset); table: an 8-bit format's 256 float32 values
+        (default: the format's own, iq_table)."""
+        container, scale, table = _iq_args(fmt, table)
+        self._dev(self.lib.pss_unpack_iq, container, _ptr(d_codes), int(n_samples), scale, _ptr(table), _ptr(d_iq))
+
     def morse_edges(self, d_iq, n_frames, n, cap, d_rise, d_fall, d_counts, threshold_db=-20.0):
         self._dev(self.lib.pss_morse_edges, _ptr(d_iq), n_frames, n, float(threshold_db), cap, _ptr(d_rise), _ptr(d_fall),
                                           _ptr(d_counts))
@@ -550,7 +609,19 @@ class Engine:
         history 30; "persistence": lines = (y,), history 10.  halo: (lo, hi) float32 arrays of the rows preceding the
         capture.  Returns dict(lines=..., pcm=..., row_lo=..., row_hi=..., db=... or None)."""
         assert h_iq.dtype == np.complex64 and h_iq.ndim == 2 and h_iq.flags.c_contiguous
-        nf, n = h_iq.shape
+        return self._stream_display(h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out)
+
+    def stream_display_nfm_codes(self, h_codes, fs, chunk_frames, fmt, table=None, mode="waterfall", window=None, disp_h=36, disp_w=112,
+                                 halo=None, want_db=False, out=None):
+        """stream_display_nfm on a capture of ADC codes [n_frames, n, 2] (uint8 / int8 / int16; pinned_empty for overlap): the codes are
+        uploaded (2 or 4 bytes per sample instead of 8) and widened on the device.  fmt / table: as unpack_iq.  Same result dict."""
+        iq = _iq_args(fmt, table)
+        h_codes = _iq_codes(h_codes, iq[0])
+        assert h_codes.ndim == 3
+        return self._stream_display(h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out)
+
+    def _stream_display(self, h_in, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out):
+        nf, n = h_in.shape[:2]
         m = 0 if mode == "waterfall" else 1
         window = (30 if m == 0 else 10) if window is None else int(window)
         n_out = self.demod_out_len(L.MODE_NFM, n, fs)
@@ -571,8 +642,12 @@ class Engine:
         if halo is not None and len(halo[0]):
             hl, hh = np.ascontiguousarray(halo[0], np.float32), np.ascontiguousarray(halo[1], np.float32)
             n_halo = len(hl)
-        self._ck(self.lib.pss_h_stream_display_nfm(self.h, _ptr(h_iq), nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w,
-                                                   _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db), _ptr(lo), _ptr(hi)))
+        tail = (nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w, _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db),
+                _ptr(lo), _ptr(hi))
+        if iq is None:
+            self._ck(self.lib.pss_h_stream_display_nfm(self.h, _ptr(h_in), *tail))
+        else:
+            self._ck(self.lib.pss_h_stream_display_nfm_codes(self.h, iq[0], iq[1], _ptr(iq[2]), _ptr(h_in), *tail))
         return {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "db": db}
 
     def stream_display_nfm_f64(self, h_iq, fs, chunk_frames, mode="waterfall", window=None, disp_h=36, disp_w=112, halo=None, want_db=False,
@@ -580,7 +655,18 @@ class Engine:
         """stream_display_nfm with compute_fft's own float64 rows from the transform to the cells: the lines (and, grids=True, the full screen
         after every chunk) the REFERENCE draws from this capture.  halo / row_lo / row_hi / db: float64.  PCIe-bound like the float32 call."""
         assert h_iq.dtype == np.complex64 and h_iq.ndim == 2 and h_iq.flags.c_contiguous
-        nf, n = h_iq.shape
+        return self._stream_display_f64(h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
+
+    def stream_display_nfm_codes_f64(self, h_codes, fs, chunk_frames, fmt, table=None, mode="waterfall", window=None, disp_h=36, disp_w=112,
+                                     halo=None, want_db=False, grids=False, out=None):
+        """stream_display_nfm_f64 on a capture of ADC codes [n_frames, n, 2] (see stream_display_nfm_codes)."""
+        iq = _iq_args(fmt, table)
+        h_codes = _iq_codes(h_codes, iq[0])
+        assert h_codes.ndim == 3
+        return self._stream_display_f64(h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
+
+    def _stream_display_f64(self, h_in, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out):
+        nf, n = h_in.shape[:2]
         m = 0 if mode == "waterfall" else 1
         window = (30 if m == 0 else 10) if window is None else int(window)
         n_out = self.demod_out_len(L.MODE_NFM, n, fs)
@@ -602,9 +688,12 @@ class Engine:
         if halo is not None and len(halo[0]):
             hl, hh = np.ascontiguousarray(halo[0], np.float64), np.ascontiguousarray(halo[1], np.float64)
             n_halo = len(hl)
-        self._ck(self.lib.pss_h_stream_display_nfm_f64(self.h, _ptr(h_iq), nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w,
-                                                       _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db), _ptr(lo), _ptr(hi),
-                                                       _ptr(ga), _ptr(gb)))
+        tail = (nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w, _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db),
+                _ptr(lo), _ptr(hi), _ptr(ga), _ptr(gb))
+        if iq is None:
+            self._ck(self.lib.pss_h_stream_display_nfm_f64(self.h, _ptr(h_in), *tail))
+        else:
+            self._ck(self.lib.pss_h_stream_display_nfm_codes_f64(self.h, iq[0], iq[1], _ptr(iq[2]), _ptr(h_in), *tail))
         out = {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "db": db}
         if grids:
             out["grids"] = (ga, gb) if m == 0 else (ga,)
@@ -719,6 +808,21 @@ class Engine:
             raise ValueError("sample rate below the target rate or unknown mode")
         pcm = np.empty((nf, n_out, 2), np.int16)
         self._ck(self.lib.pss_h_demodulate_batch(self.h, mode, _ptr(frames), nf, n, float(fs), int(chunk_frames), _ptr(pcm)))
+        return pcm
+
+    def h_demodulate_batch_codes(self, mode, codes, fs, fmt, table=None, chunk_frames=4096):
+        """h_demodulate_batch on ADC codes [n_frames][n][2] (uint8 / int8 / int16): uploaded as codes, widened on the device.
+        fmt / table: as unpack_iq."""
+        container, scale, table = _iq_args(fmt, table)
+        codes = _iq_codes(codes, container)
+        assert codes.ndim == 3
+        nf, n = codes.shape[:2]
+        n_out = self.demod_out_len(mode, n, fs)
+        if n_out < 0:
+            raise ValueError("sample rate below the target rate or unknown mode")
+        pcm = np.empty((nf, n_out, 2), np.int16)
+        self._ck(self.lib.pss_h_demodulate_batch_codes(self.h, container, scale, _ptr(table), mode, _ptr(codes), nf, n, float(fs), int(chunk_frames),
+                                                       _ptr(pcm)))
         return pcm
 
     def h_iq_correction(self, iq):

@@ -4,15 +4,19 @@
                         buffer (SoapySDR CF32, interleaved I/Q float32 — pyspecsdr.py:1870-1891);
   * audio recordings  — `start_audio_recording` / `write_audio_samples` (audio_processing.py:25-43): RIFF/WAVE, 2 channels,
                         16-bit, `np.int16(samples * 32767)`;
+  * raw code files    — what `rtl_sdr`, `hackrf_transfer` and `airspy_rx` write (`.cu8`, `.cs8`, `.cs16`): interleaved I/Q ADC codes,
+                        no header.  They stay codes up to the device (IQ_FORMATS, load_iq_codes; `codes_format=` below);
   * the audio FIFO    — `/tmp/sdrpipe` (io_manager.py:1-37): the same int16 frames, raw s16le `L R L R ...`.
 
 Nothing here computes: the int16 conversion happens on the GPU (`pss_demod*`), these helpers move bytes.
 """
+import os
 import wave
 
 import numpy as np
 
 from . import _lib as L
+from .engine import IQ_FORMATS, _IQ_DTYPES, _iq_args, _iq_codes, h_unpack_iq, iq_table  # noqa: F401  (IQ_FORMATS, iq_table: part of this module's interface)
 from .signal_processing import DEFAULT_SAMPLE_RATE, _inject_designs, get_engine
 
 _MODES = {'NFM': L.MODE_NFM, 'AM': L.MODE_AM, 'USB': L.MODE_USB, 'LSB': L.MODE_LSB, 'WFM': L.MODE_WFM}
@@ -24,6 +28,24 @@ def load_iq_recording(path):
     if s.ndim != 1 or not np.iscomplexobj(s):
         raise ValueError("not an IQ recording: expected a 1-D complex array")
     return np.ascontiguousarray(s, np.complex64)
+
+
+def load_iq_codes(path, fmt):
+    """A raw capture file of ADC codes (fmt: a name of IQ_FORMATS; int16 little-endian) as a memory-mapped [n, 2] code array.  A file that
+    ends inside a sample (an odd trailing byte or word) is not one of these: ValueError."""
+    dt = np.dtype(_IQ_DTYPES[IQ_FORMATS[fmt][0]]).newbyteorder("<")
+    size = os.path.getsize(path)
+    if size % (2 * dt.itemsize):
+        raise ValueError(f"{path}: {size} bytes is not a whole number of {fmt} samples ({2 * dt.itemsize} bytes each)")
+    if size == 0:
+        return np.empty((0, 2), dt)
+    return np.memmap(path, dtype=dt, mode="r").reshape(-1, 2)
+
+
+def unpack_iq(codes, fmt, table=None):
+    """Codes [..., 2] -> the complex64 array [...] the driver would have delivered, on the host (pss_h_unpack_iq).  table: an 8-bit
+    format's 256 float32 values when the driver's widening is not the format's own (iq_table)."""
+    return h_unpack_iq(codes, fmt, table)
 
 
 def cut_frames(samples, frame_len):
@@ -142,7 +164,8 @@ def _squelch_args(squelch, meter_every, peak_power, frame_len, mode):
     return squelch, int(meter_every), peak_power
 
 
-def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chunk_frames=4096, squelch=None, meter_every=3, peak_power=0.0):
+def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chunk_frames=4096, squelch=None, meter_every=3, peak_power=0.0,
+                         codes_format=None, table=None):
     """Every read buffer of a recording through demodulate_signal on the GPU -> int16 [n_frames][n_out][2], i.e. the
     audio the reference would have written had it played the recording buffer by buffer.
 
@@ -150,18 +173,31 @@ def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chun
     (pyspecsdr.py:2261-2263), PEAK_POWER being the maximum of the post-processed row its header last showed — every meter_every-th
     buffer (:2288-2291), starting from peak_power (:172).  Returns (pcm int16 [n_open][n_out][2] of the open buffers in order,
     open uint8 [n_frames], peak float64 [n_frames], avg float64 [n_frames]): the gate and every buffer's Peak / Avg as
-    header_strength_text prints them; rows from the cell-exact pipeline (float64 compute_fft, smoothing, median clamp)."""
+    header_strength_text prints them; rows from the cell-exact pipeline (float64 compute_fft, smoothing, median clamp).
+
+    codes_format (a name of IQ_FORMATS; None: complex64 samples): `samples` is the recording's ADC code array [n, 2] (load_iq_codes); the
+    codes are uploaded and widened on the device (table: as unpack_iq), the results are those of the unpacked recording."""
     if squelch is not None:
         squelch, meter_every, peak_power = _squelch_args(squelch, meter_every, peak_power, frame_len, mode)
-    frames = cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len)
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+        nfr = len(samples) // frame_len
+        frames = samples[:nfr * frame_len].reshape(nfr, frame_len, 2)
+    else:
+        frames = cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len)
     fs = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(sample_rate)
     if mode != 'AM':
         _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), fs)
     if squelch is None:
+        if codes_format is not None:
+            return get_engine().h_demodulate_batch_codes(_MODES[mode], frames, fs, codes_format, iq[2], chunk_frames)
         return get_engine().h_demodulate_batch(_MODES[mode], frames, fs, chunk_frames)
     import torch
     e = get_engine()
-    nf, n = frames.shape
+    nf, n = frames.shape[:2]
     n_out = e.demod_out_len(_MODES[mode], n, fs)
     if n_out < 0:
         raise ValueError("sample rate below the target rate or unknown mode")
@@ -170,7 +206,12 @@ def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chun
     for c0 in range(0, nf, int(chunk_frames)):
         c = min(int(chunk_frames), nf - c0)
         dev = lambda shape, dt: torch.empty(shape, dtype=dt, device=f"cuda:{e.device}")
-        d_iq = torch.from_numpy(np.ascontiguousarray(frames[c0:c0 + c]).view(np.float32)).to(f"cuda:{e.device}")
+        if codes_format is not None:
+            d_codes = torch.from_numpy(np.array(frames[c0:c0 + c])).to(f"cuda:{e.device}")
+            d_iq = dev((c, 2 * n), torch.float32)
+            e.unpack_iq(d_codes, c * n, d_iq, codes_format, iq[2])
+        else:
+            d_iq = torch.from_numpy(np.ascontiguousarray(frames[c0:c0 + c]).view(np.float32)).to(f"cuda:{e.device}")
         d_db32, d_lo, d_hi = dev((c, n), torch.float32), dev(c, torch.float64), dev(c, torch.float64)
         d_a, d_b, d_pcm = dev((c, disp_w), torch.int8), dev((c, disp_w), torch.int8), dev((c, n_out, 2), torch.int16)
         d_peak, d_avg, d_open = dev(c, torch.float64), dev(c, torch.float64), dev(c, torch.uint8)
@@ -183,7 +224,12 @@ def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chun
     return pcm, opened, peak, avg
 
 
-def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768):
-    pcm = demodulate_recording(load_iq_recording(npy_path), sample_rate, mode, frame_len)
+def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
+    """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
+    if codes_format is not None:
+        samples = load_iq_codes(npy_path, codes_format)
+    else:
+        samples = load_iq_recording(npy_path)
+    pcm = demodulate_recording(samples, sample_rate, mode, frame_len, codes_format=codes_format, table=table)
     write_wav(wav_path, pcm)
     return pcm
