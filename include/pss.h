@@ -314,6 +314,53 @@ int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d_iq, long n
                                int8_t *d_line_a, int8_t *d_line_b, int16_t *d_pcm, double squelch, int every, int phase, double held_in,
                                double *d_peak, double *d_avg, uint8_t *d_open, long *n_open, double *held_out);
 
+/* Scanner sweep report.  Neither sweep classifies every slice: the inline sweep (pyspecsdr.py:2539-2561) and the sweep driver
+ * (scan_frequencies, :1054-1068) both run
+ *     if peak_power > threshold:  ...bandwidth...  if bandwidth > MIN_SIGNAL_BANDWIDTH (50e3):  signals.append({..., 'type': classify_signal(...)})
+ * on the numbers pss_scan / pss_scan_threshold return, and only the slices that pass reach the classifier.  The rule, exactly:
+ *     hit[i] = (d_peak[i] > (float)threshold_db) && (d_bw[i] > min_bw)
+ * peak_power is an np.float32 and the threshold a Python float, a weak scalar under NEP 50, so NumPy compares in FLOAT32 against the threshold
+ * rounded to float32: np.float32(-30.05) > -30.05 is False although the float32 value is the larger real number.  The bandwidth is float64,
+ * np.sum(mask) * (fs / len), compared with the float64 min_bw.  A NaN on either side: no hit.
+ *
+ *   pss_scan_gate       d_peak float32 [n_slices], d_bw float64 [n_slices] -> d_hit uint8 [n_slices] (nullable), d_hit_idx int32 [n_slices]
+ *                       (nullable): the detections' indices in ascending order, entries behind the *n_hit-th stay untouched.  No atomics:
+ *                       ballot and popcount inside a wavefront, a prefix sum over the counts of tiles of 256 above it (the squelch gate's).
+ *                       THIS CALL WAITS like pss_squelch_gate: one asynchronous 16-byte copy of the count into pinned memory and one
+ *                       synchronisation of the context's stream.  It cannot be captured into a graph.
+ *   pss_h_scan_gate     the same on host arrays, pure C, no context and no GPU: the rule one slice after the other (hit, hit_idx nullable).
+ *   pss_classify_gated  pss_classify on the n_idx frames d_idx names, every output (each nullable) COMPACTED to n_idx rows in list order:
+ *                       d_label / d_bw / d_mi / d_flat [n_idx], d_psd [n_idx][1024].  The frames are read where they lie — a driver read is
+ *                       240 000 samples, 1.9 MB: nothing is gathered — by the classifier's own kernels, whose frame pointer and output row
+ *                       come from the list (one __device__ body per kernel, instantiated for both): a listed frame's results are
+ *                       pss_classify's bytes.  The scratch is sized by n_idx.  Stream-ordered, no host wait.  n_idx outside [0, n_frames]:
+ *                       PSS_E_ARG; n_idx = 0: nothing is launched, the outputs stay untouched; n_idx = n_frames: pss_classify itself (the list
+ *                       is taken to be 0 .. n_frames - 1 and not read); indices outside the batch are clamped into it.
+ *   pss_sweep_report    one sweep in one call: scan -> gate -> pss_classify_gated.
+ *                         kind = PSS_SWEEP_INLINE   pss_scan (the mask is peak - 20 dB, :2542-2552); threshold_db is the gate only
+ *                         kind = PSS_SWEEP_DRIVER   pss_scan_threshold (the absolute mask, :1049-1057); threshold_db is the mask and the gate
+ *                       d_db [n_slices][n] and d_count (nullable), d_peak, d_bw: the scan's outputs, byte for byte; d_hit (nullable), d_hit_idx,
+ *                       *n_hit: the gate's; d_label, d_cls_bw, d_mi, d_flat (each nullable): caller-sized [n_slices], filled [*n_hit], the
+ *                       classifier's results of the detections in slice order (d_cls_bw is estimate_bandwidth's figure, not d_bw).  Lengths:
+ *                       whatever the chosen scan accepts.  Contains the gate, hence its wait: not capturable.
+ *   pss_h_scan_dedupe   scan_frequencies' last step (:1084-1091) on host arrays, pure C: the records ordered by frequency (a stable sort: ties keep
+ *                       input order), key = round(f / grid_hz) * grid_hz with Python's round (half to even on the double: nearbyint), the first
+ *                       record of every key kept -> keep int32 [n]: the kept INPUT indices in sorted order, *n_keep their number.  The
+ *                       reference's grid_hz is 100e3.  PSS_E_ARG: grid_hz <= 0 or a frequency that is not finite (round() raises there).
+ * Hit indices are local to a call: a caller that shards a sweep offsets them.  Thresholds below -100 dB are outside the contract (an all-zero
+ * slice, -100 dB, would then be classified).  PSS_E_ARG: n_slices outside [0, 2^31), null d_peak / d_bw / d_iq / d_hit_idx, unknown kind, fs <= 0. */
+enum { PSS_SWEEP_INLINE = 0, PSS_SWEEP_DRIVER = 1 };
+int pss_scan_gate(pss_ctx *ctx, const float *d_peak, const double *d_bw, long n_slices, double threshold_db, double min_bw, uint8_t *d_hit,
+                  int32_t *d_hit_idx, long *n_hit);
+int pss_h_scan_gate(const float *peak, const double *bw, long n_slices, double threshold_db, double min_bw, uint8_t *hit, int32_t *hit_idx,
+                    long *n_hit);
+int pss_classify_gated(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, const int32_t *d_idx, long n_idx, int32_t *d_label,
+                       double *d_bw, float *d_mi, float *d_flat, float *d_psd);
+int pss_sweep_report(pss_ctx *ctx, int kind, const float *d_iq, long n_slices, int n, double fs, double threshold_db, double min_bw, float *d_db,
+                     float *d_peak, double *d_bw, int32_t *d_count, uint8_t *d_hit, int32_t *d_hit_idx, long *n_hit, int32_t *d_label,
+                     double *d_cls_bw, float *d_mi, float *d_flat);
+int pss_h_scan_dedupe(const double *freq, long n, double grid_hz, int32_t *keep, long *n_keep);
+
 /* complex128 read buffers.  The reference's SDR buffer is complex64 (pyspecsdr.py:1887), but its functions accept any array, and handed
  * complex128 they compute in float64 from the first statement on.  These entry points serve compute_fft (signal_processing.py:243-264: the
  * window product is float64 x float64) and demodulate_am (:179-195: np.abs / np.mean / the subtraction in float64 — the same scaled hypot and

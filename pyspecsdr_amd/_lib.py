@@ -14,6 +14,7 @@ COMM_ID_BYTES = 128
 MODE_NFM, MODE_AM, MODE_USB, MODE_LSB, MODE_WFM = 0, 1, 2, 3, 4
 NP_ARCTAN2, NP_LOG10, NP_ABS = 0, 1, 2          # pss_np_f32 operations
 IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2                  # ADC code containers (PSS_IQ_*)
+SWEEP_INLINE, SWEEP_DRIVER = 0, 1               # pss_sweep_report kinds (PSS_SWEEP_*)
 
 _p = C.c_void_p
 _SIGS = {
@@ -87,6 +88,12 @@ _SIGS = {
     "pss_demod_gated": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, C.c_long, _p, _p]),
     "pss_frame_pipeline_squelch": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p, _p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _p, _p, _p,
                                              C.c_double, C.c_int, C.c_int, C.c_double, _p, _p, _p, C.POINTER(C.c_long), C.POINTER(C.c_double)]),
+    "pss_scan_gate": (C.c_int, [_p, _p, _p, C.c_long, C.c_double, C.c_double, _p, _p, C.POINTER(C.c_long)]),
+    "pss_h_scan_gate": (C.c_int, [_p, _p, C.c_long, C.c_double, C.c_double, _p, _p, C.POINTER(C.c_long)]),
+    "pss_classify_gated": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, C.c_long, _p, _p, _p, _p, _p]),
+    "pss_sweep_report": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, C.POINTER(C.c_long),
+                                   _p, _p, _p, _p]),
+    "pss_h_scan_dedupe": (C.c_int, [_p, C.c_long, C.c_double, _p, C.POINTER(C.c_long)]),
     "pss_spectrum_db_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),
     "pss_spectrum_post_f64": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, _p]),
     "pss_h_np_f64": (C.c_int, [C.c_int, _p, C.c_long, _p]),

@@ -1893,12 +1893,24 @@ __device__ __forceinline__ float np_modf32(float a, float b)  // npy_remainderf
     return m;
 }
 
-// LDS: [part: 8 * leaves floats][val][pbuf: CLS_CH + 1][cbuf: CLS_CH][carry][plans]
-__global__ __launch_bounds__(256) void k_cls_modidx(const float2 *__restrict__ iq, int n, long n_frames, RedPlan rn, RedPlan rm,
-                                                    int part_slots, int val_slots, float *__restrict__ up_all,
-                                                    float *__restrict__ mi_out)
+// The three classifier kernels exist twice: over every frame of the batch (pss_classify) and over a list of frames (pss_classify_gated:
+// row k of every output and of the scratch belongs to frame idx[k], read where it lies).  Both are the SAME __device__ body; GATED only
+// chooses where a row's samples come from, so a listed frame's results are pss_classify's by construction.
+template <bool GATED>
+__device__ __forceinline__ long cls_frame(const int *__restrict__ idx, long k, long n_frames)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
+    if (!GATED) return k;
+    const long f = idx[k];
+    return f < 0 ? 0 : (f >= n_frames ? n_frames - 1 : f);   // a caller's own list cannot make the kernels read outside the batch
+}
+
+// LDS: [part: 8 * leaves floats][val][pbuf: CLS_CH + 1][cbuf: CLS_CH][carry][plans]
+// n_rows: rows to produce (GATED: the list's length, else n_frames)
+template <bool GATED>
+__device__ __forceinline__ void cls_modidx_body(unsigned char *smem, const float2 *__restrict__ iq, int n, long n_frames,
+                                                const int *__restrict__ idx, long n_rows, RedPlan &rn, RedPlan &rm,
+                                                int part_slots, int val_slots, float *__restrict__ up_all, float *__restrict__ mi_out)
+{
     float *part = reinterpret_cast<float *>(smem), *val = part + part_slots;
     float *pbuf = val + val_slots, *cbuf = pbuf + CLS_CH + 4, *carry = cbuf + CLS_CH;  // cbuf 16-byte aligned (val_slots % 4 == 0)
     {
@@ -1911,8 +1923,8 @@ __global__ __launch_bounds__(256) void k_cls_modidx(const float2 *__restrict__ i
     }
     const int tid = threadIdx.x, T = blockDim.x;
     const float PI32 = (float)M_PI, TWOPI32 = (float)(2.0 * M_PI), NPI32 = (float)(-M_PI);
-    for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
-        const float2 *x = iq + (size_t)f * n;
+    for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
+        const float2 *x = iq + (size_t)cls_frame<GATED>(idx, f, n_frames) * n;
         float *up = up_all + (size_t)f * n;
         const float fn = (float)n, fm = (float)(n - 1);
         // :286, :290  np.var(np.abs(samples))
@@ -1966,6 +1978,20 @@ __global__ __launch_bounds__(256) void k_cls_modidx(const float2 *__restrict__ i
         if (tid == 0) mi_out[f] = mi;
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void k_cls_modidx(const float2 *__restrict__ iq, int n, long n_frames, RedPlan rn, RedPlan rm,
+                                                    int part_slots, int val_slots, float *__restrict__ up_all,
+                                                    float *__restrict__ mi_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_modidx_body<false>(smem, iq, n, n_frames, nullptr, n_frames, rn, rm, part_slots, val_slots, up_all, mi_out);
+}
+__global__ __launch_bounds__(256) void k_cls_modidx_gated(const float2 *__restrict__ iq, int n, long n_frames, const int *__restrict__ idx,
+                                                          long n_idx, RedPlan rn, RedPlan rm, int part_slots, int val_slots,
+                                                          float *__restrict__ up_all, float *__restrict__ mi_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_modidx_body<true>(smem, iq, n, n_frames, idx, n_idx, rn, rm, part_slots, val_slots, up_all, mi_out);
 }
 
 // The part of classify_signal behind the PSD (np bins in FFT order, float32, in LDS): estimate_bandwidth (:267-280), spectral
@@ -2038,13 +2064,13 @@ __device__ __forceinline__ void cls_features(const float *psd, float *dbv, doubl
 }
 
 // LDS: [buf: 1024 double2][tw: 512 double2][cpart][cval][plan]; psd (float) and the reduction slots alias buf afterwards
-__global__ __launch_bounds__(256) void k_cls_welch(const float2 *__restrict__ iq, int n, long n_frames, double fs, RedPlan cp,
-                                                   int part_slots, int val_slots, const float *__restrict__ win, float scale,
-                                                   const float *__restrict__ mi_in, int32_t *__restrict__ label,
-                                                   double *__restrict__ bw_out, float *__restrict__ flat_out,
-                                                   float *__restrict__ psd_out)
+template <bool GATED>
+__device__ __forceinline__ void cls_welch_body(unsigned char *smem, const float2 *__restrict__ iq, int n, long n_frames,
+                                               const int *__restrict__ idx, long n_rows, double fs, RedPlan &cp, int part_slots,
+                                               int val_slots, const float *__restrict__ win, float scale, const float *__restrict__ mi_in,
+                                               int32_t *__restrict__ label, double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                               float *__restrict__ psd_out)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
     double2 *buf = reinterpret_cast<double2 *>(smem), *tw = buf + CLS_NP;
     float2 *cpart = reinterpret_cast<float2 *>(tw + CLS_NP / 2), *cval = cpart + part_slots;
     {
@@ -2064,8 +2090,8 @@ __global__ __launch_bounds__(256) void k_cls_welch(const float2 *__restrict__ iq
     __syncthreads();
     const long nseg = (n - CLS_NP) / CLS_STEP + 1;
     const bool wave_tree = cp.tail.wave_tree && !cp.n_full;
-    for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
-        const float2 *x = iq + (size_t)f * n;
+    for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
+        const float2 *x = iq + (size_t)cls_frame<GATED>(idx, f, n_frames) * n;
         double acc[4] = {0.0, 0.0, 0.0, 0.0};  // positions tid + 256 j of the bit-reversed spectrum
         for (long sg = 0; sg < nseg; sg++) {
             const float2 *xs = x + sg * CLS_STEP;
@@ -2111,18 +2137,37 @@ __global__ __launch_bounds__(256) void k_cls_welch(const float2 *__restrict__ iq
         cls_features(psd, dbv, red, redi, CLS_NP, f, fs, mi_in, label, bw_out, flat_out, psd_out);
     }
 }
+__global__ __launch_bounds__(256) void k_cls_welch(const float2 *__restrict__ iq, int n, long n_frames, double fs, RedPlan cp,
+                                                   int part_slots, int val_slots, const float *__restrict__ win, float scale,
+                                                   const float *__restrict__ mi_in, int32_t *__restrict__ label,
+                                                   double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                                   float *__restrict__ psd_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_welch_body<false>(smem, iq, n, n_frames, nullptr, n_frames, fs, cp, part_slots, val_slots, win, scale, mi_in, label, bw_out, flat_out, psd_out);
+}
+__global__ __launch_bounds__(256) void k_cls_welch_gated(const float2 *__restrict__ iq, int n, long n_frames, const int *__restrict__ idx,
+                                                         long n_idx, double fs, RedPlan cp, int part_slots, int val_slots,
+                                                         const float *__restrict__ win, float scale, const float *__restrict__ mi_in,
+                                                         int32_t *__restrict__ label, double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                                         float *__restrict__ psd_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_welch_body<true>(smem, iq, n, n_frames, idx, n_idx, fs, cp, part_slots, val_slots, win, scale, mi_in, label, bw_out, flat_out, psd_out);
+}
 
 // Reads shorter than one Welch segment (n < 1024): SciPy takes nperseg = n (_spectral_py.py _triage_segments) — ONE segment,
 // a Hann window of length n, an FFT of length n (any length).  Such reads are tiny (the sweep driver never produces them: it
 // reads 0.1 s), so the transform is the plain length-n DFT in float64, one bin per thread and pass, twiddles exp(-2 pi i j / n)
 // in LDS indexed by (i k) mod n.  LDS: [xw: 1024 double2][tw: 1024 double2][psd: 1024 f][dbv: 1024 f][red][redi][cpart][cval][plan]
-__global__ __launch_bounds__(256) void k_cls_welch_short(const float2 *__restrict__ iq, int n, long n_frames, double fs, RedPlan cp,
-                                                         int part_slots, int val_slots, const float *__restrict__ win, float scale,
-                                                         const float *__restrict__ mi_in, int32_t *__restrict__ label,
-                                                         double *__restrict__ bw_out, float *__restrict__ flat_out,
-                                                         float *__restrict__ psd_out)
+template <bool GATED>
+__device__ __forceinline__ void cls_welch_short_body(unsigned char *smem, const float2 *__restrict__ iq, int n, long n_frames,
+                                                     const int *__restrict__ idx, long n_rows, double fs, RedPlan &cp,
+                                                     int part_slots, int val_slots, const float *__restrict__ win, float scale,
+                                                     const float *__restrict__ mi_in, int32_t *__restrict__ label,
+                                                     double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                                     float *__restrict__ psd_out)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
     double2 *xw = reinterpret_cast<double2 *>(smem), *tw = xw + CLS_NP;
     float *psd = reinterpret_cast<float *>(tw + CLS_NP), *dbv = psd + CLS_NP;
     double *red = reinterpret_cast<double *>(dbv + CLS_NP);
@@ -2140,8 +2185,8 @@ __global__ __launch_bounds__(256) void k_cls_welch_short(const float2 *__restric
         tw[j] = make_double2(cs, sn);
     }
     __syncthreads();
-    for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
-        const float2 *x = iq + (size_t)f * n;
+    for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
+        const float2 *x = iq + (size_t)cls_frame<GATED>(idx, f, n_frames) * n;
         const float2 m = frame_csum(cp, cpart, cval, [&](int i) { return x[i]; });   // detrend: data - mean(data), complex64
         const float mr = __fdiv_rn(m.x, (float)n), mim = __fdiv_rn(m.y, (float)n);
         for (int i = tid; i < n; i += 256) {
@@ -2165,6 +2210,24 @@ __global__ __launch_bounds__(256) void k_cls_welch_short(const float2 *__restric
         __syncthreads();
         cls_features(psd, dbv, red, redi, n, f, fs, mi_in, label, bw_out, flat_out, psd_out);
     }
+}
+__global__ __launch_bounds__(256) void k_cls_welch_short(const float2 *__restrict__ iq, int n, long n_frames, double fs, RedPlan cp,
+                                                         int part_slots, int val_slots, const float *__restrict__ win, float scale,
+                                                         const float *__restrict__ mi_in, int32_t *__restrict__ label,
+                                                         double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                                         float *__restrict__ psd_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_welch_short_body<false>(smem, iq, n, n_frames, nullptr, n_frames, fs, cp, part_slots, val_slots, win, scale, mi_in, label, bw_out, flat_out, psd_out);
+}
+__global__ __launch_bounds__(256) void k_cls_welch_short_gated(const float2 *__restrict__ iq, int n, long n_frames, const int *__restrict__ idx,
+                                                               long n_idx, double fs, RedPlan cp, int part_slots, int val_slots,
+                                                               const float *__restrict__ win, float scale, const float *__restrict__ mi_in,
+                                                               int32_t *__restrict__ label, double *__restrict__ bw_out, float *__restrict__ flat_out,
+                                                               float *__restrict__ psd_out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    cls_welch_short_body<true>(smem, iq, n, n_frames, idx, n_idx, fs, cp, part_slots, val_slots, win, scale, mi_in, label, bw_out, flat_out, psd_out);
 }
 
 // ---- decode_morse, front half (decoders.py:149-165; called with threshold = -20 dB, pyspecsdr.py:573) ---------------------
@@ -3438,15 +3501,17 @@ extern "C" const char *pss_class_name(int label)
     return (label >= 0 && label < 6) ? names[label] : "UNKNOWN";
 }
 
-extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int32_t *d_label, double *d_bw,
-                            float *d_mi, float *d_flat, float *d_psd)
+namespace {
+// What a classifier call needs besides its buffers, for n_rows rows of n samples (pss_classify: every frame; pss_classify_gated: the listed
+// ones): the window, the summation plans, the LDS sizes and the scratch — `up` float32 [n_rows][n], `mi` float32 [n_rows] unless the caller has one.
+struct ClsCall {
+    int np, part1, val1, partc, vc;
+    float *d_win, scale, *up, *mi;
+    RedPlan rn, rm, cp;
+    size_t lds1, lds2, lds3;
+};
+int cls_prepare(pss_ctx *ctx, long n_rows, int n, double fs, float *d_mi, const void *modidx_kernel, ClsCall &c)
 {
-    if (!ctx) return PSS_E_ARG;
-    PSS_GUARD(ctx);
-    if (n_frames < 0 || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_classify: bad argument");
-    if (n < 1) return pss_fail(ctx, PSS_E_ARG, "pss_classify: empty read (welch raises on it)");
-    if (n_frames == 0) return PSS_OK;
-    if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_classify: null input");
     // Hann window as scipy.signal.get_window('hann', np) builds it (general_cosine over np.linspace(-pi, pi, np + 1); ones for
     // np <= 1), cast to float32; scale = 1 / (fs * sum(win * win)) in complex64 arithmetic with zero imaginary parts.
     // np = 1024, or the read length when that is shorter (one segment: SciPy's nperseg = n fallback)
@@ -3487,24 +3552,49 @@ extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int 
         PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // w is a local; also orders the upload behind earlier launches reading the old window
         if (np != CLS_NP) ctx->hann_short_n = np;
     }
-    const float scale = 1.0f / ((float)fs * win_sum);
-    RedPlan rn, rm, cp;
-    int l1, v1, l2, v2, lc, vc;
+    c.np = np;
+    c.d_win = d_win;
+    c.scale = 1.0f / ((float)fs * win_sum);
+    RedPlan &rn = c.rn, &rm = c.rm, &cp = c.cp;
+    int l1, v1, l2, v2, lc, &vc = c.vc;
     int r = get_red_plan(ctx, n, false, &rn, &l1, &v1);
     if (!r) r = get_red_plan(ctx, n - 1, false, &rm, &l2, &v2);
     if (!r) r = get_red_plan(ctx, np, true, &cp, &lc, &vc);
     if (r) return r;
-    const size_t szUp = align256((size_t)n_frames * n * sizeof(float)), szMi = align256((size_t)n_frames * sizeof(float));
+    const size_t szUp = align256((size_t)n_rows * n * sizeof(float)), szMi = align256((size_t)n_rows * sizeof(float));
     r = pss_ensure_scratch(ctx, szUp + szMi);
     if (r) return r;
-    float *up = reinterpret_cast<float *>(ctx->scratch);
-    float *mi = d_mi ? d_mi : reinterpret_cast<float *>(reinterpret_cast<char *>(ctx->scratch) + szUp);
-    const int part1 = 8 * (l1 > l2 ? l1 : l2), val1 = ((v1 > v2 ? v1 : v2) + 3) & ~3;
-    const size_t lds1 = sizeof(float) * ((size_t)part1 + val1 + (CLS_CH + 4) + CLS_CH + 1) + plan_lds_bytes(rn) + plan_lds_bytes(rm);
+    c.up = reinterpret_cast<float *>(ctx->scratch);
+    c.mi = d_mi ? d_mi : reinterpret_cast<float *>(reinterpret_cast<char *>(ctx->scratch) + szUp);
+    const int part1 = c.part1 = 8 * (l1 > l2 ? l1 : l2), val1 = c.val1 = ((v1 > v2 ? v1 : v2) + 3) & ~3;
+    const size_t lds1 = c.lds1 = sizeof(float) * ((size_t)part1 + val1 + (CLS_CH + 4) + CLS_CH + 1) + plan_lds_bytes(rn) + plan_lds_bytes(rm);
     if (lds1 > 64 * 1024)
-        PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(k_cls_modidx), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    const int partc = 4 * lc;
-    const size_t lds2 = sizeof(double2) * (CLS_NP + CLS_NP / 2) + sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);
+        PSS_HIP(ctx, hipFuncSetAttribute(modidx_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
+    const int partc = c.partc = 4 * lc;
+    c.lds2 = sizeof(double2) * (CLS_NP + CLS_NP / 2) + sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);
+    c.lds3 = sizeof(double2) * 2 * CLS_NP + sizeof(float) * 2 * CLS_NP + sizeof(double) * 16 + sizeof(int) * 8 +
+             sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);   // k_cls_welch_short's (np < CLS_NP)
+    return PSS_OK;
+}
+}  // namespace
+
+extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int32_t *d_label, double *d_bw,
+                            float *d_mi, float *d_flat, float *d_psd)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_frames < 0 || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_classify: bad argument");
+    if (n < 1) return pss_fail(ctx, PSS_E_ARG, "pss_classify: empty read (welch raises on it)");
+    if (n_frames == 0) return PSS_OK;
+    if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_classify: null input");
+    ClsCall c;
+    int r = cls_prepare(ctx, n_frames, n, fs, d_mi, reinterpret_cast<const void *>(k_cls_modidx), c);
+    if (r) return r;
+    const int np = c.np, part1 = c.part1, val1 = c.val1, partc = c.partc, vc = c.vc;
+    const size_t lds1 = c.lds1, lds2 = c.lds2, lds3 = c.lds3;
+    const RedPlan &rn = c.rn, &rm = c.rm, &cp = c.cp;
+    float *const d_win = c.d_win, *const up = c.up, *const mi = c.mi;
+    const float scale = c.scale;
     const long g = n_frames < 16384 ? n_frames : 16384;
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_cls_modidx");
@@ -3516,13 +3606,45 @@ extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int 
         hipLaunchKernelGGL(k_cls_welch, dim3((unsigned)g), dim3(256), lds2, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n,
                            n_frames, fs, cp, partc, vc, d_win, scale, mi, d_label, d_bw, d_flat, d_psd);
     else {
-        const size_t lds3 = sizeof(double2) * 2 * CLS_NP + sizeof(float) * 2 * CLS_NP + sizeof(double) * 16 + sizeof(int) * 8 +
-                            sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);
         hipLaunchKernelGGL(k_cls_welch_short, dim3((unsigned)g), dim3(256), lds3, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq),
                            n, n_frames, fs, cp, partc, vc, d_win, scale, mi, d_label, d_bw, d_flat, d_psd);
     }
     pss_kernel_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "classify launch");
+}
+
+// pss_classify on the n_idx frames d_idx names, every output compacted to n_idx rows in list order; the frames are read where they lie
+// (the kernels above with GATED = true: the same __device__ bodies).
+extern "C" int pss_classify_gated(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, const int32_t *d_idx, long n_idx,
+                                  int32_t *d_label, double *d_bw, float *d_mi, float *d_flat, float *d_psd)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_frames < 0 || !(fs > 0.0) || n_idx < 0 || n_idx > n_frames) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: n_idx outside [0, n_frames] or a bad argument");
+    if (n < 1) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: empty read (welch raises on it)");
+    if (n_idx == 0) return PSS_OK;                  // no detection: nothing is launched, the outputs stay as they are
+    if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: null input");
+    if (n_idx == n_frames) return pss_classify(ctx, d_iq, n_frames, n, fs, d_label, d_bw, d_mi, d_flat, d_psd);   // an ascending list of all frames
+    if (!d_idx) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: null index list");
+    ClsCall c;
+    int r = cls_prepare(ctx, n_idx, n, fs, d_mi, reinterpret_cast<const void *>(k_cls_modidx_gated), c);
+    if (r) return r;
+    const long g = n_idx < 16384 ? n_idx : 16384;
+    const float2 *iq = reinterpret_cast<const float2 *>(d_iq);
+    PssTimeScope timed(ctx);
+    pss_kernel_begin(ctx, "k_cls_modidx_gated");
+    hipLaunchKernelGGL(k_cls_modidx_gated, dim3((unsigned)g), dim3(256), c.lds1, PSS_STREAM(ctx), iq, n, n_frames, d_idx, n_idx, c.rn, c.rm, c.part1,
+                       c.val1, c.up, c.mi);
+    pss_kernel_end(ctx);
+    pss_kernel_begin(ctx, "k_cls_welch_gated");
+    if (c.np == CLS_NP)
+        hipLaunchKernelGGL(k_cls_welch_gated, dim3((unsigned)g), dim3(256), c.lds2, PSS_STREAM(ctx), iq, n, n_frames, d_idx, n_idx, fs, c.cp, c.partc,
+                           c.vc, c.d_win, c.scale, c.mi, d_label, d_bw, d_flat, d_psd);
+    else
+        hipLaunchKernelGGL(k_cls_welch_short_gated, dim3((unsigned)g), dim3(256), c.lds3, PSS_STREAM(ctx), iq, n, n_frames, d_idx, n_idx, fs, c.cp,
+                           c.partc, c.vc, c.d_win, c.scale, c.mi, d_label, d_bw, d_flat, d_psd);
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "gated classify launch");
 }
 
 extern "C" int pss_afsk_bits(pss_ctx *ctx, const double *d_audio, long n_rows, int n, double fs, const double *sos1200,

@@ -1,5 +1,5 @@
 // pss_squelch.h — device code of the squelch path (pss_squelch.hip): the header's Peak / Avg meter over float64 rows, the squelch gate
-// over the rows' peaks, and the gather of the open frames in front of the demodulator.
+// over the rows' peaks, and the gather of the open frames in front of the demodulator; and the scanner's gate, built the same way.
 //
 // Reference: draw_header sets PEAK_POWER = np.max(freq_data) and prints np.mean(freq_data) beside it (pyspecsdr.py:388-392), on every
 // third loop iteration (:2288-2291); the loop demodulates a read buffer only if PEAK_POWER >= SQUELCH (:2261-2263); PEAK_POWER starts at
@@ -252,6 +252,51 @@ __global__ __launch_bounds__(256) void k_gate_index(const double *__restrict__ p
         int before = 0;
         for (int q = 0; q < w; q++) before += wcount[q];
         if (open) d_open_idx[(long)tile_off[tile] + before + __popcll(b & ((1ull << lane) - 1ull))] = (int)i;
+        __syncthreads();
+    }
+}
+
+// ---- the scanner's gate ------------------------------------------------------------------------------------------------------------------
+// Both sweeps keep a slice as a detection if `peak_power > threshold` and then `bandwidth > MIN_SIGNAL_BANDWIDTH` (pyspecsdr.py:2549 / :2555,
+// :1054 / :1059).  peak_power is an np.float32 and the threshold a Python float, a weak scalar under NEP 50: the comparison runs in float32
+// against the threshold ROUNDED to float32.  The bandwidth is float64 on both sides.  A NaN on either side compares false: no hit.
+// Same three steps as the squelch gate above — flags and tile counts, k_gate_scan over the counts (every = 0: it reads no peak), the
+// ascending list from ballot and popcount; no atomics.
+__device__ __forceinline__ bool scan_hit(const float *__restrict__ peak, const double *__restrict__ bw, long i, float threshold, double min_bw)
+{
+    return peak[i] > threshold && bw[i] > min_bw;
+}
+
+__global__ __launch_bounds__(256) void k_scan_flags(const float *__restrict__ peak, const double *__restrict__ bw, long n_slices, float threshold,
+                                                    double min_bw, uint8_t *__restrict__ d_hit, int *__restrict__ tile_count, long n_tiles)
+{
+    __shared__ int wcount[4];
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool hit = i < n_slices && scan_hit(peak, bw, i, threshold, min_bw);
+        if (i < n_slices && d_hit) d_hit[i] = hit ? 1 : 0;
+        const unsigned long long b = __ballot(hit);
+        if ((threadIdx.x & 63) == 0) wcount[threadIdx.x >> 6] = __popcll(b);
+        __syncthreads();
+        if (threadIdx.x == 0) tile_count[tile] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_scan_index(const float *__restrict__ peak, const double *__restrict__ bw, long n_slices, float threshold,
+                                                    double min_bw, const int *__restrict__ tile_off, long n_tiles, int *__restrict__ d_hit_idx)
+{
+    __shared__ int wcount[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool hit = i < n_slices && scan_hit(peak, bw, i, threshold, min_bw);
+        const unsigned long long b = __ballot(hit);
+        if (lane == 0) wcount[w] = __popcll(b);
+        __syncthreads();
+        int before = 0;
+        for (int q = 0; q < w; q++) before += wcount[q];
+        if (hit) d_hit_idx[(long)tile_off[tile] + before + __popcll(b & ((1ull << lane) - 1ull))] = (int)i;   // < n_hit <= n_slices
         __syncthreads();
     }
 }

@@ -2,9 +2,15 @@
 // the gate with its host twin, the demodulator on the open frames only, and the one-call step built from them.  Everything here sits
 // BEHIND the existing entry points (pss_spectrum_cells, pss_spectrum_post_f64, pss_demod_signal): none of their kernels or schedules
 // changes.
+// The scanner sweep report (include/pss.h, "scanner sweep report") is the same shape of work and lives here too: scan -> gate ->
+// classifier on the detections only, behind pss_scan, pss_scan_threshold and pss_classify.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <set>
+#include <vector>
 
 #include "pss_ctx.h"
 #include "pss_squelch.h"
@@ -183,4 +189,111 @@ extern "C" int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d
     if (!r) r = pss_demod_gated(ctx, mode, d_iq, n_frames, n, fs, open_idx, count, d_pcm, nullptr);
     if (!r && n_open) *n_open = count;
     return r;
+}
+
+// ---- scanner sweep report ---------------------------------------------------------------------------------------------------------------
+// The sweeps' gate as they run it (pyspecsdr.py:2549 / :2555, :1054 / :1059), one slice after the other: pure host code, no context.
+extern "C" int pss_h_scan_gate(const float *peak, const double *bw, long n_slices, double threshold_db, double min_bw, uint8_t *hit, int32_t *hit_idx,
+                               long *n_hit)
+{
+    if (n_slices < 0 || n_slices > INT32_MAX || (n_slices > 0 && (!peak || !bw))) return PSS_E_ARG;
+    const float thr = (float)threshold_db;   // NEP 50: np.float32 > Python float compares in float32
+    long count = 0;
+    for (long i = 0; i < n_slices; i++) {
+        bool h = false;
+        if (peak[i] > thr) h = bw[i] > min_bw;
+        if (hit) hit[i] = h ? 1 : 0;
+        if (h && hit_idx) hit_idx[count] = (int32_t)i;
+        count += h;
+    }
+    if (n_hit) *n_hit = count;
+    return PSS_OK;
+}
+
+extern "C" int pss_scan_gate(pss_ctx *ctx, const float *d_peak, const double *d_bw, long n_slices, double threshold_db, double min_bw, uint8_t *d_hit,
+                             int32_t *d_hit_idx, long *n_hit)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n_slices < 0 || n_slices > INT32_MAX || (n_slices > 0 && (!d_peak || !d_bw)))
+        return pss_fail(ctx, PSS_E_ARG, "pss_scan_gate: a slice count outside [0, 2^31) or a null peak / bandwidth array");
+    if (n_slices == 0) {
+        if (n_hit) *n_hit = 0;
+        return PSS_OK;
+    }
+    const long n_tiles = (n_slices + GATE_TILE - 1) / GATE_TILE;
+    void *buf;
+    int r = sq_buffer(ctx, 0, sizeof(GateResult) + (size_t)n_tiles * sizeof(int), "gate scratch", &buf);
+    if (r) return r;
+    if (!ctx->sq_pin) PSS_HIP(ctx, hipHostMalloc(&ctx->sq_pin, sizeof(GateResult), hipHostMallocDefault));
+    GateResult *d_res = reinterpret_cast<GateResult *>(buf);
+    int *tiles = reinterpret_cast<int *>(d_res + 1);
+    const float thr = (float)threshold_db;
+    const dim3 grid((unsigned)(n_tiles < 4096 ? n_tiles : 4096));
+    {
+        PssTimeScope timed(ctx);
+        pss_kernel_begin(ctx, "k_scan_flags");
+        hipLaunchKernelGGL(k_scan_flags, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, d_bw, n_slices, thr, min_bw, d_hit, tiles, n_tiles);
+        pss_kernel_end(ctx);
+        pss_kernel_begin(ctx, "k_gate_scan");   // the squelch gate's prefix sum; every = 0: it reads no peak, held_out = 0
+        hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(256), 0, PSS_STREAM(ctx), tiles, n_tiles, static_cast<const double *>(nullptr), n_slices, 0, 0L, 0.0, d_res);
+        pss_kernel_end(ctx);
+        if (d_hit_idx) {
+            pss_kernel_begin(ctx, "k_scan_index");
+            hipLaunchKernelGGL(k_scan_index, grid, dim3(256), 0, PSS_STREAM(ctx), d_peak, d_bw, n_slices, thr, min_bw, tiles, n_tiles, d_hit_idx);
+            pss_kernel_end(ctx);
+        }
+    }
+    r = pss_hip_check(ctx, hipGetLastError(), "scan gate launch");
+    if (r) return r;
+    // as in pss_squelch_gate: the count reaches the host through 16 pinned bytes and one stream synchronisation
+    PSS_HIP(ctx, hipMemcpyAsync(ctx->sq_pin, d_res, sizeof(GateResult), hipMemcpyDeviceToHost, PSS_STREAM(ctx)));
+    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));
+    if (n_hit) *n_hit = reinterpret_cast<const GateResult *>(ctx->sq_pin)->n_open;
+    return PSS_OK;
+}
+
+// One sweep in one call: the chosen scan, the gate on its peaks and bandwidths, the classifier on the detections.  The gate waits for the count.
+extern "C" int pss_sweep_report(pss_ctx *ctx, int kind, const float *d_iq, long n_slices, int n, double fs, double threshold_db, double min_bw, float *d_db,
+                                float *d_peak, double *d_bw, int32_t *d_count, uint8_t *d_hit, int32_t *d_hit_idx, long *n_hit, int32_t *d_label,
+                                double *d_cls_bw, float *d_mi, float *d_flat)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (kind != PSS_SWEEP_INLINE && kind != PSS_SWEEP_DRIVER) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: unknown sweep kind");
+    if (n_slices < 0 || n_slices > INT32_MAX || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: a slice count outside [0, 2^31) or fs <= 0");
+    if (n_slices > 0 && (!d_iq || !d_peak || !d_bw || !d_hit_idx)) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: null d_iq / d_peak / d_bw / d_hit_idx");
+    if (n_slices == 0) {
+        if (n_hit) *n_hit = 0;
+        return PSS_OK;
+    }
+    PssTimeScope timed(ctx);
+    int r = kind == PSS_SWEEP_INLINE ? pss_scan(ctx, d_iq, n_slices, n, fs, d_db, d_peak, d_bw, d_count)
+                                     : pss_scan_threshold(ctx, d_iq, n_slices, n, fs, threshold_db, d_db, d_peak, d_bw, d_count);
+    long count = 0;
+    if (!r) r = pss_scan_gate(ctx, d_peak, d_bw, n_slices, threshold_db, min_bw, d_hit, d_hit_idx, &count);
+    if (!r) r = pss_classify_gated(ctx, d_iq, n_slices, n, fs, d_hit_idx, count, d_label, d_cls_bw, d_mi, d_flat, nullptr);
+    if (!r && n_hit) *n_hit = count;
+    return r;
+}
+
+// scan_frequencies' last step (pyspecsdr.py:1084-1091): the records ordered by frequency (sorted() is stable), the first of every
+// round(f / grid) * grid kept.  Python's round() of a float is half to even on the double = nearbyint in the default rounding mode.
+extern "C" int pss_h_scan_dedupe(const double *freq, long n, double grid_hz, int32_t *keep, long *n_keep)
+{
+    if (n < 0 || n > INT32_MAX || !(grid_hz > 0.0) || (n > 0 && (!freq || !keep))) return PSS_E_ARG;
+    std::vector<int32_t> order((size_t)n);
+    for (long i = 0; i < n; i++) {
+        if (!std::isfinite(freq[i])) return PSS_E_ARG;
+        order[(size_t)i] = (int32_t)i;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return freq[a] < freq[b]; });
+    std::set<double> seen;
+    long count = 0;
+    for (long k = 0; k < n; k++) {
+        const double key = std::nearbyint(freq[order[(size_t)k]] / grid_hz) * grid_hz;
+        if (seen.insert(key).second) keep[count++] = order[(size_t)k];
+    }
+    if (n_keep) *n_keep = count;
+    return PSS_OK;
 }

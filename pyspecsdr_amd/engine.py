@@ -99,6 +99,35 @@ def h_squelch_gate(peak, squelch, every=3, phase=0, held_in=0.0, lib=None):
     return opened, n_open.value, held.value
 
 
+def h_scan_gate(peak, bw, threshold_db, min_bw=50e3, lib=None):
+    """pss_h_scan_gate: the sweeps' gate (pyspecsdr.py:2549 / :2555, :1054 / :1059) over host arrays of per-slice peaks (float32) and
+    bandwidths (float64) -> (hit uint8 [n], hit_idx int32 [n_hit], ascending).  hit = peak > float32(threshold_db) and bw > min_bw: NumPy
+    compares the np.float32 peak with the Python-float threshold in float32.  Pure host code: needs the library, not a GPU."""
+    lib = lib or L.load()
+    peak, bw = np.ascontiguousarray(peak, np.float32), np.ascontiguousarray(bw, np.float64)
+    if peak.ndim != 1 or peak.shape != bw.shape:
+        raise ValueError("peak and bw: one value per slice each")
+    hit, idx, n_hit = np.empty(len(peak), np.uint8), np.empty(len(peak), np.int32), C.c_long()
+    r = lib.pss_h_scan_gate(_ptr(peak), _ptr(bw), len(peak), float(threshold_db), float(min_bw), _ptr(hit), _ptr(idx), C.byref(n_hit))
+    if r != 0:
+        raise PssError(r, "pss_h_scan_gate: bad argument")
+    return hit, idx[:n_hit.value].copy()
+
+
+def h_scan_dedupe(freq, grid_hz=100e3, lib=None):
+    """pss_h_scan_dedupe: scan_frequencies' duplicate removal (pyspecsdr.py:1084-1091) -> the kept input indices (int32) in order of
+    frequency: a stable sort, key round(f / grid_hz) * grid_hz with Python's round, the first record of every key.  Host code, no GPU."""
+    lib = lib or L.load()
+    freq = np.ascontiguousarray(freq, np.float64)
+    if freq.ndim != 1:
+        raise ValueError("freq: one value per record")
+    keep, n_keep = np.empty(len(freq), np.int32), C.c_long()
+    r = lib.pss_h_scan_dedupe(_ptr(freq), len(freq), float(grid_hz), _ptr(keep), C.byref(n_keep))
+    if r != 0:
+        raise PssError(r, "pss_h_scan_dedupe: grid_hz <= 0 or a frequency that is not finite")
+    return keep[:n_keep.value].copy()
+
+
 class Engine:
     """order: how calls are ordered against the caller's own GPU work.
          "torch" (default when torch is loaded): the library keeps its own non-blocking stream — which the default stream does NOT
@@ -548,6 +577,31 @@ class Engine:
         """classify_signal for a batch (pss_classify): any of label int32 / bw float64 / mi float32 / flat float32 / psd float32 [.,1024]."""
         self._dev(self.lib.pss_classify, _ptr(d_iq), n_frames, n, float(fs), _ptr(d_label), _ptr(d_bw), _ptr(d_mi),
                                        _ptr(d_flat), _ptr(d_psd))
+
+    # -- scanner sweep report (pyspecsdr.py:2539-2561, :1054-1068): gate the slices, classify only the detections
+    def scan_gate(self, d_peak, d_bw, n_slices, threshold_db, min_bw=50e3, d_hit=None, d_hit_idx=None):
+        """The sweeps' gate over a scan's peaks (float32) and bandwidths (float64) -> n_hit; d_hit uint8 [n_slices], d_hit_idx int32
+        [n_slices] (ascending, n_hit entries written).  Waits for the count (one stream synchronisation), like squelch_gate."""
+        n_hit = C.c_long()
+        self._dev(self.lib.pss_scan_gate, _ptr(d_peak), _ptr(d_bw), n_slices, float(threshold_db), float(min_bw), _ptr(d_hit), _ptr(d_hit_idx),
+                  C.byref(n_hit))
+        return n_hit.value
+
+    def classify_gated(self, d_iq, n_frames, n, fs, d_idx, n_idx, d_label=None, d_bw=None, d_mi=None, d_flat=None, d_psd=None):
+        """classify on the n_idx frames d_idx names, outputs compacted to n_idx rows in list order; the frames are read in place.  No host wait."""
+        self._dev(self.lib.pss_classify_gated, _ptr(d_iq), n_frames, n, float(fs), _ptr(d_idx), int(n_idx), _ptr(d_label), _ptr(d_bw), _ptr(d_mi),
+                  _ptr(d_flat), _ptr(d_psd))
+
+    def sweep_report(self, kind, d_iq, n_slices, n, fs, threshold_db, d_peak, d_bw, d_hit_idx, min_bw=50e3, d_db=None, d_count=None, d_hit=None,
+                     d_label=None, d_cls_bw=None, d_mi=None, d_flat=None):
+        """One sweep: scan ("inline": pss_scan, "driver": pss_scan_threshold) -> gate -> classify_gated -> n_hit.  d_label / d_cls_bw / d_mi /
+        d_flat: sized [n_slices], filled [n_hit].  Contains the gate's wait."""
+        kind = {"inline": L.SWEEP_INLINE, "driver": L.SWEEP_DRIVER}.get(kind, kind)
+        n_hit = C.c_long()
+        self._dev(self.lib.pss_sweep_report, int(kind), _ptr(d_iq), n_slices, n, float(fs), float(threshold_db), float(min_bw), _ptr(d_db),
+                  _ptr(d_peak), _ptr(d_bw), _ptr(d_count), _ptr(d_hit), _ptr(d_hit_idx), C.byref(n_hit), _ptr(d_label), _ptr(d_cls_bw), _ptr(d_mi),
+                  _ptr(d_flat))
+        return n_hit.value
 
     def class_name(self, label):
         return self.lib.pss_class_name(int(label)).decode()

@@ -16,7 +16,7 @@ import wave
 import numpy as np
 
 from . import _lib as L
-from .engine import IQ_FORMATS, _IQ_DTYPES, _iq_args, _iq_codes, h_unpack_iq, iq_table  # noqa: F401  (IQ_FORMATS, iq_table: part of this module's interface)
+from .engine import IQ_FORMATS, _IQ_DTYPES, _iq_args, _iq_codes, h_scan_dedupe, h_unpack_iq, iq_table  # noqa: F401  (IQ_FORMATS, iq_table: part of this module's interface)
 from .signal_processing import DEFAULT_SAMPLE_RATE, _inject_designs, get_engine
 
 _MODES = {'NFM': L.MODE_NFM, 'AM': L.MODE_AM, 'USB': L.MODE_USB, 'LSB': L.MODE_LSB, 'WFM': L.MODE_WFM}
@@ -150,6 +150,69 @@ def surface_scale_labels(min_val, max_val, disp_h):
         if i % 3 == 0:
             labels.append((i, f"{db_value:4.0f}dB"))
     return labels
+
+
+def sweep_frequencies(start, end, step):
+    """The centre frequencies a sweep visits (pyspecsdr.py:1033 / :1081, :2523 / :2578): the values current_freq takes in
+    `while current_freq <= end: ...; current_freq += step` — repeated float addition, not start + i * step — as float64."""
+    if not step > 0:
+        raise ValueError("step must be > 0")
+    out, current_freq = [], start
+    while current_freq <= end:
+        out.append(current_freq)
+        current_freq += step
+    return np.array(out, np.float64)
+
+
+_CLASS_NAMES = ("UNKNOWN", "FM_BROADCAST", "NARROW_FM", "AM_BROADCAST", "SSB", "DIGITAL")   # pss_class_name
+
+
+def scan_signals(freqs, peak, bw, hit_idx, labels, dedupe=False):
+    """The sweeps' list of records (pyspecsdr.py:2556-2561, :1063-1068) from a sweep report: freqs / peak (float32) / bw (float64) per
+    slice, hit_idx the detections, labels their classes in the same order (PSS_CLASS_* numbers or names).  Every record is the
+    reference's dict: 'frequency' a Python float, 'power' an np.float32, 'bandwidth' an np.float64, 'type' the class name.
+    dedupe: scan_frequencies' duplicate removal on a 100 kHz grid (:1084-1091, h_scan_dedupe)."""
+    freqs, peak, bw = np.asarray(freqs, np.float64), np.asarray(peak, np.float32), np.asarray(bw, np.float64)
+    hit_idx = np.asarray(hit_idx, np.int64)
+    if len(labels) != len(hit_idx):
+        raise ValueError("labels: one per detection")
+    signals = []
+    for i, lab in zip(hit_idx, labels):
+        name = lab if isinstance(lab, str) else (_CLASS_NAMES[int(lab)] if 0 <= int(lab) < len(_CLASS_NAMES) else "UNKNOWN")
+        signals.append({'frequency': float(freqs[i]), 'power': peak[i], 'bandwidth': bw[i], 'type': str(name)})
+    if dedupe:
+        signals = [signals[k] for k in h_scan_dedupe([s['frequency'] for s in signals], 100e3)]
+    return signals
+
+
+def scan_result_lines(signals, max_h, max_w, page=0):
+    """What display_scan_results (pyspecsdr.py:1203-1262) draws for one page of a record list on a max_h x max_w screen, as
+    (y, x, text, colour_pair, bold) tuples in drawing order: header, dash line, max_h - 7 entries per page (cut at max_w - 1, coloured by
+    type), the two footer lines.  An empty list: the "No signals found" line and the key prompt (:1212-1213)."""
+    if not signals:
+        return [(0, 0, "\nNo signals found above threshold.\n", 3, False), (2, 0, "\nPress any key to continue...", 2, False)]
+    max_h, max_w = int(max_h), int(max_w)
+    results_per_page = max_h - 7
+    if results_per_page < 1:
+        raise ValueError("max_h must be at least 8")
+    total_pages = (len(signals) + results_per_page - 1) // results_per_page
+    if not 0 <= page < total_pages:
+        raise ValueError(f"page outside [0, {total_pages})")
+    header = f"Detected Signals ({len(signals)} found) - Page {page + 1}/{total_pages}"
+    lines = [(0, 0, header, 1, True), (1, 0, "-" * len(header), 2, False)]
+    start_idx = page * results_per_page
+    end_idx = min(start_idx + results_per_page, len(signals))
+    for line_no, (i, signal) in enumerate(enumerate(signals[start_idx:end_idx], start_idx + 1), 2):
+        power_str = f"{signal['power']:.1f}".rjust(6)
+        freq_str = f"{signal['frequency'] / 1e6:.3f}".rjust(8)
+        bw_str = f"{signal['bandwidth'] / 1e3:.1f}".rjust(6)
+        type_str = signal['type'].ljust(15)
+        line = f"{str(i).rjust(3)}. {freq_str} MHz  Power: {power_str} dB  BW: {bw_str} kHz  Type: {type_str}"
+        pair = {'FM_BROADCAST': 4, 'DIGITAL': 5, 'UNKNOWN': 2}.get(signal['type'], 1)
+        lines.append((line_no, 0, line[:max_w - 1], pair, False))
+    lines.append((max_h - 1, 0, "Navigation: [n]ext page, [p]revious page, [number] to select, [q]uit", 2, False))
+    lines.append((max_h - 2, 0, "Enter choice: ", 1, True))
+    return lines
 
 
 def _squelch_args(squelch, meter_every, peak_power, frame_len, mode):
