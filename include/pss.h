@@ -544,6 +544,39 @@ int pss_h_decode_morse(pss_ctx *ctx, const float *h_iq, int n, double fs, double
 int pss_h_decode_aprs(pss_ctx *ctx, const double *h_audio, int n, double fs, const double *sos1200, const double *sos2200, int nsec,
                       char *out, long out_cap, long *out_len);
 
+/* ---- decoders for batches: the per-message halves above on the DEVICE, for every read buffer of a batch (pss_decode_dev.hip).  Device
+ * pointers, the context's stream, no host wait.  n_frames / n_rows == 0: PSS_OK, nothing is launched.  PSS_E_ARG: negative sizes, fs not
+ * above 0, null buffers.
+ *   pss_morse_text   pss_h_morse_decode for every frame of a pss_morse_edges result (d_rise / d_fall int32 [n_frames][cap], d_counts int32
+ *       [n_frames][2]).  d_text uint8 [n_frames][text_cap]: the text's bytes, zeros behind them; d_text_len int32 [n_frames]: the TRUE
+ *       length (bytes past text_cap are dropped; a text has at most 2 bytes per pulse); d_timing float64 [n_frames][3] = (dot, dash, mean
+ *       gap) in seconds — text, length and timing are the host function's, bit for bit: the class sums and the distance sum of every
+ *       candidate split are added up in observation order, the mean gap over NumPy's pairwise tree.  d_pulses int32 [n_frames]: the number
+ *       of complete pulses; 0 = the reference's early returns (empty text, timing zeros: its {"dot": 0, "dash": 0, "gap": 0}); -1 = a
+ *       truncated edge list (a count above cap): no text, zeros; -2 = edges that do not alternate (the host function returns PSS_E_ARG, the
+ *       reference raises; pss_morse_edges never produces them): no text, zeros.
+ *   pss_ax25_frames  pss_h_ax25_frame for n_rows rows of n_bits bits (one 0/1 value per byte).  d_out_len int32 [n_rows]: -1 where the host
+ *       function returns 0 (no packet), else the packet's TRUE length; d_out uint8 [n_rows][out_cap]: its bytes (code points 0..255, not
+ *       NUL-terminated), bytes past out_cap dropped, bytes behind the packet not written.
+ *   pss_real_normalise  decode_aprs's first lines for complex64 read buffers (decoders.py:121-125), d_iq interleaved [n_rows][n]: the real
+ *       parts divided by their largest magnitude IN FLOAT32 (np.real of a complex64 buffer is float32; one correctly rounded division; a
+ *       NaN propagates through the maximum; a row of zeros gives NaN), widened to float64 d_audio [n_rows][n].  The imaginary parts are
+ *       not read.  (pss_row_normalise is the same for a buffer that is float64 already.)
+ *   pss_decode_morse_batch  pss_morse_edges + pss_morse_text: decode_morse for every read buffer.  d_rise / d_fall / d_counts are work
+ *       buffers of pss_morse_edges' shapes, returned filled.
+ *   pss_decode_aprs_batch   pss_real_normalise + pss_afsk_bits + pss_ax25_frames: decode_aprs for every complex64 read buffer.  d_audio
+ *       float64 [n_rows][n] and d_bits uint8 [n_rows][pss_afsk_n_bits(n, fs)] are work buffers, returned filled (the filtered rows of
+ *       pss_afsk_bits live in the context's scratch, so the normalised audio is the caller's).  sos1200 / sos2200 / nsec: as pss_afsk_bits. */
+int pss_morse_text(pss_ctx *ctx, const int32_t *d_rise, const int32_t *d_fall, const int32_t *d_counts, long n_frames, int cap, double fs,
+                   int text_cap, uint8_t *d_text, int32_t *d_text_len, double *d_timing, int32_t *d_pulses);
+int pss_ax25_frames(pss_ctx *ctx, const uint8_t *d_bits, long n_rows, int n_bits, int out_cap, uint8_t *d_out, int32_t *d_out_len);
+int pss_real_normalise(pss_ctx *ctx, const float *d_iq, long n_rows, int n, double *d_audio);
+int pss_decode_morse_batch(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, double threshold_db, int cap, int32_t *d_rise,
+                           int32_t *d_fall, int32_t *d_counts, int text_cap, uint8_t *d_text, int32_t *d_text_len, double *d_timing,
+                           int32_t *d_pulses);
+int pss_decode_aprs_batch(pss_ctx *ctx, const float *d_iq, long n_rows, int n, double fs, const double *sos1200, const double *sos2200, int nsec,
+                          double *d_audio, uint8_t *d_bits, int out_cap, uint8_t *d_out, int32_t *d_out_len);
+
 /* classify_signal (signal_processing.py:296-322; helpers estimate_bandwidth :267-280, estimate_modulation_index :283-293) for
  * a batch of scanner reads, as the function runs once its missing `welch` import is supplied (in the reference it raises
  * NameError on every call: SURVEY App. C2, §8(f) #3).  d_iq: interleaved complex64 [n_frames][n], n >= 1.  n >= 1024: Welch

@@ -12,6 +12,13 @@ decode_morse's two pulse classes come from a deterministic search where the refe
 identical centroids for keyed signals (include/pss.h), a reproducible answer for noise.  Batched building blocks for callers that want
 only the front halves: afsk_bits(), morse_edges().
 
+For batches of read buffers both halves run on the GPU, one library call per batch (pss_decode_morse_batch, pss_decode_aprs_batch):
+
+    decode_morse_batch(frames, sample_rate, threshold=-20) -> [(text, timing dict), ...]
+    decode_aprs_batch(frames, sample_rate)                 -> [[packet] or [], ...]      complex64 buffers, normalised in float32
+
+formats.decode_recording cuts a recording into read buffers and runs them through these.
+
 The zero-edit launcher (python -m pyspecsdr_amd.run) leaves the application's own `import decoders` alone by default — its decoders.py
 then runs its bookkeeping on top of the GPU band-pass (decoders.py:3 imports bandpass_filter from signal_processing); `--gpu-decoders`
 registers this module under the name `decoders` as well.
@@ -90,6 +97,74 @@ def _n_gaps(rise, fall):
 def decode_morse(samples, sample_rate, threshold=-20):
     rise, fall = morse_edges(samples, threshold)
     return morse_from_edges(rise, fall, sample_rate)
+
+
+def _upload_frames(e, frames):
+    """Read buffers [n_frames][n] (anything np.asarray takes; complex64 as the application hands them over) -> float32 device view."""
+    import torch
+    x = np.ascontiguousarray(np.asarray(frames), np.complex64)
+    if x.ndim != 2 or x.shape[1] < 1:
+        raise ValueError("frames: [n_frames][n] read buffers, n >= 1")
+    return torch.from_numpy(x.view(np.float32)).to(f"cuda:{e.device}"), x.shape[0], x.shape[1]
+
+
+def _morse_batch_dev(e, d_iq, n_frames, n, sample_rate, threshold=-20):
+    """decode_morse for the complex64 frames on the device (d_iq: float32 [n_frames][2 n]): one library call, one download of the texts'
+    used columns -> list of (text, timing dict), each what morse_from_edges returns for that buffer."""
+    import torch
+    if n_frames == 0:
+        return []
+    dev = lambda shape, dt: torch.empty(shape, dtype=dt, device=f"cuda:{e.device}")
+    cap = n // 2 + 1
+    d_rise, d_fall, d_counts = dev((n_frames, cap), torch.int32), dev((n_frames, cap), torch.int32), dev((n_frames, 2), torch.int32)
+    d_text, d_len = dev((n_frames, 2 * cap), torch.uint8), dev(n_frames, torch.int32)
+    d_tm, d_np = dev((n_frames, 3), torch.float64), dev(n_frames, torch.int32)
+    e.decode_morse_batch(d_iq, n_frames, n, sample_rate, d_rise, d_fall, d_counts, d_text, d_len, d_tm, d_np, threshold_db=threshold)
+    ln, tm, pulses = d_len.cpu().numpy(), d_tm.cpu().numpy(), d_np.cpu().numpy()
+    if (pulses < 0).any():   # cannot happen behind pss_morse_edges with this cap: its edges alternate and number at most n // 2 + 1
+        raise ValueError("operands could not be broadcast together: rise / fall edges do not alternate")
+    text = d_text[:, :max(int(ln.max()), 1)].cpu().numpy()
+    out = []
+    for f in range(n_frames):
+        if pulses[f] == 0:                 # no complete pulse: the reference's early returns
+            out.append(("", {"dot": 0, "dash": 0, "gap": 0}))
+        else:
+            out.append((text[f, :ln[f]].tobytes().decode("ascii"),
+                        {"dot": np.float64(tm[f, 0]), "dash": np.float64(tm[f, 1]), "gap": np.float64(tm[f, 2]) if pulses[f] > 1 else 0}))
+    return out
+
+
+def _aprs_batch_dev(e, d_iq, n_rows, n, sample_rate, tables=None, want_bits=False):
+    """decode_aprs for the complex64 frames on the device -> list of packet lists (and the uint8 bit rows [n_rows][n_bits])."""
+    import torch
+    nb = max(e.afsk_n_bits(n, sample_rate), 0)
+    if n_rows == 0:
+        return ([], np.zeros((0, nb), np.uint8)) if want_bits else []
+    dev = lambda shape, dt: torch.empty(shape, dtype=dt, device=f"cuda:{e.device}")
+    s1, s2 = _bandpass_tables(sample_rate) if tables is None else tables
+    out_cap = nb // 8 + 64
+    d_audio, d_bits = dev((n_rows, n), torch.float64), dev((n_rows, nb), torch.uint8)
+    d_out, d_len = dev((n_rows, out_cap), torch.uint8), dev(n_rows, torch.int32)
+    e.decode_aprs_batch(d_iq, n_rows, n, sample_rate, d_audio, d_bits, out_cap, d_out, d_len, s1, s2)
+    ln = d_len.cpu().numpy()
+    pk = d_out[:, :max(int(ln.max()), 1)].cpu().numpy()
+    out = [[pk[r, :ln[r]].tobytes().decode("latin-1")] if ln[r] > 0 else [] for r in range(n_rows)]   # `[packet] if packet else []`
+    return (out, d_bits.cpu().numpy()) if want_bits else out
+
+
+def decode_morse_batch(frames, sample_rate, threshold=-20):
+    """decode_morse for every read buffer of frames [n_frames][n] -> list of (text, timing dict), one library call for the batch."""
+    e = _sp.get_engine()
+    d_iq, nf, n = _upload_frames(e, frames)
+    return _morse_batch_dev(e, d_iq, nf, n, sample_rate, threshold)
+
+
+def decode_aprs_batch(frames, sample_rate):
+    """decode_aprs for every complex64 read buffer of frames [n_rows][n] -> list of packet lists ([packet] or []).  The real parts are
+    normalised in float32, as the reference's division of np.real(complex64) is (decode_aprs above widens first: PARITY.md)."""
+    e = _sp.get_engine()
+    d_iq, nf, n = _upload_frames(e, frames)
+    return _aprs_batch_dev(e, d_iq, nf, n, sample_rate)
 
 
 def decode_ax25_frame(bit_stream):

@@ -573,6 +573,41 @@ class Engine:
         self._dev(self.lib.pss_morse_edges, _ptr(d_iq), n_frames, n, float(threshold_db), cap, _ptr(d_rise), _ptr(d_fall),
                                           _ptr(d_counts))
 
+    # -- decoders for batches (include/pss.h): the per-message halves on the device, and decode_morse / decode_aprs in one call per batch
+    def morse_text(self, d_rise, d_fall, d_counts, n_frames, cap, fs, d_text, d_text_len, d_timing, d_pulses, text_cap=None):
+        """decode_morse from its edge lists on, for every frame of a morse_edges result (pss_morse_text): d_text uint8 [n_frames][text_cap]
+        (default 2 * cap: a text has at most 2 bytes per pulse), d_text_len int32, d_timing float64 [n_frames][3], d_pulses int32."""
+        text_cap = 2 * int(cap) if text_cap is None else int(text_cap)
+        self._dev(self.lib.pss_morse_text, _ptr(d_rise), _ptr(d_fall), _ptr(d_counts), int(n_frames), int(cap), float(fs), text_cap,
+                  _ptr(d_text), _ptr(d_text_len), _ptr(d_timing), _ptr(d_pulses))
+
+    def ax25_frames(self, d_bits, n_rows, n_bits, out_cap, d_out, d_out_len):
+        """decode_ax25_frame for rows of bits, one 0/1 per byte (pss_ax25_frames): d_out uint8 [n_rows][out_cap], d_out_len int32
+        (-1: no packet, else the packet's true length)."""
+        self._dev(self.lib.pss_ax25_frames, _ptr(d_bits), int(n_rows), int(n_bits), int(out_cap), _ptr(d_out), _ptr(d_out_len))
+
+    def real_normalise(self, d_iq, n_rows, n, d_audio):
+        """real part / max|real part| of complex64 rows in float32, widened to float64 (pss_real_normalise; decoders.py:121-125)."""
+        self._dev(self.lib.pss_real_normalise, _ptr(d_iq), int(n_rows), int(n), _ptr(d_audio))
+
+    def decode_morse_batch(self, d_iq, n_frames, n, fs, d_rise, d_fall, d_counts, d_text, d_text_len, d_timing, d_pulses, threshold_db=-20.0,
+                           cap=None, text_cap=None):
+        """decode_morse for every read buffer of a batch in one call (pss_decode_morse_batch).  cap (default n // 2 + 1, which alternating
+        edges cannot exceed) sizes the work buffers d_rise / d_fall int32 [n_frames][cap]; d_counts int32 [n_frames][2]; the rest as
+        morse_text."""
+        cap = int(n) // 2 + 1 if cap is None else int(cap)
+        text_cap = 2 * cap if text_cap is None else int(text_cap)
+        self._dev(self.lib.pss_decode_morse_batch, _ptr(d_iq), int(n_frames), int(n), float(fs), float(threshold_db), cap, _ptr(d_rise),
+                  _ptr(d_fall), _ptr(d_counts), text_cap, _ptr(d_text), _ptr(d_text_len), _ptr(d_timing), _ptr(d_pulses))
+
+    def decode_aprs_batch(self, d_iq, n_rows, n, fs, d_audio, d_bits, out_cap, d_out, d_out_len, sos1200=None, sos2200=None):
+        """decode_aprs for every complex64 read buffer of a batch in one call (pss_decode_aprs_batch).  Work buffers, returned filled:
+        d_audio float64 [n_rows][n], d_bits uint8 [n_rows][afsk_n_bits(n, fs)]; d_out / d_out_len as ax25_frames; tables as afsk_bits."""
+        c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
+        s1, s2 = c(sos1200), c(sos2200)
+        self._dev(self.lib.pss_decode_aprs_batch, _ptr(d_iq), int(n_rows), int(n), float(fs), _ptr(s1), _ptr(s2),
+                  5 if s1 is None else s1.shape[0], _ptr(d_audio), _ptr(d_bits), int(out_cap), _ptr(d_out), _ptr(d_out_len))
+
     def classify(self, d_iq, n_frames, n, fs, d_label=None, d_bw=None, d_mi=None, d_flat=None, d_psd=None):
         """classify_signal for a batch (pss_classify): any of label int32 / bw float64 / mi float32 / flat float32 / psd float32 [.,1024]."""
         self._dev(self.lib.pss_classify, _ptr(d_iq), n_frames, n, float(fs), _ptr(d_label), _ptr(d_bw), _ptr(d_mi),

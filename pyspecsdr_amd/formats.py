@@ -287,6 +287,61 @@ def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chun
     return pcm, opened, peak, avg
 
 
+def _decode_args(sample_rate, decoder, frame_len, chunk_frames):
+    """decode_recording's argument checks (host only: made before anything touches the GPU) -> (sample_rate, frame_len, chunk_frames)."""
+    if decoder not in ('morse', 'aprs'):
+        raise ValueError(f"unknown decoder {decoder!r}: 'morse' or 'aprs'")
+    sample_rate = float(sample_rate)
+    if not sample_rate > 0 or (decoder == 'aprs' and sample_rate < 1200):
+        raise ValueError("sample_rate must be positive (aprs: at least 1200 Hz, one sample per bit)")
+    if frame_len is None:
+        frame_len = int(sample_rate * 0.5)      # the read size of both decoder screens (pyspecsdr.py:503-659)
+    if int(frame_len) != frame_len or frame_len < 1:
+        raise ValueError("frame_len must be an integer >= 1")
+    if int(chunk_frames) != chunk_frames or chunk_frames < 1:
+        raise ValueError("chunk_frames must be an integer >= 1")
+    return sample_rate, int(frame_len), int(chunk_frames)
+
+
+def decode_recording(samples, sample_rate, decoder, frame_len=None, threshold=-20, chunk_frames=256, codes_format=None, table=None):
+    """Every read buffer of a recording through decode_morse (decoder='morse') or decode_aprs ('aprs') on the GPU -> a list with one entry
+    per buffer: (text, timing dict) or a packet list, as decoders.decode_morse_batch / decode_aprs_batch return them.  frame_len defaults
+    to int(sample_rate * 0.5), the read size of both decoder screens; an incomplete tail buffer is dropped (cut_frames).  chunk_frames
+    buffers go through one library call.  codes_format / table: as demodulate_recording — `samples` is the ADC code array [n, 2]."""
+    from . import decoders as D
+    sample_rate, frame_len, chunk_frames = _decode_args(sample_rate, decoder, frame_len, chunk_frames)
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+        nfr = len(samples) // frame_len
+        frames = samples[:nfr * frame_len].reshape(nfr, frame_len, 2)
+    else:
+        samples = np.asarray(samples)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+        frames = cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len)
+    import torch
+    e = get_engine()
+    nf, n = frames.shape[:2]
+    tables = D._bandpass_tables(sample_rate) if decoder == 'aprs' else None
+    out = []
+    for c0 in range(0, nf, chunk_frames):
+        c = min(chunk_frames, nf - c0)
+        if codes_format is not None:
+            d_codes = torch.from_numpy(np.array(frames[c0:c0 + c])).to(f"cuda:{e.device}")
+            d_iq = torch.empty((c, 2 * n), dtype=torch.float32, device=f"cuda:{e.device}")
+            e.unpack_iq(d_codes, c * n, d_iq, codes_format, iq[2])
+        else:
+            d_iq = torch.from_numpy(np.ascontiguousarray(frames[c0:c0 + c]).view(np.float32)).to(f"cuda:{e.device}")
+        if decoder == 'morse':
+            out += D._morse_batch_dev(e, d_iq, c, n, sample_rate, threshold)
+        else:
+            out += D._aprs_batch_dev(e, d_iq, c, n, sample_rate, tables)
+    return out
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
