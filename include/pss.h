@@ -773,6 +773,114 @@ int pss_h_stream_display_nfm_codes_f64(pss_ctx *ctx, int container, double scale
                                        const double *h_halo_lo, const double *h_halo_hi, int n_halo, int8_t *h_line_a, int8_t *h_line_b,
                                        int16_t *h_pcm, double *h_db, double *h_row_lo, double *h_row_hi, int8_t *h_grid_a, int8_t *h_grid_b);
 
+/* ---- replaying a capture: the main loop on a host recording, any mode, any view, squelch --------------------------------
+ * Dead reads.  Before anything else the reference's loop tests the buffer it has just read,
+ *     if len(samples) == 0 or np.all(samples == 0): ...; continue                                   (pyspecsdr.py:2237)
+ * and read_samples hands the driver a zero-filled array (:1887), so a read that timed out comes back all zero and is SKIPPED: no AGC, no
+ * demodulation, no compute_fft, no push into the waterfall / persistence history, no header, no advance of ui_update_counter.  The rule on
+ * bits: a frame is dead iff every one of its 2 n float32 words satisfies (bits & 0x7fffffff) == 0 — NumPy's `== 0` exactly: -0.0 is zero, a
+ * NaN and the smallest denormal are not, whatever denormal mode the code runs in.
+ *   pss_live_frames     d_iq complex64 [n_frames][n], n >= 1, aligned to one sample (8 bytes; n may be odd) -> d_live uint8 [n_frames]
+ *                       (nullable) = !np.all(frame == 0), d_live_idx int32 [n_frames] (nullable): the live frames' indices in ascending
+ *                       order, entries behind the *n_live-th stay untouched.  k_live_flags: one wavefront per frame up to 2048 samples, one
+ *                       workgroup above; 16-byte loads between the frame's first and last 16-byte boundary; a wavefront votes after a tile
+ *                       and leaves the frame at the first set bit, so a live capture costs about one tile (1 KB) per frame and only dead
+ *                       frames are read to the end.  No atomics: ballot and popcount, the squelch gate's prefix sum over tiles of 256.
+ *                       THIS CALL WAITS like pss_squelch_gate: one asynchronous 16-byte copy of the count into pinned memory and one
+ *                       synchronisation of the context's stream.  It cannot be captured into a graph.  n_frames == 0: PSS_OK, *n_live = 0.
+ *   pss_h_live_frames   the same on host arrays, pure C, no context and no GPU (iq: any address).
+ * PSS_E_ARG: n < 1, n_frames outside [0, 2^31), null n_live, null d_iq with n_frames > 0, d_iq not 8-byte aligned.
+ *
+ * pss_h_stream_frames plays a HOST capture as the main loop would: per chunk the upload (codes are unpacked by pss_unpack_iq), the dead-read
+ * test, the resident step of the chosen view on the live frames, the downloads — on the three streams and two buffer sets of
+ * pss_h_stream_display_nfm.  Every per-frame result is COMPACTED to the live frames in order, as pss_demod_gated compacts to the open ones,
+ * and equals the resident call on the live frames of the whole capture in one batch.  Request and result are structs (here and only here:
+ * the positional form would take about 40 arguments), zero-initialisable, `size` = sizeof the struct the caller compiled against; a size
+ * this library does not know is PSS_E_ARG.
+ *   request   h_in         the capture, n_frames x n samples: complex64, or ADC codes
+ *             container    -1: complex64; PSS_IQ_*: codes with scale / h_table256 as for pss_unpack_iq
+ *             n, fs        n a power of two in [16, 65536] (the reference's reads are 256 * 2^k); chunk_frames >= 1
+ *             mode         PSS_MODE_*, the dispatcher's semantics (WFM frames IQ-corrected)
+ *             view         0 waterfall, 1 persistence, 2 gradient (pss_frame_pipeline_cells' display codes), 3 spectrum bars, 4 surface,
+ *                          5 vector
+ *             window, disp_h, disp_w   as the view's resident call takes them: views 0 - 2 pss_frame_pipeline_cells' (disp_h: view 1 only);
+ *                          view 3 pss_frame_pipeline_bars' disp_h, disp_w; view 4 pss_frame_pipeline_surface's disp_w (max_w - 8); view 5
+ *                          pss_frame_pipeline_vector's max_h = disp_h, max_w = disp_w (max_h * ((max_w + 31) / 32) <= 16384)
+ *             h_halo_lo / h_halo_hi / n_halo   float64 extremes of the rows preceding the capture; views 0 - 2 only
+ *             skip_dead    1: dead reads are skipped as above; 0: every frame is live (a zero frame is drawn as a flat -100 dB row)
+ *             squelch      NaN: ungated, every live frame is demodulated (the FIFO path, :2266-2268); otherwise the gate of
+ *                          pss_squelch_gate with every / phase / held_in.  The state (held, phase) carries from chunk to chunk; dead
+ *                          frames do not advance it
+ *   result    host pointers, each nullable unless named as required; [n_live] means caller-sized [n_frames], filled [n_live]
+ *             live uint8 [n_frames]; n_live
+ *             db32 float32 [n_live][n]; row_lo / row_hi float64 [n_live] (views 0 - 2)
+ *             peak / avg float64 [n_live], open uint8 [n_live]: with a squelch only (PSS_E_ARG otherwise: without it no meter runs)
+ *             views 0, 2: line_a, line_b int8 [n_live][disp_w], both required; view 1: line_a, required
+ *             view 3: height, level int8 [n_live][disp_w], required; range float64 [n_live][2]
+ *             view 4: mag int8 [n_live][disp_w], required; range float64 [n_live][2]
+ *             view 5: mask uint32 [n_live][disp_h][(disp_w + 31) / 32], required: the samples as read
+ *             pcm int16 [n_open][n_out][2] (n_open = n_live without a squelch); n_open; held_out, phase_out: the gate's state behind
+ *             the capture (phase_out = (phase + n_live) % every)
+ * A chunk with some dead frames is gathered into context scratch (k_gather_frames) in front of its step; a chunk without a live frame launches
+ * nothing and leaves history and gate state as they are; buffers behind n_live / n_open stay untouched.  Host waits: with skip_dead the
+ * count of live frames, with a squelch the gate's count, one stream synchronisation each per chunk — the upload of chunk k + 1 is queued
+ * before them, so the link stays busy; with skip_dead = 0 and squelch NaN there is no wait beyond pss_h_stream_display_nfm's own.
+ * Synchronous; on any error everything queued is drained before the call returns.  Not capturable.
+ * Out of scope: the per-chunk full-screen grids (pss_h_stream_display_nfm_grids keeps them); AGC, whose interval is wall-clock time; the
+ * sharded drivers.
+ * PSS_E_ARG: unknown size, view, mode or container (scale / table as pss_unpack_iq); n; chunk_frames < 1; n_frames outside [0, 2^31); a
+ * halo with views 3 - 5; display geometry the view's resident call rejects; every < 0 or phase outside [0, every); a missing required
+ * output; peak / avg / open without a squelch; null h_in with n_frames > 0. */
+typedef struct pss_stream_req {
+    uint32_t size;
+    int container;
+    const void *h_in;
+    const float *h_table256;
+    double scale;
+    long n_frames;
+    long chunk_frames;
+    double fs;
+    int n;
+    int mode;
+    int view;
+    int window;
+    int disp_h;
+    int disp_w;
+    const double *h_halo_lo;
+    const double *h_halo_hi;
+    int n_halo;
+    int skip_dead;
+    double squelch;
+    double held_in;
+    int every;
+    int phase;
+} pss_stream_req;
+typedef struct pss_stream_res {
+    uint32_t size;
+    int phase_out;
+    long n_live;
+    long n_open;
+    double held_out;
+    uint8_t *live;
+    float *db32;
+    double *row_lo;
+    double *row_hi;
+    double *peak;
+    double *avg;
+    uint8_t *open;
+    int8_t *line_a;
+    int8_t *line_b;
+    int8_t *height;
+    int8_t *level;
+    int8_t *mag;
+    double *range;
+    uint32_t *mask;
+    int16_t *pcm;
+} pss_stream_res;
+int pss_live_frames(pss_ctx *ctx, const float *d_iq, long n_frames, int n, uint8_t *d_live, int32_t *d_live_idx, long *n_live);
+int pss_h_live_frames(const float *iq, long n_frames, int n, uint8_t *live, int32_t *live_idx, long *n_live);
+int pss_h_stream_frames(pss_ctx *ctx, const pss_stream_req *req, pss_stream_res *res);
+
 /* ---- Multi-GPU: the path's exchange steps (one process per GPU, RCCL over xGMI) ----------------------------------------------------------
  * The path shards by contiguous blocks of independent frames / scanner slices (the sweep of pyspecsdr.py:2514-2590; every read buffer of
  * the loop :2236-2283 is processed on its own): every rank runs the single-GPU entry points above on its block, with NO collective in

@@ -17,6 +17,23 @@ IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2                  # ADC code containers (PSS_IQ_*)
 SWEEP_INLINE, SWEEP_DRIVER = 0, 1               # pss_sweep_report kinds (PSS_SWEEP_*)
 
 _p = C.c_void_p
+
+
+class StreamReq(C.Structure):
+    """pss_stream_req: what pss_h_stream_frames is asked to play (include/pss.h, "replaying a capture")."""
+    _fields_ = [("size", C.c_uint32), ("container", C.c_int), ("h_in", _p), ("h_table256", _p), ("scale", C.c_double), ("n_frames", C.c_long),
+                ("chunk_frames", C.c_long), ("fs", C.c_double), ("n", C.c_int), ("mode", C.c_int), ("view", C.c_int), ("window", C.c_int),
+                ("disp_h", C.c_int), ("disp_w", C.c_int), ("h_halo_lo", _p), ("h_halo_hi", _p), ("n_halo", C.c_int), ("skip_dead", C.c_int),
+                ("squelch", C.c_double), ("held_in", C.c_double), ("every", C.c_int), ("phase", C.c_int)]
+
+
+class StreamRes(C.Structure):
+    """pss_stream_res: the counts and gate state it hands back, and the host buffers it fills."""
+    _fields_ = [("size", C.c_uint32), ("phase_out", C.c_int), ("n_live", C.c_long), ("n_open", C.c_long), ("held_out", C.c_double), ("live", _p),
+                ("db32", _p), ("row_lo", _p), ("row_hi", _p), ("peak", _p), ("avg", _p), ("open", _p), ("line_a", _p), ("line_b", _p),
+                ("height", _p), ("level", _p), ("mag", _p), ("range", _p), ("mask", _p), ("pcm", _p)]
+
+
 _SIGS = {
     "pss_create": (C.c_int, [C.c_int, C.POINTER(_p)]),
     "pss_destroy": (None, [_p]),
@@ -174,6 +191,9 @@ _SIGS = {
                                                  C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p]),
     "pss_h_stream_display_nfm_codes_f64": (C.c_int, [_p, C.c_int, C.c_double, _p, _p, C.c_long, C.c_int, C.c_double, C.c_long, C.c_int, C.c_int,
                                                      C.c_int, C.c_int, _p, _p, C.c_int, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pss_live_frames": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.POINTER(C.c_long)]),
+    "pss_h_live_frames": (C.c_int, [_p, C.c_long, C.c_int, _p, _p, C.POINTER(C.c_long)]),
+    "pss_h_stream_frames": (C.c_int, [_p, C.POINTER(StreamReq), C.POINTER(StreamRes)]),
     "pss_shard_range": (C.c_int, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
     "pss_comm_id": (C.c_int, [_p]),
     "pss_comm_init": (C.c_int, [_p, _p, C.c_int, C.c_int]),

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "pss_ctx.h"
+#include "pss_live.h"
 
 static std::string g_create_err;
 
@@ -945,4 +946,217 @@ extern "C" int pss_h_stream_display_nfm_codes_f64(pss_ctx *ctx, int container, d
     if (ctx && h_grid_a && n_halo > 0) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_display_nfm_codes_f64: grids need a fresh history (no halo)");
     return stream_display<double>(ctx, h_codes, PssIqFmt::of_codes(container, scale, h_table256), n_frames, n, fs, chunk_frames, mode, window, disp_h, disp_w,
                                   h_halo_lo, h_halo_hi, n_halo, h_line_a, h_line_b, h_pcm, h_db, h_row_lo, h_row_hi, h_grid_a, h_grid_b);
+}
+
+// ---- replaying a capture (include/pss.h): the main loop on a host recording — any mode, any view, dead reads skipped, squelch ------------
+// stream_display's three streams and two buffer sets around the RESIDENT step of the view (pss_frame_pipeline_cells / _squelch / _bars /
+// _surface / _vector, the squelch composition for the views without a history), run on the chunk's live frames.  What differs from
+// stream_display: results land at the running live / open counts (pss_live::Cursor), and a chunk may make the host wait (the live count, the
+// gate's count) — so in that case the upload of chunk k + 1 is queued BEFORE chunk k's step, and the link works through the waits.
+extern "C" int pss_h_stream_frames(pss_ctx *ctx, const pss_stream_req *req, pss_stream_res *res)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (!req || !res || req->size != sizeof(pss_stream_req) || res->size != sizeof(pss_stream_res))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: null request / result, or a struct size this library does not know");
+    const int n = req->n, view = req->view, mode = req->mode, window = req->window, disp_h = req->disp_h, disp_w = req->disp_w, n_halo = req->n_halo;
+    const long n_frames = req->n_frames;
+    const bool gated = !(req->squelch != req->squelch), skip = req->skip_dead != 0, history = view <= 2;
+    if (view < 0 || view > 5) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: unknown view (0 waterfall .. 5 vector)");
+    if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: unknown demodulation mode");
+    PssIqFmt fmt;
+    if (req->container != -1) {
+        const int rf = pss_iq_check(ctx, req->container, req->scale, req->h_table256);
+        if (rf) return rf;
+        fmt = PssIqFmt::of_codes(req->container, req->scale, req->h_table256);
+    }
+    if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: n must be a power of two in [16, 65536]");
+    if (n_frames < 0 || n_frames > INT32_MAX || req->chunk_frames < 1 || (n_frames > 0 && !req->h_in))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: a frame count outside [0, 2^31), chunk_frames < 1 or a null capture");
+    if (!history && (n_halo != 0 || req->h_halo_lo || req->h_halo_hi))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: a halo belongs to the views with a history (0 - 2)");
+    if (history && (n_halo < 0 || (n_halo > 0 && (!req->h_halo_lo || !req->h_halo_hi)) || window < 1 || disp_w < 1 || (view == 1 && (disp_h < 1 || disp_h > 127))))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: bad halo, window or display geometry");
+    if (view == 3 && (disp_h < 1 || disp_h > 127 || disp_w < 1)) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: spectrum bars need disp_h in [1, 127] and disp_w >= 1");
+    if (view == 4 && disp_w < 2) return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: the surface view needs disp_w >= 2");
+    const size_t mask_words = view == 5 && disp_w >= 1 ? ((size_t)disp_w + 31) / 32 : 0;
+    if (view == 5 && (disp_h < 1 || disp_w < 1 || (size_t)disp_h * mask_words > 16384))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: the vector view needs max_h >= 1, max_w >= 1 and max_h * ((max_w + 31) / 32) <= 16384 (the mask in LDS)");
+    if (gated && (req->every < 0 || req->phase < 0 || (req->every == 0 ? req->phase != 0 : req->phase >= req->every)))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: every < 0 or phase outside [0, every)");
+    if (!gated && (res->peak || res->avg || res->open))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: peak / avg / open come with a squelch (no meter runs without one)");
+    const bool two_lines = view == 0 || view == 2;
+    if ((history && (!res->line_a || (two_lines && !res->line_b))) || (view == 3 && (!res->height || !res->level)) || (view == 4 && !res->mag) ||
+        (view == 5 && !res->mask))
+        return pss_fail(ctx, PSS_E_ARG, "pss_h_stream_frames: an output the view requires is null");
+    const int n_out = pss_demod_out_len_ctx(ctx, mode, n, req->fs);
+    if (n_out < 0) return pss_fail(ctx, PSS_E_ARG, "sample rate below the target rate");
+    pss_live::Cursor cur;
+    cur.held = gated ? req->held_in : 0.0;
+    cur.phase = gated ? req->phase : 0;
+    auto finish = [&]() {
+        res->n_live = cur.n_live, res->n_open = cur.n_open, res->held_out = gated ? cur.held : req->held_in, res->phase_out = gated ? cur.phase : req->phase;
+    };
+    if (n_frames == 0) {
+        finish();
+        return PSS_OK;
+    }
+    const long chunk = req->chunk_frames > n_frames ? n_frames : req->chunk_frames;
+    const int m = n - 4;
+    // per frame of a chunk: the view's two byte planes (lines / bars / magnitudes / mask), and a set of small numbers
+    const size_t per_a = view == 5 ? (size_t)disp_h * mask_words * sizeof(uint32_t) : (size_t)disp_w, per_b = (two_lines || view == 3) ? (size_t)disp_w : 0;
+    const size_t iq_b = (size_t)chunk * n * 2 * sizeof(float), sample_b = fmt.sample_bytes();
+    const size_t num_b = (size_t)chunk * (4 * sizeof(double) + 2);   // [range 2 | peak | avg] float64, [open | live] bytes
+    const size_t n_ext = (size_t)n_halo + (size_t)n_frames;
+    int rc = stream_res(ctx);
+    if (rc) return rc;
+    hipStream_t s_up = ctx->st_up, s_dn = ctx->st_dn;
+    hipEvent_t *up_done = ctx->st_ev, *cmp_done = ctx->st_ev + 2, *dn_done = ctx->st_ev + 4;
+    void *d_iq[2], *d_db[2], *d_pcm[2], *d_a[2], *d_b[2] = {nullptr, nullptr}, *d_num[2], *d_codes[2] = {nullptr, nullptr};
+    void *d_post = nullptr, *d_ext = nullptr, *d_work = nullptr;
+    for (int i = 0; i < 2; i++) {
+        if (!rc) rc = stream_buf(ctx, 0 + i, iq_b, &d_iq[i]);
+        if (!rc) rc = stream_buf(ctx, 2 + i, (size_t)chunk * n * sizeof(float), &d_db[i]);
+        if (!rc) rc = stream_buf(ctx, 4 + i, (size_t)chunk * n_out * 2 * sizeof(int16_t), &d_pcm[i]);
+        if (!rc) rc = stream_buf(ctx, 6 + i, (size_t)chunk * per_a, &d_a[i]);
+        if (!rc && per_b) rc = stream_buf(ctx, 8 + i, (size_t)chunk * per_b, &d_b[i]);
+        if (!rc && fmt.codes) rc = stream_buf(ctx, 18 + i, (size_t)chunk * n * sample_b, &d_codes[i]);
+        if (!rc) rc = stream_buf(ctx, 20 + i, num_b, &d_num[i]);
+    }
+    if (!rc && !history && gated) rc = stream_buf(ctx, 10, (size_t)chunk * m * sizeof(double), &d_post);
+    if (!rc && history) rc = stream_buf(ctx, 11, 2 * n_ext * sizeof(double), &d_ext);
+    // the chunk's live frames gathered in front of its step, and the two index lists (live frames, open frames)
+    const size_t gather_b = skip ? iq_b : 0;
+    if (!rc) rc = stream_buf(ctx, 22, gather_b + 2 * (size_t)chunk * sizeof(int32_t), &d_work);
+    if (rc) return rc;
+    float *d_gather = reinterpret_cast<float *>(d_work);
+    int32_t *d_live_idx = reinterpret_cast<int32_t *>(static_cast<char *>(d_work) + gather_b), *d_open_idx = d_live_idx + chunk;
+    auto cleanup = [&]() { stream_drain(ctx); };
+#define STREAM_HIP(call)                                          \
+    do {                                                          \
+        rc = pss_hip_check(ctx, (call), #call);                   \
+        if (rc) { cleanup(); return rc; }                         \
+    } while (0)
+    double *d_lo = reinterpret_cast<double *>(d_ext), *d_hi = history ? d_lo + n_ext : nullptr;
+    if (n_halo) {
+        STREAM_HIP(hipMemcpyAsync(d_lo, req->h_halo_lo, sizeof(double) * n_halo, hipMemcpyHostToDevice, ctx->stream));
+        STREAM_HIP(hipMemcpyAsync(d_hi, req->h_halo_hi, sizeof(double) * n_halo, hipMemcpyHostToDevice, ctx->stream));
+    }
+    const char *h_bytes = static_cast<const char *>(req->h_in);
+    const long n_chunks = (n_frames + chunk - 1) / chunk;
+    // chunk j goes up into buffer set j & 1, which is free once chunk j - 2 has been downloaded: the HOST waits for that, the upload itself
+    // carries no dependency (see stream_display)
+    auto upload = [&](long j) -> int {
+        const int b = (int)(j & 1);
+        const long f0 = j * chunk, cnt = (n_frames - f0) < chunk ? (n_frames - f0) : chunk;
+        int r = PSS_OK;
+        if (j >= 2) r = pss_hip_check(ctx, hipEventSynchronize(dn_done[b]), "hipEventSynchronize(dn_done)");
+        if (!r) r = pss_hip_check(ctx, hipMemcpyAsync(fmt.codes ? d_codes[b] : d_iq[b], h_bytes + (size_t)f0 * n * sample_b, (size_t)cnt * n * sample_b,
+                                                      hipMemcpyHostToDevice, s_up), "hipMemcpyAsync(upload)");
+        if (!r) r = pss_hip_check(ctx, hipEventRecord(up_done[b], s_up), "hipEventRecord(up_done)");
+        return r;
+    };
+    const bool waits = skip || gated;   // a chunk's step makes the host wait: the next upload is queued in front of it
+    for (long k = 0; k < n_chunks; k++) {
+        const int b = (int)(k & 1);
+        const long f0 = k * chunk, cnt = (n_frames - f0) < chunk ? (n_frames - f0) : chunk;
+        if (k == 0 || !waits) rc = upload(k);
+        if (!rc && waits && k + 1 < n_chunks) rc = upload(k + 1);
+        if (rc) { cleanup(); return rc; }
+        STREAM_HIP(hipStreamWaitEvent(ctx->stream, up_done[b], 0));
+        if (k >= 2) STREAM_HIP(hipStreamWaitEvent(ctx->stream, dn_done[b], 0));
+        if (fmt.codes) {
+            rc = pss_unpack_iq(ctx, fmt.container, d_codes[b], cnt * (long)n, fmt.scale, fmt.h_table256, (float *)d_iq[b]);
+            if (rc) { cleanup(); return rc; }
+        }
+        double *d_range = reinterpret_cast<double *>(d_num[b]), *d_peak = d_range + 2 * chunk, *d_avg = d_peak + chunk;
+        uint8_t *d_open = reinterpret_cast<uint8_t *>(d_avg + chunk), *d_live = d_open + chunk;
+        long nl = cnt, no = 0;
+        double held_next = cur.held;
+        const float *src = (const float *)d_iq[b];
+        if (skip) {
+            rc = pss_live_frames(ctx, src, cnt, n, d_live, d_live_idx, &nl);   // waits for the count
+            if (!rc && nl > 0 && nl < cnt) {
+                rc = pss_gather_frames(ctx, src, cnt, n, d_live_idx, nl, d_gather);
+                src = d_gather;
+            }
+            if (rc) { cleanup(); return rc; }
+        }
+        if (nl > 0) {
+            PssFlagScope keep(ctx->no_small_batch, true);   // chunks of a stream are throughput work: fused large-batch kernels
+            if (history) {
+                // live frames cur.n_live .. of the capture sit at positions n_halo + cur.n_live .. of the extremes arrays: the history reaches back
+                // over the live frames before them and the caller's halo, and skips dead reads as the reference's deque does
+                const long before = (long)n_halo + cur.n_live;
+                const int halo_k = (int)(before < (long)(window - 1) ? before : (long)(window - 1));
+                double *lo_k = d_lo + before - halo_k, *hi_k = d_hi + before - halo_k;
+                if (gated)
+                    rc = pss_frame_pipeline_squelch(ctx, mode, src, nl, n, req->fs, (float *)d_db[b], nullptr, lo_k, hi_k, halo_k, window, view, disp_h, disp_w,
+                                                    (int8_t *)d_a[b], (int8_t *)d_b[b], (int16_t *)d_pcm[b], req->squelch, req->every, cur.phase, cur.held,
+                                                    d_peak, d_avg, d_open, &no, &held_next);
+                else
+                    rc = pss_frame_pipeline_cells(ctx, mode, src, nl, n, req->fs, (float *)d_db[b], nullptr, lo_k, hi_k, halo_k, window, view, disp_h, disp_w,
+                                                  (int8_t *)d_a[b], (int8_t *)d_b[b], (int16_t *)d_pcm[b]);
+            } else {
+                // the views without a history; with a squelch the display half alone, then meter -> gate -> demodulator on the open frames
+                int16_t *pcm_now = gated ? nullptr : (int16_t *)d_pcm[b];
+                double *post = gated ? (double *)d_post : nullptr;
+                if (view == 3)
+                    rc = pss_frame_pipeline_bars(ctx, mode, src, nl, n, req->fs, (float *)d_db[b], nullptr, post, disp_h, disp_w, (int8_t *)d_a[b], (int8_t *)d_b[b],
+                                                 d_range, pcm_now);
+                else if (view == 4)
+                    rc = pss_frame_pipeline_surface(ctx, mode, src, nl, n, req->fs, (float *)d_db[b], nullptr, post, disp_w, (int8_t *)d_a[b], d_range, pcm_now);
+                else
+                    rc = pss_frame_pipeline_vector(ctx, mode, src, nl, n, req->fs, (float *)d_db[b], nullptr, post, disp_h, disp_w, (uint32_t *)d_a[b], pcm_now);
+                if (gated) {
+                    if (!rc) rc = pss_row_meter_f64(ctx, post, nl, m, d_peak, d_avg);
+                    if (!rc) rc = pss_squelch_gate(ctx, d_peak, nl, req->squelch, req->every, cur.phase, cur.held, d_open, d_open_idx, &no, &held_next);
+                    if (!rc) rc = pss_demod_gated(ctx, mode, src, nl, n, req->fs, d_open_idx, no, (int16_t *)d_pcm[b], nullptr);
+                }
+            }
+            if (!gated) no = nl;
+            if (rc) { cleanup(); return rc; }
+        }
+        STREAM_HIP(hipEventRecord(cmp_done[b], ctx->stream));
+        STREAM_HIP(hipStreamWaitEvent(s_dn, cmp_done[b], 0));
+#define DOWN(host, dev, count, per) \
+    if ((host) && (count) > 0) STREAM_HIP(hipMemcpyAsync((char *)(host) + (size_t)(at) * (per), (dev), (size_t)(count) * (per), hipMemcpyDeviceToHost, s_dn))
+        long at = f0;
+        if (skip) DOWN(res->live, d_live, cnt, 1);
+        at = cur.n_live;
+        DOWN(res->db32, d_db[b], nl, (size_t)n * sizeof(float));
+        if (history) {
+            DOWN(res->line_a, d_a[b], nl, per_a);
+            if (two_lines) DOWN(res->line_b, d_b[b], nl, per_b);
+        } else if (view == 3) {
+            DOWN(res->height, d_a[b], nl, per_a);
+            DOWN(res->level, d_b[b], nl, per_b);
+        } else if (view == 4) {
+            DOWN(res->mag, d_a[b], nl, per_a);
+        } else {
+            DOWN(res->mask, d_a[b], nl, per_a);
+        }
+        if (view == 3 || view == 4) DOWN(res->range, d_range, nl, 2 * sizeof(double));
+        if (gated) {
+            DOWN(res->peak, d_peak, nl, sizeof(double));
+            DOWN(res->avg, d_avg, nl, sizeof(double));
+            DOWN(res->open, d_open, nl, 1);
+        }
+        at = cur.n_open;
+        DOWN(res->pcm, d_pcm[b], no, (size_t)n_out * 2 * sizeof(int16_t));
+#undef DOWN
+        STREAM_HIP(hipEventRecord(dn_done[b], s_dn));
+        cur.advance(nl, no, held_next, gated ? req->every : 0);
+    }
+    STREAM_HIP(hipStreamSynchronize(ctx->stream));
+    if (history && cur.n_live > 0) {
+        if (res->row_lo) STREAM_HIP(hipMemcpy(res->row_lo, d_lo + n_halo, sizeof(double) * cur.n_live, hipMemcpyDeviceToHost));
+        if (res->row_hi) STREAM_HIP(hipMemcpy(res->row_hi, d_hi + n_halo, sizeof(double) * cur.n_live, hipMemcpyDeviceToHost));
+    }
+#undef STREAM_HIP
+    cleanup();
+    if (!skip && res->live) memset(res->live, 1, (size_t)n_frames);   // every frame counts as live
+    finish();
+    return PSS_OK;
 }

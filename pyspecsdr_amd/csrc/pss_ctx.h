@@ -72,8 +72,8 @@ struct pss_ctx {
     // (creating and freeing them per capture cost ~2 ms of a 17 ms capture)
     hipStream_t st_up = nullptr, st_dn = nullptr;
     hipEvent_t st_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // up_done[2], cmp_done[2], dn_done[2]
-    void *st_buf[20] = {};         // [0..11]: the chunk buffer sets; [12..15]: per-chunk display grids (two sets x two planes); [16..17]: the last `window` post-processed rows (ping-pong); [18..19]: the chunk's ADC codes as uploaded (the *_codes calls, pss_ingest.hip)
-    size_t st_cap[20] = {};
+    void *st_buf[24] = {};         // [0..11]: the chunk buffer sets; [12..15]: per-chunk display grids (two sets x two planes); [16..17]: the last `window` post-processed rows (ping-pong); [18..19]: the chunk's ADC codes as uploaded (the *_codes calls, pss_ingest.hip); [20..23]: pss_h_stream_frames' per-frame numbers (two sets), gathered live frames and index lists (its other buffers are [0..11] and [18..19])
+    size_t st_cap[24] = {};
     float *d_hann_short = nullptr;  // the same for reads shorter than 1024 samples (window length = read length hann_short_n)
     float hann_short_sum = 0.0f;
     int hann_short_n = 0;
@@ -230,6 +230,10 @@ struct PssIqFmt {
     }
     size_t sample_bytes() const { return codes ? (size_t)pss_iq_code_bytes(container) : 2 * sizeof(float); }   // behind pss_iq_check
 };
+
+// implemented in pss_squelch.hip: d_dst[k] = frame d_idx[k] of the batch [n_frames][n], k < n_idx (indices outside the batch are clamped into it);
+// d_iq aligned to one sample (8 bytes).  Stream-ordered.
+int pss_gather_frames(pss_ctx *ctx, const float *d_iq, long n_frames, int n, const int32_t *d_idx, long n_idx, float *d_dst);
 
 // implemented in pss_fft.hip
 bool pss_hilbert_supported(int n);

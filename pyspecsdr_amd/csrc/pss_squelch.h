@@ -301,6 +301,106 @@ __global__ __launch_bounds__(256) void k_scan_index(const float *__restrict__ pe
     }
 }
 
+// ---- dead reads --------------------------------------------------------------------------------------------------------------------------
+// The loop skips a read buffer whose samples are all zero before anything else sees it (pyspecsdr.py:2237: np.all(samples == 0), the
+// zero-filled array of a read that timed out, :1887).  live[f] = some word of frame f has a bit set below the sign, NumPy's `== 0` decided on
+// the bits (-0.0 is zero; a NaN and a denormal are not, in any denormal mode).
+// G lanes per frame: 64 (one wavefront per frame, four frames per workgroup) or 256 (one workgroup per frame, its four wavefronts on
+// interleaved tiles).  A tile is 64 lanes x 16 bytes; a wavefront votes after its first tile and then after every four, and leaves at the
+// first vote that saw a set bit: a live frame costs its first tile, only a dead one is read to the end.  The frame's pointer is 8-byte
+// aligned and no more (d_iq + f * 2n words, n may be odd): two words in front of the first 16-byte boundary and two behind the last whole
+// group go to single lanes.  No atomics; the flags do not depend on the schedule.
+constexpr int LIVE_WAVE_MAX_N = 2048;   // frames of up to this many samples (16 KB, the meter's boundary in bytes): one wavefront per frame
+
+template <int G>
+__global__ __launch_bounds__(256) void k_live_flags(const uint32_t *__restrict__ iq, long n_frames, int n, uint8_t *__restrict__ live)
+{
+    constexpr int FPB = 256 / G;   // frames per workgroup pass
+    __shared__ int any_s[4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int slot = threadIdx.x / G, t = threadIdx.x % G;
+    const size_t words = 2 * (size_t)n;
+    const size_t first = G == 256 ? (size_t)wave * 64 : 0;   // this wavefront's first group of 16 bytes
+    for (long base = (long)blockIdx.x * FPB; base < n_frames; base += (long)gridDim.x * FPB) {
+        const long f = base + slot;
+        const bool has = f < n_frames;   // the same for every lane of a wavefront
+        const uint32_t *p = iq + (size_t)(has ? f : 0) * words;
+        const unsigned head = (reinterpret_cast<uintptr_t>(p) & 15) ? 2u : 0u;   // words >= 2
+        const size_t n_groups = (words - head) >> 2, tail0 = (size_t)head + (n_groups << 2);
+        const uint4 *v = reinterpret_cast<const uint4 *>(p + head);
+        bool nz = false;
+        if (has) {
+            if ((unsigned)t < head) nz = (p[t] & 0x7fffffffu) != 0;
+            else if (tail0 + ((unsigned)t - head) < words) nz = (p[tail0 + ((unsigned)t - head)] & 0x7fffffffu) != 0;
+        }
+        unsigned long long b = __ballot(nz);
+        size_t g0 = first;
+        if (!b && has && g0 < n_groups) {   // the first tile alone: what a live frame costs
+            const size_t g = g0 + lane;
+            bool z = false;
+            if (g < n_groups) {
+                const uint4 q = v[g];
+                z = ((q.x | q.y | q.z | q.w) & 0x7fffffffu) != 0;
+            }
+            b = __ballot(z);
+            g0 += G;
+        }
+        while (!b && has && g0 < n_groups) {   // four tiles in flight per vote
+            uint4 q[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const size_t g = g0 + (size_t)u * G + lane;
+                q[u] = g < n_groups ? v[g] : make_uint4(0u, 0u, 0u, 0u);
+            }
+            const uint32_t m = (q[0].x | q[0].y | q[0].z | q[0].w) | (q[1].x | q[1].y | q[1].z | q[1].w) | (q[2].x | q[2].y | q[2].z | q[2].w) |
+                               (q[3].x | q[3].y | q[3].z | q[3].w);
+            b = __ballot((m & 0x7fffffffu) != 0);
+            g0 += 4 * (size_t)G;
+        }
+        if (G == 64) {
+            if (has && lane == 0) live[f] = b ? 1 : 0;
+        } else {
+            if (lane == 0) any_s[wave] = b ? 1 : 0;
+            __syncthreads();
+            if (threadIdx.x == 0 && has) live[f] = (any_s[0] | any_s[1] | any_s[2] | any_s[3]) ? 1 : 0;
+            __syncthreads();
+        }
+    }
+}
+
+// the gate's two list steps over flags that are already bytes: counts per tile of 256 for k_gate_scan, then the ascending list
+__global__ __launch_bounds__(256) void k_flag_count(const uint8_t *__restrict__ flag, long n_frames, int *__restrict__ tile_count, long n_tiles)
+{
+    __shared__ int wcount[4];
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool on = i < n_frames && flag[i] != 0;
+        const unsigned long long b = __ballot(on);
+        if ((threadIdx.x & 63) == 0) wcount[threadIdx.x >> 6] = __popcll(b);
+        __syncthreads();
+        if (threadIdx.x == 0) tile_count[tile] = wcount[0] + wcount[1] + wcount[2] + wcount[3];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(256) void k_flag_index(const uint8_t *__restrict__ flag, long n_frames, const int *__restrict__ tile_off, long n_tiles,
+                                                    int *__restrict__ d_idx)
+{
+    __shared__ int wcount[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long i = tile * GATE_TILE + threadIdx.x;
+        const bool on = i < n_frames && flag[i] != 0;
+        const unsigned long long b = __ballot(on);
+        if (lane == 0) wcount[w] = __popcll(b);
+        __syncthreads();
+        int before = 0;
+        for (int q = 0; q < w; q++) before += wcount[q];
+        if (on) d_idx[(long)tile_off[tile] + before + __popcll(b & ((1ull << lane) - 1ull))] = (int)i;   // < n_live <= n_frames
+        __syncthreads();
+    }
+}
+
 // ---- gather of the open frames ---------------------------------------------------------------------------------------------------------
 // dst[k] = src[idx[k]] for frames of `per_frame` elements of V (uint4: 16 bytes per lane; uint2 for an odd frame length or a batch that
 // starts 8 bytes off a 16-byte boundary).  An index outside [0, n_frames) is clamped:

@@ -4,6 +4,8 @@
 // changes.
 // The scanner sweep report (include/pss.h, "scanner sweep report") is the same shape of work and lives here too: scan -> gate ->
 // classifier on the detections only, behind pss_scan, pss_scan_threshold and pss_classify.
+// The dead-read test (include/pss.h, "replaying a capture") is a third gate over a batch — flags, the same prefix sum, the ascending list —
+// and shares the scratch and the pinned count with the other two.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "pss_ctx.h"
+#include "pss_live.h"
 #include "pss_squelch.h"
 
 namespace {
@@ -121,6 +124,23 @@ extern "C" int pss_squelch_gate(pss_ctx *ctx, const double *d_peak, long n_frame
     return PSS_OK;
 }
 
+// dst[k] = frame idx[k] of the batch, k < n_idx (k_gather_frames: 16 bytes per lane, 8 for an odd frame length or a batch that starts 8 bytes off
+// a 16-byte boundary).  d_iq aligned to one sample; dst from hipMalloc.  Stream-ordered.
+int pss_gather_frames(pss_ctx *ctx, const float *d_iq, long n_frames, int n, const int32_t *d_idx, long n_idx, float *d_dst)
+{
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_iq);
+    const dim3 grid((unsigned)(n_idx < 2048 ? n_idx : 2048));
+    pss_kernel_begin(ctx, "k_gather_frames");
+    if (n % 2 == 0 && a % 16 == 0)
+        hipLaunchKernelGGL(k_gather_frames<uint4>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint4 *>(d_iq), d_idx, n_idx, n_frames,
+                           (long)n / 2, reinterpret_cast<uint4 *>(d_dst));
+    else
+        hipLaunchKernelGGL(k_gather_frames<uint2>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint2 *>(d_iq), d_idx, n_idx, n_frames,
+                           (long)n, reinterpret_cast<uint2 *>(d_dst));
+    pss_kernel_end(ctx);
+    return pss_hip_check(ctx, hipGetLastError(), "k_gather_frames launch");
+}
+
 extern "C" int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n_frames, int n, double fs, const int32_t *d_open_idx, long n_open,
                                int16_t *d_pcm, double *d_audio)
 {
@@ -132,24 +152,76 @@ extern "C" int pss_demod_gated(pss_ctx *ctx, int mode, const float *d_iq, long n
     if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: null IQ buffer");
     if (n_open == n_frames) return pss_demod_signal(ctx, mode, d_iq, n_frames, n, fs, d_pcm, d_audio);   // an ascending list of all frames: no copy
     if (!d_open_idx) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: null index list");
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_iq);
-    if (a % 8) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: d_iq is not aligned to one complex64 sample (8 bytes)");
+    if (reinterpret_cast<uintptr_t>(d_iq) % 8) return pss_fail(ctx, PSS_E_ARG, "pss_demod_gated: d_iq is not aligned to one complex64 sample (8 bytes)");
     void *gathered;
     int r = sq_buffer(ctx, 1, (size_t)n_open * n * 2 * sizeof(float), "open frames", &gathered);
     if (r) return r;
     PssTimeScope timed(ctx);
-    const dim3 grid((unsigned)(n_open < 2048 ? n_open : 2048));
-    pss_kernel_begin(ctx, "k_gather_frames");
-    if (n % 2 == 0 && a % 16 == 0)
-        hipLaunchKernelGGL(k_gather_frames<uint4>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint4 *>(d_iq), d_open_idx, n_open, n_frames,
-                           (long)n / 2, reinterpret_cast<uint4 *>(gathered));
-    else
-        hipLaunchKernelGGL(k_gather_frames<uint2>, grid, dim3(256), 0, PSS_STREAM(ctx), reinterpret_cast<const uint2 *>(d_iq), d_open_idx, n_open, n_frames,
-                           (long)n, reinterpret_cast<uint2 *>(gathered));
-    pss_kernel_end(ctx);
-    r = pss_hip_check(ctx, hipGetLastError(), "k_gather_frames launch");
+    r = pss_gather_frames(ctx, d_iq, n_frames, n, d_open_idx, n_open, reinterpret_cast<float *>(gathered));
     if (!r) r = pss_demod_signal(ctx, mode, reinterpret_cast<const float *>(gathered), n_open, n, fs, d_pcm, d_audio);
     return r;
+}
+
+// ---- dead reads (include/pss.h, "replaying a capture") ----------------------------------------------------------------------------------
+// The loop's first test on a read buffer (pyspecsdr.py:2237), one frame after the other: pure host code, no context.
+extern "C" int pss_h_live_frames(const float *iq, long n_frames, int n, uint8_t *live, int32_t *live_idx, long *n_live)
+{
+    if (n < 1 || n_frames < 0 || n_frames > INT32_MAX || !n_live || (n_frames > 0 && !iq)) return PSS_E_ARG;
+    *n_live = pss_live::live_frames(iq, n_frames, n, live, live_idx);
+    return PSS_OK;
+}
+
+extern "C" int pss_live_frames(pss_ctx *ctx, const float *d_iq, long n_frames, int n, uint8_t *d_live, int32_t *d_live_idx, long *n_live)
+{
+    if (!ctx) return PSS_E_ARG;
+    PSS_GUARD(ctx);
+    if (n < 1 || n_frames < 0 || n_frames > INT32_MAX || !n_live || (n_frames > 0 && !d_iq))
+        return pss_fail(ctx, PSS_E_ARG, "pss_live_frames: n < 1, a frame count outside [0, 2^31), or a null d_iq / n_live");
+    if (n_frames == 0) {
+        *n_live = 0;
+        return PSS_OK;
+    }
+    if (reinterpret_cast<uintptr_t>(d_iq) % 8) return pss_fail(ctx, PSS_E_ARG, "pss_live_frames: d_iq is not aligned to one complex64 sample (8 bytes)");
+    const long n_tiles = (n_frames + GATE_TILE - 1) / GATE_TILE;
+    const size_t tiles_b = (sizeof(GateResult) + (size_t)n_tiles * sizeof(int) + 15) & ~(size_t)15;
+    void *buf;
+    int r = sq_buffer(ctx, 0, tiles_b + (d_live ? 0 : (size_t)n_frames), "gate scratch", &buf);   // the flags, if the caller keeps none
+    if (r) return r;
+    if (!ctx->sq_pin) PSS_HIP(ctx, hipHostMalloc(&ctx->sq_pin, sizeof(GateResult), hipHostMallocDefault));
+    GateResult *d_res = reinterpret_cast<GateResult *>(buf);
+    int *tiles = reinterpret_cast<int *>(d_res + 1);
+    uint8_t *flags = d_live ? d_live : reinterpret_cast<uint8_t *>(buf) + tiles_b;
+    const uint32_t *words = reinterpret_cast<const uint32_t *>(d_iq);
+    const dim3 grid((unsigned)(n_tiles < 4096 ? n_tiles : 4096));
+    {
+        PssTimeScope timed(ctx);
+        pss_kernel_begin(ctx, "k_live_flags");
+        if (n <= LIVE_WAVE_MAX_N) {
+            const long groups = (n_frames + 3) / 4;
+            hipLaunchKernelGGL(k_live_flags<64>, dim3((unsigned)(groups < 8192 ? groups : 8192)), dim3(256), 0, PSS_STREAM(ctx), words, n_frames, n, flags);
+        } else {
+            hipLaunchKernelGGL(k_live_flags<256>, dim3((unsigned)(n_frames < 4096 ? n_frames : 4096)), dim3(256), 0, PSS_STREAM(ctx), words, n_frames, n, flags);
+        }
+        pss_kernel_end(ctx);
+        pss_kernel_begin(ctx, "k_flag_count");
+        hipLaunchKernelGGL(k_flag_count, grid, dim3(256), 0, PSS_STREAM(ctx), flags, n_frames, tiles, n_tiles);
+        pss_kernel_end(ctx);
+        pss_kernel_begin(ctx, "k_gate_scan");   // the squelch gate's prefix sum; every = 0: it reads no peak
+        hipLaunchKernelGGL(k_gate_scan, dim3(1), dim3(256), 0, PSS_STREAM(ctx), tiles, n_tiles, static_cast<const double *>(nullptr), n_frames, 0, 0L, 0.0, d_res);
+        pss_kernel_end(ctx);
+        if (d_live_idx) {
+            pss_kernel_begin(ctx, "k_flag_index");
+            hipLaunchKernelGGL(k_flag_index, grid, dim3(256), 0, PSS_STREAM(ctx), flags, n_frames, tiles, n_tiles, d_live_idx);
+            pss_kernel_end(ctx);
+        }
+    }
+    r = pss_hip_check(ctx, hipGetLastError(), "live frames launch");
+    if (r) return r;
+    // as in pss_squelch_gate: the count reaches the host through 16 pinned bytes and one stream synchronisation
+    PSS_HIP(ctx, hipMemcpyAsync(ctx->sq_pin, d_res, sizeof(GateResult), hipMemcpyDeviceToHost, PSS_STREAM(ctx)));
+    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));
+    *n_live = reinterpret_cast<const GateResult *>(ctx->sq_pin)->n_open;
+    return PSS_OK;
 }
 
 // One loop iteration per read buffer WITH the squelch: the display half of pss_frame_pipeline_cells (pss_spectrum_cells: the same kernels), the

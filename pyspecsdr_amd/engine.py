@@ -32,6 +32,8 @@ def _ptr(x):
 # the batched steps' `display` argument and the reference's history length of each view (pyspecsdr.py:130-131, :151-152, :1648)
 _DISPLAYS = {"waterfall": 0, "persistence": 1, "gradient": 2}
 _WINDOWS = (30, 10, 30)
+# pss_h_stream_frames' `view`: the three display codes, then the views without a history (current_display_mode, pyspecsdr.py:167)
+_VIEWS = {"waterfall": 0, "persistence": 1, "gradient": 2, "spectrum": 3, "surface": 4, "vector": 5}
 
 
 # Read buffers as ADC codes (include/pss.h "ADC codes"): name -> (container, scale, offset), the four grids of tests/adc_cases.GRIDS.
@@ -818,6 +820,91 @@ class Engine:
         self._ck(self.lib.pss_h_stream_spectrum_nfm(self.h, _ptr(h_iq), nf, n, float(fs), int(chunk_frames),
                                                      _ptr(h_db), _ptr(h_pcm)))
         return h_db, h_pcm
+
+    # -- replaying a capture (include/pss.h "replaying a capture"): dead reads, and the main loop on a host recording
+    def live_frames(self, d_iq, n_frames, n, d_live=None, d_live_idx=None):
+        """The loop's first test on every read buffer (pyspecsdr.py:2237): d_live uint8 [n_frames] = not np.all(frame == 0), decided on the
+        bits; d_live_idx int32 [n_frames]: the live frames in ascending order -> n_live.  Waits for the count like squelch_gate."""
+        n_live = C.c_long()
+        self._dev(self.lib.pss_live_frames, _ptr(d_iq), n_frames, n, _ptr(d_live), _ptr(d_live_idx), C.byref(n_live))
+        return n_live.value
+
+    @staticmethod
+    def h_live_frames(frames, lib=None):
+        """pss_h_live_frames on a host array complex64 [n_frames][n] -> (live uint8 [n_frames], live_idx int32 [n_live]).  Pure host code:
+        needs the library, not a GPU."""
+        frames = np.ascontiguousarray(frames, np.complex64)
+        if frames.ndim != 2 or frames.shape[1] < 1:
+            raise ValueError("frames: complex64 [n_frames][n], n >= 1")
+        nf, n = frames.shape
+        live, idx, n_live = np.empty(nf, np.uint8), np.empty(nf, np.int32), C.c_long()
+        r = (lib or L.load()).pss_h_live_frames(_ptr(frames), nf, n, _ptr(live), _ptr(idx), C.byref(n_live))
+        if r != 0:
+            raise PssError(r, "pss_h_live_frames: bad argument")
+        return live, idx[:n_live.value].copy()
+
+    def stream_frames(self, h_in, fs, chunk_frames, mode=L.MODE_WFM, view="spectrum", fmt=None, table=None, skip_dead=True, squelch=None,
+                      meter_every=3, phase=0, peak_power=0.0, window=None, disp_h=36, disp_w=112, halo=None, want_db=False, out=None):
+        """pss_h_stream_frames: a host capture played as the main loop would — complex64 [n_frames, n], or with fmt (a name of IQ_FORMATS /
+        a (container, scale, offset); table as unpack_iq) ADC codes [n_frames, n, 2]; pinned_empty arrays overlap copy and compute.
+        view: "waterfall", "persistence", "gradient" (window: the history, default 30 / 10 / 30; halo = (lo, hi) float64), "spectrum"
+        (disp_h, disp_w), "surface" (disp_w = max_w - 8) or "vector" (disp_h = max_h, disp_w = max_w).  skip_dead: all-zero read buffers are
+        skipped as the reference's loop skips them.  squelch: a level in dB (None: every live buffer is demodulated), metered every
+        meter_every-th live buffer from `phase`, starting from peak_power.
+        Returns a dict trimmed to the live / open buffers: live, n_live, n_open, held_out, phase_out, pcm, db (want_db), the view's outputs
+        (lines + row_lo / row_hi; height, level, range; mag, range; mask) and, with a squelch, peak, avg, open.  out: a previous call's
+        dict with its untrimmed arrays under "buffers" to write into again (keeps pinned outputs)."""
+        v = _VIEWS[view] if isinstance(view, str) else int(view)
+        iq = None if fmt is None else _iq_args(fmt, table)
+        if iq is None:
+            assert h_in.dtype == np.complex64 and h_in.ndim == 2 and h_in.flags.c_contiguous
+        else:
+            h_in = _iq_codes(h_in, iq[0])
+            assert h_in.ndim == 3
+        nf, n = h_in.shape[:2]
+        if window is None:
+            window = _WINDOWS[v] if v <= 2 else 0
+        n_out = max(self.demod_out_len(int(mode), n, fs), 0)   # a rate the demodulator rejects: the call reports it
+        gated = squelch is not None
+        words = (int(disp_w) + 31) // 32
+        shapes = {"live": ((nf,), np.uint8), "pcm": ((nf, n_out, 2), np.int16)}
+        if want_db:
+            shapes["db32"] = ((nf, n), np.float32)
+        if v <= 2:
+            shapes.update(line_a=((nf, disp_w), np.int8), row_lo=((nf,), np.float64), row_hi=((nf,), np.float64))
+            if v != 1:
+                shapes["line_b"] = ((nf, disp_w), np.int8)
+        elif v == 3:
+            shapes.update(height=((nf, disp_w), np.int8), level=((nf, disp_w), np.int8), range=((nf, 2), np.float64))
+        elif v == 4:
+            shapes.update(mag=((nf, disp_w), np.int8), range=((nf, 2), np.float64))
+        elif v == 5:
+            shapes["mask"] = ((nf, max(int(disp_h), 0), words), np.uint32)
+        if gated:
+            shapes.update(peak=((nf,), np.float64), avg=((nf,), np.float64), open=((nf,), np.uint8))
+        buf = out["buffers"] if out is not None else {k: np.empty(s, dt) for k, (s, dt) in shapes.items()}
+        for k, (s, dt) in shapes.items():
+            assert buf[k].shape == s and buf[k].dtype == dt and buf[k].flags.c_contiguous, f"out: {k} must be {dt.__name__} {s}"
+        hl = hh = None
+        if halo is not None and len(halo[0]):
+            hl, hh = np.ascontiguousarray(halo[0], np.float64), np.ascontiguousarray(halo[1], np.float64)
+        req = L.StreamReq(size=C.sizeof(L.StreamReq), container=-1 if iq is None else iq[0], h_in=_ptr(h_in),
+                          h_table256=None if iq is None else _ptr(iq[2]), scale=0.0 if iq is None else iq[1], n_frames=nf,
+                          chunk_frames=int(chunk_frames), fs=float(fs), n=n, mode=int(mode), view=v, window=int(window), disp_h=int(disp_h),
+                          disp_w=int(disp_w), h_halo_lo=_ptr(hl), h_halo_hi=_ptr(hh), n_halo=0 if hl is None else len(hl), skip_dead=int(bool(skip_dead)),
+                          squelch=float(squelch) if gated else float("nan"), held_in=float(peak_power), every=int(meter_every) if gated else 0,
+                          phase=int(phase) if gated else 0)
+        res = L.StreamRes(size=C.sizeof(L.StreamRes), **{k: _ptr(a) for k, a in buf.items()})
+        self._ck(self.lib.pss_h_stream_frames(self.h, C.byref(req), C.byref(res)))
+        nl, no = res.n_live, res.n_open
+        d = {"buffers": buf, "live": buf["live"], "n_live": nl, "n_open": no, "held_out": res.held_out, "phase_out": res.phase_out,
+             "pcm": buf["pcm"][:no], "db": buf["db32"][:nl] if want_db else None}
+        for k in ("row_lo", "row_hi", "height", "level", "mag", "range", "mask", "peak", "avg", "open"):
+            if k in buf:
+                d[k] = buf[k][:nl]
+        if v <= 2:
+            d["lines"] = (buf["line_a"][:nl],) if v == 1 else (buf["line_a"][:nl], buf["line_b"][:nl])
+        return d
 
     # -- host convenience (single frame, synchronous)
     def h_compute_fft(self, iq):

@@ -287,6 +287,58 @@ def demodulate_recording(samples, sample_rate, mode='NFM', frame_len=32768, chun
     return pcm, opened, peak, avg
 
 
+# display width = screen width - offset, display height = screen height - 4: the layouts of draw_waterfall / draw_persistence (pyspecsdr.py
+# :1342, :1512), draw_gradient_waterfall (:1640), draw_spectrogram (:399); the surface plot resamples to max_width - 8 (:1571) and draws on
+# the whole screen, as the constellation does (:1719)
+_VIEW_OFFSETS = {'waterfall': 8, 'persistence': 8, 'gradient': 10, 'spectrum': 7, 'surface': 8}
+
+
+def view_geometry(view, screen):
+    """(disp_h, disp_w) as Engine.stream_frames takes them for `view` on a screen of (max_height, max_width) cells."""
+    max_h, max_w = int(screen[0]), int(screen[1])
+    if view == 'vector':
+        return max_h, max_w
+    if view not in _VIEW_OFFSETS:
+        raise ValueError(f"unknown view {view!r}")
+    return max_h - 4, max_w - _VIEW_OFFSETS[view]
+
+
+def replay_recording(samples, sample_rate, mode='WFM', view='spectrum', frame_len=32768, chunk_frames=256, squelch=-60, codes_format=None,
+                     table=None, screen=(40, 120), meter_every=3, peak_power=0.0, cells=False):
+    """A recording played as the reference's main loop would play it, with the reference's defaults (WFM, the SPECTRUM view, SQUELCH -60,
+    pyspecsdr.py:2855, :167, :171): cut into read buffers (cut_frames), all-zero buffers skipped (:2237), every live buffer's view drawn and
+    its audio gated by the squelch (None: no gate) -> Engine.stream_frames' dict, everything per buffer compacted to the live ones.
+    samples: the 1-D complex64 recording, or with codes_format (a name of IQ_FORMATS) its ADC code array [n, 2] (load_iq_codes; table as
+    unpack_iq).  screen: (max_height, max_width) of the terminal; the view's display size follows as the draw functions derive it
+    (view_geometry).  cells=True adds "cells": the expanded grids of the views that return a compact form (bars_cells -> (glyph, colour),
+    surface_cells, vector_cells)."""
+    if mode not in _MODES:
+        raise ValueError(f"unknown demodulation mode {mode!r}")
+    disp_h, disp_w = view_geometry(view, screen)
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+        nfr = len(samples) // frame_len
+        frames = np.ascontiguousarray(samples[:nfr * frame_len]).reshape(nfr, frame_len, 2)
+    else:
+        frames = np.ascontiguousarray(cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len))
+    fs = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(sample_rate)
+    if mode != 'AM':
+        _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), fs)
+    out = get_engine().stream_frames(frames, fs, chunk_frames, mode=_MODES[mode], view=view, fmt=codes_format, table=table, skip_dead=True,
+                                     squelch=squelch, meter_every=meter_every, peak_power=peak_power, disp_h=disp_h, disp_w=disp_w)
+    if cells:
+        if view == 'spectrum':
+            out["cells"] = bars_cells(out["height"], out["level"], disp_h)
+        elif view == 'surface':
+            out["cells"] = surface_cells(out["mag"], screen[0], screen[1])
+        elif view == 'vector':
+            out["cells"] = vector_cells(out["mask"], screen[0], screen[1])
+    return out
+
+
 def _decode_args(sample_rate, decoder, frame_len, chunk_frames):
     """decode_recording's argument checks (host only: made before anything touches the GPU) -> (sample_rate, frame_len, chunk_frames)."""
     if decoder not in ('morse', 'aprs'):
