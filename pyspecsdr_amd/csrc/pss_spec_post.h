@@ -75,14 +75,33 @@ __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restri
         const __amdgpu_buffer_rsrc_t ro64 = make_rsrc((ROW64 && db64) ? db64 + (size_t)f_first * N : nullptr, (ROW64 && db64) ? (unsigned)(rows_here * N * 8) : 0u);
         const int lane_el = fl * N + t;
         double dbv[16];
-        auto emit = [&](int i, int k, double2 X) {
-            const double d64 = db64_of_exact(power_of(X));
-            const int e0 = ((k - t) + N / 2) & (N - 1);        // fftshift; compile-time constant per call
-            if constexpr (ROW64) buf_store_f64(ro64, lane_el * 8, e0 * 8, d64);
-            if constexpr (ROW32) buf_store_f32(ro32, lane_el * 4, e0 * 4, (float)d64);
-            dbv[i] = d64;
+        unsigned hmax = 0;                                     // largest high word of the lane's 16 powers: +inf / NaN are tested once per frame
+        auto emit = [&](int i, int, double2 X) {                // (the bin index: the stores below derive it from i)
+            const double pw = power_of(X);
+            hmax = max(hmax, db_hi32(pw));
+            dbv[i] = db64_core(pw);
         };
         r16_core<2, true>(v, ex, tw1, tw2, t, emit);
+        if (__builtin_amdgcn_ballot_w64(hmax >= DB_HI_NONFINITE) != 0) {
+            // A frame with a +inf or NaN power (wave-uniform; never taken for real samples).  db64_core has made finite numbers of those bins, all
+            // beyond +-DB_FINITE_LIMIT where no finite power of a complex64 frame lands: +inf -> DB_NONFINITE_IMAGE exactly, a NaN (quiet, as
+            // every NaN that arithmetic produced: mantissa >= 1.5) -> above it with the sign bit clear, below -DB_FINITE_LIMIT with it set.  They
+            // become the power again — +inf, or the quiet NaN of that sign — before the rows are stored and the 16 values handed on.
+            // (A second transform of the frame with the per-value test instead costs this kernel 44 bytes of scratch per lane.)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const double d = dbv[i];
+                const double nonfinite = d == DB_NONFINITE_IMAGE ? __builtin_inf() : __builtin_copysign(__builtin_nan(""), d);
+                dbv[i] = __builtin_fabs(d) < DB_FINITE_LIMIT ? d : nonfinite;
+            }
+        }
+        // the row stores after the transform, in one run: the evaluation's table reads do not queue behind them (loads and stores share one counter)
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            const int e0 = ((256 * (i % R3) + T * (i / R3)) + N / 2) & (N - 1);      // fftshift; bin k = 256 j1 + t + T c of value i = c R3 + j1
+            if constexpr (ROW64) buf_store_f64(ro64, lane_el * 8, e0 * 8, dbv[i]);
+            if constexpr (ROW32) buf_store_f32(ro32, lane_el * 4, e0 * 4, (float)dbv[i]);
+        }
         frame_sync<true>();                                    // every lane has read its stage-3 operands: the exchange buffer is free
         // the row into k_post_sel's staging layout: element e (after fftshift) at stage[(e / EPL) * S + e % EPL]
 #pragma unroll
