@@ -228,6 +228,12 @@ static void csum_f32(const float *x, long n, float *rr, float *ri) /* n complex 
         *rr += cr; *ri += ci;
     }
 }
+/* np.add.reduce of n complex64 elements -> out2 = (real, imag): the tree above, exported for the tests that sweep it over lengths */
+void pss_o_csum_f32(const float *x, long n, float *out2)
+{
+    out2[0] = 0.0f; out2[1] = 0.0f;
+    if (n > 0) csum_f32(x, n, &out2[0], &out2[1]);
+}
 /* np.var(complex64 array) -> float32 (numpy _methods._var): mean = add.reduce / n (true_divide), x = arr - mean, then the
  * fast path for built-in complex types: view as float pairs, square every float, add the two squares (three separately
  * rounded float32 operations, no fused multiply-add), ret = add.reduce(.) / n.  (Found by fuzzing against the reference:

@@ -25,6 +25,7 @@ float pss_o_rcp14f(float x);                 /* VRCP14PS, bit-exact model (64-en
 float pss_o_atan2f(float y, float x);        /* numpy.arctan2 float32 == Intel SVML __svml_atan2f16 (la)     */
 float pss_o_cabsf(float re, float im);       /* numpy.abs(complex64)                                          */
 float pss_o_pairwise_sum_f32(const float *a, long n); /* numpy add.reduce float32 (8192-element chunks, pairwise inside) */
+void pss_o_csum_f32(const float *x, long n, float *out2);  /* numpy add.reduce complex64 (n complex elements, interleaved) -> (re, im) */
 float pss_o_log10f_np(float x);              /* np.log10 float32 (SVML __svml_log10f16 model, bit-pinned: tests/golden/log10f.npz) */
 void pss_o_log10f_np_many(const float *x, float *y, long n);
 void pss_o_atan2f_many(const float *y, const float *x, float *out, long n);

@@ -143,7 +143,8 @@ __global__ __launch_bounds__(FIR_T) void k_nfm_front(const float2 *__restrict__ 
         }
         __syncthreads();
         // right odd extension (scipy _arraytools.odd_ext): ext[27+M+k] = 2u[M-1] - u[M-2-k]; only when the last
-        // 28 outputs of the frame all have full windows (M - 28 >= 64) and live in this work item
+        // 28 outputs of the frame all have full windows (M - 28 >= 64) and live in this work item (where they straddle two,
+        // k_nfm_edge writes it)
         if (M - 1 - EDGE >= 64 && i0 + FIR_CH >= M && i0 <= M - 1 - EDGE && tid < EDGE)
             Uf[EDGE + M + tid] = __dsub_rn(__dmul_rn(2.0, edge[EDGE]), edge[EDGE - 1 - tid]);
     }
@@ -186,6 +187,13 @@ __global__ __launch_bounds__(128) void k_nfm_edge(const float2 *__restrict__ iq,
     if (M < 92 && tid >= 32 && tid < 32 + EDGE) {
         const int k = tid - 32;
         Uf[EDGE + M + k] = __dsub_rn(__dmul_rn(2.0, u[M - 1]), u[M - 2 - k]);
+    }
+    // M mod FIR_CH in 1..27 (M > FIR_CH): the frame's last 28 outputs straddle two work items of k_nfm_front, so neither of them held
+    // all of u[M-28..M-1] and the right extension is still unwritten.  k_nfm_front has finished (this kernel follows it on the stream):
+    // the same two operations on its outputs read back.
+    if (M >= 92 && (M - 1) / FIR_CH * FIR_CH > M - 1 - EDGE && tid >= 32 && tid < 32 + EDGE) {
+        const int k = tid - 32;
+        Uf[EDGE + M + k] = __dsub_rn(__dmul_rn(2.0, Uf[EDGE + M - 1]), Uf[EDGE + M - 2 - k]);
     }
 }
 

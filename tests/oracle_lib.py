@@ -41,6 +41,7 @@ def lib():
         L.pss_o_cabsf.argtypes = [C.c_float, C.c_float]
         L.pss_o_pairwise_sum_f32.restype = C.c_float
         L.pss_o_pairwise_sum_f32.argtypes = [_f32p, C.c_long]
+        L.pss_o_csum_f32.restype, L.pss_o_csum_f32.argtypes = None, [_f32p, C.c_long, _f32p]
         L.pss_o_cabs.restype, L.pss_o_cabs.argtypes = C.c_double, [C.c_double, C.c_double]
         L.pss_o_compute_fft.argtypes = [_f32p, C.c_int, _f64p]
         L.pss_o_postprocess.argtypes = [_f64p, C.c_int, _f64p]
@@ -126,6 +127,19 @@ def cabsf(re, im):
     out = np.empty_like(re)
     lib().pss_o_cabsf_many(re, im, out, re.size)
     return out
+
+
+def pairwise_sum_f32(a):
+    """np.add.reduce of a float32 array (NumPy's pairwise tree in 8192-element chunks)."""
+    a = np.ascontiguousarray(a, np.float32)
+    return np.float32(lib().pss_o_pairwise_sum_f32(a, a.size))
+
+
+def csum_f32(x):
+    """np.add.reduce of a complex64 array (the tree over the interleaved floats, chunks of 8192 complex elements)."""
+    out = np.empty(2, np.float32)
+    lib().pss_o_csum_f32(_iq(x), len(x), out)
+    return out.view(np.complex64)[0]
 
 
 def compute_fft(iq):

@@ -2,11 +2,38 @@
 """Fuzz the C oracle against the reference itself (build container only: needs /root/reference): random frames of random
 lengths, signal kinds and sample rates through NFM / AM / WFM / iq_correction / power, bit for bit.
     python tools/fuzz_oracle_vs_reference.py        # prints the case counts and the number of mismatches
-A run of 240 cases per function found the np.var form used by iq_correction (squares + add, no FMA); clean since."""
+    python tools/fuzz_oracle_vs_reference.py --lengths   # sweep mode: walks tests/length_cases.py's lists instead of drawing lengths
+A run of 240 cases per function found the np.var form used by iq_correction (squares + add, no FMA); clean since.
+Sweep mode: demodulate_ssb (USB and LSB, 2.4 MS/s and 48 kS/s) and demodulate_am at every length of AM_SSB_LENGTHS, one frame each: frames equal
+bit for bit, frames within 2e-14 (the oracle skips hilbert() at lengths that are no power of two), int16 equal, and the lengths at which the
+reference raises (the exception type the engine then has to raise).  profiles/length_sweep.txt keeps the counts."""
 import sys, warnings; sys.path.insert(0,'/root/reference'); import os; sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests')); sys.dont_write_bytecode=True
 import numpy as np, signal_processing as sp, scipy.signal as ss
 import oracle_lib as O
 warnings.simplefilter('ignore')
+def sweep_lengths():
+    import length_cases as LC
+    am_sos = ss.butter(5, [300 / 11025, 3000 / 11025], btype='band', output='sos')
+    for mode, fs in [('USB', 2.4e6), ('LSB', 2.4e6), ('USB', 48e3), ('LSB', 48e3), ('AM', 2.4e6)]:
+        taps = ss.firwin(65, 3000 / fs, window='hamming')
+        c = dict(lengths=0, bit_equal=0, within_2e14=0, beyond_2e14=0, int16_differs=0, reference_raised=[])
+        for n in LC.AM_SSB_LENGTHS:
+            x = (LC.iq_frames if mode == 'AM' else LC.fm_frames)(1, n, seed=2)[0]
+            c['lengths'] += 1
+            try:
+                ref = sp.demodulate_signal(x, fs, mode)[:, 0]
+            except Exception as ex:
+                c['reference_raised'].append((n, type(ex).__name__))
+                continue
+            got = O.demod_am(x, am_sos) if mode == 'AM' else O.demod_ssb(x, taps)
+            if np.array_equal(ref.view(np.uint64), got.view(np.uint64)) or np.array_equal(ref, got, equal_nan=True): c['bit_equal'] += 1
+            elif np.allclose(got, ref, rtol=0, atol=2e-14, equal_nan=True): c['within_2e14'] += 1
+            else: c['beyond_2e14'] += 1; print(mode, fs, n, 'max |diff|', np.nanmax(np.abs(ref - got)))
+            pr = np.where(np.isnan(ref), 0.0, np.trunc(ref * 32767)).astype(np.int32).astype(np.int16)
+            if not np.array_equal(O.pcm16_stereo(got)[:, 0], pr): c['int16_differs'] += 1; print(mode, fs, n, 'int16 differs')
+        print(f'oracle vs reference, demodulate_signal(..., {mode!r}) at {fs:g} S/s over AM_SSB_LENGTHS:', c)
+if '--lengths' in sys.argv:
+    sweep_lengths(); sys.exit(0)
 rng=np.random.default_rng(int(os.environ.get("FUZZ_SEED", "2026")))
 def rnd_iq(n):
     kind=rng.integers(0,4)
