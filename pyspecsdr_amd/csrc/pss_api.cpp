@@ -153,8 +153,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     for (auto &kv : ctx->win) hipFree(kv.second);
     for (auto &kv : ctx->bs) { hipFree(kv.second.d_chirp); hipFree(kv.second.d_B); hipFree(kv.second.d_win); }
     for (auto &kv : ctx->plans) {
-        hipFree(kv.second.d_leaf_off); hipFree(kv.second.d_leaf_len); hipFree(kv.second.d_node_l);
-        hipFree(kv.second.d_node_r); hipFree(kv.second.d_level_start); hipFree(kv.second.d_roots);
+        hipFree(kv.second.d_tab);
     }
     for (auto &kv : ctx->nfm) if (kv.second.d_rev) hipFree(kv.second.d_rev);
     if (ctx->scratch) hipFree(ctx->scratch);

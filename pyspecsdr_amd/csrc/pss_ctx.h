@@ -22,11 +22,10 @@ struct PssWfmFilt {
     double alpha;                       // de-emphasis pole exp(-1/(75e-6 fs))
 };
 
-struct PssPairwisePlan {  // numpy pairwise-sum tree for one frame length (see pss_demod.hip)
+struct PssPairwisePlan {  // numpy pairwise-sum forest of one group length (pss_npsum.h: Forest; uploaded by get_plan of pss_demod.hip)
     int n_leaves = 0, n_nodes = 0, n_levels = 0, n_roots = 0;
-    int wave_tree = 0;  // 64 (leaf, accumulator) pairs and a perfectly balanced tree over equal leaves: one wavefront can fold it with xor shuffles
-    int *d_leaf_off = nullptr, *d_leaf_len = nullptr, *d_node_l = nullptr, *d_node_r = nullptr, *d_level_start = nullptr;
-    int *d_roots = nullptr;
+    int wave_tree = 0;  // Forest::wave_tree: one wavefront can fold it with xor shuffles
+    int *d_tab = nullptr;  // ONE device allocation: leaf_off, leaf_len, node_l, node_r, level_start, roots back to back (PlanDev points into it)
 };
 
 struct pss_ctx {

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "pss_ctx.h"
+#include "pss_npsum.h"
 
 namespace {
 
@@ -43,38 +44,6 @@ const char *morse_lookup(const std::string &s)
     for (const auto &e : MORSE)
         if (s == e.sym) return e.txt;
     return nullptr;
-}
-
-// np.add.reduce over contiguous float64: 8192-element chunks added in order, inside a chunk NumPy's pairwise tree (8 accumulators, blocks
-// of 128, halves rounded down to multiples of 8) — what np.mean(gaps) sums with
-double pairwise_chunk(const double *a, long n)
-{
-    if (n < 8) {
-        double r = 0.0;
-        for (long i = 0; i < n; i++) r += a[i];
-        return r;
-    }
-    if (n <= 128) {
-        double r[8];
-        long i;
-        for (int j = 0; j < 8; j++) r[j] = a[j];
-        for (i = 8; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    long n2 = n / 2;
-    n2 -= n2 % 8;
-    return pairwise_chunk(a, n2) + pairwise_chunk(a + n2, n - n2);
-}
-double np_sum(const double *a, long n)
-{
-    const long B = 8192;
-    if (n <= B) return pairwise_chunk(a, n);
-    double acc = pairwise_chunk(a, B);
-    for (long st = B; st < n; st += B) acc += pairwise_chunk(a + st, (n - st) < B ? (n - st) : B);
-    return acc;
 }
 
 // The two pulse classes: every split of the sorted lengths that one Lloyd step maps to itself, best mean |x - c| first.
@@ -163,7 +132,7 @@ extern "C" int pss_h_morse_decode(const int32_t *rise, long n_rise, const int32_
     if (!letter.empty()) flush();
     timing3[0] = dot;
     timing3[1] = dash;
-    timing3[2] = gap.empty() ? 0.0 : np_sum(gap.data(), (long)gap.size()) / (double)gap.size();
+    timing3[2] = gap.empty() ? 0.0 : pss_np::np_sum(gap.data(), (long)gap.size()) / (double)gap.size();
     if ((long)out.size() + 1 > text_cap) return PSS_E_ARG;
     memcpy(text, out.c_str(), out.size() + 1);
     return (int)out.size();

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include "pss_ctx.h"
+#include "pss_npsum.h"
 
 namespace {
 
@@ -37,63 +38,12 @@ struct Pulses {
     __device__ double gap(int i) const { return (double)((long long)rise[i + 1] - (long long)fall[i]) / fs; }
 };
 
-// np.add.reduce over the np_ - 1 gaps: 8192-element chunks in order; inside a chunk NumPy's pairwise tree (halves rounded down to multiples
-// of 8, blocks of <= 128 with 8 accumulators) — pairwise_chunk / np_sum of pss_decode.cpp, the recursion unrolled onto an explicit stack
-// (a chunk of 8192 splits at most 7 times).  One lane.
-__device__ double gap_leaf(const Pulses &p, int a, int n)
-{
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; i++) r += p.gap(a + i);
-        return r;
-    }
-    double r[8];
-    int i;
-    for (int j = 0; j < 8; j++) r[j] = p.gap(a + j);
-    for (i = 8; i < n - (n % 8); i += 8)
-        for (int j = 0; j < 8; j++) r[j] += p.gap(a + i + j);
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; i++) res += p.gap(a + i);
-    return res;
-}
-__device__ double gap_chunk(const Pulses &p, int a, int n)
-{
-    // post-order walk: `pend` holds the right halves still to be summed, `val` the sums of the left halves waiting for them
-    int pa[16], pn[16], depth_at[16], sp = 0, vp = 0, depth = 0;
-    double val[16];
-    int vdepth[16];
-    double acc = 0.0;
-    for (;;) {
-        while (n > 128) {   // descend to the leftmost leaf, remembering the right halves
-            int n2 = n / 2;
-            n2 -= n2 % 8;
-            pa[sp] = a + n2, pn[sp] = n - n2, depth_at[sp] = depth + 1, sp++;
-            n = n2;
-            depth++;
-        }
-        acc = gap_leaf(p, a, n);
-        // a right half just finished at `depth` joins the left half waiting at the same depth
-        while (vp > 0 && vdepth[vp - 1] == depth) {
-            acc = val[vp - 1] + acc;
-            vp--;
-            depth--;
-        }
-        if (sp == 0) return acc;
-        // acc is a left half at `depth`: park it, go to its right sibling
-        val[vp] = acc, vdepth[vp] = depth, vp++;
-        sp--;
-        a = pa[sp], n = pn[sp], depth = depth_at[sp];
-    }
-}
+// np.add.reduce over the np_ - 1 gaps (pss_npsum.h; np.mean(gaps) of pss_decode.cpp).  One lane.
 // (not inlined: one lane runs it once per frame, and inlined its 8 accumulators and divisions cost k_morse_text 52 spilled VGPRs and
 // three quarters of its occupancy)
-__device__ __attribute__((noinline)) double gap_sum(const Pulses &p, int n)
+__device__ __attribute__((noinline)) double gap_sum(Pulses p, int n)   // by value: three registers, no stack object in the kernel
 {
-    const int B = 8192;
-    if (n <= B) return gap_chunk(p, 0, n);
-    double acc = gap_chunk(p, 0, B);
-    for (int st = B; st < n; st += B) acc += gap_chunk(p, st, (n - st) < B ? (n - st) : B);
-    return acc;
+    return pss_np::np_sum<8, double>([&](int i) { return p.gap(i); }, n);
 }
 
 // (dist, threshold) order of two_classes: the smaller mean distance, equal distances keep the smaller threshold

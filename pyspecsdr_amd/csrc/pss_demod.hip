@@ -17,11 +17,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <type_traits>
-#include <functional>
 #include <vector>
 
 #include "pss_ctx.h"
 #include "pss_device.h"
+#include "pss_npsum.h"
 
 namespace {
 
@@ -360,11 +360,10 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // numpy float32 pairwise mean of |x| (KIND 1, AM: signal_processing.py:185) or |x|^2 (KIND 0, power: :327).
-// The reduction tree (8192-element chunks added sequentially; inside a chunk: block 128, 8 accumulators, halves
-// rounded down to multiples of 8) is generated on the host for the frame length and replayed level by level; one
+// The reduction tree (pss_npsum.h) is generated on the host for the frame length and replayed level by level; one
 // workgroup per frame.
 // ---------------------------------------------------------------------------------------------------
-// (k_pairwise itself follows the shared reduction helpers further down)
+// (k_pairwise itself follows further down)
 
 // ---------------------------------------------------------------------------------------------------
 // AM: envelope - mean (float32) -> 5-section Butterworth band-pass, forward only, zero state (float64): k_am_grp below.
@@ -935,231 +934,19 @@ __global__ __launch_bounds__(TPB) void k_finalize(const double *__restrict__ Yf,
 // One workgroup per frame.  The routine is a chain of eight float32 reductions whose results feed the next
 // elementwise step; each reduction walks numpy's own summation tree (PssPairwisePlan) so every intermediate scalar
 // has numpy's bits.  The frame (8 KB at n=1024) is re-read from L1/L2 per pass; intermediates are recomputed.
-struct PlanDev {
-    const int *leaf_off, *leaf_len, *node_l, *node_r, *level_start, *roots;
-    int n_leaves, n_levels, n_roots, n_nodes;
-    int wave_tree;  // see PssPairwisePlan::wave_tree
-};
-// The plan tables are walked with DEPENDENT loads several times per reduction (offsets -> elements, one round per tree
-// level): read from global memory that was ~8 us per pass and dominated k_iqcorr (8 passes per frame).  Every workgroup
-// copies the tables it needs into LDS once and works from there.
-__device__ __forceinline__ int plan_ints(const PlanDev &p)
+// (pss_npsum.h: the rule, the tables and the workgroup walker wg_sum / frame_sum — float: a real sum, float2 with 4 accumulators: a
+// complex64 sum, float2 with 8: two real sums over the SAME elements and the SAME real plan in one walk, elem(i) -> (a_i, b_i))
+using pss_np::PlanDev;
+using pss_np::RedPlan;
+using pss_np::plan_to_lds;
+using pss_np::wg_sum;
+using pss_np::frame_sum;
+// np.sum of a float64 array, and of its squares, by ONE lane (k_am_env_c128 / k_power_c128; k_afsk_bits).  Not inlined: inlined, the walk's
+// stacks and accumulators are promoted to registers (k_afsk_bits: 464 VGPRs)
+__device__ __attribute__((noinline)) double np_sum_f64(const double *a, int n) { return pss_np::np_sum(a, n); }
+__device__ __attribute__((noinline)) double np_sum_sq_f64(const double *a, int n)
 {
-    return p.n_leaves ? 2 * p.n_leaves + 2 * p.n_nodes + (p.n_levels + 1) + p.n_roots : 0;
-}
-__device__ __forceinline__ void plan_to_lds(PlanDev &p, int *&cur)
-{
-    if (!p.n_leaves) return;
-    const int tid = threadIdx.x, T = blockDim.x;
-    int *lo = cur, *ll = lo + p.n_leaves, *nl = ll + p.n_leaves, *nr = nl + p.n_nodes, *ls = nr + p.n_nodes, *rt = ls + p.n_levels + 1;
-    for (int i = tid; i < p.n_leaves; i += T) { lo[i] = p.leaf_off[i]; ll[i] = p.leaf_len[i]; }
-    for (int i = tid; i < p.n_nodes; i += T) { nl[i] = p.node_l[i]; nr[i] = p.node_r[i]; }
-    for (int i = tid; i <= p.n_levels; i += T) ls[i] = p.level_start[i];
-    for (int i = tid; i < p.n_roots; i += T) rt[i] = p.roots[i];
-    p.leaf_off = lo; p.leaf_len = ll; p.node_l = nl; p.node_r = nr; p.level_start = ls; p.roots = rt;
-    cur = rt + p.n_roots;
-}
-// A frame is reduced in GROUPS of up to RED_K ufunc chunks (8192 elements each): numpy adds the chunk sums sequentially,
-// sum = ((S0 + S1) + S2) + ..., so a group's plan is a forest (one pairwise tree per chunk) whose roots are added in
-// order onto the running sum.  Frames up to RED_K chunks are one (tail) group; longer ones loop over full groups first —
-// the LDS footprint no longer grows with the frame (1 Mi-sample read buffers, pyspecsdr.py:2236 with SAMPLES = 12).
-struct RedPlan {
-    PlanDev full, tail;
-    int n_full, glen;  // full groups of glen elements each, then the tail group (tail.n_leaves may be 0)
-};
-// A leaf of numpy's tree is <= 128 elements summed into 8 running accumulators; those 8 partial sums are independent,
-// so a lane owns one (leaf, accumulator) pair — at n = 1024 that is exactly one wavefront per frame — and one lane per
-// leaf then folds the 8 partials and the < 8 tail elements in numpy's order.  part: 8 floats per leaf.
-template <bool WT = false, class F>
-__device__ __forceinline__ float wg_rsum(const PlanDev &p, float *part, float *val, F elem, float carry, bool have)
-{
-    const int tid = threadIdx.x, T = blockDim.x;
-    if constexpr (WT) {  // the host guarantees: p.wave_tree, a 64-thread workgroup, a single group (no carry)
-        // n = 1024: 8 leaves x 8 accumulators = the 64 lanes of the one wavefront of this workgroup, and numpy's tree is
-        // perfectly balanced — ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) inside a leaf, adjacent halves above it.  IEEE addition is
-        // commutative, so an xor-butterfly computes exactly those sums (in every lane): no LDS, no barriers.
-        const int lane = tid & 63;  // (in a wider workgroup every wavefront computes the same sums redundantly)
-        const int l = lane >> 3, k = lane & 7, off = l * 128;
-        float r = elem(off + k);
-#pragma unroll
-        for (int i = 8; i < 128; i += 8) r = __fadd_rn(r, elem(off + i + k));
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) r = __fadd_rn(r, __shfl_xor(r, m));
-        return r;
-    }
-    for (int slot = tid; slot < p.n_leaves * 8; slot += T) {
-        const int l = slot >> 3, k = slot & 7, off = p.leaf_off[l], len = p.leaf_len[l];
-        if (len == 128) {
-            // a full leaf: all 16 operands of this accumulator requested before the dependent chain of additions starts (four ahead,
-            // a CU's 2048 threads kept ~64 KB in flight and the pass ran at 3.7 TB/s)
-            float v[16];
-#pragma unroll
-            for (int j = 0; j < 16; j++) v[j] = elem(off + 8 * j + k);
-            float r = v[0];
-#pragma unroll
-            for (int j = 1; j < 16; j++) r = __fadd_rn(r, v[j]);
-            part[slot] = r;
-        } else if (len >= 8) {
-            // the additions are a dependent chain in numpy's order; the operands are not: fetch four ahead of the chain
-            float r = elem(off + k);
-            const int end = len - (len % 8);
-            int i = 8;
-            for (; i + 24 < end; i += 32) {
-                const float a = elem(off + i + k), b = elem(off + i + 8 + k), c = elem(off + i + 16 + k), d = elem(off + i + 24 + k);
-                r = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(r, a), b), c), d);
-            }
-            for (; i < end; i += 8) r = __fadd_rn(r, elem(off + i + k));
-            part[slot] = r;
-        }
-    }
-    __syncthreads();
-    for (int l = tid; l < p.n_leaves; l += T) {
-        const int off = p.leaf_off[l], len = p.leaf_len[l];
-        float res;
-        if (len < 8) {
-            res = 0.0f;
-            for (int i = 0; i < len; i++) res = __fadd_rn(res, elem(off + i));
-        } else {
-            const float *r = part + 8 * l;
-            res = __fadd_rn(__fadd_rn(__fadd_rn(r[0], r[1]), __fadd_rn(r[2], r[3])),
-                            __fadd_rn(__fadd_rn(r[4], r[5]), __fadd_rn(r[6], r[7])));
-            for (int i = len - (len % 8); i < len; i++) res = __fadd_rn(res, elem(off + i));
-        }
-        val[l] = res;
-    }
-    __syncthreads();
-    for (int lv = 0; lv < p.n_levels; lv++) {
-        for (int k = p.level_start[lv] + tid; k < p.level_start[lv + 1]; k += T)
-            val[p.n_leaves + k] = __fadd_rn(val[p.node_l[k]], val[p.node_r[k]]);
-        __syncthreads();
-    }
-    const int res = p.n_leaves + p.level_start[p.n_levels];  // free slot behind the nodes
-    if (tid == 0) {
-        float acc = have ? __fadd_rn(carry, val[p.roots[0]]) : val[p.roots[0]];
-        for (int k = 1; k < p.n_roots; k++) acc = __fadd_rn(acc, val[p.roots[k]]);
-        val[res] = acc;
-    }
-    __syncthreads();
-    const float sum = val[res];
-    __syncthreads();
-    return sum;
-}
-// complex64 reduce: elem(ci) -> float2 of complex element ci; leaves are float ranges of the interleaved array, the 8
-// float accumulators are 4 complex ones: a lane owns one (leaf, complex accumulator) pair.  part: 4 float2 per leaf.
-template <bool WT = false, class F>
-__device__ __forceinline__ float2 wg_csum(const PlanDev &p, float2 *part, float2 *val, F elem, float2 carry, bool have)
-{
-    const int tid = threadIdx.x, T = blockDim.x;
-    if constexpr (WT) {
-        // 1024 complex = 2048 floats: 16 leaves x 4 complex accumulators = 64 lanes; same butterfly as wg_rsum
-        const int lane = tid & 63;
-        const int l = lane >> 2, k = lane & 3, off = l * 64;  // complex offset of the leaf
-        float2 r = elem(off + k);
-#pragma unroll
-        for (int i = 4; i < 64; i += 4) {
-            const float2 v = elem(off + i + k);
-            r.x = __fadd_rn(r.x, v.x);
-            r.y = __fadd_rn(r.y, v.y);
-        }
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            r.x = __fadd_rn(r.x, __shfl_xor(r.x, m));
-            r.y = __fadd_rn(r.y, __shfl_xor(r.y, m));
-        }
-        return r;
-    }
-    for (int slot = tid; slot < p.n_leaves * 4; slot += T) {
-        const int l = slot >> 2, k = slot & 3, off = p.leaf_off[l] >> 1, len = p.leaf_len[l];  // off: complex, len: floats
-        if (len >= 8) {
-            float2 r = elem(off + k);
-            const int end = len - (len % 8);
-            int i = 8;
-            for (; i + 24 < end; i += 32) {  // operands fetched four ahead of the dependent additions
-                const float2 a = elem(off + (i >> 1) + k), b = elem(off + ((i + 8) >> 1) + k), c = elem(off + ((i + 16) >> 1) + k),
-                             d = elem(off + ((i + 24) >> 1) + k);
-                r.x = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(r.x, a.x), b.x), c.x), d.x);
-                r.y = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(r.y, a.y), b.y), c.y), d.y);
-            }
-            for (; i < end; i += 8) {
-                const float2 v = elem(off + (i >> 1) + k);
-                r.x = __fadd_rn(r.x, v.x);
-                r.y = __fadd_rn(r.y, v.y);
-            }
-            part[slot] = r;
-        }
-    }
-    __syncthreads();
-    for (int l = tid; l < p.n_leaves; l += T) {
-        const int off = p.leaf_off[l] >> 1, len = p.leaf_len[l];
-        float rr, ri;
-        if (len < 8) {
-            rr = 0.0f; ri = 0.0f;
-            for (int i = 0; i < len; i += 2) { const float2 v = elem(off + (i >> 1)); rr = __fadd_rn(rr, v.x); ri = __fadd_rn(ri, v.y); }
-        } else {
-            const float2 *r = part + 4 * l;
-            rr = __fadd_rn(__fadd_rn(r[0].x, r[1].x), __fadd_rn(r[2].x, r[3].x));
-            ri = __fadd_rn(__fadd_rn(r[0].y, r[1].y), __fadd_rn(r[2].y, r[3].y));
-            for (int i = len - (len % 8); i < len; i += 2) { const float2 v = elem(off + (i >> 1)); rr = __fadd_rn(rr, v.x); ri = __fadd_rn(ri, v.y); }
-        }
-        val[l] = make_float2(rr, ri);
-    }
-    __syncthreads();
-    for (int lv = 0; lv < p.n_levels; lv++) {
-        for (int k = p.level_start[lv] + tid; k < p.level_start[lv + 1]; k += T) {
-            const float2 a = val[p.node_l[k]], b = val[p.node_r[k]];
-            val[p.n_leaves + k] = make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y));
-        }
-        __syncthreads();
-    }
-    const int res = p.n_leaves + p.level_start[p.n_levels];
-    if (tid == 0) {
-        float2 acc = val[p.roots[0]];
-        if (have) acc = make_float2(__fadd_rn(carry.x, acc.x), __fadd_rn(carry.y, acc.y));
-        for (int k = 1; k < p.n_roots; k++) {
-            const float2 v = val[p.roots[k]];
-            acc = make_float2(__fadd_rn(acc.x, v.x), __fadd_rn(acc.y, v.y));
-        }
-        val[res] = acc;
-    }
-    __syncthreads();
-    const float2 sum = val[res];
-    __syncthreads();
-    return sum;
-}
-// whole-frame reductions: loop over the groups, elem(i) indexed from the start of the frame
-template <bool WT = false, class F>
-__device__ __forceinline__ float frame_rsum(const RedPlan &rp, float *part, float *val, F elem)
-{
-    if constexpr (WT) return wg_rsum<true>(rp.tail, part, val, elem, 0.0f, false);
-    float acc = 0.0f;
-    bool have = false;
-    for (int g = 0; g < rp.n_full; g++) {
-        const int base = g * rp.glen;
-        acc = wg_rsum(rp.full, part, val, [&](int i) { return elem(base + i); }, acc, have);
-        have = true;
-    }
-    if (rp.tail.n_leaves) {
-        const int base = rp.n_full * rp.glen;
-        acc = wg_rsum(rp.tail, part, val, [&](int i) { return elem(base + i); }, acc, have);
-    }
-    return acc;
-}
-template <bool WT = false, class F>
-__device__ __forceinline__ float2 frame_csum(const RedPlan &rp, float2 *part, float2 *val, F elem)
-{
-    if constexpr (WT) return wg_csum<true>(rp.tail, part, val, elem, make_float2(0.0f, 0.0f), false);
-    float2 acc = make_float2(0.0f, 0.0f);
-    bool have = false;
-    for (int g = 0; g < rp.n_full; g++) {
-        const int base = g * rp.glen;
-        acc = wg_csum(rp.full, part, val, [&](int i) { return elem(base + i); }, acc, have);
-        have = true;
-    }
-    if (rp.tail.n_leaves) {
-        const int base = rp.n_full * rp.glen;
-        acc = wg_csum(rp.tail, part, val, [&](int i) { return elem(base + i); }, acc, have);
-    }
-    return acc;
+    return pss_np::np_sum<8, double>([&](int i) { return __dmul_rn(a[i], a[i]); }, n);
 }
 
 // np.mean float32 of |x| (KIND 1, AM: signal_processing.py:185) or |x|^2 (KIND 0, power: :327), one workgroup per frame;
@@ -1179,7 +966,7 @@ __global__ __launch_bounds__(256) void k_pairwise(const float2 *__restrict__ iq,
     }
     for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
         const float2 *x = iq + (size_t)f * n;
-        const float sum = frame_rsum<WT>(rp, part, val, [&](int i) {
+        const float sum = frame_sum<float, 8, WT>(rp, part, val, [&](int i) {
             const float2 v = x[i];
             const float m = cabsf_np(v.x, v.y);
             if (KIND == 1 && env) env[(size_t)f * n + i] = m;  // the AM envelope (:182), reused by the band-pass kernel
@@ -1190,88 +977,6 @@ __global__ __launch_bounds__(256) void k_pairwise(const float2 *__restrict__ iq,
             out[f] = KIND == 0 ? __fmul_rn(10.0f, log10f_np(__fadd_rn(mean, 1e-10f))) : mean;  // 10*log10(power + 1e-10), float32 (SVML model)
         }
     }
-}
-
-// Two real float32 reductions over the SAME elements with the SAME (real) plan in one walk: elem(i) -> (a_i, b_i); both sums have numpy's
-// bits (the trees are identical, the additions component-wise).  part / val: float2 arrays of the slot counts of the float versions.
-template <bool WT = false, class F>
-__device__ __forceinline__ float2 wg_rsum2(const PlanDev &p, float2 *part, float2 *val, F elem, float2 carry, bool have)
-{
-    const int tid = threadIdx.x, T = blockDim.x;
-    auto add = [](float2 a, float2 b) { return make_float2(__fadd_rn(a.x, b.x), __fadd_rn(a.y, b.y)); };
-    if constexpr (WT) {
-        const int lane = tid & 63;
-        const int l = lane >> 3, k = lane & 7, off = l * 128;
-        float2 r = elem(off + k);
-#pragma unroll
-        for (int i = 8; i < 128; i += 8) r = add(r, elem(off + i + k));
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) r = add(r, make_float2(__shfl_xor(r.x, m), __shfl_xor(r.y, m)));
-        return r;
-    }
-    for (int slot = tid; slot < p.n_leaves * 8; slot += T) {
-        const int l = slot >> 3, k = slot & 7, off = p.leaf_off[l], len = p.leaf_len[l];
-        if (len == 128) {
-            float2 v[16];
-#pragma unroll
-            for (int j = 0; j < 16; j++) v[j] = elem(off + 8 * j + k);
-            float2 r = v[0];
-#pragma unroll
-            for (int j = 1; j < 16; j++) r = add(r, v[j]);
-            part[slot] = r;
-        } else if (len >= 8) {
-            float2 r = elem(off + k);
-            const int end = len - (len % 8);
-            for (int i = 8; i < end; i += 8) r = add(r, elem(off + i + k));
-            part[slot] = r;
-        }
-    }
-    __syncthreads();
-    for (int l = tid; l < p.n_leaves; l += T) {
-        const int off = p.leaf_off[l], len = p.leaf_len[l];
-        float2 res;
-        if (len < 8) {
-            res = make_float2(0.0f, 0.0f);
-            for (int i = 0; i < len; i++) res = add(res, elem(off + i));
-        } else {
-            const float2 *r = part + 8 * l;
-            res = add(add(add(r[0], r[1]), add(r[2], r[3])), add(add(r[4], r[5]), add(r[6], r[7])));
-            for (int i = len - (len % 8); i < len; i++) res = add(res, elem(off + i));
-        }
-        val[l] = res;
-    }
-    __syncthreads();
-    for (int lv = 0; lv < p.n_levels; lv++) {
-        for (int k = p.level_start[lv] + tid; k < p.level_start[lv + 1]; k += T) val[p.n_leaves + k] = add(val[p.node_l[k]], val[p.node_r[k]]);
-        __syncthreads();
-    }
-    const int res = p.n_leaves + p.level_start[p.n_levels];
-    if (tid == 0) {
-        float2 acc = have ? add(carry, val[p.roots[0]]) : val[p.roots[0]];
-        for (int k = 1; k < p.n_roots; k++) acc = add(acc, val[p.roots[k]]);
-        val[res] = acc;
-    }
-    __syncthreads();
-    const float2 sum = val[res];
-    __syncthreads();
-    return sum;
-}
-template <bool WT = false, class F>
-__device__ __forceinline__ float2 frame_rsum2(const RedPlan &rp, float2 *part, float2 *val, F elem)
-{
-    if constexpr (WT) return wg_rsum2<true>(rp.tail, part, val, elem, make_float2(0.0f, 0.0f), false);
-    float2 acc = make_float2(0.0f, 0.0f);
-    bool have = false;
-    for (int g = 0; g < rp.n_full; g++) {
-        const int base = g * rp.glen;
-        acc = wg_rsum2(rp.full, part, val, [&](int i) { return elem(base + i); }, acc, have);
-        have = true;
-    }
-    if (rp.tail.n_leaves) {
-        const int base = rp.n_full * rp.glen;
-        acc = wg_rsum2(rp.tail, part, val, [&](int i) { return elem(base + i); }, acc, have);
-    }
-    return acc;
 }
 
 // measure_signal_power (signal_processing.py:325-328) AND the AM demodulator's mean of |x| + envelope (:182-185) from ONE pass over the
@@ -1291,7 +996,7 @@ __global__ __launch_bounds__(256) void k_pairwise2(const float2 *__restrict__ iq
     }
     for (long f = blockIdx.x; f < n_frames; f += gridDim.x) {
         const float2 *x = iq + (size_t)f * n;
-        const float2 sum = frame_rsum2<WT>(rp, part, val, [&](int i) {
+        const float2 sum = frame_sum<float2, 8, WT>(rp, part, val, [&](int i) {
             const float2 v = x[i];
             const float m = cabsf_np(v.x, v.y);
             if (env) env[(size_t)f * n + i] = m;
@@ -1391,18 +1096,18 @@ __global__ __launch_bounds__(256) void k_iqcorr(const float2 *__restrict__ iq, i
         // tree as before (same bits); with one wavefront per frame (WT) they are straight-line code and the independent ones of a group
         // overlap their 16-deep dependent addition chains instead of running them back to back.
         // :48 centered = samples - mean(samples)
-        float2 s = frame_csum<WT>(cp, cpart, cval, X);
+        float2 s = frame_sum<float2, 4, WT>(cp, cpart, cval, X);
         // :52 q_amplitude
-        const float qsum = frame_rsum<WT>(rp, rpart, rval, [&](int i) { float q = X(i).y; return __fmul_rn(q, q); });
+        const float qsum = frame_sum<float, 8, WT>(rp, rpart, rval, [&](int i) { float q = X(i).y; return __fmul_rn(q, q); });
         const float mr = __fdiv_rn(s.x, fn), mi = __fdiv_rn(s.y, fn);
         const float qa = sqrtf(__fmul_rn(2.0f, __fdiv_rn(qsum, fn)));
         const float scl = __fdiv_rn(1.0f, qa);  // :55 complex64 / float32 scalar multiplies by the reciprocal
         // :49 input_power = var(centered): mean again, re^2 + im^2 as three separately rounded float32 operations, mean
-        s = frame_csum<WT>(cp, cpart, cval, [&](int i) { float2 v = X(i); return make_float2(__fsub_rn(v.x, mr), __fsub_rn(v.y, mi)); });
+        s = frame_sum<float2, 4, WT>(cp, cpart, cval, [&](int i) { float2 v = X(i); return make_float2(__fsub_rn(v.x, mr), __fsub_rn(v.y, mi)); });
         // :60-61 alpha, sin(phi)
         float asum, psum;
-        if constexpr (WT) {     // both trees in one walk over the same elements (wg_rsum2: component-wise, numpy's bits for both)
-            const float2 ap = frame_rsum2<true>(rp, cpart, cval, [&](int i) {
+        if constexpr (WT) {     // both trees in one walk over the same elements (a float2 of two real sums: component-wise, numpy's bits for both)
+            const float2 ap = frame_sum<float2, 8, true>(rp, cpart, cval, [&](int i) {
                 float2 v = X(i);
                 const float is = __fmul_rn(v.x, scl);
                 return make_float2(__fmul_rn(is, is), __fmul_rn(is, __fmul_rn(v.y, scl)));
@@ -1410,11 +1115,11 @@ __global__ __launch_bounds__(256) void k_iqcorr(const float2 *__restrict__ iq, i
             asum = ap.x;
             psum = ap.y;
         } else {
-            asum = frame_rsum<WT>(rp, rpart, rval, [&](int i) {
+            asum = frame_sum<float, 8, WT>(rp, rpart, rval, [&](int i) {
                 const float is = __fmul_rn(X(i).x, scl);
                 return __fmul_rn(is, is);
             });
-            psum = frame_rsum<WT>(rp, rpart, rval, [&](int i) {
+            psum = frame_sum<float, 8, WT>(rp, rpart, rval, [&](int i) {
                 float2 v = X(i);
                 return __fmul_rn(__fmul_rn(v.x, scl), __fmul_rn(v.y, scl));
             });
@@ -1425,16 +1130,16 @@ __global__ __launch_bounds__(256) void k_iqcorr(const float2 *__restrict__ iq, i
         const float cosphi = sqrtf(__fsub_rn(1.0f, __fmul_rn(sinphi, sinphi)));  // :64
         const float ia = __fdiv_rn(1.0f, alpha), qa2 = __fdiv_rn(-sinphi, alpha), sc = __fdiv_rn(1.0f, cosphi);
         auto corrected = [&](int i) { return iqc_corrected(X(i), scl, ia, qa2, sc); };
-        const float ipsum = frame_rsum<WT>(rp, rpart, rval, [&](int i) {
+        const float ipsum = frame_sum<float, 8, WT>(rp, rpart, rval, [&](int i) {
             float2 v = X(i);
             const float dr = __fsub_rn(__fsub_rn(v.x, mr), m2r), di = __fsub_rn(__fsub_rn(v.y, mi), m2i);
             return __fadd_rn(__fmul_rn(dr, dr), __fmul_rn(di, di));  // np.var fast path: squares, then add (no fma)
         });
         // :80 var(corrected), rescale to the input power
-        s = frame_csum<WT>(cp, cpart, cval, corrected);
+        s = frame_sum<float2, 4, WT>(cp, cpart, cval, corrected);
         const float input_power = __fdiv_rn(ipsum, fn);
         const float m3r = __fdiv_rn(s.x, fn), m3i = __fdiv_rn(s.y, fn);
-        const float v2 = __fdiv_rn(frame_rsum<WT>(rp, rpart, rval, [&](int i) {
+        const float v2 = __fdiv_rn(frame_sum<float, 8, WT>(rp, rpart, rval, [&](int i) {
             float2 c = corrected(i);
             const float dr = __fsub_rn(c.x, m3r), di = __fsub_rn(c.y, m3i);
             return __fadd_rn(__fmul_rn(dr, dr), __fmul_rn(di, di));  // np.var fast path: squares, then add (no fma)
@@ -1854,38 +1559,11 @@ __global__ __launch_bounds__(TILE) void k_sosfilt(const double *__restrict__ x, 
     }
 }
 
-// decode_afsk (decoders.py:94-112) after the two band-pass rows exist: energy of each band over every bit period (np.sum of
-// the squares: float64 pairwise tree, 8192-element chunks added in order) and the comparison.  One thread per (row, bit).
-__device__ double pairwise_sq_f64(const double *a, int n)
-{
-    if (n < 8) {
-        double res = 0.0;
-        for (int i = 0; i < n; i++) res = __dadd_rn(res, __dmul_rn(a[i], a[i]));
-        return res;
-    }
-    if (n <= 128) {
-        double r[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) r[j] = __dmul_rn(a[j], a[j]);
-        int i;
-        for (i = 8; i < n - (n % 8); i += 8) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) r[j] = __dadd_rn(r[j], __dmul_rn(a[i + j], a[i + j]));
-        }
-        double res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                               __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-        for (; i < n; i++) res = __dadd_rn(res, __dmul_rn(a[i], a[i]));
-        return res;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    return __dadd_rn(pairwise_sq_f64(a, n2), pairwise_sq_f64(a + n2, n - n2));
-}
 // ---- classify_signal (signal_processing.py:296-322 with `welch` bound to scipy.signal.welch) ----------
 // Two kernels, one workgroup per frame.
 // k_cls_modidx: estimate_modulation_index (:283-293), float32 exactly as NumPy evaluates it: np.abs / np.angle (SVML
 //   atan2f model), np.unwrap's float32 arithmetic — its cumsum is a SEQUENTIAL float32 sum, so one lane walks it, chunk
-//   by chunk through LDS — np.diff, and both np.var's on NumPy's own summation trees (frame_rsum).  The unwrapped phase
+//   by chunk through LDS — np.diff, and both np.var's on NumPy's own summation trees (frame_sum).  The unwrapped phase
 //   goes through a global scratch (float32 [frame][n]).
 // k_cls_welch: Welch PSD (SciPy _spectral_helper: periodic Hann, 1024-sample segments every 512, per-segment mean
 //   removed, two-sided, density scaling, mean over segments) with the segment FFT in float64 (the reference's is
@@ -1937,8 +1615,8 @@ __device__ __forceinline__ void cls_modidx_body(unsigned char *smem, const float
         const float fn = (float)n, fm = (float)(n - 1);
         // :286, :290  np.var(np.abs(samples))
         auto A = [&](int i) { const float2 v = x[i]; return cabsf_np(v.x, v.y); };
-        const float amean = __fdiv_rn(frame_rsum(rn, part, val, A), fn);
-        const float amp_var = __fdiv_rn(frame_rsum(rn, part, val, [&](int i) { const float d = __fsub_rn(A(i), amean); return __fmul_rn(d, d); }), fn);
+        const float amean = __fdiv_rn(frame_sum<float, 8>(rn, part, val, A), fn);
+        const float amp_var = __fdiv_rn(frame_sum<float, 8>(rn, part, val, [&](int i) { const float d = __fsub_rn(A(i), amean); return __fmul_rn(d, d); }), fn);
         // :287  np.unwrap(np.angle(samples)) -> up[]
         if (tid == 0) *carry = 0.0f;
         for (int base = 0; base < n - 1; base += CLS_CH) {
@@ -1979,8 +1657,8 @@ __device__ __forceinline__ void cls_modidx_body(unsigned char *smem, const float
         float mi = NAN;  // np.var of an empty array
         if (n > 1) {
             auto D = [&](int i) { return __fsub_rn(up[i + 1], up[i]); };
-            const float dmean = __fdiv_rn(frame_rsum(rm, part, val, D), fm);
-            const float phase_var = __fdiv_rn(frame_rsum(rm, part, val, [&](int i) { const float d = __fsub_rn(D(i), dmean); return __fmul_rn(d, d); }), fm);
+            const float dmean = __fdiv_rn(frame_sum<float, 8>(rm, part, val, D), fm);
+            const float phase_var = __fdiv_rn(frame_sum<float, 8>(rm, part, val, [&](int i) { const float d = __fsub_rn(D(i), dmean); return __fmul_rn(d, d); }), fm);
             mi = __fdiv_rn(phase_var, __fadd_rn(amp_var, (float)1e-10));  // :293
         }
         if (tid == 0) mi_out[f] = mi;
@@ -2105,8 +1783,8 @@ __device__ __forceinline__ void cls_welch_body(unsigned char *smem, const float2
             const float2 *xs = x + sg * CLS_STEP;
             // detrend: data - mean(data), complex64.  1024 complex = NumPy's perfectly balanced tree: each wavefront folds it with
             // shuffles on its own (redundantly, no barrier); the general LDS walk remains for plans that are not (never here)
-            const float2 m = wave_tree ? wg_csum<true>(cp.tail, cpart, cval, [&](int i) { return xs[i]; }, make_float2(0.0f, 0.0f), false)
-                                       : frame_csum(cp, cpart, cval, [&](int i) { return xs[i]; });
+            const float2 m = wave_tree ? wg_sum<float2, 4, true>(cp.tail, cpart, cval, [&](int i) { return xs[i]; }, make_float2(0.0f, 0.0f), false)
+                                       : frame_sum<float2, 4>(cp, cpart, cval, [&](int i) { return xs[i]; });
             const float mr = __fdiv_rn(m.x, (float)CLS_NP), mim = __fdiv_rn(m.y, (float)CLS_NP);
 #pragma unroll
             for (int j = 0; j < 4; j++) {
@@ -2195,7 +1873,7 @@ __device__ __forceinline__ void cls_welch_short_body(unsigned char *smem, const 
     __syncthreads();
     for (long f = blockIdx.x; f < n_rows; f += gridDim.x) {
         const float2 *x = iq + (size_t)cls_frame<GATED>(idx, f, n_frames) * n;
-        const float2 m = frame_csum(cp, cpart, cval, [&](int i) { return x[i]; });   // detrend: data - mean(data), complex64
+        const float2 m = frame_sum<float2, 4>(cp, cpart, cval, [&](int i) { return x[i]; });   // detrend: data - mean(data), complex64
         const float mr = __fdiv_rn(m.x, (float)n), mim = __fdiv_rn(m.y, (float)n);
         for (int i = tid; i < n; i += 256) {
             const float2 v = x[i];
@@ -2324,13 +2002,7 @@ __global__ __launch_bounds__(256) void k_afsk_bits(const double *__restrict__ f1
         const long r = idx / n_bits;
         const int b = (int)(idx - r * n_bits);
         const double *a1 = f1 + (size_t)r * n + (size_t)b * w, *a2 = f2 + (size_t)r * n + (size_t)b * w;
-        double e1 = 0.0, e2 = 0.0;
-        for (int st = 0; st < w; st += 8192) {
-            const int len = (w - st) < 8192 ? (w - st) : 8192;
-            const double c1 = pairwise_sq_f64(a1 + st, len), c2 = pairwise_sq_f64(a2 + st, len);
-            e1 = st ? __dadd_rn(e1, c1) : c1;
-            e2 = st ? __dadd_rn(e2, c2) : c2;
-        }
+        const double e1 = np_sum_sq_f64(a1, w), e2 = np_sum_sq_f64(a2, w);
         bits[idx] = e2 > e1;
     }
 }
@@ -2424,117 +2096,40 @@ __global__ __launch_bounds__(AGC_T) void k_agc(const float *__restrict__ power, 
 
 // ---- host helpers --------------------------------------------------------------------------------
 
-void plan_rec(int off, int n, std::vector<int> &lo, std::vector<int> &ll, std::vector<int> &nl, std::vector<int> &nr,
-              std::vector<int> &lev, int &slot, int &level)
-{
-    if (n <= 128) {
-        lo.push_back(off);
-        ll.push_back(n);
-        slot = (int)lo.size() - 1;  // leaf slot (internal nodes are renumbered later)
-        level = 0;
-        return;
-    }
-    int n2 = n / 2;
-    n2 -= n2 % 8;
-    int sl, sr, l1, l2;
-    plan_rec(off, n2, lo, ll, nl, nr, lev, sl, l1);
-    plan_rec(off + n2, n - n2, lo, ll, nl, nr, lev, sr, l2);
-    nl.push_back(sl);
-    nr.push_back(sr);
-    level = 1 + (l1 > l2 ? l1 : l2);
-    lev.push_back(level);
-    slot = -(int)nl.size();  // internal node id k encoded as -(k+1)
-}
-
-// Plan of ONE GROUP of `len` elements (at most RED_K ufunc chunks): a forest, one pairwise tree per 8192-element chunk,
-// plus the list of roots in chunk order (numpy adds the chunk sums sequentially).
-// cplx: the tree numpy walks for a complex64 reduce — same recursion over the 2 len interleaved FLOATS, chunks of 8192
-// complex elements; leaf offsets/lengths are then in floats (always even).  Stored under key -len.
-constexpr int RED_K = 8;
+// Plan of ONE GROUP of `len` elements (at most RED_K ufunc chunks): pss_np::build_forest's tables in device memory, back to back in
+// PlanDev's order.  cplx: the tree numpy walks for a complex64 reduce, stored under key -len.
 int get_plan(pss_ctx *ctx, int len, PssPairwisePlan **out, bool cplx = false)
 {
     const int key = cplx ? -len : len;
-    const int n = cplx ? 2 * len : len;
     auto it = ctx->plans.find(key);
     if (it == ctx->plans.end()) {
-        std::vector<int> lo, ll, nl, nr, lev, roots;
-        int level = 0;
-        const int B = cplx ? 16384 : 8192;
-        for (int st = 0; st < n; st += B) {
-            int s2, l2;
-            plan_rec(st, (n - st) < B ? (n - st) : B, lo, ll, nl, nr, lev, s2, l2);
-            roots.push_back(s2);
-            level = level > l2 ? level : l2;
-        }
-        const int nleaf = (int)lo.size(), nnode = (int)nl.size();
-        // order internal nodes by level; remap ids
-        std::vector<int> order(nnode ? nnode : 1), newid(nnode ? nnode : 1), lstart(level + 2, 0);
-        int pos = 0;
-        for (int lv = 1; lv <= level; lv++) {
-            lstart[lv - 1] = pos;
-            for (int k = 0; k < nnode; k++)
-                if (lev[k] == lv) { order[pos] = k; newid[k] = pos; pos++; }
-        }
-        lstart[level] = pos;
-        auto slot_of = [&](int sl) { return sl >= 0 ? sl : nleaf + newid[-sl - 1]; };
-        std::vector<int> L(nnode ? nnode : 1), R(nnode ? nnode : 1);
-        for (int k = 0; k < nnode; k++) { L[k] = slot_of(nl[order[k]]); R[k] = slot_of(nr[order[k]]); }
-        for (auto &rt : roots) rt = slot_of(rt);
+        const pss_np::Forest f = pss_np::build_forest(len, cplx);
         PssPairwisePlan p;
-        p.n_leaves = nleaf; p.n_nodes = nnode; p.n_levels = level; p.n_roots = (int)roots.size();
-        {   // one wavefront can fold the tree with shuffles if 64 (leaf, accumulator) pairs cover equal 128-float leaves in order
-            // and every node joins two adjacent, equally sized halves (true for 1024 floats and for 1024 complex)
-            bool ok = roots.size() == 1 && nleaf * (cplx ? 4 : 8) == 64;
-            for (int l = 0; ok && l < nleaf; l++) ok = ll[l] == 128 && lo[l] == 128 * l;
-            std::function<int(int, int &)> span = [&](int slot, int &first) -> int {  // leaves under slot, -1 if not perfect
-                if (slot < nleaf) { first = slot; return 1; }
-                int fl, fr;
-                const int a = span(L[slot - nleaf], fl), b = span(R[slot - nleaf], fr);
-                if (a < 0 || b < 0 || a != b || fr != fl + a) return -1;
-                first = fl;
-                return a + b;
-            };
-            int first = 0;
-            if (ok) ok = span(roots[0], first) == nleaf && first == 0;
-            p.wave_tree = ok ? 1 : 0;
-        }
-        PSS_HIP(ctx, hipMalloc(&p.d_leaf_off, sizeof(int) * nleaf));
-        PSS_HIP(ctx, hipMalloc(&p.d_leaf_len, sizeof(int) * nleaf));
-        PSS_HIP(ctx, hipMalloc(&p.d_node_l, sizeof(int) * L.size()));
-        PSS_HIP(ctx, hipMalloc(&p.d_node_r, sizeof(int) * R.size()));
-        PSS_HIP(ctx, hipMalloc(&p.d_level_start, sizeof(int) * (level + 1)));
-        PSS_HIP(ctx, hipMalloc(&p.d_roots, sizeof(int) * roots.size()));
-        PSS_HIP(ctx, hipMemcpy(p.d_leaf_off, lo.data(), sizeof(int) * nleaf, hipMemcpyHostToDevice));
-        PSS_HIP(ctx, hipMemcpy(p.d_leaf_len, ll.data(), sizeof(int) * nleaf, hipMemcpyHostToDevice));
-        PSS_HIP(ctx, hipMemcpy(p.d_node_l, L.data(), sizeof(int) * L.size(), hipMemcpyHostToDevice));
-        PSS_HIP(ctx, hipMemcpy(p.d_node_r, R.data(), sizeof(int) * R.size(), hipMemcpyHostToDevice));
-        PSS_HIP(ctx, hipMemcpy(p.d_level_start, lstart.data(), sizeof(int) * (level + 1), hipMemcpyHostToDevice));
-        PSS_HIP(ctx, hipMemcpy(p.d_roots, roots.data(), sizeof(int) * roots.size(), hipMemcpyHostToDevice));
-        ctx->plans[key] = p;
+        p.n_leaves = f.n_leaves(); p.n_nodes = f.n_nodes(); p.n_levels = f.n_levels; p.n_roots = (int)f.roots.size();
+        p.wave_tree = f.wave_tree ? 1 : 0;
+        std::vector<int> tab;
+        for (const std::vector<int> *v : {&f.leaf_off, &f.leaf_len, &f.node_l, &f.node_r, &f.level_start, &f.roots}) tab.insert(tab.end(), v->begin(), v->end());
+        PSS_HIP(ctx, hipMalloc(&p.d_tab, sizeof(int) * tab.size()));
+        const hipError_t e = hipMemcpy(p.d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) hipFree(p.d_tab);   // not in ctx->plans yet: pss_destroy would not free it
+        PSS_HIP(ctx, e);
+        it = ctx->plans.emplace(key, p).first;
     }
-    *out = &ctx->plans[key];
+    *out = &it->second;
     return PSS_OK;
 }
 
 PlanDev plan_dev(const PssPairwisePlan *p)
 {
     if (!p) return PlanDev{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, 0};
-    return PlanDev{p->d_leaf_off, p->d_leaf_len, p->d_node_l, p->d_node_r, p->d_level_start, p->d_roots, p->n_leaves, p->n_levels,
-                   p->n_roots, p->n_nodes, p->wave_tree};
+    const int *lo = p->d_tab, *ll = lo + p->n_leaves, *nl = ll + p->n_leaves, *nr = nl + p->n_nodes, *ls = nr + p->n_nodes, *rt = ls + p->n_levels + 1;
+    return PlanDev{lo, ll, nl, nr, ls, rt, p->n_leaves, p->n_levels, p->n_roots, p->n_nodes, p->wave_tree};
 }
 
-// Group decomposition of a frame of n elements; slots = the largest (leaves, leaves + nodes + 1) over its group plans.
-size_t plan_lds_bytes(const RedPlan &rp)
+// Group decomposition of a frame of n elements
+int get_red_plan(pss_ctx *ctx, int n, bool cplx, RedPlan *rp)
 {
-    size_t ints = 0;
-    for (const PlanDev *p : {&rp.full, &rp.tail})
-        if (p->n_leaves) ints += (size_t)2 * p->n_leaves + 2 * p->n_nodes + (p->n_levels + 1) + p->n_roots;
-    return ints * sizeof(int);
-}
-
-int get_red_plan(pss_ctx *ctx, int n, bool cplx, RedPlan *rp, int *max_leaves, int *max_vals)
-{
-    const int glen = RED_K * 8192;
+    const int glen = pss_np::RED_K * pss_np::CHUNK;
     PssPairwisePlan *full = nullptr, *tail = nullptr;
     const int n_full = n > glen ? n / glen : 0, rem = n - n_full * glen;
     int r;
@@ -2544,60 +2139,27 @@ int get_red_plan(pss_ctx *ctx, int n, bool cplx, RedPlan *rp, int *max_leaves, i
     rp->tail = plan_dev(tail);
     rp->n_full = n_full;
     rp->glen = glen;
-    *max_leaves = 0; *max_vals = 0;
-    for (const PssPairwisePlan *p : {full, tail})
-        if (p) {
-            *max_leaves = p->n_leaves > *max_leaves ? p->n_leaves : *max_leaves;
-            const int v = p->n_leaves + p->n_nodes + 1;
-            *max_vals = v > *max_vals ? v : *max_vals;
-        }
     return PSS_OK;
 }
 
-template <int KIND>
-int launch_pairwise(pss_ctx *ctx, const float *d_iq, long n_frames, int n, float *d_out, float *d_env = nullptr)
+// k_pairwise<KIND> (V = float; out: d_out, d_env) and k_pairwise2 (V = float2, both sums in one walk; out: d_power, d_mean, d_env)
+template <class V, class K, class... Out>
+int launch_pairwise(pss_ctx *ctx, K kern, K kern_wt, const char *what, const float *d_iq, long n_frames, int n, Out... out)
 {
     RedPlan rp;
-    int leaves, vals;
-    int r = get_red_plan(ctx, n, false, &rp, &leaves, &vals);
+    int r = get_red_plan(ctx, n, false, &rp);
     if (r) return r;
-    const int part_slots = 8 * leaves;
-    const size_t lds = sizeof(float) * (size_t)(part_slots + vals) + plan_lds_bytes(rp);
-    const int lanes = 8 * leaves;  // one lane per (leaf, accumulator) pair
-    const int T = lanes <= 64 ? 64 : (lanes <= 128 ? 128 : 256);
-    const bool wt = T == 64 && !rp.n_full && rp.tail.wave_tree;  // n = 1024: the whole tree folds inside one wavefront
-    auto kern = wt ? k_pairwise<KIND, true> : k_pairwise<KIND, false>;
-    if (lds > 64 * 1024)
-        PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                         (int)lds));
-    long g = n_frames < 8192 ? n_frames : 8192;  // several frames per workgroup: the plan tables are copied to LDS once (a grid capped at what the CUs hold at once — 2048 workgroups — measured 20 % slower: the dispatcher's backfill of finished workgroups is the better balance)
-    pss_kernel_begin(ctx, "k_pairwise");
-    hipLaunchKernelGGL(kern, dim3((int)g), dim3(T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, rp,
-                       part_slots, vals, d_out, d_env);
-    pss_kernel_end(ctx);
-    return pss_hip_check(ctx, hipGetLastError(), "k_pairwise launch");
-}
-
-int launch_pairwise2(pss_ctx *ctx, const float *d_iq, long n_frames, int n, float *d_power, float *d_mean, float *d_env)
-{
-    RedPlan rp;
-    int leaves, vals;
-    int r = get_red_plan(ctx, n, false, &rp, &leaves, &vals);
-    if (r) return r;
-    const int part_slots = 8 * leaves;
-    const size_t lds = sizeof(float2) * (size_t)(part_slots + vals) + plan_lds_bytes(rp);
-    const int lanes = 8 * leaves;
-    const int T = lanes <= 64 ? 64 : (lanes <= 128 ? 128 : 256);
-    const bool wt = T == 64 && !rp.n_full && rp.tail.wave_tree;
-    auto kern = wt ? k_pairwise2<true> : k_pairwise2<false>;
+    const pss_np::SumGeom geo = pss_np::sum_geometry({{&rp, 8, sizeof(V)}}, sizeof(V));
+    const size_t lds = geo.lds_bytes();
+    if (geo.wave_tree) kern = kern_wt;  // n = 1024: the whole tree folds inside one wavefront
     if (lds > 64 * 1024)
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const long g = n_frames < 8192 ? n_frames : 8192;
+    const long g = n_frames < 8192 ? n_frames : 8192;  // several frames per workgroup: the plan tables are copied to LDS once (a grid capped at what the CUs hold at once — 2048 workgroups — measured 20 % slower: the dispatcher's backfill of finished workgroups is the better balance)
     pss_kernel_begin(ctx, "k_pairwise");
-    hipLaunchKernelGGL(kern, dim3((int)g), dim3(T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, rp, part_slots, vals,
-                       d_power, d_mean, d_env);
+    hipLaunchKernelGGL(kern, dim3((int)g), dim3(geo.T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, rp,
+                       geo.part_slots, geo.val_slots, out...);
     pss_kernel_end(ctx);
-    return pss_hip_check(ctx, hipGetLastError(), "k_pairwise2 launch");
+    return pss_hip_check(ctx, hipGetLastError(), what);
 }
 
 int nfm_filters(pss_ctx *ctx, double fs, PssNfmFilt **out)
@@ -2731,20 +2293,16 @@ extern "C" int pss_iq_correction(pss_ctx *ctx, const float *d_iq, long n_frames,
 static int iq_correction_launch(pss_ctx *ctx, const float *d_iq, long n_frames, int n, float *d_out_iq, float *d_raw, float *d_scal)
 {
     RedPlan rp, cp;
-    int rl, rv, cl, cv;
-    int r = get_red_plan(ctx, n, false, &rp, &rl, &rv);
+    int r = get_red_plan(ctx, n, false, &rp);
     if (r) return r;
-    r = get_red_plan(ctx, n, true, &cp, &cl, &cv);
+    r = get_red_plan(ctx, n, true, &cp);
     if (r) return r;
-    // LDS: partial sums (8 floats | 4 float2 per leaf) + tree values, optionally the frame itself
-    size_t part_slots = (size_t)(rl * 4 > cl * 4 ? rl * 4 : cl * 4);  // in float2
-    size_t val_slots = (size_t)(rv > cv ? rv : cv);
+    // LDS: partial sums (8 floats | 4 float2 per leaf) + tree values in float2 slots, optionally the frame itself
+    const pss_np::SumGeom geo = pss_np::sum_geometry({{&rp, 8, sizeof(float)}, {&cp, 4, sizeof(float2)}}, sizeof(float2));
     // staging pays while >= 2 workgroups fit a CU (measured: 0.59 vs 0.91 ms at 65536 x 1024, but 2.6 vs 1.8 ms at 8192 x 16384)
     const bool staged = n <= 8192;
-    size_t lds = (part_slots + val_slots + (staged ? (size_t)n : 0)) * sizeof(float2) + plan_lds_bytes(rp) + plan_lds_bytes(cp);
-    const int lanes = rl * 8 > cl * 4 ? rl * 8 : cl * 4;
-    const int T = lanes <= 64 ? 64 : (lanes <= 128 ? 128 : 256);  // one lane per (leaf, accumulator) pair
-    const bool wt = T == 64 && staged && !rp.n_full && !cp.n_full && rp.tail.wave_tree && cp.tail.wave_tree;  // n = 1024
+    const size_t lds = geo.lds_bytes() + (staged ? (size_t)n : 0) * sizeof(float2);
+    const bool wt = staged && geo.wave_tree;  // n = 1024
     auto kern = wt ? k_iqcorr<true, true> : (staged ? k_iqcorr<true, false> : k_iqcorr<false, false>);
     if (lds > 64 * 1024)
         PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -2752,8 +2310,8 @@ static int iq_correction_launch(pss_ctx *ctx, const float *d_iq, long n_frames, 
     long g = n_frames < 8192 ? n_frames : 8192;  // several frames per workgroup: the plan tables are copied to LDS once (a grid capped at what the CUs hold at once — 2048 workgroups — measured 20 % slower: the dispatcher's backfill of finished workgroups is the better balance)
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_iqcorr");
-    hipLaunchKernelGGL(kern, dim3((int)g), dim3(T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, a, b,
-                       (int)part_slots, (int)val_slots, reinterpret_cast<float2 *>(d_out_iq), d_raw, d_scal);
+    hipLaunchKernelGGL(kern, dim3((int)g), dim3(geo.T), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), n, n_frames, a, b,
+                       geo.part_slots, geo.val_slots, reinterpret_cast<float2 *>(d_out_iq), d_raw, d_scal);
     pss_kernel_end(ctx);
     return pss_hip_check(ctx, hipGetLastError(), "k_iqcorr launch");
 }
@@ -2765,7 +2323,7 @@ extern "C" int pss_power_db(pss_ctx *ctx, const float *d_iq, long n_frames, int 
     if (n < 1 || n_frames < 0 || (n_frames > 0 && (!d_iq || !d_power))) return pss_fail(ctx, PSS_E_ARG, "bad power arguments");
     if (n_frames == 0) return PSS_OK;
     PssTimeScope timed(ctx);
-    int r = launch_pairwise<0>(ctx, d_iq, n_frames, n, d_power);
+    int r = launch_pairwise<float>(ctx, k_pairwise<0, false>, k_pairwise<0, true>, "k_pairwise launch", d_iq, n_frames, n, d_power, (float *)nullptr);
     return r;
 }
 
@@ -2963,7 +2521,8 @@ static int demod_am(pss_ctx *ctx, const float *d_iq, long n_frames, int n, int16
     AmCoef c;
     sos_biquads(c.s, sos, 5);
     PssTimeScope timed(ctx);
-    r = d_power ? launch_pairwise2(ctx, d_iq, n_frames, n, d_power, mu, env) : launch_pairwise<1>(ctx, d_iq, n_frames, n, mu, env);
+    r = d_power ? launch_pairwise<float2>(ctx, k_pairwise2<false>, k_pairwise2<true>, "k_pairwise2 launch", d_iq, n_frames, n, d_power, mu, env)
+                : launch_pairwise<float>(ctx, k_pairwise<1, false>, k_pairwise<1, true>, "k_pairwise launch", d_iq, n_frames, n, mu, env);
     if (r) return r;
     pss_kernel_begin(ctx, "k_am_grp");
     hipLaunchKernelGGL(k_am_grp, dim3((unsigned)((n_frames + GRP_G - 1) / GRP_G)), dim3(256), 0, PSS_STREAM(ctx), env, mu, Yf, mx, n, n_frames, c);
@@ -3285,7 +2844,7 @@ extern "C" int pss_sosfilt(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
 // ---- complex128 read buffers: demodulate_am in float64 from the first statement (signal_processing.py:179-195) ---------------------------------
 // The reference's SDR buffer is complex64, but handed complex128 its functions compute in float64: np.abs(complex128) is the same scaled hypot
 // as the complex64 loop in float64 (mx * sqrt(fma(r, r, 1)), r = mn / mx; probed bit for bit), np.mean the same pairwise tree over float64
-// (8192-element chunks added in order; blocks of 128 with 8 accumulators), the subtraction float64; sosfilt and the normalisation are float64
+// (pss_npsum.h), the subtraction float64; sosfilt and the normalisation are float64
 // anyway.  Plain kernels, one workgroup per frame, the mean by one thread — a conformance path, not a throughput path.
 namespace {
 __device__ double cabs_np64(double re, double im)
@@ -3295,54 +2854,6 @@ __device__ double cabs_np64(double re, double im)
     if (mx == 0.0) return 0.0;
     const double r = __ddiv_rn(mn, mx);
     return __dmul_rn(mx, __dsqrt_rn(__fma_rn(r, r, 1.0)));
-}
-// numpy's DOUBLE_pairwise_sum over a[0 .. n), n <= 8192: the recursion as an explicit post-order walk (depth <= 7)
-__device__ double pairwise_chunk_f64(const double *a, int n)
-{
-    struct Fr { int off, len, st; double left; };
-    Fr stk[12];
-    int sp = 0;
-    double ret = 0.0;
-    stk[sp++] = Fr{0, n, 0, 0.0};
-    while (sp > 0) {
-        Fr &fr = stk[sp - 1];
-        if (fr.len <= 128) {
-            const double *x = a + fr.off;
-            const int len = fr.len;
-            double res;
-            if (len < 8) {
-                res = 0.0;
-                for (int i = 0; i < len; i++) res = __dadd_rn(res, x[i]);
-            } else {
-                double r[8];
-                for (int j = 0; j < 8; j++) r[j] = x[j];
-                int i = 8;
-                for (; i < len - (len % 8); i += 8)
-                    for (int j = 0; j < 8; j++) r[j] = __dadd_rn(r[j], x[i + j]);
-                res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])), __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-                for (; i < len; i++) res = __dadd_rn(res, x[i]);
-            }
-            ret = res;
-            sp--;
-        } else if (fr.st == 0) {
-            int n2 = fr.len / 2;
-            n2 -= n2 % 8;
-            fr.st = 1;
-            stk[sp] = Fr{fr.off, n2, 0, 0.0};
-            sp++;
-        } else if (fr.st == 1) {
-            int n2 = fr.len / 2;
-            n2 -= n2 % 8;
-            fr.left = ret;
-            fr.st = 2;
-            stk[sp] = Fr{fr.off + n2, fr.len - n2, 0, 0.0};
-            sp++;
-        } else {
-            ret = __dadd_rn(fr.left, ret);
-            sp--;
-        }
-    }
-    return ret;
 }
 // envelope |x| (float64), its mean, X[f][i] = |x[i]| - mean
 __global__ __launch_bounds__(256) void k_am_env_c128(const double2 *__restrict__ iq, int n, long n_frames, double *__restrict__ X)
@@ -3354,9 +2865,7 @@ __global__ __launch_bounds__(256) void k_am_env_c128(const double2 *__restrict__
         for (int i = threadIdx.x; i < n; i += blockDim.x) e[i] = cabs_np64(x[i].x, x[i].y);
         __syncthreads();
         if (threadIdx.x == 0) {
-            double acc = pairwise_chunk_f64(e, n < 8192 ? n : 8192);
-            for (int st = 8192; st < n; st += 8192) acc = __dadd_rn(acc, pairwise_chunk_f64(e + st, (n - st) < 8192 ? (n - st) : 8192));
-            mu_s = __ddiv_rn(acc, (double)n);
+            mu_s = __ddiv_rn(np_sum_f64(e, n), (double)n);
         }
         __syncthreads();
         const double mu = mu_s;
@@ -3376,9 +2885,7 @@ __global__ __launch_bounds__(256) void k_power_c128(const double2 *__restrict__ 
         }
         __syncthreads();
         if (threadIdx.x == 0) {
-            double acc = pairwise_chunk_f64(e, n < 8192 ? n : 8192);
-            for (int st = 8192; st < n; st += 8192) acc = __dadd_rn(acc, pairwise_chunk_f64(e + st, (n - st) < 8192 ? (n - st) : 8192));
-            P[f] = __ddiv_rn(acc, (double)n);
+            P[f] = __ddiv_rn(np_sum_f64(e, n), (double)n);
         }
         __syncthreads();
     }
@@ -3530,31 +3037,8 @@ int cls_prepare(pss_ctx *ctx, long n_rows, int n, double fs, float *d_mi, const 
         std::vector<float> w(np);
         const double start = -M_PI, step = (M_PI - (-M_PI)) / (double)np;
         for (int i = 0; i < np; i++) w[i] = np == 1 ? 1.0f : (float)(0.5 + 0.5 * cos((double)i * step + start));
-        // (win * win).sum(): numpy's pairwise sum over the 2 np interleaved floats of the complex64 array (imaginary lanes all
-        // zero): blocks of <= 128 floats with 8 accumulators striding the array, a plain loop below 8 floats
-        std::vector<float> z(2 * np, 0.0f);
-        for (int i = 0; i < np; i++) z[2 * i] = w[i] * w[i];
-        std::function<float(const float *, int)> pw = [&](const float *a, int nn) -> float {  // real part of numpy's pairwise complex sum
-            if (nn < 8) {
-                float res = 0.0f;
-                for (int i = 0; i < nn; i += 2) res += a[i];
-                return res;
-            }
-            if (nn <= 128) {
-                float r[8];
-                for (int k = 0; k < 8; k++) r[k] = a[k];
-                int i;
-                for (i = 8; i < nn - (nn % 8); i += 8)
-                    for (int k = 0; k < 8; k++) r[k] += a[i + k];
-                float res = ((r[0] + r[2]) + (r[4] + r[6]));
-                for (; i < nn; i += 2) res += a[i];
-                return res;
-            }
-            int n2 = nn / 2;
-            n2 -= n2 % 8;
-            return pw(a, n2) + pw(a + n2, nn - n2);
-        };
-        win_sum = pw(z.data(), 2 * np);
+        // (win * win).sum(): numpy's pairwise sum of the complex64 array (imaginary parts all zero), real part
+        win_sum = pss_np::np_sum<4, pss_np::Cx<float>>([&](int i) { return pss_np::Cx<float>{w[i] * w[i], 0.0f}; }, np).re;
         if (!d_win) PSS_HIP(ctx, hipMalloc(&d_win, sizeof(float) * CLS_NP));
         PSS_HIP(ctx, hipMemcpyAsync(d_win, w.data(), sizeof(float) * np, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
         PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // w is a local; also orders the upload behind earlier launches reading the old window
@@ -3564,24 +3048,26 @@ int cls_prepare(pss_ctx *ctx, long n_rows, int n, double fs, float *d_mi, const 
     c.d_win = d_win;
     c.scale = 1.0f / ((float)fs * win_sum);
     RedPlan &rn = c.rn, &rm = c.rm, &cp = c.cp;
-    int l1, v1, l2, v2, lc, &vc = c.vc;
-    int r = get_red_plan(ctx, n, false, &rn, &l1, &v1);
-    if (!r) r = get_red_plan(ctx, n - 1, false, &rm, &l2, &v2);
-    if (!r) r = get_red_plan(ctx, np, true, &cp, &lc, &vc);
+    int r = get_red_plan(ctx, n, false, &rn);
+    if (!r) r = get_red_plan(ctx, n - 1, false, &rm);
+    if (!r) r = get_red_plan(ctx, np, true, &cp);
     if (r) return r;
+    const pss_np::SumGeom g1 = pss_np::sum_geometry({{&rn, 8, sizeof(float)}, {&rm, 8, sizeof(float)}}, sizeof(float));
+    const pss_np::SumGeom gc = pss_np::sum_geometry({{&cp, 4, sizeof(float2)}}, sizeof(float2));
     const size_t szUp = align256((size_t)n_rows * n * sizeof(float)), szMi = align256((size_t)n_rows * sizeof(float));
     r = pss_ensure_scratch(ctx, szUp + szMi);
     if (r) return r;
     c.up = reinterpret_cast<float *>(ctx->scratch);
     c.mi = d_mi ? d_mi : reinterpret_cast<float *>(reinterpret_cast<char *>(ctx->scratch) + szUp);
-    const int part1 = c.part1 = 8 * (l1 > l2 ? l1 : l2), val1 = c.val1 = ((v1 > v2 ? v1 : v2) + 3) & ~3;
-    const size_t lds1 = c.lds1 = sizeof(float) * ((size_t)part1 + val1 + (CLS_CH + 4) + CLS_CH + 1) + plan_lds_bytes(rn) + plan_lds_bytes(rm);
+    const int part1 = c.part1 = g1.part_slots, val1 = c.val1 = (g1.val_slots + 3) & ~3;
+    const size_t lds1 = c.lds1 = sizeof(float) * ((size_t)part1 + val1 + (CLS_CH + 4) + CLS_CH + 1) + g1.plan_bytes;
     if (lds1 > 64 * 1024)
         PSS_HIP(ctx, hipFuncSetAttribute(modidx_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    const int partc = c.partc = 4 * lc;
-    c.lds2 = sizeof(double2) * (CLS_NP + CLS_NP / 2) + sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);
+    c.partc = gc.part_slots;
+    c.vc = gc.val_slots;
+    c.lds2 = sizeof(double2) * (CLS_NP + CLS_NP / 2) + gc.lds_bytes();
     c.lds3 = sizeof(double2) * 2 * CLS_NP + sizeof(float) * 2 * CLS_NP + sizeof(double) * 16 + sizeof(int) * 8 +
-             sizeof(float2) * ((size_t)partc + vc) + plan_lds_bytes(cp);   // k_cls_welch_short's (np < CLS_NP)
+             gc.lds_bytes();   // k_cls_welch_short's (np < CLS_NP)
     return PSS_OK;
 }
 }  // namespace

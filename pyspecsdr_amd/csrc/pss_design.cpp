@@ -20,35 +20,15 @@
 #include <cstring>
 #include <vector>
 
+#include "pss_npsum.h"
+
 typedef std::complex<double> cplx;
 
 // NumPy's arithmetic, restated where it is not the obvious one (this unit is compiled with -ffp-contract=off):
-//   np.add.reduce on a contiguous float64 array: pairwise summation — eight running sums over blocks of eight, combined as
-//   ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), the remainder added one by one; halves above 128 elements;
+//   np.add.reduce on a contiguous float64 array: pairwise summation (pss_npsum.h);
 //   complex128 multiply: (ar br - ai bi, ar bi + ai br), no fused multiply-add; complex128 divide: Smith's algorithm
 //   (ratio of the divisor's smaller to its larger component, one reciprocal).
 namespace {
-double np_pairwise_sum(const double *a, long n)
-{
-    if (n < 8) {
-        double r = 0.0;
-        for (long i = 0; i < n; i++) r += a[i];
-        return r;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; j++) r[j] = a[j];
-        long i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    long n2 = n / 2;
-    n2 -= n2 % 8;
-    return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
 inline std::complex<double> np_cmul(std::complex<double> a, std::complex<double> b)
 {
     return std::complex<double>(a.real() * b.real() - a.imag() * b.imag(), a.real() * b.imag() + a.imag() * b.real());
@@ -223,7 +203,7 @@ extern "C" int pss_design_firwin(int numtaps, double cutoff, double *taps)
         taps[i] = h * w;
         hc[i] = taps[i] * std::cos(M_PI * m * 0.0);          // scale_frequency = 0
     }
-    const double s = np_pairwise_sum(hc.data(), numtaps);
+    const double s = pss_np::np_sum(hc.data(), numtaps);
     for (int i = 0; i < numtaps; i++) taps[i] /= s;
     return PSS_OK;
 }

@@ -11,18 +11,18 @@
 #include <cstdint>
 #include <vector>
 
+#include "pss_npsum.h"
+
 namespace pss_sq {
 
 // ---- row meter ------------------------------------------------------------------------------------------------------------------------
-// np.mean of a float64 row is add.reduce / len, and add.reduce is NumPy's pairwise sum over buffer chunks of 8192 elements added up in
-// order.  Inside a chunk: a block of more than 128 elements is split at n / 2 rounded down to a multiple of 8 and the halves are added;
-// a block of 8 .. 128 elements runs 8 strided accumulators r[j] += x[i + j], folds them as ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and adds the
-// last len % 8 elements one by one; fewer than 8 elements are added one by one from 0.  Every addition is therefore fixed; what is free
-// is WHO performs it.  Here 8 lanes share a leaf block, lane j holding accumulator j (a wave reads 8 segments of 64 contiguous bytes per
-// load instruction), the fold is three xor shuffles, the leaf sums go to LDS and the tree above them is added level by level.
-// The tree of one chunk length is the same for every row, so the host walks it once per call (MeterPlan, passed by value).
-constexpr int CHUNK = 8192;     // NumPy's reduction buffer, in elements
-constexpr int LEAF = 128;       // PW_BLOCKSIZE
+// np.mean of a float64 row is add.reduce / len: NumPy's pairwise sum (pss_npsum.h states the rule and builds the tables).  Every addition
+// is fixed; what is free is WHO performs it.  Here 8 lanes share a leaf block, lane j holding accumulator j (a wave reads 8 segments of
+// 64 contiguous bytes per load instruction) and taking np.max in the same walk, the fold is three xor shuffles, the leaf sums go to LDS
+// and the tree above them is added level by level.
+// The tree of one chunk length is the same for every row, so the host builds it once per call (MeterPlan, passed by value).
+using pss_np::CHUNK;            // NumPy's reduction buffer, in elements
+using pss_np::LEAF;             // PW_BLOCKSIZE
 constexpr int MAX_LEAVES = 128; // a chunk of <= 8192 elements has at most 128 leaf blocks (depth <= 7, no leaf below depth-6 blocks of > 128)
 
 struct MeterPlan {
@@ -40,54 +40,19 @@ struct MeterPlans {
     int n_chunks;
 };
 
-// host side: the pairwise tree of one chunk of n <= 8192 elements
-inline void build_plan(int n, MeterPlan &p)
+// host side: the pairwise tree of one chunk of n <= 8192 elements, pss_np::build_forest's tables in the compact by-value form
+inline void fill_plan(int n, MeterPlan &p)
 {
-    struct Inner { int l, r, h; };
-    std::vector<Inner> inner;
-    int n_leaves = 0;
-    constexpr int INNER0 = 1000;   // temporary ids: leaves 0 .., inner nodes INNER0 ..
-    struct Walk {
-        std::vector<Inner> &inner;
-        MeterPlan &p;
-        int &n_leaves;
-        int go(int off, int len, int &h)
-        {
-            if (len <= LEAF) {
-                p.leaf_off[n_leaves] = (uint16_t)off;
-                p.leaf_len[n_leaves] = (uint8_t)len;
-                h = 0;
-                return n_leaves++;
-            }
-            int n2 = len / 2;
-            n2 -= n2 % 8;
-            int hl, hr;
-            const int l = go(off, n2, hl), r = go(off + n2, len - n2, hr);
-            h = std::max(hl, hr) + 1;
-            inner.push_back({l, r, h});
-            return INNER0 + (int)inner.size() - 1;
-        }
-    } walk{inner, p, n_leaves};
+    const pss_np::Forest f = pss_np::build_forest(n);
     p = MeterPlan{};
-    int h_root = 0;
-    const int root = walk.go(0, n, h_root);
-    std::vector<int> order(inner.size()), pos(inner.size());
-    for (size_t k = 0; k < order.size(); k++) order[k] = (int)k;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return inner[a].h < inner[b].h; });
-    for (size_t k = 0; k < order.size(); k++) pos[order[k]] = (int)k;
-    auto slot = [&](int id) { return id < INNER0 ? id : n_leaves + pos[id - INNER0]; };
-    for (size_t k = 0; k < order.size(); k++) {
-        p.node_l[k] = (uint8_t)slot(inner[order[k]].l);
-        p.node_r[k] = (uint8_t)slot(inner[order[k]].r);
-    }
-    for (int h = 1, k = 0; h <= h_root; h++) {
-        p.level_start[h - 1] = (uint8_t)k;
-        while (k < (int)order.size() && inner[order[k]].h == h) k++;
-        p.level_start[h] = (uint8_t)k;
-    }
-    p.n_leaves = n_leaves;
-    p.n_levels = h_root;
-    p.root = slot(root);
+    std::copy(f.leaf_off.begin(), f.leaf_off.end(), p.leaf_off);
+    std::copy(f.leaf_len.begin(), f.leaf_len.end(), p.leaf_len);
+    std::copy(f.node_l.begin(), f.node_l.end(), p.node_l);
+    std::copy(f.node_r.begin(), f.node_r.end(), p.node_r);
+    std::copy(f.level_start.begin(), f.level_start.end(), p.level_start);
+    p.n_leaves = f.n_leaves();
+    p.n_levels = f.n_levels;
+    p.root = f.roots[0];
 }
 
 __device__ __forceinline__ double nan_max(double a, double b)   // np.max's step: a NaN wins
@@ -137,6 +102,7 @@ __global__ __launch_bounds__(256) void k_row_meter(const double *__restrict__ ro
                         r = __dadd_rn(r, v[k]);
                         m = nan_max(m, v[k]);
                     }
+                // the leaf's fold ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) of pss_npsum.h (fold_acc), accumulator j in lane j: three xor shuffles
                 r = __dadd_rn(r, __shfl_xor(r, 1));
                 r = __dadd_rn(r, __shfl_xor(r, 2));
                 r = __dadd_rn(r, __shfl_xor(r, 4));

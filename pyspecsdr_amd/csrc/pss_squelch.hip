@@ -46,8 +46,8 @@ extern "C" int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows
     pl.n_full = len > CHUNK ? len / CHUNK : 0;
     const int rem = len - pl.n_full * CHUNK;
     pl.n_chunks = pl.n_full + (rem > 0 ? 1 : 0);
-    if (pl.n_full) build_plan(CHUNK, pl.full);
-    if (rem > 0) build_plan(rem, pl.tail);
+    if (pl.n_full) fill_plan(CHUNK, pl.full);
+    if (rem > 0) fill_plan(rem, pl.tail);
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_row_meter");
     if (len <= METER_WAVE_MAX_LEN) {

@@ -3,7 +3,7 @@ and tools/make_goldens_lengths.py.  NumPy only.
 
 Every kernel family has structure that depends on the frame length; the lists walk each regime and its edges:
 
-  REDUCE_LENGTHS    NumPy's summation tree as plan_rec / get_plan / get_red_plan rebuild it: sequential below 8, eight accumulators and
+  REDUCE_LENGTHS    NumPy's summation tree as pss_npsum.h states it (build_forest; get_plan / get_red_plan group it): sequential below 8, eight accumulators and
                     a tail up to 128, uneven halves above (129..255 the first), 8192-element chunks and 8-chunk groups with tails of
                     fewer than 8 elements (b + d, d = -9..9), a full group plus one chunk (73 728) and two groups plus one (139 264).
   DEMOD_LENGTHS     every residue of M = n - 1 modulo the forward kernels' chunk sizes (24 for k_nfm_fwd after a 64-output prologue, 16

@@ -1,7 +1,7 @@
 """Frame lengths swept through the demodulators, the classifier and the NumPy-sum kernels: one launch set per length, every frame against
 the CPU oracle (oracle/pss_oracle.c), over the lists of tests/length_cases.py.
 
-What depends on the length and is walked here: the summation plans (plan_rec / get_plan / get_red_plan behind k_pairwise<0/1>,
+What depends on the length and is walked here: the summation plans (pss_npsum.h's build_forest behind get_plan / get_red_plan and k_pairwise<0/1>,
 k_pairwise2, the three k_iqcorr variants, k_cls_modidx and the float64 twins k_power_c128 / k_am_env_c128), the chunk phases of the
 forward kernels (k_nfm_fwd, k_wfm_fwd, k_wfm_mrg, k_iir4_sys, k_nfm_front, k_ssb_fir, k_am_grp), n_out = ceil((n - 1) / q), and the
 classifier's segment count and unwrap chunks.
@@ -22,7 +22,7 @@ point and path (profiles/length_sweep.txt keeps them).
 The reference raises at none of the AM / SSB lengths (tools/fuzz_oracle_vs_reference.py --lengths ran it over all of them), so the
 engine may raise at none either; NFM raises ValueError at n = 28 on every path as the reference's sosfiltfilt does.
 
-Each test takes its own Engine: a sweep leaves a summation plan (six small device allocations) per length in its context, which the
+Each test takes its own Engine: a sweep leaves a summation plan (one small device allocation) per length in its context, which the
 session's shared engine should not carry into the later tests.
 
 Measured on one MI355X, the host oracle included (the first test of a group pays for the frames and the reference its paths share): the

@@ -71,6 +71,23 @@ def test_row_meter_equals_numpy_on_random_rows(length):
         assert not bad, (length, n_rows, bad[:5], peak[bad[0]], want_peak[bad[0]], avg[bad[0]], want_avg[bad[0]])
 
 
+def test_row_meter_tables_at_every_tree_regime():
+    """The meter's tables come from the shared builder (pss_npsum.h: build_forest -> fill_plan): three random rows at every length
+    below 300 (leaf and first uneven-split regimes, k_row_meter<64>) and at b - 9 .. b + 9 for b = 2048 (the switch to
+    k_row_meter<256>), 8192, 16384 and 65536 (chunk edges), against np.max / np.mean; every failing length is reported."""
+    from length_cases import REDUCE_LENGTHS
+    lengths = [n for n in REDUCE_LENGTHS if n < 300] + [b + d for b in (2048, 8192, 16384, 65536) for d in range(-9, 10)]
+    assert set(lengths) <= set(REDUCE_LENGTHS) and len(lengths) == 299 + 4 * 19
+    bad = []
+    for length in lengths:
+        rows = S.random_rows(3, length, 31 * length)
+        want_peak, want_avg = S.meter_model(rows)
+        peak, avg = meter(rows)
+        if not (S.same_bits(peak, want_peak) and S.exact_bits(avg, want_avg)):
+            bad.append(length)
+    assert not bad, bad
+
+
 @pytest.mark.parametrize("length,cap", [(12, METER_WAVE_CAP_ROWS), (1020, METER_WAVE_CAP_ROWS), (2052, METER_GROUP_CAP_ROWS), (8193, METER_GROUP_CAP_ROWS)])
 def test_row_meter_one_row_past_each_grid_cap(length, cap):
     n_rows = cap + 1
