@@ -661,6 +661,31 @@ int pss_h_demodulate(pss_ctx *ctx, int mode, const float *h_iq, int n, double fs
 /* scipy.signal.sosfilt(sos, x) with zero initial state on n_rows independent float64 rows of n samples (one lane per row);
  * sos: HOST pointer, nsec <= 8 rows of 6.  The building block behind bandpass_filter (signal_processing.py:34-42). */
 int pss_sosfilt(pss_ctx *ctx, const double *d_x, long n_rows, int n, const double *sos, int nsec, double *d_y);
+/* scipy.signal.lfilter(b, a, x) with zero initial state on n_rows independent float64 rows of n samples (one lane per row) — what the
+ * reference's lowpass_filter (signal_processing.py:28-31) runs with butter_lowpass's (b, a).  b, a: HOST tables of ncoef values each,
+ * 2 <= ncoef <= 9, a[0] finite and not 0; both are divided by a[0] first, as lfilter does.  Direct form II transposed, unfused:
+ * y = z[0] + b[0] x; z[k] = (z[k + 1] + x b[k + 1]) - y a[k + 1]; the last z = x b[N] - y a[N].  pss_h_lfilter: the same on host rows, pure
+ * host code (no context, no GPU). */
+int pss_lfilter(pss_ctx *ctx, const double *d_x, long n_rows, int n, const double *b, const double *a, int ncoef, double *d_y);
+int pss_h_lfilter(const double *h_x, long n_rows, int n, const double *b, const double *a, int ncoef, double *h_y);
+
+/* ---- FM mono: decode_mono (signal_processing.py:331-359), broadcast FM to mono int16 at fs / 6, bit for bit ----
+ * Per frame of n complex64 samples: angle(x[i] * conj(x[i + 1])) in float32 (NumPy's FMA product and arctan2) times
+ * float32(fs / (2 pi pi 75e3)); scipy.signal.decimate(., 6, ftype="fir") in float32 (firwin(121, 1 / 6) as float32, zero phase, one
+ * multiply and one add per tap in upfirdn's order); the 75 us de-emphasis bilinear([1], [75e-6, 1], fs) — designed for the rate BEFORE
+ * the decimation, as the reference does — run by lfilter in float64; minus np.mean; * 0.75 * 32768; astype(int16), which truncates to
+ * int32 and keeps the low 16 bits (a full-deviation signal at 2.4 MS/s wraps; NaN, inf and values outside int32 give 0).
+ * n_out = pss_decode_mono_len(n) = ceil((n - 1) / 6), 0 for n = 0 and 1 (n < 0: PSS_E_ARG).
+ * pss_decode_mono: d_iq [n_frames][n] complex64 (8-byte aligned); d_pcm int16 [n_frames][n_out]; d_audio (optional) float64, the value
+ * the cast sees; d_dec (optional) float32, the decimated row before the de-emphasis — at least one of the three.  Any n >= 0; n <= 1
+ * succeeds and writes nothing.  Kernels k_mono_fwd (float32, to the decimated rows), k_mono_bwd (float64 recurrence and mean, one lane per
+ * frame) and k_mono_out (scale and cast).
+ * pss_h_decode_mono: one host frame, pure host code (no context, no GPU): the same statements (pss_mono.h) on one thread.
+ * pss_design_deemph: scipy.signal.bilinear([1], [tau, 1], fs) -> b[2], a[2] (a[0] = 1), every bit. */
+int pss_decode_mono_len(int n);
+int pss_decode_mono(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, float *d_dec);
+int pss_h_decode_mono(const float *h_iq, int n, double fs, int16_t *h_pcm, double *h_audio, float *h_dec);
+int pss_design_deemph(double tau, double fs, double b[2], double a[2]);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -166,6 +166,12 @@ _SIGS = {
     "pss_h_demodulate_batch": (C.c_int, [_p, C.c_int, _p, C.c_long, C.c_int, C.c_double, C.c_long, _p]),
     "pss_h_measure_power": (C.c_int, [_p, _p, C.c_int, _p]),
     "pss_sosfilt": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, C.c_int, _p]),
+    "pss_lfilter": (C.c_int, [_p, _p, C.c_long, C.c_int, _p, _p, C.c_int, _p]),
+    "pss_h_lfilter": (C.c_int, [_p, C.c_long, C.c_int, _p, _p, C.c_int, _p]),
+    "pss_decode_mono_len": (C.c_int, [C.c_int]),
+    "pss_decode_mono": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p]),
+    "pss_h_decode_mono": (C.c_int, [_p, C.c_int, C.c_double, _p, _p, _p]),
+    "pss_design_deemph": (C.c_int, [C.c_double, C.c_double, _p, _p]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

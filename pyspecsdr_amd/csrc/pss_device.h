@@ -15,24 +15,26 @@ namespace pss {
 
 // VRCP14PS bit-exact model (x86 AVX-512 reciprocal approximation): 64-segment piecewise-linear in the
 // top 16 mantissa bits.  Table derived and exhaustively verified by tools/derive_rcp14.c.
-// {intercept, slope} per segment, one 8-byte load per lookup
-static __constant__ uint2 RCP14_AB[64] = {
-    {67107072u, 1009u}, {66074112u, 977u}, {65073664u, 949u}, {64102400u, 921u},
-    {63159040u, 893u}, {62244608u, 869u}, {61354752u, 843u}, {60491264u, 821u},
-    {59650560u, 797u}, {58833920u, 777u}, {58038272u, 755u}, {57264640u, 735u},
-    {56511488u, 717u}, {55778048u, 699u}, {55062784u, 681u}, {54365184u, 663u},
-    {53686016u, 647u}, {53022976u, 631u}, {52377088u, 617u}, {51745536u, 601u},
-    {51129600u, 587u}, {50528000u, 573u}, {49940992u, 561u}, {49366272u, 547u},
-    {48805376u, 535u}, {48257024u, 523u}, {47721728u, 513u}, {47196672u, 501u},
-    {46683904u, 491u}, {46181632u, 479u}, {45690368u, 469u}, {45209344u, 459u},
-    {44739072u, 451u}, {44277504u, 441u}, {43826176u, 433u}, {43382784u, 423u},
-    {42949120u, 415u}, {42523904u, 407u}, {42106880u, 399u}, {41698048u, 391u},
-    {41297920u, 385u}, {40903936u, 377u}, {40517888u, 369u}, {40139520u, 363u},
-    {39768320u, 357u}, {39402752u, 349u}, {39044608u, 343u}, {38692864u, 337u},
-    {38347520u, 331u}, {38008064u, 325u}, {37674496u, 319u}, {37347840u, 315u},
-    {37025280u, 309u}, {36708608u, 303u}, {36398080u, 299u}, {36091648u, 293u},
-    {35791360u, 289u}, {35495680u, 285u}, {35204352u, 279u}, {34919168u, 275u},
-    {34638080u, 271u}, {34361088u, 267u}, {34088192u, 263u}, {33819392u, 259u}};
+// {intercept, slope} per segment, one 8-byte load per lookup.  The rows are a macro so that a host copy (pss_mono.hip's host twin) is the
+// same text.
+#define PSS_RCP14_ROWS \
+    {67107072u, 1009u}, {66074112u, 977u}, {65073664u, 949u}, {64102400u, 921u}, \
+    {63159040u, 893u}, {62244608u, 869u}, {61354752u, 843u}, {60491264u, 821u}, \
+    {59650560u, 797u}, {58833920u, 777u}, {58038272u, 755u}, {57264640u, 735u}, \
+    {56511488u, 717u}, {55778048u, 699u}, {55062784u, 681u}, {54365184u, 663u}, \
+    {53686016u, 647u}, {53022976u, 631u}, {52377088u, 617u}, {51745536u, 601u}, \
+    {51129600u, 587u}, {50528000u, 573u}, {49940992u, 561u}, {49366272u, 547u}, \
+    {48805376u, 535u}, {48257024u, 523u}, {47721728u, 513u}, {47196672u, 501u}, \
+    {46683904u, 491u}, {46181632u, 479u}, {45690368u, 469u}, {45209344u, 459u}, \
+    {44739072u, 451u}, {44277504u, 441u}, {43826176u, 433u}, {43382784u, 423u}, \
+    {42949120u, 415u}, {42523904u, 407u}, {42106880u, 399u}, {41698048u, 391u}, \
+    {41297920u, 385u}, {40903936u, 377u}, {40517888u, 369u}, {40139520u, 363u}, \
+    {39768320u, 357u}, {39402752u, 349u}, {39044608u, 343u}, {38692864u, 337u}, \
+    {38347520u, 331u}, {38008064u, 325u}, {37674496u, 319u}, {37347840u, 315u}, \
+    {37025280u, 309u}, {36708608u, 303u}, {36398080u, 299u}, {36091648u, 293u}, \
+    {35791360u, 289u}, {35495680u, 285u}, {35204352u, 279u}, {34919168u, 275u}, \
+    {34638080u, 271u}, {34361088u, 267u}, {34088192u, 263u}, {33819392u, 259u}
+static __constant__ uint2 RCP14_AB[64] = {PSS_RCP14_ROWS};
 
 // `tab`: the segment table — RCP14_AB itself (constant memory: a vector load of ~300 clocks even when it hits), or a copy the kernel
 // keeps in LDS (k_nfm_fwd, k_spectrum_r16<DISC>: the lookup sits in the middle of every sample's dependent chain)

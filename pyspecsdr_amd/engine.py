@@ -1034,6 +1034,71 @@ class Engine:
         sos = np.ascontiguousarray(sos, np.float64)
         self._dev(self.lib.pss_sosfilt, _ptr(d_x), n_rows, n, _ptr(sos), sos.shape[0], _ptr(d_y))
 
+    @staticmethod
+    def _ba(b, a):
+        b, a = np.ascontiguousarray(b, np.float64), np.ascontiguousarray(a, np.float64)
+        if b.ndim != 1 or a.shape != b.shape or not 2 <= len(b) <= 9:
+            raise ValueError("lfilter: b and a of the same length, 2 .. 9 coefficients each")
+        return b, a
+
+    def lfilter(self, d_x, n_rows, n, b, a, d_y):
+        """scipy.signal.lfilter(b, a, x) from a zero state on float64 rows [n_rows][n] on the device (pss_lfilter); b, a: host tables."""
+        b, a = self._ba(b, a)
+        self._dev(self.lib.pss_lfilter, _ptr(d_x), n_rows, n, _ptr(b), _ptr(a), len(b), _ptr(d_y))
+
+    @staticmethod
+    def h_lfilter(x, b, a, lib=None):
+        """pss_h_lfilter: the same on host rows (1-D or 2-D, along the last axis) -> float64.  Pure host code: needs the library, not a GPU."""
+        b, a = Engine._ba(b, a)
+        x = np.ascontiguousarray(x, np.float64)
+        y = np.empty_like(x)
+        n = x.shape[-1] if x.ndim else 0
+        if (lib or L.load()).pss_h_lfilter(_ptr(x), x.size // n if n else 0, n, _ptr(b), _ptr(a), len(b), _ptr(y)) != 0:
+            raise ValueError("pss_h_lfilter: bad arguments (a[0] must be finite and not 0)")
+        return y
+
+    # -- FM mono: decode_mono (signal_processing.py:331-359)
+    def decode_mono_len(self, n):
+        return self.lib.pss_decode_mono_len(int(n))
+
+    def decode_mono(self, d_iq, n_frames, n, fs, d_pcm=None, d_audio=None, d_dec=None):
+        """d_iq complex64 [n_frames][n] -> d_pcm int16 [n_frames][n_out], n_out = decode_mono_len(n); optional d_audio float64 (the value the
+        int16 cast sees) and d_dec float32 (the decimated row before the de-emphasis)."""
+        self._dev(self.lib.pss_decode_mono, _ptr(d_iq), n_frames, n, float(fs), _ptr(d_pcm), _ptr(d_audio), _ptr(d_dec))
+
+    @staticmethod
+    def h_decode_mono(iq, fs, stages=False, lib=None):
+        """pss_h_decode_mono: one host buffer -> int16 (n_out,); stages=True: (pcm, audio float64, dec float32).  Pure host code: the
+        kernels' statements on one thread, no GPU."""
+        lib = lib or L.load()
+        iq = np.ascontiguousarray(iq, np.complex64)
+        if iq.ndim != 1:
+            raise ValueError("samples must be a 1-D complex array")
+        n_out = lib.pss_decode_mono_len(len(iq))
+        pcm, audio, dec = np.empty(n_out, np.int16), np.empty(n_out, np.float64), np.empty(n_out, np.float32)
+        if lib.pss_h_decode_mono(_ptr(iq), len(iq), float(fs), _ptr(pcm), _ptr(audio), _ptr(dec)) != 0:
+            raise ValueError("pss_h_decode_mono: the sample rate must be finite and > 0")
+        return (pcm, audio, dec) if stages else pcm
+
+    def h_decode_mono_batch(self, frames, fs, chunk_frames=4096):
+        """frames: complex64 [n_frames][n] in host memory -> int16 [n_frames][n_out]; chunk_frames frames go through one pss_decode_mono."""
+        import torch
+        frames = np.ascontiguousarray(frames, np.complex64)
+        if frames.ndim != 2 or int(chunk_frames) < 1:
+            raise ValueError("frames: [n_frames][n]; chunk_frames >= 1")
+        nf, n = frames.shape
+        n_out = self.decode_mono_len(n)
+        pcm = np.empty((nf, n_out), np.int16)
+        if n_out == 0:
+            return pcm
+        for c0 in range(0, nf, int(chunk_frames)):
+            c = min(int(chunk_frames), nf - c0)
+            d_iq = torch.from_numpy(frames[c0:c0 + c].view(np.float32)).to(f"cuda:{self.device}")
+            d_pcm = torch.empty((c, n_out), dtype=torch.int16, device=f"cuda:{self.device}")
+            self.decode_mono(d_iq, c, n, fs, d_pcm)
+            pcm[c0:c0 + c] = d_pcm.cpu().numpy()
+        return pcm
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

@@ -394,6 +394,41 @@ def decode_recording(samples, sample_rate, decoder, frame_len=None, threshold=-2
     return out
 
 
+def decode_mono_recording(samples, fs, frame_len=32768, codes_format=None, table=None, chunk_frames=4096):
+    """Every read buffer of a recording through decode_mono (signal_processing.py:331-359) on the GPU -> int16 [n_frames][n_out], mono
+    broadcast-FM audio at fs / 6, n_out = ceil((frame_len - 1) / 6).  An incomplete tail buffer is dropped (cut_frames).  codes_format /
+    table: as demodulate_recording — `samples` is the ADC code array [n, 2], widened on the device."""
+    if int(frame_len) != frame_len or frame_len < 1 or int(chunk_frames) != chunk_frames or chunk_frames < 1:
+        raise ValueError("frame_len and chunk_frames must be integers >= 1")
+    frame_len, chunk_frames = int(frame_len), int(chunk_frames)
+    e = get_engine()
+    if codes_format is None:
+        samples = np.asarray(samples)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+        return e.h_decode_mono_batch(cut_frames(np.ascontiguousarray(samples, np.complex64), frame_len), fs, chunk_frames)
+    iq = _iq_args(codes_format, table)
+    samples = _iq_codes(samples, iq[0])
+    if samples.ndim != 2:
+        raise ValueError("codes: [n, 2]")
+    import torch
+    nf = len(samples) // frame_len
+    frames = samples[:nf * frame_len].reshape(nf, frame_len, 2)
+    n_out = e.decode_mono_len(frame_len)
+    pcm = np.empty((nf, n_out), np.int16)
+    if n_out == 0:
+        return pcm
+    for c0 in range(0, nf, chunk_frames):
+        c = min(chunk_frames, nf - c0)
+        d_codes = torch.from_numpy(np.array(frames[c0:c0 + c])).to(f"cuda:{e.device}")
+        d_iq = torch.empty((c, 2 * frame_len), dtype=torch.float32, device=f"cuda:{e.device}")
+        d_pcm = torch.empty((c, n_out), dtype=torch.int16, device=f"cuda:{e.device}")
+        e.unpack_iq(d_codes, c * frame_len, d_iq, codes_format, iq[2])
+        e.decode_mono(d_iq, c, frame_len, fs, d_pcm)
+        pcm[c0:c0 + c] = d_pcm.cpu().numpy()
+    return pcm
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:

@@ -16,6 +16,9 @@ the reference's main loop imports with `from signal_processing import *` (pyspec
     bandpass_filter(data, lowcut, highcut, sample_rate)    :34-42    -> float64 (N,)   (decoders.py:100-101)
     classify_signal(samples, sample_rate, bandwidth)       :296-322  -> label str (the reference raises NameError: see the function)
     estimate_modulation_index(samples)                     :283-293  -> np.float32
+    decode_mono(samples, fs)                               :331-359  -> int16 (n_out,), n_out = ceil((N - 1) / 6): broadcast FM, mono
+    lowpass_filter(data, cutoff, fs, order)                :28-31    -> float64, real input only (complex input: TypeError, not served)
+    butter_lowpass / butter_bandpass                       :13-25    -> (b, a): designs only, the host SciPy's own
 
 Every call runs on the GPU through the C ABI; there is no NumPy/SciPy compute path here.
 """
@@ -27,7 +30,8 @@ from .engine import Engine
 # what `from signal_processing import *` hands to the caller (pyspecsdr.py:98): the reference's public callables
 __all__ = ["bandpass_filter", "iq_correction", "mono_to_stereo", "demodulate_nfm", "demodulate_wfm", "demodulate_am",
            "demodulate_ssb", "demodulate_signal", "compute_fft", "estimate_modulation_index", "classify_signal",
-           "measure_signal_power", "DEFAULT_SAMPLE_RATE", "BUTTER_ORDER"]
+           "measure_signal_power", "decode_mono", "lowpass_filter", "butter_lowpass", "butter_bandpass", "DEFAULT_SAMPLE_RATE",
+           "BUTTER_ORDER"]
 
 DEFAULT_SAMPLE_RATE = 22050  # pyspecconst.py:3
 BUTTER_ORDER = 5             # pyspecconst.py:5
@@ -278,3 +282,41 @@ def measure_signal_power(samples):
         power = get_engine().h_mean_power_c128(samples)
         return 10 * np.log10(power + 1e-10)
     return get_engine().h_measure_power(_samples(samples))
+
+
+def decode_mono(samples, fs):
+    """signal_processing.py:331-359 -> int16 (n_out,): FM discriminator, FIR decimation by 6, 75 us de-emphasis, DC removal, int16 — mono
+    broadcast audio at fs / 6.  (An empty or one-sample buffer gives int16[0]; the reference warns about the mean of an empty slice.)"""
+    return get_engine().h_decode_mono_batch(_samples(samples)[None, :], fs, 1)[0]
+
+
+# Designs only: like every table above these are the host SciPy's own (a host that runs the reference has SciPy).
+def butter_bandpass(lowcut, highcut, fs, order=5):
+    from scipy.signal import butter
+    nyq = 0.5 * fs
+    return butter(order, [lowcut / nyq, highcut / nyq], btype='band')
+
+
+def butter_lowpass(cutoff, fs, order=5):
+    from scipy.signal import butter
+    return butter(order, cutoff / (0.5 * fs), btype='low', analog=False)
+
+
+def lowpass_filter(data, cutoff=3000, fs=DEFAULT_SAMPLE_RATE, order=5):
+    """signal_processing.py:28-31: lfilter(*butter_lowpass(cutoff, fs, order), data) on the device -> float64, along the last axis of a
+    1-D or 2-D real array (float32 input is widened first, as lfilter does).  Complex input is not served: TypeError.  order <= 8."""
+    d = np.asarray(data)
+    if np.iscomplexobj(d):
+        raise TypeError("lowpass_filter: complex input is not served (real float32 / float64 rows only)")
+    if d.ndim not in (1, 2):
+        raise ValueError("lowpass_filter: a 1-D or 2-D array, filtered along its last axis")
+    b, a = butter_lowpass(cutoff, fs, order=order)
+    x = np.ascontiguousarray(d, np.float64)
+    if x.size == 0:
+        return np.zeros(x.shape, np.float64)
+    import torch
+    e = get_engine()
+    d_x = torch.from_numpy(x).to(f"cuda:{e.device}")
+    d_y = torch.empty_like(d_x)
+    e.lfilter(d_x, x.size // x.shape[-1], x.shape[-1], b, a, d_y)
+    return d_y.cpu().numpy()
