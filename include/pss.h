@@ -686,6 +686,36 @@ int pss_decode_mono_len(int n);
 int pss_decode_mono(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, int16_t *d_pcm, double *d_audio, float *d_dec);
 int pss_h_decode_mono(const float *h_iq, int n, double fs, int16_t *h_pcm, double *h_audio, float *h_dec);
 int pss_design_deemph(double tau, double fs, double b[2], double a[2]);
+
+/* ---- digital down-converter: K channels of one capture at fs / decim (mix, low-pass FIR, decimate) ----
+ * What the reference asks its radio for (sdr.set_center_freq, sdr.sample_rate = ...) done to a capture.  The arithmetic is the project's
+ * own, stated once in csrc/pss_ddc.h (PARITY.md "down-converter"); the device and the host twin agree on every bit.
+ * pss_ddc_word: the 64-bit frequency word of offset_hz at fs, w = the integer nearest to (offset_hz / fs) 2^64 modulo 2^64, and the offset
+ *   that results, w / 2^64 fs with w read as signed (effective_hz may be NULL).  PSS_E_ARG unless fs is finite and > 0 and |offset_hz| <= fs / 2.
+ *   A signal at +offset_hz lands at 0 Hz.
+ * pss_ddc_out_len: ceil(n_capture / decim); < 0 on n_capture < 0 or decim outside [1, 4096].
+ * pss_ddc_default_taps: scipy.signal.decimate's own FIR, firwin(20 decim + 1, 1 / decim) through pss_design_firwin; decim = 1: the single
+ *   tap 1.0.  decim in [1, 204] (at most 4097 taps); *n_taps is set, taps (room for 20 decim + 1 values; NULL: only the count) is filled.
+ * pss_h_ddc_rotor: the oscillator alone, (c, s)[t] = exp(-2 pi i w (index0 + t) / 2^64), t < n; host code.
+ * pss_ddc: d_iq complex64, 8-byte aligned, holds samples [buf_index0, buf_index0 + n_buf) of a capture of n_capture samples; the phase of
+ *   a sample follows from its index in the CAPTURE, so any chunking of a capture gives the same bits.  words [n_chan], taps [n_taps]: HOST
+ *   tables, as for pss_lfilter.  Output m of channel c, y[m] = sum over k of taps[k] z[m decim + lead - k] with z the mixed capture and zero
+ *   outside [0, n_capture), goes to complex64 element c out_stride + (m - m_begin) of d_out (8-byte aligned) for m in [m_begin, m_end);
+ *   elements between rows are not touched.  lead = 0: lfilter(taps, 1, z)[::decim]; lead = (n_taps - 1) / 2 with the default taps:
+ *   scipy.signal.decimate(z, decim, ftype='fir', zero_phase=True).  Every sample of the capture that an output needs must lie in the
+ *   buffer.  PSS_E_ARG (reason in pss_last_error): decim outside [1, 4096], n_taps outside [1, 4097], n_chan < 1, lead outside
+ *   [0, n_taps - 1], a tap that is not finite, a null pointer, a buffer that is not inside the capture, [m_begin, m_end) outside
+ *   [0, ceil(n_capture / decim)], out_stride < m_end - m_begin, a needed sample outside the buffer, a misaligned device pointer.  A
+ *   refused call writes nothing.  One kernel, k_ddc (float64, mixer and FIR staged in LDS).
+ * pss_h_ddc: the same on host buffers, pure host code (no context, no GPU; the reason of a refusal: pss_last_error(NULL)). */
+int pss_ddc_word(double offset_hz, double fs, uint64_t *word, double *effective_hz);
+long pss_ddc_out_len(long n_capture, int decim);
+int pss_ddc_default_taps(int decim, double *taps, int *n_taps);
+int pss_h_ddc_rotor(uint64_t word, long index0, long n, double *c, double *s);
+int pss_ddc(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n_capture, const uint64_t *words, int n_chan, int decim,
+            const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
+int pss_h_ddc(const float *h_iq, long n_buf, long buf_index0, long n_capture, const uint64_t *words, int n_chan, int decim,
+              const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -172,6 +172,12 @@ _SIGS = {
     "pss_decode_mono": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, _p]),
     "pss_h_decode_mono": (C.c_int, [_p, C.c_int, C.c_double, _p, _p, _p]),
     "pss_design_deemph": (C.c_int, [C.c_double, C.c_double, _p, _p]),
+    "pss_ddc_word": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "pss_ddc_out_len": (C.c_long, [C.c_long, C.c_int]),
+    "pss_ddc_default_taps": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
+    "pss_h_ddc_rotor": (C.c_int, [C.c_uint64, C.c_long, C.c_long, _p, _p]),
+    "pss_ddc": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, _p, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_h_ddc": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, _p, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

@@ -101,6 +101,11 @@ struct pss_ctx {
     void *sq_buf[3] = {};
     size_t sq_cap[3] = {};
     void *sq_pin = nullptr;
+    // down-converter (pss_ddc.hip): the device copy of the call's host tables (rotor knots, taps, frequency words), grow-only, and the bytes
+    // it holds — a call with the same tables as the last one uploads nothing
+    void *ddc_tab = nullptr;
+    size_t ddc_tab_bytes = 0;
+    std::vector<unsigned char> ddc_host;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;

@@ -1099,6 +1099,75 @@ class Engine:
             pcm[c0:c0 + c] = d_pcm.cpu().numpy()
         return pcm
 
+    # -- digital down-converter: K channels of a capture at fs / decim (pss_ddc; the arithmetic: csrc/pss_ddc.h)
+    @staticmethod
+    def ddc_word(offset_hz, fs, lib=None):
+        """pss_ddc_word -> (word, effective_hz): the 64-bit frequency word of offset_hz at fs and the offset that results.  Host code."""
+        w, eff = C.c_uint64(), C.c_double()
+        if (lib or L.load()).pss_ddc_word(float(offset_hz), float(fs), C.byref(w), C.byref(eff)) != 0:
+            raise ValueError("ddc_word: fs must be finite and > 0 and |offset_hz| <= fs / 2")
+        return w.value, eff.value
+
+    @staticmethod
+    def ddc_default_taps(decim, lib=None):
+        """pss_ddc_default_taps: scipy.signal.decimate's FIR, firwin(20 decim + 1, 1 / decim); decim = 1: [1.0].  Host code."""
+        lib = lib or L.load()
+        n = C.c_int()
+        if lib.pss_ddc_default_taps(int(decim), None, C.byref(n)) != 0:
+            raise ValueError("ddc_default_taps: decim outside [1, 204]; pass taps for a larger decimation")
+        taps = np.empty(n.value, np.float64)
+        r = lib.pss_ddc_default_taps(int(decim), _ptr(taps), C.byref(n))
+        if r != 0:
+            raise PssError(r, "pss_ddc_default_taps")
+        return taps
+
+    @staticmethod
+    def h_ddc_rotor(word, index0, n, lib=None):
+        """pss_h_ddc_rotor -> (c, s) float64 [n]: the oscillator exp(-2 pi i word (index0 + t) / 2^64).  Host code."""
+        lib = lib or L.load()
+        c, s = np.empty(int(n), np.float64), np.empty(int(n), np.float64)
+        if lib.pss_h_ddc_rotor(int(word) & (2 ** 64 - 1), int(index0), int(n), _ptr(c), _ptr(s)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return c, s
+
+    @staticmethod
+    def _ddc_args(lib, n_buf, words, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
+        """The defaults of ddc / h_ddc -> (words, taps, the integer arguments in the C order behind them)."""
+        if not (isinstance(words, np.ndarray) and words.dtype == np.uint64):   # Python integers: NumPy would take a mixed list through float64
+            words = np.array([int(w) & (2 ** 64 - 1) for w in np.atleast_1d(np.asarray(words, object))], np.uint64)
+        words = np.ascontiguousarray(np.atleast_1d(words), np.uint64)
+        taps = Engine.ddc_default_taps(decim, lib) if taps is None else np.ascontiguousarray(np.atleast_1d(taps), np.float64)
+        if words.ndim != 1 or taps.ndim != 1:
+            raise ValueError("words and taps: 1-D tables")
+        n_capture = int(n_buf) if n_capture is None else int(n_capture)
+        n_out = lib.pss_ddc_out_len(n_capture, int(decim))
+        lead = (len(taps) - 1) // 2 if lead is None else int(lead)
+        m_begin = int(m_begin)
+        m_end = max(n_out, 0) if m_end is None else int(m_end)
+        out_stride = m_end - m_begin if out_stride is None else int(out_stride)
+        return words, taps, (int(n_buf), int(buf_index0), n_capture), (len(words), int(decim)), (len(taps), lead, m_begin, m_end), out_stride
+
+    def ddc(self, d_iq, n_buf, words, decim, d_out, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, out_stride=None):
+        """d_iq complex64: samples [buf_index0, buf_index0 + n_buf) of a capture of n_capture samples (default: the buffer is the capture)
+        -> d_out complex64, output m of channel c at element c * out_stride + (m - m_begin), m in [m_begin, m_end) (default: all
+        n_out = ceil(n_capture / decim), rows back to back).  words: the channels' frequency words (ddc_word); taps: host float64 table
+        (default: ddc_default_taps(decim)); lead: the tap that sits on the output's own sample (default (len(taps) - 1) // 2: zero phase)."""
+        words, taps, a, b, c, out_stride = self._ddc_args(self.lib, n_buf, words, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride)
+        self._dev(self.lib.pss_ddc, _ptr(d_iq), *a, _ptr(words), *b, _ptr(taps), *c, _ptr(d_out), out_stride)
+
+    @staticmethod
+    def h_ddc(iq, words, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_ddc: the same on a host buffer -> complex64 [K][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        iq = np.ascontiguousarray(iq, np.complex64)
+        if iq.ndim != 1:
+            raise ValueError("iq: a 1-D complex buffer")
+        words, taps, a, b, c, stride = Engine._ddc_args(lib, len(iq), words, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
+        out = np.empty((len(words), max(stride, 0)), np.complex64)
+        if lib.pss_h_ddc(_ptr(iq), *a, _ptr(words), *b, _ptr(taps), *c, _ptr(out), stride) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

@@ -429,6 +429,105 @@ def decode_mono_recording(samples, fs, frame_len=32768, codes_format=None, table
     return pcm
 
 
+def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, codes_format, table, m_end=None):
+    """tune_recording's work -> (device tensor float32 [K][2 * m_end], effective offsets): the capture goes up in chunks of about
+    chunk_samples samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place
+    of the one result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit."""
+    import torch
+    e = get_engine()
+    fs, decim = float(fs), int(decim)
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+    else:
+        samples = np.ascontiguousarray(samples, np.complex64)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+    pairs = [e.ddc_word(f, fs) for f in np.atleast_1d(np.asarray(offsets_hz, np.float64))]
+    words, effective = np.array([p[0] for p in pairs], np.uint64), np.array([p[1] for p in pairs], np.float64)
+    taps = e.ddc_default_taps(decim) if taps is None else np.ascontiguousarray(taps, np.float64)
+    n_taps = len(taps)
+    lead = (n_taps - 1) // 2 if lead is None else int(lead)
+    n = len(samples)
+    n_out = e.lib.pss_ddc_out_len(n, decim)
+    if n_out < 0:
+        raise ValueError("decim outside [1, 4096]")
+    if m_end is None:
+        m_end = n_out
+    dev = f"cuda:{e.device}"
+    d_out = torch.empty((len(words), 2 * m_end), dtype=torch.float32, device=dev)
+    per_chunk = max(1, int(chunk_samples) // decim)
+    for m0 in range(0, max(m_end, 1), per_chunk):
+        m1 = min(m_end, m0 + per_chunk)
+        lo, hi = max(0, m0 * decim + lead - (n_taps - 1)), min(n, (m1 - 1) * decim + lead + 1)
+        hi = max(hi, lo)
+        if codes_format is not None:
+            d_codes = torch.from_numpy(np.array(samples[lo:hi])).to(dev)
+            d_iq = torch.empty(2 * (hi - lo) + 2, dtype=torch.float32, device=dev)
+            if hi > lo:
+                e.unpack_iq(d_codes, hi - lo, d_iq, codes_format, iq[2])
+        else:
+            d_iq = torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev) if hi > lo else torch.empty(2, dtype=torch.float32, device=dev)
+        # m1 == m0 (an empty capture) still goes through the call: it checks the arguments and writes nothing
+        e.ddc(d_iq, hi - lo, words, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
+              out_stride=m_end)
+    return d_out, effective
+
+
+def tune_recording(samples, fs, offsets_hz, decim, taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None):
+    """What the reference asks its radio for — another centre frequency (sdr.set_center_freq: the arrow keys, bookmarks, band presets,
+    both sweeps) and another sample rate (sdr.sample_rate = 48000 before the Morse decoder reads, pyspecsdr.py:552; the bandwidth keys) —
+    done to a capture: the K channels at fs + offsets_hz, low-pass filtered and decimated by `decim` on the GPU (pss_ddc) ->
+    (channels complex64 [K][ceil(n / decim)], fs / decim, effective_offsets float64 [K]).  A signal at +offset lands at 0 Hz; the
+    offsets that result differ from the asked ones by less than fs / 2^64.  taps: a float64 low-pass table (default:
+    scipy.signal.decimate's own FIR, firwin(20 decim + 1, 1 / decim); needs decim <= 204); lead: the tap that sits on an output's own
+    sample (default the middle one: zero phase, scipy.signal.decimate(..., ftype='fir')).  The capture is streamed in chunks of
+    chunk_samples samples plus the halos the taps need; the result does not depend on chunk_samples.  codes_format / table: as
+    demodulate_recording — `samples` is the ADC code array [n, 2], widened per chunk on the device."""
+    d_out, effective = _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, codes_format, table)
+    return d_out.cpu().numpy().view(np.complex64), float(fs) / int(decim), effective
+
+
+def demodulate_channels(samples, fs, offsets_hz, decim, mode='NFM', frame_len=32768, **tune_kw):
+    """Listen to K channels of one wideband capture: tune_recording's channels, cut into read buffers of frame_len samples at fs / decim
+    and demodulated as demodulate_signal would -> int16 [K][n_frames][n_out][2].  The down-converter stops at a multiple of frame_len
+    (an incomplete tail buffer is dropped, as cut_frames does), so its result IS the batch of K * n_frames read buffers on the device:
+    nothing comes back to the host between the two steps.  tune_kw: taps, lead, chunk_samples, codes_format, table."""
+    import torch
+    if mode not in _MODES:
+        raise ValueError(f"unknown demodulation mode {mode!r}")
+    if int(frame_len) != frame_len or frame_len < 1:
+        raise ValueError("frame_len must be an integer >= 1")
+    frame_len, decim = int(frame_len), int(decim)
+    e = get_engine()
+    n_total = e.lib.pss_ddc_out_len(len(samples), decim)
+    if n_total < 0:
+        raise ValueError("decim outside [1, 4096]")
+    n_frames = n_total // frame_len
+    rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(fs) / decim
+    if mode != 'AM':
+        _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), rate)
+    n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
+    if n_out < 0:
+        raise ValueError("the channel rate fs / decim is below the target rate")
+    kw = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
+    for k in tune_kw:
+        if k not in kw:
+            raise TypeError(f"unexpected argument {k!r}")
+    kw.update(tune_kw)
+    d_iq, _ = _tune_device(samples, fs, offsets_hz, decim, kw['taps'], kw['lead'], kw['chunk_samples'], kw['codes_format'], kw['table'],
+                           m_end=n_frames * frame_len)
+    k = d_iq.shape[0]
+    d_pcm = torch.empty((k * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
+    if k * n_frames:
+        e.demod_signal(_MODES[mode], d_iq, k * n_frames, frame_len, rate, d_pcm)
+    return d_pcm.cpu().numpy().reshape(k, n_frames, n_out, 2)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
