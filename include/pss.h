@@ -716,6 +716,29 @@ int pss_ddc(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n
             const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
 int pss_h_ddc(const float *h_iq, long n_buf, long buf_index0, long n_capture, const uint64_t *words, int n_chan, int decim,
               const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
+/* ---- polyphase channeliser: EVERY channel of a uniform grid of n_chan channels, fs / n_chan apart, of one capture at fs / decim ----
+ * What the reference's scan_frequencies and band sweep step their tuner through, done to a capture in one pass.  Row c of the output is
+ * the channel at c fs / n_chan for c < n_chan / 2 and at (c - n_chan) fs / n_chan otherwise (row n_chan / 2: the band edge); output m of
+ * row c is y_c[m] = sum over k of taps[k] x[j] exp(-2 pi i c j / n_chan), j = m decim + lead - k, x zero outside [0, n_capture) — what
+ * pss_ddc computes for the word c 2^64 / n_chan, evaluated as n_chan branch sums and one n_chan-point DFT per output instant.  The
+ * arithmetic is the project's own, stated once in csrc/pss_pfb.h (PARITY.md "channeliser"); the device and the host twin agree on every
+ * bit of every finite sample (the sign of a zero is not part of the contract).
+ * pss_pfb_default_taps: firwin(20 n_chan + 1, 1 / n_chan) through pss_design_firwin; *n_taps is set, taps (room for 20 n_chan + 1
+ *   values; NULL: only the count) is filled.  PSS_E_ARG unless n_chan is a power of two in [2, 1024].
+ * pss_pfb: buffer and output conventions are pss_ddc's: d_iq complex64, 8-byte aligned, holds samples [buf_index0, buf_index0 + n_buf) of
+ *   a capture of n_capture samples; the phase of a sample follows from its index in the CAPTURE, so any chunking of a capture gives the same
+ *   bits.  taps [n_taps]: a HOST table, uploaded when its bytes differ from the last call's.  Output m of row c goes to complex64 element
+ *   c out_stride + (m - m_begin) of d_out (8-byte aligned) for m in [m_begin, m_end); n_out = pss_ddc_out_len(n_capture, decim).  decim
+ *   need not divide n_chan.  PSS_E_ARG (reason in pss_last_error): n_chan not a power of two in [2, 1024], decim outside [1, n_chan],
+ *   n_taps outside [1, 32 n_chan], lead outside [0, n_taps - 1], a tap that is not finite, a null or misaligned pointer, a buffer that is
+ *   not inside the capture, [m_begin, m_end) outside [0, n_out], out_stride < m_end - m_begin, a needed sample outside the buffer.  A
+ *   refused call writes nothing.  One kernel, k_pfb (float64: chains in registers, DFT and transpose in LDS).
+ * pss_h_pfb: the same on host buffers, pure host code (no context, no GPU; the reason of a refusal: pss_last_error(NULL)). */
+int pss_pfb_default_taps(int n_chan, double *taps, int *n_taps);
+int pss_pfb(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
+            const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
+int pss_h_pfb(const float *h_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
+              const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -176,6 +176,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     for (auto &b : ctx->sq_buf) if (b) hipFree(b);
     if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
     if (ctx->ddc_tab) hipFree(ctx->ddc_tab);
+    if (ctx->pfb_tab) hipFree(ctx->pfb_tab);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

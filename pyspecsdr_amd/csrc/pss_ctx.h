@@ -106,6 +106,10 @@ struct pss_ctx {
     void *ddc_tab = nullptr;
     size_t ddc_tab_bytes = 0;
     std::vector<unsigned char> ddc_host;
+    // polyphase channeliser (pss_pfb.hip): the same for its tables (rotor knots, taps)
+    void *pfb_tab = nullptr;
+    size_t pfb_tab_bytes = 0;
+    std::vector<unsigned char> pfb_host;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;

@@ -1168,6 +1168,56 @@ class Engine:
             raise ValueError(lib.pss_last_error(None).decode())
         return out
 
+    # -- polyphase channeliser: every channel of a uniform grid of n_chan channels at fs / decim (pss_pfb; the arithmetic: csrc/pss_pfb.h)
+    @staticmethod
+    def pfb_default_taps(n_chan, lib=None):
+        """pss_pfb_default_taps: firwin(20 n_chan + 1, 1 / n_chan), n_chan a power of two in [2, 1024].  Host code."""
+        lib = lib or L.load()
+        n = C.c_int()
+        if lib.pss_pfb_default_taps(int(n_chan), None, C.byref(n)) != 0:
+            raise ValueError("pfb_default_taps: n_chan must be a power of two in [2, 1024]")
+        taps = np.empty(n.value, np.float64)
+        r = lib.pss_pfb_default_taps(int(n_chan), _ptr(taps), C.byref(n))
+        if r != 0:
+            raise PssError(r, "pss_pfb_default_taps")
+        return taps
+
+    @staticmethod
+    def _pfb_args(lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
+        """The defaults of pfb / h_pfb -> (taps, the integer arguments in the C order either side of them)."""
+        taps = Engine.pfb_default_taps(n_chan, lib) if taps is None else np.ascontiguousarray(np.atleast_1d(taps), np.float64)
+        if taps.ndim != 1:
+            raise ValueError("taps: a 1-D table")
+        n_capture = int(n_buf) if n_capture is None else int(n_capture)
+        n_out = lib.pss_ddc_out_len(n_capture, int(decim)) if 1 <= int(decim) <= 4096 else 0
+        lead = (len(taps) - 1) // 2 if lead is None else int(lead)
+        m_begin = int(m_begin)
+        m_end = max(n_out, 0) if m_end is None else int(m_end)
+        out_stride = m_end - m_begin if out_stride is None else int(out_stride)
+        return taps, (int(n_buf), int(buf_index0), n_capture, int(n_chan), int(decim)), (len(taps), lead, m_begin, m_end), out_stride
+
+    def pfb(self, d_iq, n_buf, n_chan, decim, d_out, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, out_stride=None):
+        """d_iq complex64: samples [buf_index0, buf_index0 + n_buf) of a capture of n_capture samples (default: the buffer is the capture)
+        -> d_out complex64 [n_chan] rows, output m of row c at element c * out_stride + (m - m_begin), m in [m_begin, m_end) (default: all
+        n_out = ceil(n_capture / decim), rows back to back).  Row c is the channel at c fs / n_chan (c < n_chan / 2) or (c - n_chan) fs /
+        n_chan.  taps: host float64 table (default: pfb_default_taps(n_chan)); lead: the tap that sits on the output's own sample (default
+        (len(taps) - 1) // 2: zero phase)."""
+        taps, a, b, out_stride = self._pfb_args(self.lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride)
+        self._dev(self.lib.pss_pfb, _ptr(d_iq), *a, _ptr(taps), *b, _ptr(d_out), out_stride)
+
+    @staticmethod
+    def h_pfb(iq, n_chan, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_pfb: the same on a host buffer -> complex64 [n_chan][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        iq = np.ascontiguousarray(iq, np.complex64)
+        if iq.ndim != 1:
+            raise ValueError("iq: a 1-D complex buffer")
+        taps, a, b, stride = Engine._pfb_args(lib, len(iq), n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
+        out = np.empty((max(int(n_chan), 0), max(stride, 0)), np.complex64)
+        if lib.pss_h_pfb(_ptr(iq), *a, _ptr(taps), *b, _ptr(out), stride) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

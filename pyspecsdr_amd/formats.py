@@ -528,6 +528,115 @@ def demodulate_channels(samples, fs, offsets_hz, decim, mode='NFM', frame_len=32
     return d_pcm.cpu().numpy().reshape(k, n_frames, n_out, 2)
 
 
+def bank_offsets(fs, n_chan):
+    """The offset in Hz of each row of the channeliser's output -> float64 [n_chan]: c fs / n_chan for c < n_chan / 2 and
+    (c - n_chan) fs / n_chan otherwise (row n_chan / 2, the band edge, reads -fs / 2)."""
+    n_chan = int(n_chan)
+    if n_chan < 2 or n_chan > 1024 or n_chan & (n_chan - 1):
+        raise ValueError("n_chan must be a power of two in [2, 1024]")
+    c = np.arange(n_chan, dtype=np.float64)
+    return np.where(c < n_chan // 2, c, c - n_chan) * (float(fs) / n_chan)
+
+
+def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format, table, m_end=None):
+    """channelize_recording's work -> device tensor float32 [n_chan][2 * m_end]: the capture goes up in chunks of about chunk_samples
+    samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place of the one
+    result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit."""
+    import torch
+    e = get_engine()
+    n_chan = int(n_chan)
+    bank_offsets(1.0, n_chan)
+    decim = n_chan // 2 if decim is None else int(decim)
+    if decim < 1 or decim > n_chan:
+        raise ValueError("decim outside [1, n_chan]")
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+    else:
+        samples = np.ascontiguousarray(samples, np.complex64)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+    taps = e.pfb_default_taps(n_chan) if taps is None else np.ascontiguousarray(taps, np.float64)
+    n_taps = len(taps)
+    lead = (n_taps - 1) // 2 if lead is None else int(lead)
+    n = len(samples)
+    n_out = e.lib.pss_ddc_out_len(n, decim)
+    if m_end is None:
+        m_end = n_out
+    dev = f"cuda:{e.device}"
+    d_out = torch.empty((n_chan, 2 * m_end), dtype=torch.float32, device=dev)
+    per_chunk = max(1, int(chunk_samples) // decim)
+    for m0 in range(0, max(m_end, 1), per_chunk):
+        m1 = min(m_end, m0 + per_chunk)
+        lo, hi = max(0, m0 * decim + lead - (n_taps - 1)), min(n, (m1 - 1) * decim + lead + 1)
+        hi = max(hi, lo)
+        if codes_format is not None:
+            d_codes = torch.from_numpy(np.array(samples[lo:hi])).to(dev)
+            d_iq = torch.empty(2 * (hi - lo) + 2, dtype=torch.float32, device=dev)
+            if hi > lo:
+                e.unpack_iq(d_codes, hi - lo, d_iq, codes_format, iq[2])
+        else:
+            d_iq = torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev) if hi > lo else torch.empty(2, dtype=torch.float32, device=dev)
+        # m1 == m0 (an empty capture) still goes through the call: it checks the arguments and writes nothing
+        e.pfb(d_iq, hi - lo, n_chan, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
+              out_stride=m_end)
+    return d_out, decim
+
+
+def channelize_recording(samples, fs, n_chan, decim=None, taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None):
+    """What the reference's scan_frequencies and band sweep step their tuner through (pyspecsdr.py:1022-1093, :2523-2578) — a uniform grid
+    of centre frequencies — done to a capture in one pass: all n_chan channels, fs / n_chan apart, low-pass filtered and decimated by
+    `decim` on the GPU (pss_pfb, a polyphase filter bank) -> (channels complex64 [n_chan][ceil(n / decim)], offsets_hz float64 [n_chan]
+    (bank_offsets), fs / decim).  A signal at fs + offsets_hz[c] lands at 0 Hz of row c; row c equals tune_recording's channel at that
+    offset up to the two statements' rounding.  n_chan: a power of two in [2, 1024]; decim in [1, n_chan] (default n_chan // 2, the 2x
+    oversampled bank; n_chan: critically sampled).  taps: a float64 low-pass table of at most 32 n_chan taps (default firwin(20 n_chan +
+    1, 1 / n_chan)); lead: the tap that sits on an output's own sample (default the middle one: zero phase).  The capture is streamed in
+    chunks of chunk_samples samples plus the halos the taps need; the result does not depend on chunk_samples.  codes_format / table: as
+    demodulate_recording — `samples` is the ADC code array [n, 2], widened per chunk on the device."""
+    d_out, decim = _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format, table)
+    return d_out.cpu().numpy().view(np.complex64), bank_offsets(fs, n_chan), float(fs) / decim
+
+
+def demodulate_bank(samples, fs, n_chan, decim=None, mode='NFM', frame_len=32768, **kw):
+    """Listen to every channel of the grid: channelize_recording's rows, cut into read buffers of frame_len samples at fs / decim and
+    demodulated as demodulate_signal would -> int16 [n_chan][n_frames][n_out][2].  The bank stops at a multiple of frame_len (an incomplete
+    tail buffer is dropped, as cut_frames does), so its result IS the batch of n_chan * n_frames read buffers on the device: nothing comes
+    back to the host between the two steps.  kw: taps, lead, chunk_samples, codes_format, table."""
+    import torch
+    if mode not in _MODES:
+        raise ValueError(f"unknown demodulation mode {mode!r}")
+    if int(frame_len) != frame_len or frame_len < 1:
+        raise ValueError("frame_len must be an integer >= 1")
+    frame_len, n_chan = int(frame_len), int(n_chan)
+    bank_offsets(1.0, n_chan)
+    decim = n_chan // 2 if decim is None else int(decim)
+    if decim < 1 or decim > n_chan:
+        raise ValueError("decim outside [1, n_chan]")
+    e = get_engine()
+    n_frames = e.lib.pss_ddc_out_len(len(samples), decim) // frame_len
+    rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(fs) / decim
+    if mode != 'AM':
+        _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), rate)
+    n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
+    if n_out < 0:
+        raise ValueError("the channel rate fs / decim is below the target rate")
+    opts = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
+    for k in kw:
+        if k not in opts:
+            raise TypeError(f"unexpected argument {k!r}")
+    opts.update(kw)
+    d_iq, _ = _bank_device(samples, n_chan, decim, opts['taps'], opts['lead'], opts['chunk_samples'], opts['codes_format'], opts['table'],
+                           m_end=n_frames * frame_len)
+    d_pcm = torch.empty((n_chan * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
+    if n_frames:
+        e.demod_signal(_MODES[mode], d_iq, n_chan * n_frames, frame_len, rate, d_pcm)
+    return d_pcm.cpu().numpy().reshape(n_chan, n_frames, n_out, 2)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
