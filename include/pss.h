@@ -739,6 +739,27 @@ int pss_pfb(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n
             const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
 int pss_h_pfb(const float *h_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
               const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
+/* ---- channeliser for band plans: the same for every n_chan = 2^a 3^b 5^c in [2, 1024] (25 kHz, 12.5 kHz and 10 kHz grids at 2.4 and
+ * 10 MS/s: 96, 192, 240, 400, 800, 1000 channels) — what the reference's memory-channel mode steps its tuner through, done to a capture.
+ * Row c of the output is the channel at c fs / n_chan for c <= (n_chan - 1) / 2 and at (c - n_chan) fs / n_chan otherwise (odd n_chan
+ * has no band-edge row); output m of row c is the sum pss_pfb states, evaluated as n_chan branch sums (pss_pfb's, with a true modulo for
+ * the first tap) and one mixed-radix n_chan-point DFT per output instant: radix 5, 3 and 2 stages in that order, twiddles from a table of
+ * n_chan entries.  The arithmetic is stated once in csrc/pss_bank.h (PARITY.md "channeliser for band plans"); the device and the host
+ * twin agree on every bit of every finite sample (the sign of a zero is not part of the contract).
+ * A power-of-two n_chan is DELEGATED: after the arguments have passed the checks below, all three calls hand it to pss_pfb_default_taps /
+ * pss_pfb / pss_h_pfb, so its bytes are pss_pfb's by construction.
+ * pss_bank_default_taps: firwin(20 n_chan + 1, 1 / n_chan) through pss_design_firwin; *n_taps is set, taps (room for 20 n_chan + 1
+ *   values; NULL: only the count) is filled.  PSS_E_ARG unless n_chan = 2^a 3^b 5^c in [2, 1024].
+ * pss_bank: the arguments, the buffer and output conventions and the refusals are pss_pfb's, with "n_chan not of the form 2^a 3^b 5^c in
+ *   [2, 1024]" in place of the power-of-two rule: decim in [1, n_chan] (it need not divide n_chan), at most 32 n_chan taps.  The reason of
+ *   a refusal starts with "pss_bank: "; a refused call writes nothing.  One kernel, k_bank (float64: chains in registers, DFT and
+ *   transpose in LDS); the device copy of the tables (twiddles, taps, digit reversal) is kept on the context.
+ * pss_h_bank: the same on host buffers, pure host code (no context, no GPU; the reason of a refusal: pss_last_error(NULL), "pss_h_bank: "). */
+int pss_bank_default_taps(int n_chan, double *taps, int *n_taps);
+int pss_bank(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
+             const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
+int pss_h_bank(const float *h_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
+               const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -181,6 +181,9 @@ _SIGS = {
     "pss_pfb_default_taps": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
     "pss_pfb": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
     "pss_h_pfb": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_bank_default_taps": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
+    "pss_bank": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_h_bank": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

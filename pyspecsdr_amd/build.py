@@ -32,6 +32,7 @@ UNITS = [
     ("pss_mono.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # decode_mono and lfilter: NumPy's / SciPy's float32 and float64 operations one by one
     ("pss_ddc.hip", ["-ffp-contract=off"]),   # the down-converter: every fused multiply-add is written as fma, nothing else is fused
     ("pss_pfb.hip", ["-ffp-contract=off"]),   # the polyphase channeliser: the same rule
+    ("pss_bank.hip", ["-ffp-contract=off"]),   # the channeliser for 2^a 3^b 5^c grids: the same rule
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("pss_decode.cpp", ["-x", "hip", "-ffp-contract=off"]),   # host only: the decoders' per-message halves

@@ -110,6 +110,10 @@ struct pss_ctx {
     void *pfb_tab = nullptr;
     size_t pfb_tab_bytes = 0;
     std::vector<unsigned char> pfb_host;
+    // channeliser for band plans (pss_bank.hip): the same for its tables (twiddles of M, taps, digit reversal)
+    void *bank_tab = nullptr;
+    size_t bank_tab_bytes = 0;
+    std::vector<unsigned char> bank_host;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;

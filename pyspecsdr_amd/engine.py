@@ -1218,6 +1218,47 @@ class Engine:
             raise ValueError(lib.pss_last_error(None).decode())
         return out
 
+    # -- channeliser for band plans: the same for every n_chan = 2^a 3^b 5^c in [2, 1024] (pss_bank; the arithmetic: csrc/pss_bank.h)
+    @staticmethod
+    def bank_default_taps(n_chan, lib=None):
+        """pss_bank_default_taps: firwin(20 n_chan + 1, 1 / n_chan), n_chan = 2^a 3^b 5^c in [2, 1024].  Host code."""
+        lib = lib or L.load()
+        n = C.c_int()
+        if lib.pss_bank_default_taps(int(n_chan), None, C.byref(n)) != 0:
+            raise ValueError("bank_default_taps: n_chan must be of the form 2^a 3^b 5^c in [2, 1024]")
+        taps = np.empty(n.value, np.float64)
+        r = lib.pss_bank_default_taps(int(n_chan), _ptr(taps), C.byref(n))
+        if r != 0:
+            raise PssError(r, "pss_bank_default_taps")
+        return taps
+
+    @staticmethod
+    def _bank_args(lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
+        """The defaults of bank / h_bank: _pfb_args' with bank_default_taps."""
+        if taps is None:
+            taps = Engine.bank_default_taps(n_chan, lib)
+        return Engine._pfb_args(lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride)
+
+    def bank(self, d_iq, n_buf, n_chan, decim, d_out, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, out_stride=None):
+        """pfb for any n_chan = 2^a 3^b 5^c in [2, 1024] (pss_bank): the same arguments and layout.  Row c is the channel at c fs / n_chan
+        (c <= (n_chan - 1) / 2) or (c - n_chan) fs / n_chan.  taps default: bank_default_taps(n_chan).  A power-of-two n_chan runs
+        pss_pfb's code."""
+        taps, a, b, out_stride = self._bank_args(self.lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride)
+        self._dev(self.lib.pss_bank, _ptr(d_iq), *a, _ptr(taps), *b, _ptr(d_out), out_stride)
+
+    @staticmethod
+    def h_bank(iq, n_chan, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_bank: the same on a host buffer -> complex64 [n_chan][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        iq = np.ascontiguousarray(iq, np.complex64)
+        if iq.ndim != 1:
+            raise ValueError("iq: a 1-D complex buffer")
+        taps, a, b, stride = Engine._bank_args(lib, len(iq), n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
+        out = np.empty((max(int(n_chan), 0), max(stride, 0)), np.complex64)
+        if lib.pss_h_bank(_ptr(iq), *a, _ptr(taps), *b, _ptr(out), stride) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

@@ -538,14 +538,16 @@ def bank_offsets(fs, n_chan):
     return np.where(c < n_chan // 2, c, c - n_chan) * (float(fs) / n_chan)
 
 
-def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format, table, m_end=None):
+def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format, table, m_end=None, entry='pfb'):
     """channelize_recording's work -> device tensor float32 [n_chan][2 * m_end]: the capture goes up in chunks of about chunk_samples
     samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place of the one
-    result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit."""
+    result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit.  entry: 'pfb' (pss_pfb, n_chan a
+    power of two) or 'bank' (pss_bank, n_chan = 2^a 3^b 5^c) — the streaming is the same."""
     import torch
     e = get_engine()
     n_chan = int(n_chan)
-    bank_offsets(1.0, n_chan)
+    offsets, default_taps, run = {'pfb': (bank_offsets, e.pfb_default_taps, e.pfb), 'bank': (plan_offsets, e.bank_default_taps, e.bank)}[entry]
+    offsets(1.0, n_chan)
     decim = n_chan // 2 if decim is None else int(decim)
     if decim < 1 or decim > n_chan:
         raise ValueError("decim outside [1, n_chan]")
@@ -560,7 +562,7 @@ def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format
         samples = np.ascontiguousarray(samples, np.complex64)
         if samples.ndim != 1:
             raise ValueError("samples: a 1-D recording")
-    taps = e.pfb_default_taps(n_chan) if taps is None else np.ascontiguousarray(taps, np.float64)
+    taps = default_taps(n_chan) if taps is None else np.ascontiguousarray(taps, np.float64)
     n_taps = len(taps)
     lead = (n_taps - 1) // 2 if lead is None else int(lead)
     n = len(samples)
@@ -582,8 +584,8 @@ def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format
         else:
             d_iq = torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev) if hi > lo else torch.empty(2, dtype=torch.float32, device=dev)
         # m1 == m0 (an empty capture) still goes through the call: it checks the arguments and writes nothing
-        e.pfb(d_iq, hi - lo, n_chan, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
-              out_stride=m_end)
+        run(d_iq, hi - lo, n_chan, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
+            out_stride=m_end)
     return d_out, decim
 
 
@@ -601,21 +603,25 @@ def channelize_recording(samples, fs, n_chan, decim=None, taps=None, lead=None, 
     return d_out.cpu().numpy().view(np.complex64), bank_offsets(fs, n_chan), float(fs) / decim
 
 
-def demodulate_bank(samples, fs, n_chan, decim=None, mode='NFM', frame_len=32768, **kw):
-    """Listen to every channel of the grid: channelize_recording's rows, cut into read buffers of frame_len samples at fs / decim and
-    demodulated as demodulate_signal would -> int16 [n_chan][n_frames][n_out][2].  The bank stops at a multiple of frame_len (an incomplete
-    tail buffer is dropped, as cut_frames does), so its result IS the batch of n_chan * n_frames read buffers on the device: nothing comes
-    back to the host between the two steps.  kw: taps, lead, chunk_samples, codes_format, table."""
+def _demodulate_rows(samples, fs, n_chan, decim, mode, frame_len, kw, entry, rows=None):
+    """demodulate_bank's and monitor_channels' work -> (int16 [K][n_frames][n_out][2], decim): the bank (_bank_device through `entry`)
+    stops at a multiple of frame_len, `rows` of its result (None: all n_chan) are gathered on the device and demodulated as one batch of
+    K * n_frames read buffers.  kw: taps, lead, chunk_samples, codes_format, table."""
     import torch
     if mode not in _MODES:
         raise ValueError(f"unknown demodulation mode {mode!r}")
     if int(frame_len) != frame_len or frame_len < 1:
         raise ValueError("frame_len must be an integer >= 1")
     frame_len, n_chan = int(frame_len), int(n_chan)
-    bank_offsets(1.0, n_chan)
+    {'pfb': bank_offsets, 'bank': plan_offsets}[entry](1.0, n_chan)
     decim = n_chan // 2 if decim is None else int(decim)
     if decim < 1 or decim > n_chan:
         raise ValueError("decim outside [1, n_chan]")
+    opts = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
+    for k in kw:
+        if k not in opts:
+            raise TypeError(f"unexpected argument {k!r}")
+    opts.update(kw)
     e = get_engine()
     n_frames = e.lib.pss_ddc_out_len(len(samples), decim) // frame_len
     rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(fs) / decim
@@ -624,17 +630,110 @@ def demodulate_bank(samples, fs, n_chan, decim=None, mode='NFM', frame_len=32768
     n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
     if n_out < 0:
         raise ValueError("the channel rate fs / decim is below the target rate")
-    opts = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
-    for k in kw:
-        if k not in opts:
-            raise TypeError(f"unexpected argument {k!r}")
-    opts.update(kw)
     d_iq, _ = _bank_device(samples, n_chan, decim, opts['taps'], opts['lead'], opts['chunk_samples'], opts['codes_format'], opts['table'],
-                           m_end=n_frames * frame_len)
-    d_pcm = torch.empty((n_chan * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
-    if n_frames:
-        e.demod_signal(_MODES[mode], d_iq, n_chan * n_frames, frame_len, rate, d_pcm)
-    return d_pcm.cpu().numpy().reshape(n_chan, n_frames, n_out, 2)
+                           m_end=n_frames * frame_len, entry=entry)
+    if rows is not None:
+        d_iq = d_iq.index_select(0, torch.from_numpy(rows).to(d_iq.device))
+    k = d_iq.shape[0]
+    d_pcm = torch.empty((k * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
+    if k * n_frames:
+        e.demod_signal(_MODES[mode], d_iq, k * n_frames, frame_len, rate, d_pcm)
+    return d_pcm.cpu().numpy().reshape(k, n_frames, n_out, 2), decim
+
+
+def demodulate_bank(samples, fs, n_chan, decim=None, mode='NFM', frame_len=32768, **kw):
+    """Listen to every channel of the grid: channelize_recording's rows, cut into read buffers of frame_len samples at fs / decim and
+    demodulated as demodulate_signal would -> int16 [n_chan][n_frames][n_out][2].  The bank stops at a multiple of frame_len (an incomplete
+    tail buffer is dropped, as cut_frames does), so its result IS the batch of n_chan * n_frames read buffers on the device: nothing comes
+    back to the host between the two steps.  kw: taps, lead, chunk_samples, codes_format, table."""
+    return _demodulate_rows(samples, fs, n_chan, decim, mode, frame_len, kw, 'pfb')[0]
+
+
+def _smooth5(n):
+    """n = 2^a 3^b 5^c."""
+    for p in (2, 3, 5):
+        while n > 1 and n % p == 0:
+            n //= p
+    return n == 1
+
+
+def _plan_ok(n_chan):
+    return 2 <= n_chan <= 1024 and _smooth5(n_chan)
+
+
+def plan_offsets(fs, n_chan):
+    """bank_offsets for the channeliser of band plans, any n_chan = 2^a 3^b 5^c in [2, 1024] -> float64 [n_chan]: c fs / n_chan for
+    c <= (n_chan - 1) / 2 and (c - n_chan) fs / n_chan otherwise (even n_chan: row n_chan / 2, the band edge, reads -fs / 2; odd n_chan
+    has no such row)."""
+    n_chan = int(n_chan)
+    if not _plan_ok(n_chan):
+        raise ValueError("n_chan must be of the form 2^a 3^b 5^c in [2, 1024]")
+    c = np.arange(n_chan, dtype=np.float64)
+    return np.where(c <= (n_chan - 1) // 2, c, c - n_chan) * (float(fs) / n_chan)
+
+
+def plan_bank(fs, spacing_hz, min_rate=None):
+    """The bank of a band plan -> (n_chan, decim): the grid of a capture at fs with channels spacing_hz apart has n_chan = fs / spacing_hz
+    channels, which must be an integer (to 1e-9 relative) of the form 2^a 3^b 5^c in [2, 1024]; decim is the largest divisor of n_chan
+    that leaves a channel rate fs / decim >= min_rate (default max(2 spacing_hz, 48 000): the NFM demodulator needs a channel rate above
+    30 kS/s, which n_chan // 2 misses on a 12.5 kHz grid).  12.5 kHz at 2.4 MS/s -> (192, 48): 50 kS/s."""
+    fs, spacing_hz = float(fs), float(spacing_hz)
+    if not (fs > 0 and spacing_hz > 0):
+        raise ValueError("fs and spacing_hz must be positive")
+    ratio = fs / spacing_hz
+    n_chan = int(round(ratio))
+    if abs(ratio - n_chan) > 1e-9 * ratio:
+        raise ValueError(f"fs / spacing_hz = {ratio!r} is not an integer: the grid does not close on this capture")
+    if not _plan_ok(n_chan):
+        near = [next((m for m in rng if _plan_ok(m)), None) for rng in (range(min(n_chan - 1, 1024), 1, -1), range(max(n_chan + 1, 2), 1025))]
+        raise ValueError(f"fs / spacing_hz = {n_chan} channels is not of the form 2^a 3^b 5^c in [2, 1024]; the nearest such counts: "
+                         + ", ".join(str(m) for m in near if m is not None))
+    min_rate = max(2.0 * spacing_hz, 48000.0) if min_rate is None else float(min_rate)
+    fits = [d for d in range(1, n_chan + 1) if n_chan % d == 0 and fs / d >= min_rate]
+    if not fits:
+        raise ValueError(f"the capture's own rate {fs!r} is below min_rate {min_rate!r}")
+    return n_chan, fits[-1]
+
+
+def channelize_plan(samples, fs, spacing_hz, decim=None, taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None):
+    """channelize_recording for a band plan — what the reference's memory-channel mode steps its tuner through, done to a capture in one
+    pass: every channel of the grid spacing_hz apart (25 kHz: marine VHF, 2 m repeaters; 12.5 kHz: PMR446; 10 kHz: CB) on the GPU
+    (pss_bank) -> (channels complex64 [n_chan][ceil(n / decim)], offsets_hz float64 [n_chan] (plan_offsets), fs / decim).  n_chan and
+    the default decim are plan_bank(fs, spacing_hz)'s.  taps, lead, chunk_samples, codes_format, table: as channelize_recording; the
+    result does not depend on chunk_samples."""
+    n_chan, d = plan_bank(fs, spacing_hz)
+    d_out, decim = _bank_device(samples, n_chan, d if decim is None else decim, taps, lead, chunk_samples, codes_format, table, entry='bank')
+    return d_out.cpu().numpy().view(np.complex64), plan_offsets(fs, n_chan), float(fs) / decim
+
+
+def plan_rows(fs, center_hz, channels_hz, spacing_hz):
+    """The row of each listed channel frequency in the bank of a capture centred on center_hz -> int array [K]: f belongs to row
+    round((f - center_hz) / spacing_hz) mod n_chan.  ValueError lists every f more than 1 Hz off the grid or outside +-fs / 2."""
+    n_chan, _ = plan_bank(fs, spacing_hz)
+    f = np.atleast_1d(np.asarray(channels_hz, np.float64))
+    if f.ndim != 1:
+        raise ValueError("channels_hz: a list of frequencies")
+    steps = (f - float(center_hz)) / float(spacing_hz)
+    rows = np.rint(steps)
+    off = (np.abs(steps - rows) * float(spacing_hz) > 1.0) | (np.abs(f - float(center_hz)) > float(fs) / 2) | ~np.isfinite(f)
+    if off.any():
+        raise ValueError("not on the grid of this capture (more than 1 Hz off a channel centre, or outside +-fs / 2): "
+                         + ", ".join(repr(float(v)) for v in f[off]))
+    return np.mod(rows.astype(np.int64), n_chan)
+
+
+def monitor_channels(samples, fs, center_hz, channels_hz, spacing_hz, mode='NFM', frame_len=32768, **kw):
+    """The reference's memory-channel mode done to a capture: listen to the listed channel frequencies of one wideband capture centred on
+    center_hz -> (pcm int16 [K][n_frames][n_out][2], rows int [K], fs / decim).  The whole grid goes through the bank (channelize_plan's
+    work), the K listed rows (plan_rows) are gathered on the device and demodulated as demodulate_signal would; nothing comes back to the
+    host in between.  The bank stops at a multiple of frame_len, as demodulate_bank does.  kw: decim, taps, lead, chunk_samples,
+    codes_format, table."""
+    kw = dict(kw)
+    decim = kw.pop('decim', None)
+    n_chan, d = plan_bank(fs, spacing_hz)
+    rows = plan_rows(fs, center_hz, channels_hz, spacing_hz)
+    pcm, decim = _demodulate_rows(samples, fs, n_chan, d if decim is None else decim, mode, frame_len, kw, 'bank', rows=rows)
+    return pcm, rows, float(fs) / decim
 
 
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
