@@ -760,6 +760,37 @@ int pss_bank(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long 
              const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
 int pss_h_bank(const float *h_iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim,
                const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
+/* ---- rational resampler for batches of rows: scipy.signal.resample_poly(x, up, down) bit for bit — the step between a channel row at
+ * fs / D (50 kS/s on a 12.5 kHz plan) and the rates the demodulators turn into exactly DEFAULT_SAMPLE_RATE audio.  up / down is reduced by
+ * its gcd; both 1: a copy.  Output j of a row of n_in samples is upfirdn's: one IEEE multiply and one IEEE add per tap in ascending sample
+ * order from +0, in the row's real type, the float64 table cast to that type and scaled by up in it.  The arithmetic is stated once in
+ * csrc/pss_resample.h (PARITY.md "Resampler"); the device and the host twin agree on every byte.  complex64 rows: the contract with SciPy
+ * covers finite samples (SciPy multiplies by h + 0i there); rows with inf / NaN never fault, their values are those of the statement.
+ * pss_resample_out_len: ceil(n_in up / down) at the reduced factors; PSS_E_ARG (negative) unless 1 <= up, down <= 4096 and
+ *   0 <= n_in <= 2^48.
+ * pss_resample_default_taps: firwin(20 max(u, d) + 1, 1 / max(u, d), window=('kaiser', 5.0)) at the reduced factors u, d, in float64 (before
+ *   the cast and the scaling by up), through the library's designer with Cephes' i0; u = d = 1: the one tap 1.0 (not used).  *n_taps is
+ *   set, taps (NULL: only the count) is filled.
+ * pss_resample: each of the n_rows rows is n_in samples long; the buffer d_x holds samples [buf_index0, buf_index0 + n_buf) of every row,
+ *   x_stride elements apart.  Outputs [j_begin, j_end) of row r go to element r y_stride + (j - j_begin) of d_y; elements between rows are
+ *   not touched.  An output's index arithmetic follows from its index in the ROW, so any chunking gives the same bytes.  taps: a HOST
+ *   float64 low-pass table; the device copy of the plan's table is kept on the context and uploaded when its bytes differ from the last
+ *   call's.  One kernel, k_resample (three instances).  n_rows = 0 or an empty window succeeds and writes nothing.
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_resample: "; a refused call writes nothing): up or down outside [1, 4096];
+ *   n_taps outside [1, 32 max(u, d) + 1]; a tap that is not finite; an unknown dtype; a null or misaligned pointer; a buffer not inside
+ *   the row; [j_begin, j_end) outside [0, n_out]; a stride shorter than its window (x_stride < n_buf, y_stride < j_end - j_begin); a
+ *   needed sample outside the buffer; n_in above 2^48.
+ * pss_h_resample: the same on host buffers, pure host code (no context, no GPU; the reason of a refusal: pss_last_error(NULL),
+ *   "pss_h_resample: "). */
+#define PSS_RS_F32 0   /* float32 rows */
+#define PSS_RS_F64 1   /* float64 rows */
+#define PSS_RS_C64 2   /* complex64 rows (float32 pairs) */
+long pss_resample_out_len(long n_in, int up, int down);
+int pss_resample_default_taps(int up, int down, double *taps, int *n_taps);
+int pss_resample(pss_ctx *ctx, const void *d_x, int dtype, long n_rows, long x_stride, long n_buf, long buf_index0, long n_in, int up, int down,
+                 const double *taps, int n_taps, long j_begin, long j_end, void *d_y, long y_stride);
+int pss_h_resample(const void *h_x, int dtype, long n_rows, long x_stride, long n_buf, long buf_index0, long n_in, int up, int down,
+                   const double *taps, int n_taps, long j_begin, long j_end, void *h_y, long y_stride);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -15,6 +15,7 @@ MODE_NFM, MODE_AM, MODE_USB, MODE_LSB, MODE_WFM = 0, 1, 2, 3, 4
 NP_ARCTAN2, NP_LOG10, NP_ABS = 0, 1, 2          # pss_np_f32 operations
 IQ_U8, IQ_S8, IQ_S16 = 0, 1, 2                  # ADC code containers (PSS_IQ_*)
 SWEEP_INLINE, SWEEP_DRIVER = 0, 1               # pss_sweep_report kinds (PSS_SWEEP_*)
+RS_F32, RS_F64, RS_C64 = 0, 1, 2                # pss_resample row types (PSS_RS_*)
 
 _p = C.c_void_p
 
@@ -184,6 +185,12 @@ _SIGS = {
     "pss_bank_default_taps": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
     "pss_bank": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
     "pss_h_bank": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_resample_out_len": (C.c_long, [C.c_long, C.c_int, C.c_int]),
+    "pss_resample_default_taps": (C.c_int, [C.c_int, C.c_int, _p, C.POINTER(C.c_int)]),
+    "pss_resample": (C.c_int, [_p, _p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_long, C.c_long,
+                               _p, C.c_long]),
+    "pss_h_resample": (C.c_int, [_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_long, C.c_long,
+                                 _p, C.c_long]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

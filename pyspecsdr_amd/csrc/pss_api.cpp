@@ -178,6 +178,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->ddc_tab) hipFree(ctx->ddc_tab);
     if (ctx->pfb_tab) hipFree(ctx->pfb_tab);
     if (ctx->bank_tab) hipFree(ctx->bank_tab);
+    if (ctx->rs_tab) hipFree(ctx->rs_tab);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

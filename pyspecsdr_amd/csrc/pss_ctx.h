@@ -114,6 +114,10 @@ struct pss_ctx {
     void *bank_tab = nullptr;
     size_t bank_tab_bytes = 0;
     std::vector<unsigned char> bank_host;
+    // rational resampler (pss_resample.hip): the same for its table (the plan's numbers, then the taps in visit order)
+    void *rs_tab = nullptr;
+    size_t rs_tab_bytes = 0;
+    std::vector<unsigned char> rs_host;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;
@@ -266,4 +270,6 @@ bool pss_ssb_fused_supported(int n);
 // NumPy's float64 tan / exp under its AVX512_SKX dispatch (SVML's _ha routines restated, pss_design.cpp)
 double pss_np_tan(double x);
 double pss_np_exp(double x);
+// scipy.signal.firwin(numtaps, cutoff, window=('kaiser', beta)) for an odd numtaps >= 3 and 0 <= beta <= 8 (pss_design.cpp)
+int pss_design_firwin_kaiser(int numtaps, double cutoff, double beta, double *taps);
 int pss_ssb_hilbert_fused(pss_ctx *ctx, const float *d_iq, long n_rows, int n, const double *taps65, double *d_audio, int16_t *d_pcm);

@@ -183,29 +183,74 @@ extern "C" int pss_h_np_f64(int op, const double *x, long n, double *out)
 // np.sinc (pi * where(x == 0, 1e-20, x); sin(y) / y), general_cosine's fac = linspace(-pi, pi, M) and w = 0.54 cos(0 fac) +
 // (1 - 0.54) cos(fac), the scale by np.sum(h * cos(0)) (pairwise).  NumPy's float64 sin / cos are libm's (checked on the build image:
 // np.sin == math.sin on 200 000 arguments), so the taps equal SciPy's bit for bit (tests: 400 cutoffs).
-extern "C" int pss_design_firwin(int numtaps, double cutoff, double *taps)
+// W(i): the window's value at tap i
+template <class FW>
+static int firwin_windowed(int numtaps, double cutoff, double *taps, FW W)
 {
     if (numtaps < 1 || !taps) return PSS_E_ARG;
     if (!(cutoff > 0.0 && cutoff < 1.0)) return PSS_E_CUTOFF;  // scipy: "Invalid cutoff frequency"
     const double alpha = 0.5 * (numtaps - 1);
-    const double step = numtaps > 1 ? (M_PI - (-M_PI)) / (double)(numtaps - 1) : 0.0;
     std::vector<double> hc(numtaps);
     for (int i = 0; i < numtaps; i++) {
         const double m = (double)i - alpha;
         const double x = cutoff * m;
         const double y = M_PI * (x == 0.0 ? 1.0e-20 : x);  // np.sinc
         const double h = cutoff * (std::sin(y) / y);
-        double fac = (double)i * step + (-M_PI);             // np.linspace: arange * step + start, the last element set to stop
-        if (i == numtaps - 1 && numtaps > 1) fac = M_PI;
-        double w = 0.0;
-        w += 0.54 * std::cos(0.0 * fac);
-        w += (1.0 - 0.54) * std::cos(fac);
-        taps[i] = h * w;
+        taps[i] = h * W(i);
         hc[i] = taps[i] * std::cos(M_PI * m * 0.0);          // scale_frequency = 0
     }
     const double s = pss_np::np_sum(hc.data(), numtaps);
     for (int i = 0; i < numtaps; i++) taps[i] /= s;
     return PSS_OK;
+}
+
+extern "C" int pss_design_firwin(int numtaps, double cutoff, double *taps)
+{
+    const double step = numtaps > 1 ? (M_PI - (-M_PI)) / (double)(numtaps - 1) : 0.0;
+    return firwin_windowed(numtaps, cutoff, taps, [&](int i) {
+        double fac = (double)i * step + (-M_PI);             // np.linspace: arange * step + start, the last element set to stop
+        if (i == numtaps - 1 && numtaps > 1) fac = M_PI;
+        double w = 0.0;
+        w += 0.54 * std::cos(0.0 * fac);
+        w += (1.0 - 0.54) * std::cos(fac);
+        return w;
+    });
+}
+
+// scipy.special.i0 on |x| <= 8: Cephes' Chebyshev series for exp(-x) I0(x) (Cephes Math Library 2.8, i0.c: the coefficients and
+// chbevl's recurrence), times libm's exp
+static double cephes_i0_le8(double x)
+{
+    static const double A[30] = {
+        -4.41534164647933937950E-18, 3.33079451882223809783E-17,  -2.43127984654795469359E-16, 1.71539128555513303061E-15,
+        -1.16853328779934516808E-14, 7.67618549860493561688E-14,  -4.85644678311192946090E-13, 2.95505266312963983461E-12,
+        -1.72682629144155570723E-11, 9.67580903537323691224E-11,  -5.18979560163526290666E-10, 2.65982372468238665035E-9,
+        -1.30002500998624804212E-8,  6.04699502254191894932E-8,   -2.67079385394061173391E-7,  1.11738753912010371815E-6,
+        -4.41673835845875056359E-6,  1.64484480707288970893E-5,   -5.75419501008210370398E-5,  1.88502885095841655729E-4,
+        -5.76375574538582365885E-4,  1.63947561694133579842E-3,   -4.32430999505057594430E-3,  1.05464603945949983183E-2,
+        -2.37374148058994688156E-2,  4.93052842396707084878E-2,   -9.49010970480476444210E-2,  1.71620901522208775349E-1,
+        -3.04682672343198398683E-1,  6.76795274409476084995E-1};
+    if (x < 0) x = -x;
+    const double y = (x / 2.0) - 2.0;
+    double b0 = A[0], b1 = 0.0, b2 = 0.0;
+    for (int i = 1; i < 30; i++) {
+        b2 = b1;
+        b1 = b0;
+        b0 = y * b1 - b2 + A[i];
+    }
+    return std::exp(x) * (0.5 * (b0 - b2));
+}
+
+// scipy.signal.firwin(numtaps, cutoff, window=('kaiser', beta)), 0 <= beta <= 8: the same chain behind scipy.signal.windows.kaiser's
+// w = i0(beta sqrt(1 - ((n - alpha) / alpha)^2)) / i0(beta)  (numtaps odd and > 1: the symmetric window as it is)
+int pss_design_firwin_kaiser(int numtaps, double cutoff, double beta, double *taps)
+{
+    if (numtaps < 3 || !(numtaps & 1) || !(beta >= 0.0 && beta <= 8.0)) return PSS_E_ARG;
+    const double alpha = (double)(numtaps - 1) / 2.0, den = cephes_i0_le8(beta);
+    return firwin_windowed(numtaps, cutoff, taps, [&](int i) {
+        const double r = ((double)i - alpha) / alpha;
+        return cephes_i0_le8(beta * std::sqrt(1.0 - r * r)) / den;
+    });
 }
 
 // scipy.signal.cheby1(order, rp, wn, output='sos') (what scipy.signal.decimate designs: order 8, rp 0.05, wn 0.8 / q): cheb1ap ->

@@ -1259,6 +1259,69 @@ class Engine:
             raise ValueError(lib.pss_last_error(None).decode())
         return out
 
+    # -- rational resampler for rows: scipy.signal.resample_poly bit for bit (pss_resample; the arithmetic: csrc/pss_resample.h)
+    RS_DTYPES = {np.dtype(np.float32): L.RS_F32, np.dtype(np.float64): L.RS_F64, np.dtype(np.complex64): L.RS_C64}
+
+    @staticmethod
+    def resample_out_len(n_in, up, down, lib=None):
+        """pss_resample_out_len: ceil(n_in up / down) at the reduced factors.  Host code."""
+        n = (lib or L.load()).pss_resample_out_len(int(n_in), int(up), int(down))
+        if n < 0:
+            raise ValueError("resample_out_len: up and down in [1, 4096], 0 <= n_in <= 2^48")
+        return n
+
+    @staticmethod
+    def resample_default_taps(up, down, lib=None):
+        """pss_resample_default_taps: resample_poly's own design, firwin(20 m + 1, 1 / m, window=('kaiser', 5.0)) with m = max(up, down) after
+        the reduction, float64 (before the cast to the row's type and the scaling by up).  Host code."""
+        lib = lib or L.load()
+        n = C.c_int()
+        if lib.pss_resample_default_taps(int(up), int(down), None, C.byref(n)) != 0:
+            raise ValueError("resample_default_taps: up and down in [1, 4096]")
+        taps = np.empty(n.value, np.float64)
+        r = lib.pss_resample_default_taps(int(up), int(down), _ptr(taps), C.byref(n))
+        if r != 0:
+            raise PssError(r, "pss_resample_default_taps")
+        return taps
+
+    @staticmethod
+    def _resample_args(lib, n_buf, up, down, taps, buf_index0, n_in, j_begin, j_end):
+        """The defaults of resample / h_resample -> (taps, n_in, j_begin, j_end)."""
+        taps = Engine.resample_default_taps(up, down, lib) if taps is None else np.ascontiguousarray(np.atleast_1d(taps), np.float64)
+        if taps.ndim != 1:
+            raise ValueError("taps: a 1-D table")
+        n_in = int(n_buf) + int(buf_index0) if n_in is None else int(n_in)
+        if j_end is None:
+            j_end = max(lib.pss_resample_out_len(n_in, int(up), int(down)), 0)
+        return taps, n_in, int(j_begin), int(j_end)
+
+    def resample(self, d_x, dtype, n_rows, n_buf, up, down, d_y, taps=None, x_stride=None, buf_index0=0, n_in=None, j_begin=0, j_end=None,
+                 y_stride=None):
+        """d_x: n_rows rows of `dtype` (float32, float64 or complex64), samples [buf_index0, buf_index0 + n_buf) of rows n_in samples long
+        (default: the buffer is the row), x_stride elements apart (default n_buf) -> d_y, output j of row r at element r * y_stride +
+        (j - j_begin), j in [j_begin, j_end) (default: all ceil(n_in up / down), rows back to back).  taps: host float64 table (default:
+        resample_default_taps(up, down))."""
+        taps, n_in, j_begin, j_end = self._resample_args(self.lib, n_buf, up, down, taps, buf_index0, n_in, j_begin, j_end)
+        code = self.RS_DTYPES.get(np.dtype(dtype), -1)
+        self._dev(self.lib.pss_resample, _ptr(d_x), code, int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_in,
+                  int(up), int(down), _ptr(taps), len(taps), j_begin, j_end, _ptr(d_y), int(j_end - j_begin if y_stride is None else y_stride))
+
+    @staticmethod
+    def h_resample(x, up, down, taps=None, buf_index0=0, n_in=None, j_begin=0, j_end=None, lib=None):
+        """pss_h_resample: the same on a host array [n_rows][n_buf] or [n_buf] -> the same type, [n_rows][j_end - j_begin] or
+        [j_end - j_begin].  Pure host code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        x = np.asarray(x)
+        if x.ndim not in (1, 2) or x.dtype not in Engine.RS_DTYPES:
+            raise ValueError("x: a 1-D or 2-D float32, float64 or complex64 array")
+        rows = np.ascontiguousarray(x.reshape(-1, x.shape[-1]))
+        taps, n_in, j_begin, j_end = Engine._resample_args(lib, rows.shape[1], up, down, taps, buf_index0, n_in, j_begin, j_end)
+        out = np.empty((rows.shape[0], max(j_end - j_begin, 0)), x.dtype)
+        if lib.pss_h_resample(_ptr(rows), Engine.RS_DTYPES[x.dtype], rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_in, int(up),
+                              int(down), _ptr(taps), len(taps), j_begin, j_end, _ptr(out), out.shape[1]) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out if x.ndim == 2 else out[0]
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

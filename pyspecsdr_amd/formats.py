@@ -492,11 +492,117 @@ def tune_recording(samples, fs, offsets_hz, decim, taps=None, lead=None, chunk_s
     return d_out.cpu().numpy().view(np.complex64), float(fs) / int(decim), effective
 
 
+_AUDIO_MID = {'AM': 22050, 'USB': 22050, 'LSB': 22050, 'RAW': 22050, 'NFM': 44100, 'WFM': 110250}
+
+
+def plan_resample(rate_in, rate_out):
+    """The factors that take rate_in to rate_out -> (up, down), reduced by their gcd: 50 000 -> 44 100 is (441, 500).  Both rates must be
+    integers (to 1e-9 relative) and neither reduced factor may pass 4096 (pss_resample's limit)."""
+    out = []
+    for name, rate in (("rate_in", rate_in), ("rate_out", rate_out)):
+        rate = float(rate)
+        if not (np.isfinite(rate) and rate >= 0.5):
+            raise ValueError(f"{name} = {rate!r} must be a positive rate")
+        r = int(round(rate))
+        if abs(rate - r) > 1e-9 * rate:
+            raise ValueError(f"{name} = {rate!r} is not an integer: no ratio of integers takes one rate to the other")
+        out.append(r)
+    g = int(np.gcd(out[0], out[1]))
+    up, down = out[1] // g, out[0] // g
+    for name, f in (("up", up), ("down", down)):
+        if f > 4096:
+            raise ValueError(f"{name} = {f} (rate_out / rate_in = {up} / {down} reduced) is above 4096")
+    return up, down
+
+
+def plan_audio(rate_in, mode):
+    """The resampling in front of the demodulator whose PCM then comes out at exactly DEFAULT_SAMPLE_RATE -> (up, down, rate_mid): AM / USB /
+    LSB / RAW do not decimate, rate_mid = 22 050; NFM's 15 kHz FIR needs a channel rate above 30 kS/s and decimates by
+    int(rate / 22 050): rate_mid = 44 100; WFM (pilot, L - R band up to 53 kHz): 110 250."""
+    if mode not in _AUDIO_MID:
+        raise ValueError(f"unknown demodulation mode {mode!r}")
+    rate_mid = _AUDIO_MID[mode]
+    up, down = plan_resample(rate_in, rate_mid)
+    return up, down, float(rate_mid)
+
+
+def resample_halo(n_in, up, down, n_taps, j_begin, j_end):
+    """The samples [lo, hi) of a row of n_in samples that outputs [j_begin, j_end) of pss_resample read (csrc/pss_resample.h restated in
+    integers; empty: lo == hi)."""
+    g = int(np.gcd(int(up), int(down)))
+    up, down, n_in = int(up) // g, int(down) // g, int(n_in)
+    n_out = -(-n_in * up // down)
+    if not 0 <= j_begin <= j_end <= n_out:
+        raise ValueError("[j_begin, j_end) outside [0, n_out]")
+    if j_begin == j_end:
+        return 0, 0
+    if up == 1 and down == 1:
+        return j_begin, j_end
+    half_len = (n_taps - 1) // 2
+    pre = down - half_len % down
+    pre_remove = (half_len + pre) // down
+    post = max(0, (n_out + pre_remove - 1) * down - ((n_in - 1) * up + n_taps + pre - 1))
+    hpp = -(-(pre + n_taps + post) // up)
+    lo = max(0, (j_begin + pre_remove) * down // up - hpp + 1)
+    hi = min(n_in - 1, (j_end - 1 + pre_remove) * down // up) + 1
+    return (lo, hi) if lo < hi else (0, 0)
+
+
+def resample_recording(rows, up, down, taps=None, chunk_samples=1 << 22):
+    """scipy.signal.resample_poly(rows, up, down, axis=-1) for host rows [n_rows][n] or [n] (float32, float64 or complex64) on the GPU
+    (pss_resample) -> the same type, [n_rows][ceil(n up / down)].  The rows go up in chunks of about chunk_samples input samples, each
+    with exactly the halo its outputs read (resample_halo); an output's arithmetic follows from its index in the row, so the result does
+    not depend on chunk_samples.  taps: a float64 low-pass table (default: resample_poly's own Kaiser design)."""
+    import torch
+    e = get_engine()
+    x = np.asarray(rows)
+    if x.ndim not in (1, 2) or x.dtype not in e.RS_DTYPES:
+        raise ValueError("rows: a 1-D or 2-D float32, float64 or complex64 array")
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    r2 = np.ascontiguousarray(x.reshape(-1, x.shape[-1]))
+    n_rows, n = r2.shape
+    taps = e.resample_default_taps(up, down) if taps is None else np.ascontiguousarray(taps, np.float64)
+    n_out = e.resample_out_len(n, up, down)
+    cplx = x.dtype == np.complex64
+    real = np.float32 if cplx else x.dtype
+    width = 2 if cplx else 1
+    dev = f"cuda:{e.device}"
+    d_y = torch.empty((n_rows, n_out * width), dtype=torch.from_numpy(np.empty(0, real)).dtype, device=dev)
+    g = int(np.gcd(int(up), int(down)))
+    per_chunk = max(1, int(chunk_samples) * (int(up) // g) // (int(down) // g))
+    for j0 in range(0, n_out if n_rows else 0, per_chunk):
+        j1 = min(n_out, j0 + per_chunk)
+        lo, hi = resample_halo(n, up, down, len(taps), j0, j1)
+        d_x = torch.from_numpy(np.ascontiguousarray(r2[:, lo:hi]).view(real)).to(dev) if hi > lo else None
+        e.resample(d_x, x.dtype, n_rows, hi - lo, up, down, d_y.data_ptr() + j0 * width * np.dtype(real).itemsize, taps=taps, buf_index0=lo,
+                   n_in=n, j_begin=j0, j_end=j1, y_stride=n_out)
+    out = d_y.cpu().numpy()
+    out = out.view(np.complex64) if cplx else out
+    return out if x.ndim == 2 else out[0]
+
+
+def _exact_rate_rows(d_iq, rate_in, mode, frame_len):
+    """exact_rate=True: the complex64 rows d_iq (float32 [K][2 m]) at rate_in resampled on the device to plan_audio's rate_mid and stopped at
+    a multiple of frame_len -> (float32 [K][2 n_frames frame_len], n_frames, rate_mid)."""
+    import torch
+    e = get_engine()
+    up, down, rate_mid = plan_audio(rate_in, mode)
+    k, m = d_iq.shape[0], d_iq.shape[1] // 2
+    n_frames = e.resample_out_len(m, up, down) // frame_len
+    d_rs = torch.empty((k, 2 * n_frames * frame_len), dtype=torch.float32, device=d_iq.device)
+    if k * n_frames:
+        e.resample(d_iq.contiguous(), np.complex64, k, m, up, down, d_rs, j_end=n_frames * frame_len)
+    return d_rs, n_frames, rate_mid
+
+
 def demodulate_channels(samples, fs, offsets_hz, decim, mode='NFM', frame_len=32768, **tune_kw):
     """Listen to K channels of one wideband capture: tune_recording's channels, cut into read buffers of frame_len samples at fs / decim
     and demodulated as demodulate_signal would -> int16 [K][n_frames][n_out][2].  The down-converter stops at a multiple of frame_len
     (an incomplete tail buffer is dropped, as cut_frames does), so its result IS the batch of K * n_frames read buffers on the device:
-    nothing comes back to the host between the two steps.  tune_kw: taps, lead, chunk_samples, codes_format, table."""
+    nothing comes back to the host between the two steps.  tune_kw: taps, lead, chunk_samples, codes_format, table, exact_rate
+    (True: the channels are resampled on the device to plan_audio(fs / decim, mode)'s rate before they are cut into read buffers, so the
+    PCM is at exactly DEFAULT_SAMPLE_RATE; the frame count follows the resampled length)."""
     import torch
     if mode not in _MODES:
         raise ValueError(f"unknown demodulation mode {mode!r}")
@@ -507,20 +613,26 @@ def demodulate_channels(samples, fs, offsets_hz, decim, mode='NFM', frame_len=32
     n_total = e.lib.pss_ddc_out_len(len(samples), decim)
     if n_total < 0:
         raise ValueError("decim outside [1, 4096]")
-    n_frames = n_total // frame_len
-    rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(fs) / decim
-    if mode != 'AM':
-        _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), rate)
-    n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
-    if n_out < 0:
-        raise ValueError("the channel rate fs / decim is below the target rate")
-    kw = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
+    kw = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None, exact_rate=False)
     for k in tune_kw:
         if k not in kw:
             raise TypeError(f"unexpected argument {k!r}")
     kw.update(tune_kw)
+    n_frames = n_total // frame_len
+    rate = float(fs) / decim
+    if kw['exact_rate']:
+        rate = plan_audio(rate, mode)[2]
+    if mode == 'AM':
+        rate = float(DEFAULT_SAMPLE_RATE)
+    else:
+        _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), rate)
+    n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
+    if n_out < 0:
+        raise ValueError("the channel rate fs / decim is below the target rate")
     d_iq, _ = _tune_device(samples, fs, offsets_hz, decim, kw['taps'], kw['lead'], kw['chunk_samples'], kw['codes_format'], kw['table'],
-                           m_end=n_frames * frame_len)
+                           m_end=None if kw['exact_rate'] else n_frames * frame_len)
+    if kw['exact_rate']:
+        d_iq, n_frames, _ = _exact_rate_rows(d_iq, float(fs) / decim, mode, frame_len)
     k = d_iq.shape[0]
     d_pcm = torch.empty((k * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
     if k * n_frames:
@@ -604,9 +716,10 @@ def channelize_recording(samples, fs, n_chan, decim=None, taps=None, lead=None, 
 
 
 def _demodulate_rows(samples, fs, n_chan, decim, mode, frame_len, kw, entry, rows=None):
-    """demodulate_bank's and monitor_channels' work -> (int16 [K][n_frames][n_out][2], decim): the bank (_bank_device through `entry`)
-    stops at a multiple of frame_len, `rows` of its result (None: all n_chan) are gathered on the device and demodulated as one batch of
-    K * n_frames read buffers.  kw: taps, lead, chunk_samples, codes_format, table."""
+    """demodulate_bank's and monitor_channels' work -> (int16 [K][n_frames][n_out][2], decim, rate of the read buffers): the bank
+    (_bank_device through `entry`) stops at a multiple of frame_len, `rows` of its result (None: all n_chan) are gathered on the device and
+    demodulated as one batch of K * n_frames read buffers.  kw: taps, lead, chunk_samples, codes_format, table, exact_rate (True: the whole
+    rows, resampled to plan_audio's rate by _exact_rate_rows before the cut)."""
     import torch
     if mode not in _MODES:
         raise ValueError(f"unknown demodulation mode {mode!r}")
@@ -617,35 +730,40 @@ def _demodulate_rows(samples, fs, n_chan, decim, mode, frame_len, kw, entry, row
     decim = n_chan // 2 if decim is None else int(decim)
     if decim < 1 or decim > n_chan:
         raise ValueError("decim outside [1, n_chan]")
-    opts = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None)
+    opts = dict(taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None, exact_rate=False)
     for k in kw:
         if k not in opts:
             raise TypeError(f"unexpected argument {k!r}")
     opts.update(kw)
     e = get_engine()
     n_frames = e.lib.pss_ddc_out_len(len(samples), decim) // frame_len
-    rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else float(fs) / decim
+    rate_out = float(fs) / decim
+    if opts['exact_rate']:
+        rate_out = plan_audio(rate_out, mode)[2]
+    rate = float(DEFAULT_SAMPLE_RATE) if mode == 'AM' else rate_out
     if mode != 'AM':
         _inject_designs({'NFM': 'nfm', 'WFM': 'wfm'}.get(mode, 'ssb'), rate)
     n_out = e.demod_out_len(_MODES[mode], frame_len, rate)
     if n_out < 0:
         raise ValueError("the channel rate fs / decim is below the target rate")
     d_iq, _ = _bank_device(samples, n_chan, decim, opts['taps'], opts['lead'], opts['chunk_samples'], opts['codes_format'], opts['table'],
-                           m_end=n_frames * frame_len, entry=entry)
+                           m_end=None if opts['exact_rate'] else n_frames * frame_len, entry=entry)
     if rows is not None:
         d_iq = d_iq.index_select(0, torch.from_numpy(rows).to(d_iq.device))
+    if opts['exact_rate']:
+        d_iq, n_frames, _ = _exact_rate_rows(d_iq, float(fs) / decim, mode, frame_len)
     k = d_iq.shape[0]
     d_pcm = torch.empty((k * n_frames, n_out, 2), dtype=torch.int16, device=d_iq.device)
     if k * n_frames:
         e.demod_signal(_MODES[mode], d_iq, k * n_frames, frame_len, rate, d_pcm)
-    return d_pcm.cpu().numpy().reshape(k, n_frames, n_out, 2), decim
+    return d_pcm.cpu().numpy().reshape(k, n_frames, n_out, 2), decim, rate_out
 
 
 def demodulate_bank(samples, fs, n_chan, decim=None, mode='NFM', frame_len=32768, **kw):
     """Listen to every channel of the grid: channelize_recording's rows, cut into read buffers of frame_len samples at fs / decim and
     demodulated as demodulate_signal would -> int16 [n_chan][n_frames][n_out][2].  The bank stops at a multiple of frame_len (an incomplete
     tail buffer is dropped, as cut_frames does), so its result IS the batch of n_chan * n_frames read buffers on the device: nothing comes
-    back to the host between the two steps.  kw: taps, lead, chunk_samples, codes_format, table."""
+    back to the host between the two steps.  kw: taps, lead, chunk_samples, codes_format, table, exact_rate (as monitor_channels)."""
     return _demodulate_rows(samples, fs, n_chan, decim, mode, frame_len, kw, 'pfb')[0]
 
 
@@ -727,13 +845,16 @@ def monitor_channels(samples, fs, center_hz, channels_hz, spacing_hz, mode='NFM'
     center_hz -> (pcm int16 [K][n_frames][n_out][2], rows int [K], fs / decim).  The whole grid goes through the bank (channelize_plan's
     work), the K listed rows (plan_rows) are gathered on the device and demodulated as demodulate_signal would; nothing comes back to the
     host in between.  The bank stops at a multiple of frame_len, as demodulate_bank does.  kw: decim, taps, lead, chunk_samples,
-    codes_format, table."""
+    codes_format, table, exact_rate.  exact_rate=True: the gathered rows are resampled on the device (pss_resample) to plan_audio(fs /
+    decim, mode)'s rate before they are cut into read buffers, so the PCM is at exactly DEFAULT_SAMPLE_RATE — what write_wav and the
+    audio FIFO promise; the frame count follows the resampled length and the rate returned is that rate (44 100.0 for NFM, 22 050.0
+    for AM / USB / LSB, 110 250.0 for WFM).  Default False: a 50 kS/s channel row gives NFM audio at 25 000 Hz and AM audio at 50 000 Hz."""
     kw = dict(kw)
     decim = kw.pop('decim', None)
     n_chan, d = plan_bank(fs, spacing_hz)
     rows = plan_rows(fs, center_hz, channels_hz, spacing_hz)
-    pcm, decim = _demodulate_rows(samples, fs, n_chan, d if decim is None else decim, mode, frame_len, kw, 'bank', rows=rows)
-    return pcm, rows, float(fs) / decim
+    pcm, decim, rate = _demodulate_rows(samples, fs, n_chan, d if decim is None else decim, mode, frame_len, kw, 'bank', rows=rows)
+    return pcm, rows, rate
 
 
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):

@@ -18,6 +18,7 @@ the reference's main loop imports with `from signal_processing import *` (pyspec
     estimate_modulation_index(samples)                     :283-293  -> np.float32
     decode_mono(samples, fs)                               :331-359  -> int16 (n_out,), n_out = ceil((N - 1) / 6): broadcast FM, mono
     lowpass_filter(data, cutoff, fs, order)                :28-31    -> float64, real input only (complex input: TypeError, not served)
+    resample_poly(x, up, down, ...)                        :7 (imported from scipy.signal, never called) -> SciPy's bytes
     butter_lowpass / butter_bandpass                       :13-25    -> (b, a): designs only, the host SciPy's own
 
 Every call runs on the GPU through the C ABI; there is no NumPy/SciPy compute path here.
@@ -30,8 +31,8 @@ from .engine import Engine
 # what `from signal_processing import *` hands to the caller (pyspecsdr.py:98): the reference's public callables
 __all__ = ["bandpass_filter", "iq_correction", "mono_to_stereo", "demodulate_nfm", "demodulate_wfm", "demodulate_am",
            "demodulate_ssb", "demodulate_signal", "compute_fft", "estimate_modulation_index", "classify_signal",
-           "measure_signal_power", "decode_mono", "lowpass_filter", "butter_lowpass", "butter_bandpass", "DEFAULT_SAMPLE_RATE",
-           "BUTTER_ORDER"]
+           "measure_signal_power", "decode_mono", "lowpass_filter", "butter_lowpass", "butter_bandpass", "resample_poly",
+           "DEFAULT_SAMPLE_RATE", "BUTTER_ORDER"]
 
 DEFAULT_SAMPLE_RATE = 22050  # pyspecconst.py:3
 BUTTER_ORDER = 5             # pyspecconst.py:5
@@ -320,3 +321,43 @@ def lowpass_filter(data, cutoff=3000, fs=DEFAULT_SAMPLE_RATE, order=5):
     d_y = torch.empty_like(d_x)
     e.lfilter(d_x, x.size // x.shape[-1], x.shape[-1], b, a, d_y)
     return d_y.cpu().numpy()
+
+
+def resample_poly(x, up, down, axis=0, window=('kaiser', 5.0), padtype='constant', cval=None):
+    """scipy.signal.resample_poly (the name signal_processing.py:7 imports): 1-D and 2-D float32 / float64 / complex64 input with a string
+    or tuple window and zero padding runs on the device (pss_resample) and returns SciPy's bytes — the low-pass table is designed by the
+    host SciPy's firwin, as every other table of this module is.  Anything else (integer input, array windows, other padtypes, more
+    axes) is handed to scipy.signal.resample_poly unchanged."""
+    a = np.asarray(x)
+    served = (a.ndim in (1, 2) and a.dtype in Engine.RS_DTYPES and a.size > 0 and isinstance(window, (str, tuple)) and padtype == 'constant'
+              and (cval is None or cval == 0) and isinstance(up, (int, np.integer)) and isinstance(down, (int, np.integer))
+              and 1 <= up <= 4096 and 1 <= down <= 4096 and isinstance(axis, (int, np.integer)) and -a.ndim <= axis < a.ndim)
+    if not served:
+        from scipy.signal import resample_poly as scipy_resample_poly
+        return scipy_resample_poly(x, up, down, axis=axis, window=window, padtype=padtype, cval=cval)
+    import math
+    g = math.gcd(int(up), int(down))
+    up, down = int(up) // g, int(down) // g
+    if up == down == 1:
+        return a.copy()
+    taps = None
+    if USE_SCIPY_DESIGNS or window != ('kaiser', 5.0):
+        try:
+            from scipy.signal import firwin
+            m = max(up, down)
+            taps = firwin(20 * m + 1, 1.0 / m, window=window)
+        except ImportError:
+            if window != ('kaiser', 5.0):
+                raise
+    import torch
+    e = get_engine()
+    rows = np.ascontiguousarray(np.moveaxis(a, axis, -1))
+    r2 = rows.reshape(-1, rows.shape[-1])
+    cplx = a.dtype == np.complex64
+    n_out = e.resample_out_len(r2.shape[1], up, down)
+    d_x = torch.from_numpy(r2.view(np.float32) if cplx else r2).to(f"cuda:{e.device}")
+    d_y = torch.empty((r2.shape[0], n_out * (2 if cplx else 1)), dtype=d_x.dtype, device=d_x.device)
+    e.resample(d_x, a.dtype, r2.shape[0], r2.shape[1], up, down, d_y, taps=taps)
+    y = d_y.cpu().numpy()
+    y = (y.view(np.complex64) if cplx else y).reshape(rows.shape[:-1] + (n_out,))
+    return np.moveaxis(y, -1, axis)
