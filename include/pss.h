@@ -791,6 +791,34 @@ int pss_resample(pss_ctx *ctx, const void *d_x, int dtype, long n_rows, long x_s
                  const double *taps, int n_taps, long j_begin, long j_end, void *d_y, long y_stride);
 int pss_h_resample(const void *h_x, int dtype, long n_rows, long x_stride, long n_buf, long buf_index0, long n_in, int up, int down,
                    const double *taps, int n_taps, long j_begin, long j_end, void *h_y, long y_stride);
+/* ---- survey of a capture: Welch's averaged periodogram and its max-hold row (scipy.signal.welch and spectrogram(mode='psd').max(-1) with
+ * return_onesided=False, float64), the step in front of plan_bank / tune_recording: what is in this capture, and where.  n_rows rows of n
+ * complex64 samples, row_stride samples apart (a capture is one row, the output of pss_bank M rows).  Segment s of a row covers samples
+ * [s step, s step + nperseg): SciPy's noverlap = nperseg - step, L = (n - nperseg) / step + 1 segments, no padding, no partial segment.
+ * Per segment, in float64: the samples widened exactly, minus the segment's own mean where detrend = 1 (SciPy's 'constant'), times win, the
+ * nperseg-point DFT, p[k] = re^2 + im^2.  mean[row][k] = (sum over segments p[k] / L) scale, max[row][k] = (max over segments p[k]) scale
+ * with np.max's rule (a NaN wins), bins in FFT order.  scale: 1 / (fs sum win^2) for SciPy's 'density', 1 / (sum win)^2 for 'spectrum'.
+ * The sum over segments is a fixed tree of L alone (csrc/pss_welch.h states it with the rest of the arithmetic): the same call gives the
+ * same bytes, row r of a batch the bytes of a one-row call on row r.  Against SciPy on the capture widened to complex128 every bin is
+ * inside the derived bound of tests/welch_bounds.py (PARITY.md "Survey").  A row with a NaN sample in a used segment has no finite bin;
+ * other rows are not touched by it.
+ * pss_welch_segments: L (0 when n < nperseg); PSS_E_ARG (negative) for an nperseg or step outside the ranges below.
+ * pss_welch_default_window: scipy.signal.get_window('hann', nperseg), the periodic Hann 0.5 - 0.5 cos(2 pi i / nperseg) evaluated in SciPy's
+ *   order, into h_win.
+ * pss_welch: d_iq, d_mean [n_rows][nperseg] and d_max (NULL: no max-hold row) are device pointers, h_win [nperseg] is a HOST table (its
+ *   device copy is kept on the context and uploaded when its bytes differ from the last call's).  Two kernels, k_welch (one instance per
+ *   nperseg, with and without the max row) and k_welch_fold; the block partials live in context-owned scratch.
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_welch: "; a refused call writes nothing): nperseg not in {256, 512, 1024, 2048,
+ *   4096}; step outside [1, nperseg]; n < nperseg; n_rows < 1; row_stride < n; a null window, mean or iq; a detrend outside {0, 1}; a scale
+ *   that is not finite and positive; a device pointer not aligned to 8 bytes.
+ * pss_h_welch: the same on host buffers, pure C++ (no context, no GPU; the reason of a refusal: pss_last_error(NULL), "pss_h_welch: ").
+ *   Its transform is a radix-2 one: it agrees with the device within the same bound, not bit for bit. */
+long pss_welch_segments(long n, int nperseg, int step);
+int pss_welch_default_window(int nperseg, double *h_win);
+int pss_welch(pss_ctx *ctx, const float *d_iq, long n_rows, long n, long row_stride, int nperseg, int step, const double *h_win, int detrend,
+              double scale, double *d_mean, double *d_max);
+int pss_h_welch(const float *iq, long n_rows, long n, long row_stride, int nperseg, int step, const double *win, int detrend, double scale,
+                double *mean, double *max);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

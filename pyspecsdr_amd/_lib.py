@@ -191,6 +191,10 @@ _SIGS = {
                                _p, C.c_long]),
     "pss_h_resample": (C.c_int, [_p, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_long, C.c_long,
                                  _p, C.c_long]),
+    "pss_welch_segments": (C.c_long, [C.c_long, C.c_int, C.c_int]),
+    "pss_welch_default_window": (C.c_int, [C.c_int, _p]),
+    "pss_welch": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_double, _p, _p]),
+    "pss_h_welch": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_double, _p, _p]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

@@ -34,6 +34,7 @@ UNITS = [
     ("pss_pfb.hip", ["-ffp-contract=off"]),   # the polyphase channeliser: the same rule
     ("pss_bank.hip", ["-ffp-contract=off"]),   # the channeliser for 2^a 3^b 5^c grids: the same rule
     ("pss_resample.hip", ["-ffp-contract=off"]),   # the rational resampler: SciPy's upfirdn, one multiply and one add per tap
+    ("pss_welch.hip", ["-ffp-contract=off"]),   # the capture survey: every fused multiply-add is written as fma
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("pss_decode.cpp", ["-x", "hip", "-ffp-contract=off"]),   # host only: the decoders' per-message halves

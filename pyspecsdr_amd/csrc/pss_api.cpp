@@ -179,6 +179,8 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->pfb_tab) hipFree(ctx->pfb_tab);
     if (ctx->bank_tab) hipFree(ctx->bank_tab);
     if (ctx->rs_tab) hipFree(ctx->rs_tab);
+    if (ctx->welch_win) hipFree(ctx->welch_win);
+    if (ctx->welch_part) hipFree(ctx->welch_part);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

@@ -118,6 +118,12 @@ struct pss_ctx {
     void *rs_tab = nullptr;
     size_t rs_tab_bytes = 0;
     std::vector<unsigned char> rs_host;
+    // capture survey (pss_welch.hip): the device copy of the caller's window and the doubles it holds, and the block partials, grow-only
+    void *welch_win = nullptr;
+    size_t welch_win_bytes = 0;
+    std::vector<double> welch_host;
+    void *welch_part = nullptr;
+    size_t welch_part_bytes = 0;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
     bool kskip = false;

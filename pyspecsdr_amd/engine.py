@@ -1322,6 +1322,85 @@ class Engine:
             raise ValueError(lib.pss_last_error(None).decode())
         return out if x.ndim == 2 else out[0]
 
+    # -- survey of a capture: Welch's averaged periodogram and its max-hold row (pss_welch; the arithmetic: csrc/pss_welch.h)
+    _WELCH_WINDOWS = {}   # the default window of each nperseg, made once
+
+    @staticmethod
+    def welch_segments(n, nperseg, step, lib=None):
+        """pss_welch_segments: (n - nperseg) // step + 1 segments, 0 when n < nperseg.  Host code."""
+        L_ = (lib or L.load()).pss_welch_segments(int(n), int(nperseg), int(step))
+        if L_ < 0:
+            raise ValueError("welch_segments: nperseg in {256, 512, 1024, 2048, 4096}, step in [1, nperseg]")
+        return L_
+
+    @staticmethod
+    def welch_default_window(nperseg, lib=None):
+        """The default window: scipy.signal.get_window('hann', nperseg) where SciPy imports, pss_welch_default_window's table (the same
+        periodic Hann, within 2^-53) otherwise.  Host code."""
+        lib = lib or L.load()
+        if lib.pss_welch_segments(int(nperseg), int(nperseg), 1) < 0:
+            raise ValueError("welch_default_window: nperseg in {256, 512, 1024, 2048, 4096}")
+        w = Engine._WELCH_WINDOWS.get(int(nperseg))
+        if w is None:
+            try:
+                from scipy.signal import get_window
+                w = np.ascontiguousarray(get_window("hann", int(nperseg)), np.float64)
+            except ImportError:
+                w = Engine.welch_c_window(nperseg, lib)
+            Engine._WELCH_WINDOWS[int(nperseg)] = w
+        return w.copy()
+
+    @staticmethod
+    def welch_c_window(nperseg, lib=None):
+        """pss_welch_default_window itself: 0.5 - 0.5 cos(2 pi i / nperseg).  Host code."""
+        w = np.empty(max(int(nperseg), 0), np.float64)
+        if (lib or L.load()).pss_welch_default_window(int(nperseg), _ptr(w)) != 0:
+            raise ValueError("welch_default_window: nperseg in {256, 512, 1024, 2048, 4096}")
+        return w
+
+    @staticmethod
+    def _welch_args(lib, nperseg, window, scaling, fs):
+        """The defaults of welch / h_welch -> (window, scale), the scale computed in NumPy as SciPy does."""
+        w = Engine.welch_default_window(nperseg, lib) if window is None else np.ascontiguousarray(window, np.float64)
+        if w.shape != (int(nperseg),):
+            raise ValueError("window: nperseg float64 values")
+        if scaling == "density":
+            scale = 1.0 / (float(fs) * (w * w).sum())
+        elif scaling == "spectrum":
+            scale = 1.0 / w.sum() ** 2
+        else:
+            raise ValueError("scaling: 'density' or 'spectrum'")
+        return w, float(scale)
+
+    def welch(self, d_iq, n_rows, n, nperseg, step, d_mean, d_max=None, window=None, detrend=True, scaling='density', fs=1.0, row_stride=None):
+        """d_iq: n_rows rows of n complex64 samples, row_stride samples apart (default n) -> d_mean float64 [n_rows][nperseg]: SciPy's
+        welch(x.astype(complex128), fs, window, nperseg, noverlap=nperseg - step, detrend='constant' | False, return_onesided=False,
+        scaling=scaling), FFT order; d_max (optional): the max over the segments of the same periodograms
+        (spectrogram(..., mode='psd').max(-1)).  window: host float64 [nperseg] (default: periodic Hann)."""
+        w, scale = self._welch_args(self.lib, nperseg, window, scaling, fs)
+        self._dev(self.lib.pss_welch, _ptr(d_iq), int(n_rows), int(n), int(n if row_stride is None else row_stride), int(nperseg), int(step), _ptr(w),
+                  int(detrend), scale, _ptr(d_mean), _ptr(d_max))
+
+    @staticmethod
+    def h_welch(x, nperseg, step, window=None, detrend=True, scaling='density', fs=1.0, want_max=True, lib=None):
+        """pss_h_welch: the same on a host array [n_rows][n] or [n] (complex64) -> (mean, max) float64 [n_rows][nperseg] or [nperseg]
+        (max is None with want_max=False).  Pure host code; its transform is a radix-2 one, so it agrees with the device within the
+        bound of tests/welch_bounds.py, not bit for bit."""
+        lib = lib or L.load()
+        x = np.asarray(x)
+        if x.ndim not in (1, 2) or x.dtype != np.complex64:
+            raise ValueError("x: a 1-D or 2-D complex64 array")
+        rows = np.ascontiguousarray(x.reshape(-1, x.shape[-1]))
+        w, scale = Engine._welch_args(lib, nperseg, window, scaling, fs)
+        mean = np.empty((rows.shape[0], int(nperseg)), np.float64)
+        mx = np.empty_like(mean) if want_max else None
+        if lib.pss_h_welch(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(nperseg), int(step), _ptr(w), int(detrend), scale, _ptr(mean),
+                           _ptr(mx)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        if x.ndim == 1:
+            return mean[0], (mx[0] if want_max else None)
+        return mean, mx
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

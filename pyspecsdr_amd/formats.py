@@ -492,6 +492,93 @@ def tune_recording(samples, fs, offsets_hz, decim, taps=None, lead=None, chunk_s
     return d_out.cpu().numpy().view(np.complex64), float(fs) / int(decim), effective
 
 
+def survey_freqs(fs, nperseg):
+    """The frequencies of a survey row in ascending order: fftshift(fftfreq(nperseg, 1 / fs))."""
+    return np.fft.fftshift(np.fft.fftfreq(int(nperseg), 1.0 / float(fs)))
+
+
+def survey_recording(samples, fs, nperseg=4096, overlap=0.5, window=None, detrend=True, scaling='density', chunk_samples=1 << 22, codes_format=None,
+                     table=None):
+    """What is in this capture, and where — the question the reference answers by retuning its radio and looking (scan_frequencies, the band
+    sweep), answered for a capture in one pass on the GPU (pss_welch): Welch's averaged periodogram (scipy.signal.welch in float64, the
+    reference's own PSD estimator, signal_processing.py:299) and the max-hold trace of the same periodograms.
+    -> dict(freqs_hz, mean, max, mean_db, max_db, n_segments, nperseg, step): float64 rows of nperseg bins in ascending frequency; dB is
+    the reference's 10 log10(p + 1e-10) (signal_processing.py:270).  The step is nperseg - int(nperseg * overlap), SciPy's noverlap rule.
+    The capture goes up in chunks of chunk_samples samples into one resident device row (codes_format / table: `samples` is the ADC code
+    array [n, 2], widened per chunk on the device); the result does not depend on chunk_samples."""
+    import torch
+    e = get_engine()
+    fs, nperseg = float(fs), int(nperseg)
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    if not 0.0 <= overlap < 1.0:
+        raise ValueError("overlap in [0, 1)")
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+    else:
+        samples = np.ascontiguousarray(samples, np.complex64)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+    n = len(samples)
+    step = nperseg - int(nperseg * overlap)
+    n_segments = e.welch_segments(n, nperseg, step)
+    if n_segments < 1:
+        raise ValueError("the capture is shorter than nperseg")
+    dev = f"cuda:{e.device}"
+    d_iq = torch.empty(2 * n, dtype=torch.float32, device=dev)
+    for lo in range(0, n, int(chunk_samples)):
+        hi = min(n, lo + int(chunk_samples))
+        if codes_format is not None:
+            d_codes = torch.from_numpy(np.array(samples[lo:hi])).to(dev)
+            e.unpack_iq(d_codes, hi - lo, d_iq.data_ptr() + 8 * lo, codes_format, iq[2])
+        else:
+            d_iq[2 * lo:2 * hi].copy_(torch.from_numpy(samples[lo:hi].view(np.float32)))
+    d_rows = torch.empty((2, nperseg), dtype=torch.float64, device=dev)
+    e.welch(d_iq, 1, n, nperseg, step, d_rows[0], d_rows[1], window=window, detrend=detrend, scaling=scaling, fs=fs)
+    rows = np.fft.fftshift(d_rows.cpu().numpy(), axes=1)
+    with np.errstate(invalid="ignore"):
+        db = 10 * np.log10(rows + 1e-10)
+    return dict(freqs_hz=survey_freqs(fs, nperseg), mean=rows[0], max=rows[1], mean_db=db[0], max_db=db[1], n_segments=n_segments, nperseg=nperseg,
+                step=step)
+
+
+def survey_signals(db, fs, margin_db=10.0, floor_db=None, min_bins=2):
+    """The signals of a survey row: `db` is a dB row in ascending frequency (survey_recording's mean_db or max_db).  A bin is occupied where
+    db > floor + margin_db (a NaN compares false); floor: floor_db, or the median of the row's finite values.  Every maximal run [a, b] of
+    consecutive occupied bins (no wrap-around) of at least min_bins bins gives
+    dict(lo_hz, hi_hz, center_hz, bandwidth_hz, peak_hz, peak_db, bins=(a, b)) with bandwidth_hz = (b - a + 1) fs / N, the reference's
+    count * fs / N (pyspecsdr.py:2549-2552), lo_hz and hi_hz the edges of bins a and b, center_hz their middle.  Sorted by frequency.  Host
+    code in NumPy: the row is N numbers."""
+    db = np.asarray(db, np.float64)
+    if db.ndim != 1 or len(db) < 1:
+        raise ValueError("db: a 1-D row")
+    n, fs = len(db), float(fs)
+    if floor_db is None:
+        finite = db[np.isfinite(db)]
+        if len(finite) == 0:
+            return []
+        floor_db = float(np.median(finite))
+    with np.errstate(invalid="ignore"):
+        mask = db > float(floor_db) + float(margin_db)
+    edges = np.diff(np.concatenate(([0], mask.astype(np.int8), [0])))
+    starts, ends = np.nonzero(edges == 1)[0], np.nonzero(edges == -1)[0] - 1
+    freqs = np.fft.fftshift(np.fft.fftfreq(n, 1.0 / fs))
+    bin_hz = fs / n
+    out = []
+    for a, b in zip(starts, ends):
+        a, b = int(a), int(b)
+        if b - a + 1 < min_bins:
+            continue
+        lo, hi = float(freqs[a]) - bin_hz / 2, float(freqs[b]) + bin_hz / 2
+        k = a + int(np.argmax(db[a:b + 1]))
+        out.append(dict(lo_hz=lo, hi_hz=hi, center_hz=(lo + hi) / 2, bandwidth_hz=(b - a + 1) * bin_hz, peak_hz=float(freqs[k]), peak_db=float(db[k]),
+                        bins=(a, b)))
+    return out
+
+
 _AUDIO_MID = {'AM': 22050, 'USB': 22050, 'LSB': 22050, 'RAW': 22050, 'NFM': 44100, 'WFM': 110250}
 
 
