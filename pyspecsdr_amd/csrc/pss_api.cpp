@@ -41,6 +41,19 @@ int pss_ensure_buffer(pss_ctx *ctx, void **buf, size_t *cap, size_t bytes, const
     return PSS_OK;
 }
 
+int pss_table_sync(pss_ctx *ctx, PssDevTable *t, const void *img, size_t bytes, const char *what, size_t capacity)
+{
+    if (t->host.size() == bytes && memcmp(t->host.data(), img, bytes) == 0) return PSS_OK;
+    t->host.clear();   // first: pss_ensure_buffer may free the buffer the mirror describes, and every step below may fail
+    int r = pss_ensure_buffer(ctx, &t->dev, &t->cap, capacity > bytes ? capacity : bytes, what);
+    if (r) return r;
+    PSS_HIP(ctx, hipMemcpyAsync(t->dev, img, bytes, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
+    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // img may be a local; the upload is ordered behind earlier launches reading the old tables
+    const unsigned char *b = static_cast<const unsigned char *>(img);
+    t->host.assign(b, b + bytes);
+    return PSS_OK;
+}
+
 int pss_ensure_scratch(pss_ctx *ctx, size_t bytes)
 {
     return pss_ensure_buffer(ctx, &ctx->scratch, &ctx->scratch_bytes, bytes, "scratch");
@@ -175,11 +188,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->stage) hipFree(ctx->stage);
     for (auto &b : ctx->sq_buf) if (b) hipFree(b);
     if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
-    if (ctx->ddc_tab) hipFree(ctx->ddc_tab);
-    if (ctx->pfb_tab) hipFree(ctx->pfb_tab);
-    if (ctx->bank_tab) hipFree(ctx->bank_tab);
-    if (ctx->rs_tab) hipFree(ctx->rs_tab);
-    if (ctx->welch_win) hipFree(ctx->welch_win);
+    for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win}) t->release();
     if (ctx->welch_part) hipFree(ctx->welch_part);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);

@@ -27,7 +27,7 @@
 #include <vector>
 
 #include "pss_bank.h"
-#include "pss_chan_args.h"
+#include "pss_chan.h"
 #include "pss_ctx.h"
 
 namespace {
@@ -160,7 +160,7 @@ const Tables &host_tables(int M)
     return t;
 }
 
-// The argument rules of pss_bank and pss_h_bank: the channelisers' shared ones (pss_chan_args.h) with bank_ok for the channel count.
+// The argument rules of pss_bank and pss_h_bank: the channelisers' shared ones (pss_chan.h) with bank_ok for the channel count.
 int bank_check(pss_ctx *ctx, const char *who, const void *iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim, const double *taps,
                int n_taps, int lead, long m_begin, long m_end, const void *out, long out_stride)
 {
@@ -186,21 +186,9 @@ extern "C" int pss_h_bank(const float *h_iq, long n_buf, long buf_index0, long n
     if (r || m_begin == m_end) return r;
     if (pow2(n_chan)) return pss_h_pfb(h_iq, n_buf, buf_index0, n_capture, n_chan, decim, taps, n_taps, lead, m_begin, m_end, h_out, out_stride);
     const Tables &tab = host_tables(n_chan);
-    const long lo = buf_index0, hi = buf_index0 + n_buf;
-    std::vector<double> vr(n_chan), vi(n_chan);
-    std::vector<float> y(2 * (size_t)n_chan);
-    for (long m = m_begin; m < m_end; m++) {
-        instant(m, n_chan, decim, taps, n_taps, lead, tab.tw.data(), tab.rev.data(), [&](long j, float &xr, float &xi) {
-            const bool in = j >= lo && j < hi;
-            xr = in ? h_iq[2 * (j - lo)] : 0.0f;
-            xi = in ? h_iq[2 * (j - lo) + 1] : 0.0f;
-        }, vr.data(), vi.data(), y.data());
-        for (int c = 0; c < n_chan; c++) {
-            float *o = h_out + 2 * ((size_t)c * out_stride + (m - m_begin));
-            o[0] = y[2 * c];
-            o[1] = y[2 * c + 1];
-        }
-    }
+    pss_chan_host_loop(h_iq, n_buf, buf_index0, n_chan, m_begin, m_end, h_out, out_stride, [&](long m, auto x, double *vr, double *vi, float *y) {
+        instant(m, n_chan, decim, taps, n_taps, lead, tab.tw.data(), tab.rev.data(), x, vr, vi, y);
+    });
     return PSS_OK;
 }
 
@@ -212,22 +200,16 @@ extern "C" int pss_bank(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_in
     int r = bank_check(ctx, "pss_bank", d_iq, n_buf, buf_index0, n_capture, n_chan, decim, taps, n_taps, lead, m_begin, m_end, d_out, out_stride);
     if (r || m_begin == m_end) return r;
     if (pow2(n_chan)) return pss_pfb(ctx, d_iq, n_buf, buf_index0, n_capture, n_chan, decim, taps, n_taps, lead, m_begin, m_end, d_out, out_stride);
-    // the host tables, back to back: twiddles, taps, digit reversal.  Uploaded when they differ from what the device copy holds.
+    // the host tables, back to back: twiddles, taps, digit reversal (pss_table_sync: uploaded when they differ from the device copy)
     const Tables &tab = host_tables(n_chan);
     const size_t o_taps = sizeof(double) * 2 * (size_t)n_chan, o_rev = o_taps + sizeof(double) * (size_t)n_taps, bytes = o_rev + sizeof(int) * (size_t)n_chan;
     std::vector<unsigned char> img(bytes);
     memcpy(img.data(), tab.tw.data(), o_taps);
     memcpy(img.data() + o_taps, taps, o_rev - o_taps);
     memcpy(img.data() + o_rev, tab.rev.data(), bytes - o_rev);
-    if (img != ctx->bank_host) {
-        ctx->bank_host.clear();
-        r = pss_ensure_buffer(ctx, &ctx->bank_tab, &ctx->bank_tab_bytes, bytes, "pss_bank tables");
-        if (r) return r;
-        PSS_HIP(ctx, hipMemcpyAsync(ctx->bank_tab, img.data(), bytes, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
-        PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // img is a local; the upload is ordered behind earlier launches reading the old tables
-        ctx->bank_host.swap(img);
-    }
-    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->bank_tab);
+    r = pss_table_sync(ctx, &ctx->bank_tab, img.data(), bytes, "pss_bank tables");
+    if (r) return r;
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->bank_tab.dev);
     int n2, n3, n5;
     factor(n_chan, n2, n3, n5);
     const int G = tile_group(n_chan), R = tile_instants(n_chan);

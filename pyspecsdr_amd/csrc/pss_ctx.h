@@ -28,6 +28,20 @@ struct PssPairwisePlan {  // numpy pairwise-sum forest of one group length (pss_
     int *d_tab = nullptr;  // ONE device allocation: leaf_off, leaf_len, node_l, node_r, level_start, roots back to back (PlanDev points into it)
 };
 
+// The device copy of a call's host tables, grow-only, and the host bytes it mirrors: a call with the same tables as the last one uploads
+// nothing (pss_table_sync below keeps the two in step)
+struct PssDevTable {
+    void *dev = nullptr;
+    size_t cap = 0;
+    std::vector<unsigned char> host;
+    void release()
+    {
+        if (dev) hipFree(dev);
+        dev = nullptr, cap = 0;
+        host.clear();
+    }
+};
+
 struct pss_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -101,28 +115,13 @@ struct pss_ctx {
     void *sq_buf[3] = {};
     size_t sq_cap[3] = {};
     void *sq_pin = nullptr;
-    // down-converter (pss_ddc.hip): the device copy of the call's host tables (rotor knots, taps, frequency words), grow-only, and the bytes
-    // it holds — a call with the same tables as the last one uploads nothing
-    void *ddc_tab = nullptr;
-    size_t ddc_tab_bytes = 0;
-    std::vector<unsigned char> ddc_host;
-    // polyphase channeliser (pss_pfb.hip): the same for its tables (rotor knots, taps)
-    void *pfb_tab = nullptr;
-    size_t pfb_tab_bytes = 0;
-    std::vector<unsigned char> pfb_host;
-    // channeliser for band plans (pss_bank.hip): the same for its tables (twiddles of M, taps, digit reversal)
-    void *bank_tab = nullptr;
-    size_t bank_tab_bytes = 0;
-    std::vector<unsigned char> bank_host;
-    // rational resampler (pss_resample.hip): the same for its table (the plan's numbers, then the taps in visit order)
-    void *rs_tab = nullptr;
-    size_t rs_tab_bytes = 0;
-    std::vector<unsigned char> rs_host;
-    // capture survey (pss_welch.hip): the device copy of the caller's window and the doubles it holds, and the block partials, grow-only
-    void *welch_win = nullptr;
-    size_t welch_win_bytes = 0;
-    std::vector<double> welch_host;
-    void *welch_part = nullptr;
+    // the channel family's cached tables, one per unit so that alternating calls do not evict each other
+    PssDevTable ddc_tab;     // pss_ddc.hip: rotor knots, taps, frequency words
+    PssDevTable pfb_tab;     // pss_pfb.hip: rotor knots, taps
+    PssDevTable bank_tab;    // pss_bank.hip: twiddles of M, taps, digit reversal
+    PssDevTable rs_tab;      // pss_resample.hip: the plan's numbers, then the taps in visit order
+    PssDevTable welch_win;   // pss_welch.hip: the caller's window
+    void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;
     std::string tfilter;  // pss_timing_filter: only launches of this kernel get events (and no per-call events); empty = all
@@ -171,6 +170,9 @@ int pss_fail(pss_ctx *ctx, int code, const std::string &msg);
 int pss_hip_check(pss_ctx *ctx, hipError_t e, const char *what);
 int pss_ensure_scratch(pss_ctx *ctx, size_t bytes);
 int pss_ensure_buffer(pss_ctx *ctx, void **buf, size_t *cap, size_t bytes, const char *what);
+// Make t's device copy hold the `bytes` bytes at `img`: nothing where the mirror already equals them, otherwise an upload on the context's
+// stream that has finished on return (img may be a local).  capacity: what to allocate where the buffer must grow (0: bytes).
+int pss_table_sync(pss_ctx *ctx, PssDevTable *t, const void *img, size_t bytes, const char *what, size_t capacity = 0);
 void pss_time_begin(pss_ctx *ctx);
 void pss_time_end(pss_ctx *ctx);
 // The timing bracket of a call (pss_last_kernel_ms): nested brackets are no-ops, the outermost one closes on every way out of its scope

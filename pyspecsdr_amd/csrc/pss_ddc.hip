@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "pss_chan.h"
 #include "pss_ctx.h"
 #include "pss_ddc.h"
 
@@ -117,16 +118,6 @@ __global__ __launch_bounds__(DDC_T) void k_ddc(const float2 *__restrict__ iq, lo
     }
 }
 
-const double *host_knots()
-{
-    static const std::vector<double> k = [] {
-        std::vector<double> v(2 * KNOTS);
-        build_knots(v.data());
-        return v;
-    }();
-    return k.data();
-}
-
 // The argument rules of pss_ddc and pss_h_ddc.  ctx: where the reason goes (NULL: the library's own slot).
 int ddc_check(pss_ctx *ctx, const char *who, const void *iq, long n_buf, long buf_index0, long n_capture, const uint64_t *words, int n_chan, int decim,
               const double *taps, int n_taps, int lead, long m_begin, long m_end, const void *out, long out_stride)
@@ -136,24 +127,7 @@ int ddc_check(pss_ctx *ctx, const char *who, const void *iq, long n_buf, long bu
     if (n_taps < 1 || n_taps > MAX_TAPS) return bad("n_taps outside [1, 4097]");
     if (n_chan < 1) return bad("n_chan < 1");
     if (!words || !taps) return bad("null words or taps");
-    if (lead < 0 || lead > n_taps - 1) return bad("lead outside [0, n_taps - 1]");
-    for (int k = 0; k < n_taps; k++)
-        if (!std::isfinite(taps[k])) return bad("a tap that is not finite");
-    if (n_capture < 0 || n_buf < 0 || buf_index0 < 0 || n_buf > n_capture || buf_index0 > n_capture - n_buf)
-        return bad("the buffer [buf_index0, buf_index0 + n_buf) is not inside the capture [0, n_capture)");
-    if (m_begin < 0 || m_end < m_begin || m_end > out_len(n_capture, decim)) return bad("[m_begin, m_end) outside [0, ceil(n_capture / decim)]");
-    if (out_stride < m_end - m_begin) return bad("out_stride < m_end - m_begin");
-    if (m_begin == m_end) return PSS_OK;
-    if (!out) return bad("null output");
-    // the samples the outputs need, cut to the capture: they must lie in the buffer
-    long need_lo = m_begin * decim + lead - (n_taps - 1), need_hi = (m_end - 1) * decim + lead + 1;
-    if (need_lo < 0) need_lo = 0;
-    if (need_hi > n_capture) need_hi = n_capture;
-    if (need_lo < need_hi) {
-        if (!iq) return bad("null input");
-        if (need_lo < buf_index0 || need_hi > buf_index0 + n_buf) return bad("an output needs a sample of the capture that the buffer does not hold");
-    }
-    return PSS_OK;
+    return pss_chan_window_check(ctx, who, false, iq, n_buf, buf_index0, n_capture, decim, taps, n_taps, lead, m_begin, m_end, out, out_stride);
 }
 
 }  // namespace
@@ -190,7 +164,7 @@ extern "C" int pss_h_ddc_rotor(uint64_t word, long index0, long n, double *c, do
 {
     if (index0 < 0 || n < 0 || index0 > INT64_MAX - n || (n > 0 && (!c || !s)))
         return pss_fail(nullptr, PSS_E_ARG, "pss_h_ddc_rotor: index0, n >= 0 without overflow; c and s not null");
-    const double *knots = host_knots();
+    const double *knots = pss_host_knots();
     for (long t = 0; t < n; t++) rotor(phase_of(word, index0 + t), knots, c[t], s[t]);
     return PSS_OK;
 }
@@ -201,7 +175,7 @@ extern "C" int pss_h_ddc(const float *h_iq, long n_buf, long buf_index0, long n_
     const int r = ddc_check(nullptr, "pss_h_ddc", h_iq, n_buf, buf_index0, n_capture, words, n_chan, decim, taps, n_taps, lead, m_begin, m_end, h_out,
                             out_stride);
     if (r || m_begin == m_end) return r;
-    const double *knots = host_knots();
+    const double *knots = pss_host_knots();
     // per channel and per run of outputs: the mixed samples once, then the outputs
     const long run = 4096;
     std::vector<double> z;
@@ -235,22 +209,16 @@ extern "C" int pss_ddc(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_ind
     if (r || m_begin == m_end) return r;
     if ((reinterpret_cast<uintptr_t>(d_iq) & 7) || (reinterpret_cast<uintptr_t>(d_out) & 7))
         return pss_fail(ctx, PSS_E_ARG, "pss_ddc: d_iq and d_out must be 8-byte aligned");
-    // the host tables, back to back: knots, taps, words.  Uploaded when they differ from what the device copy holds.
+    // the host tables, back to back: knots, taps, words (pss_table_sync: uploaded when they differ from the device copy)
     const size_t o_taps = sizeof(double) * 2 * KNOTS, o_words = o_taps + sizeof(double) * (size_t)n_taps;
     const size_t bytes = o_words + sizeof(uint64_t) * (size_t)n_chan;
     std::vector<unsigned char> tab(bytes);
-    memcpy(tab.data(), host_knots(), o_taps);
+    memcpy(tab.data(), pss_host_knots(), o_taps);
     memcpy(tab.data() + o_taps, taps, o_words - o_taps);
     memcpy(tab.data() + o_words, words, bytes - o_words);
-    if (tab != ctx->ddc_host) {
-        ctx->ddc_host.clear();
-        r = pss_ensure_buffer(ctx, &ctx->ddc_tab, &ctx->ddc_tab_bytes, bytes, "pss_ddc tables");
-        if (r) return r;
-        PSS_HIP(ctx, hipMemcpyAsync(ctx->ddc_tab, tab.data(), bytes, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
-        PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // tab is a local; the upload is ordered behind earlier launches reading the old tables
-        ctx->ddc_host.swap(tab);
-    }
-    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->ddc_tab);
+    r = pss_table_sync(ctx, &ctx->ddc_tab, tab.data(), bytes, "pss_ddc tables");
+    if (r) return r;
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->ddc_tab.dev);
     const int M = tile_outputs(decim, n_taps);
     const int L = M == 1 ? 1 : decim, ROW = tile_row(M, decim, n_taps);
     const long n_tiles = (m_end - m_begin + M - 1) / M;

@@ -21,7 +21,7 @@
 #include <string>
 #include <vector>
 
-#include "pss_chan_args.h"
+#include "pss_chan.h"
 #include "pss_ctx.h"
 #include "pss_pfb.h"
 
@@ -118,17 +118,7 @@ __global__ __launch_bounds__(PFB_T) void k_pfb(const float2 *__restrict__ iq, lo
     }
 }
 
-const double *host_knots()
-{
-    static const std::vector<double> k = [] {
-        std::vector<double> v(2 * pss_dc::KNOTS);
-        pss_dc::build_knots(v.data());
-        return v;
-    }();
-    return k.data();
-}
-
-// The argument rules of pss_pfb and pss_h_pfb: the channelisers' shared ones (pss_chan_args.h) for a power-of-two channel count.
+// The argument rules of pss_pfb and pss_h_pfb: the channelisers' shared ones (pss_chan.h) for a power-of-two channel count.
 int pfb_check(pss_ctx *ctx, const char *who, const void *iq, long n_buf, long buf_index0, long n_capture, int n_chan, int decim, const double *taps,
               int n_taps, int lead, long m_begin, long m_end, const void *out, long out_stride)
 {
@@ -151,22 +141,10 @@ extern "C" int pss_h_pfb(const float *h_iq, long n_buf, long buf_index0, long n_
 {
     const int r = pfb_check(nullptr, "pss_h_pfb", h_iq, n_buf, buf_index0, n_capture, n_chan, decim, taps, n_taps, lead, m_begin, m_end, h_out, out_stride);
     if (r || m_begin == m_end) return r;
-    const double *knots = host_knots();
-    const long lo = buf_index0, hi = buf_index0 + n_buf;
-    std::vector<double> vr(n_chan), vi(n_chan);
-    std::vector<float> y(2 * (size_t)n_chan);
-    for (long m = m_begin; m < m_end; m++) {
-        instant(m, n_chan, decim, taps, n_taps, lead, knots, [&](long j, float &xr, float &xi) {
-            const bool in = j >= lo && j < hi;
-            xr = in ? h_iq[2 * (j - lo)] : 0.0f;
-            xi = in ? h_iq[2 * (j - lo) + 1] : 0.0f;
-        }, vr.data(), vi.data(), y.data());
-        for (int c = 0; c < n_chan; c++) {
-            float *o = h_out + 2 * ((size_t)c * out_stride + (m - m_begin));
-            o[0] = y[2 * c];
-            o[1] = y[2 * c + 1];
-        }
-    }
+    const double *knots = pss_host_knots();
+    pss_chan_host_loop(h_iq, n_buf, buf_index0, n_chan, m_begin, m_end, h_out, out_stride, [&](long m, auto x, double *vr, double *vi, float *y) {
+        instant(m, n_chan, decim, taps, n_taps, lead, knots, x, vr, vi, y);
+    });
     return PSS_OK;
 }
 
@@ -177,20 +155,14 @@ extern "C" int pss_pfb(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_ind
     PSS_GUARD(ctx);
     int r = pfb_check(ctx, "pss_pfb", d_iq, n_buf, buf_index0, n_capture, n_chan, decim, taps, n_taps, lead, m_begin, m_end, d_out, out_stride);
     if (r || m_begin == m_end) return r;
-    // the host tables, back to back: knots, taps.  Uploaded when they differ from what the device copy holds.
+    // the host tables, back to back: knots, taps (pss_table_sync: uploaded when they differ from the device copy)
     const size_t o_taps = sizeof(double) * 2 * pss_dc::KNOTS, bytes = o_taps + sizeof(double) * (size_t)n_taps;
     std::vector<unsigned char> tab(bytes);
-    memcpy(tab.data(), host_knots(), o_taps);
+    memcpy(tab.data(), pss_host_knots(), o_taps);
     memcpy(tab.data() + o_taps, taps, bytes - o_taps);
-    if (tab != ctx->pfb_host) {
-        ctx->pfb_host.clear();
-        r = pss_ensure_buffer(ctx, &ctx->pfb_tab, &ctx->pfb_tab_bytes, bytes, "pss_pfb tables");
-        if (r) return r;
-        PSS_HIP(ctx, hipMemcpyAsync(ctx->pfb_tab, tab.data(), bytes, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
-        PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // tab is a local; the upload is ordered behind earlier launches reading the old tables
-        ctx->pfb_host.swap(tab);
-    }
-    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->pfb_tab);
+    r = pss_table_sync(ctx, &ctx->pfb_tab, tab.data(), bytes, "pss_pfb tables");
+    if (r) return r;
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(ctx->pfb_tab.dev);
     const int R = tile_instants(n_chan);
     const long n_m = m_end - m_begin, n_tiles = (n_m + R - 1) / R;
     PssTimeScope timed(ctx);

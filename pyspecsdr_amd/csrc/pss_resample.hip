@@ -164,22 +164,16 @@ template <class E, class T>
 int launch(pss_ctx *ctx, const Plan &p, const void *d_x, long n_rows, long x_stride, long buf_index0, const double *taps, long j_begin, long j_end,
            void *d_y, long y_stride)
 {
-    // the plan's numbers and the table in visit order, back to back: uploaded when they differ from what the device copy holds
+    // the plan's numbers and the table in visit order, back to back (pss_table_sync: uploaded when they differ from the device copy)
     const long n_tab = table_len(p);
     const long head[4] = {p.up, p.down, p.hpp, (long)sizeof(T)};
     const size_t bytes = sizeof(head) + sizeof(T) * (size_t)(n_tab > 0 ? n_tab : 1);
     std::vector<unsigned char> tab(bytes, 0);
     memcpy(tab.data(), head, sizeof(head));
     if (!p.copy) build_visit(p, taps, reinterpret_cast<T *>(tab.data() + sizeof(head)));
-    if (tab != ctx->rs_host) {
-        ctx->rs_host.clear();
-        int r = pss_ensure_buffer(ctx, &ctx->rs_tab, &ctx->rs_tab_bytes, bytes, "pss_resample table");
-        if (r) return r;
-        PSS_HIP(ctx, hipMemcpyAsync(ctx->rs_tab, tab.data(), bytes, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
-        PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // tab is a local; the upload is ordered behind earlier launches reading the old table
-        ctx->rs_host.swap(tab);
-    }
-    const T *d_tab = reinterpret_cast<const T *>(reinterpret_cast<const unsigned char *>(ctx->rs_tab) + sizeof(head));
+    const int r = pss_table_sync(ctx, &ctx->rs_tab, tab.data(), bytes, "pss_resample table");
+    if (r) return r;
+    const T *d_tab = reinterpret_cast<const T *>(reinterpret_cast<const unsigned char *>(ctx->rs_tab.dev) + sizeof(head));
     const RsGeom G = geom(p, n_rows, x_stride, buf_index0, j_begin, j_end, y_stride);
     const long n_groups = (G.n_items + RS_T - 1) / RS_T;
     PssTimeScope timed(ctx);

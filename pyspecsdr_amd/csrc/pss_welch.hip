@@ -247,22 +247,16 @@ extern "C" int pss_welch(pss_ctx *ctx, const float *d_iq, long n_rows, long n, l
     if (n_rows > INT64_MAX / 32 / nperseg / G.nb) return pss_fail(ctx, PSS_E_ARG, "pss_welch: n_rows times the blocks of a row overflows");
     G.n_items = n_rows * G.nb;
     const int planes = d_max ? 2 : 1;
-    // the window: uploaded when its bytes differ from what the device copy holds
-    if (ctx->welch_host.size() != (size_t)nperseg || memcmp(ctx->welch_host.data(), h_win, sizeof(double) * nperseg) != 0) {
-        ctx->welch_host.clear();
-        int r = pss_ensure_buffer(ctx, &ctx->welch_win, &ctx->welch_win_bytes, sizeof(double) * MAX_N, "pss_welch window");
-        if (r) return r;
-        PSS_HIP(ctx, hipMemcpyAsync(ctx->welch_win, h_win, sizeof(double) * nperseg, hipMemcpyHostToDevice, PSS_STREAM(ctx)));
-        PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));   // h_win is the caller's; ordered behind earlier launches reading the old window
-        ctx->welch_host.assign(h_win, h_win + nperseg);
-    }
-    int r = pss_ensure_buffer(ctx, &ctx->welch_part, &ctx->welch_part_bytes, sizeof(double) * (size_t)G.n_items * planes * nperseg, "pss_welch partials");
+    // the window (pss_table_sync: uploaded when its bytes differ from the device copy), in a buffer that holds the longest one
+    int r = pss_table_sync(ctx, &ctx->welch_win, h_win, sizeof(double) * nperseg, "pss_welch window", sizeof(double) * MAX_N);
+    if (r) return r;
+    r = pss_ensure_buffer(ctx, &ctx->welch_part, &ctx->welch_part_bytes, sizeof(double) * (size_t)G.n_items * planes * nperseg, "pss_welch partials");
     if (r) return r;
     const double2 *tw;
     const double *hamming;
     r = pss_fft_tables(ctx, nperseg, &tw, &hamming);
     if (r) return r;
-    const double *d_win = reinterpret_cast<const double *>(ctx->welch_win);
+    const double *d_win = reinterpret_cast<const double *>(ctx->welch_win.dev);
     double *d_part = reinterpret_cast<double *>(ctx->welch_part);
     PssTimeScope timed(ctx);
     switch (nperseg) {

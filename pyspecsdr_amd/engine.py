@@ -1109,17 +1109,24 @@ class Engine:
         return w.value, eff.value
 
     @staticmethod
+    def _default_taps(lib, entry, why, *args):
+        """A pss_*_default_taps entry point asked twice, for the length and then for the table -> float64 taps.  why: the ValueError's
+        text where it refuses the integer arguments."""
+        f = getattr(lib or L.load(), entry)
+        args = [int(a) for a in args]
+        n = C.c_int()
+        if f(*args, None, C.byref(n)) != 0:
+            raise ValueError(why)
+        taps = np.empty(n.value, np.float64)
+        r = f(*args, _ptr(taps), C.byref(n))
+        if r != 0:
+            raise PssError(r, entry)
+        return taps
+
+    @staticmethod
     def ddc_default_taps(decim, lib=None):
         """pss_ddc_default_taps: scipy.signal.decimate's FIR, firwin(20 decim + 1, 1 / decim); decim = 1: [1.0].  Host code."""
-        lib = lib or L.load()
-        n = C.c_int()
-        if lib.pss_ddc_default_taps(int(decim), None, C.byref(n)) != 0:
-            raise ValueError("ddc_default_taps: decim outside [1, 204]; pass taps for a larger decimation")
-        taps = np.empty(n.value, np.float64)
-        r = lib.pss_ddc_default_taps(int(decim), _ptr(taps), C.byref(n))
-        if r != 0:
-            raise PssError(r, "pss_ddc_default_taps")
-        return taps
+        return Engine._default_taps(lib, "pss_ddc_default_taps", "ddc_default_taps: decim outside [1, 204]; pass taps for a larger decimation", decim)
 
     @staticmethod
     def h_ddc_rotor(word, index0, n, lib=None):
@@ -1172,15 +1179,7 @@ class Engine:
     @staticmethod
     def pfb_default_taps(n_chan, lib=None):
         """pss_pfb_default_taps: firwin(20 n_chan + 1, 1 / n_chan), n_chan a power of two in [2, 1024].  Host code."""
-        lib = lib or L.load()
-        n = C.c_int()
-        if lib.pss_pfb_default_taps(int(n_chan), None, C.byref(n)) != 0:
-            raise ValueError("pfb_default_taps: n_chan must be a power of two in [2, 1024]")
-        taps = np.empty(n.value, np.float64)
-        r = lib.pss_pfb_default_taps(int(n_chan), _ptr(taps), C.byref(n))
-        if r != 0:
-            raise PssError(r, "pss_pfb_default_taps")
-        return taps
+        return Engine._default_taps(lib, "pss_pfb_default_taps", "pfb_default_taps: n_chan must be a power of two in [2, 1024]", n_chan)
 
     @staticmethod
     def _pfb_args(lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
@@ -1206,31 +1205,28 @@ class Engine:
         self._dev(self.lib.pss_pfb, _ptr(d_iq), *a, _ptr(taps), *b, _ptr(d_out), out_stride)
 
     @staticmethod
-    def h_pfb(iq, n_chan, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
-        """pss_h_pfb: the same on a host buffer -> complex64 [n_chan][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
+    def _h_chan(entry, args_of, iq, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, lib):
+        """h_pfb / h_bank: the host twin `entry` with the defaults of args_of (_pfb_args / _bank_args)."""
         lib = lib or L.load()
         iq = np.ascontiguousarray(iq, np.complex64)
         if iq.ndim != 1:
             raise ValueError("iq: a 1-D complex buffer")
-        taps, a, b, stride = Engine._pfb_args(lib, len(iq), n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
+        taps, a, b, stride = args_of(lib, len(iq), n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
         out = np.empty((max(int(n_chan), 0), max(stride, 0)), np.complex64)
-        if lib.pss_h_pfb(_ptr(iq), *a, _ptr(taps), *b, _ptr(out), stride) != 0:
+        if getattr(lib, entry)(_ptr(iq), *a, _ptr(taps), *b, _ptr(out), stride) != 0:
             raise ValueError(lib.pss_last_error(None).decode())
         return out
+
+    @staticmethod
+    def h_pfb(iq, n_chan, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_pfb: the same on a host buffer -> complex64 [n_chan][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
+        return Engine._h_chan("pss_h_pfb", Engine._pfb_args, iq, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, lib)
 
     # -- channeliser for band plans: the same for every n_chan = 2^a 3^b 5^c in [2, 1024] (pss_bank; the arithmetic: csrc/pss_bank.h)
     @staticmethod
     def bank_default_taps(n_chan, lib=None):
         """pss_bank_default_taps: firwin(20 n_chan + 1, 1 / n_chan), n_chan = 2^a 3^b 5^c in [2, 1024].  Host code."""
-        lib = lib or L.load()
-        n = C.c_int()
-        if lib.pss_bank_default_taps(int(n_chan), None, C.byref(n)) != 0:
-            raise ValueError("bank_default_taps: n_chan must be of the form 2^a 3^b 5^c in [2, 1024]")
-        taps = np.empty(n.value, np.float64)
-        r = lib.pss_bank_default_taps(int(n_chan), _ptr(taps), C.byref(n))
-        if r != 0:
-            raise PssError(r, "pss_bank_default_taps")
-        return taps
+        return Engine._default_taps(lib, "pss_bank_default_taps", "bank_default_taps: n_chan must be of the form 2^a 3^b 5^c in [2, 1024]", n_chan)
 
     @staticmethod
     def _bank_args(lib, n_buf, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
@@ -1249,15 +1245,7 @@ class Engine:
     @staticmethod
     def h_bank(iq, n_chan, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
         """pss_h_bank: the same on a host buffer -> complex64 [n_chan][m_end - m_begin].  Pure host code: the kernel's statements on one thread."""
-        lib = lib or L.load()
-        iq = np.ascontiguousarray(iq, np.complex64)
-        if iq.ndim != 1:
-            raise ValueError("iq: a 1-D complex buffer")
-        taps, a, b, stride = Engine._bank_args(lib, len(iq), n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
-        out = np.empty((max(int(n_chan), 0), max(stride, 0)), np.complex64)
-        if lib.pss_h_bank(_ptr(iq), *a, _ptr(taps), *b, _ptr(out), stride) != 0:
-            raise ValueError(lib.pss_last_error(None).decode())
-        return out
+        return Engine._h_chan("pss_h_bank", Engine._bank_args, iq, n_chan, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, lib)
 
     # -- rational resampler for rows: scipy.signal.resample_poly bit for bit (pss_resample; the arithmetic: csrc/pss_resample.h)
     RS_DTYPES = {np.dtype(np.float32): L.RS_F32, np.dtype(np.float64): L.RS_F64, np.dtype(np.complex64): L.RS_C64}
@@ -1274,15 +1262,7 @@ class Engine:
     def resample_default_taps(up, down, lib=None):
         """pss_resample_default_taps: resample_poly's own design, firwin(20 m + 1, 1 / m, window=('kaiser', 5.0)) with m = max(up, down) after
         the reduction, float64 (before the cast to the row's type and the scaling by up).  Host code."""
-        lib = lib or L.load()
-        n = C.c_int()
-        if lib.pss_resample_default_taps(int(up), int(down), None, C.byref(n)) != 0:
-            raise ValueError("resample_default_taps: up and down in [1, 4096]")
-        taps = np.empty(n.value, np.float64)
-        r = lib.pss_resample_default_taps(int(up), int(down), _ptr(taps), C.byref(n))
-        if r != 0:
-            raise PssError(r, "pss_resample_default_taps")
-        return taps
+        return Engine._default_taps(lib, "pss_resample_default_taps", "resample_default_taps: up and down in [1, 4096]", up, down)
 
     @staticmethod
     def _resample_args(lib, n_buf, up, down, taps, buf_index0, n_in, j_begin, j_end):

@@ -429,13 +429,12 @@ def decode_mono_recording(samples, fs, frame_len=32768, codes_format=None, table
     return pcm
 
 
-def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, codes_format, table, m_end=None):
-    """tune_recording's work -> (device tensor float32 [K][2 * m_end], effective offsets): the capture goes up in chunks of about
+def _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m_end, plan):
+    """The streaming _tune_device and _bank_device share -> device tensor float32 [rows][2 * m_end]: the capture goes up in chunks of about
     chunk_samples samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place
-    of the one result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit."""
+    of the one result.  plan() -> (taps, rows, run) is asked once the capture is in its form; run(d_iq, n_buf, out_ptr, **window) is the
+    entry point's call with buf_index0, n_capture, lead, m_begin, m_end and out_stride."""
     import torch
-    e = get_engine()
-    fs, decim = float(fs), int(decim)
     if int(chunk_samples) != chunk_samples or chunk_samples < 1:
         raise ValueError("chunk_samples must be an integer >= 1")
     if codes_format is not None:
@@ -447,9 +446,7 @@ def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, code
         samples = np.ascontiguousarray(samples, np.complex64)
         if samples.ndim != 1:
             raise ValueError("samples: a 1-D recording")
-    pairs = [e.ddc_word(f, fs) for f in np.atleast_1d(np.asarray(offsets_hz, np.float64))]
-    words, effective = np.array([p[0] for p in pairs], np.uint64), np.array([p[1] for p in pairs], np.float64)
-    taps = e.ddc_default_taps(decim) if taps is None else np.ascontiguousarray(taps, np.float64)
+    taps, rows, run = plan()
     n_taps = len(taps)
     lead = (n_taps - 1) // 2 if lead is None else int(lead)
     n = len(samples)
@@ -459,7 +456,7 @@ def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, code
     if m_end is None:
         m_end = n_out
     dev = f"cuda:{e.device}"
-    d_out = torch.empty((len(words), 2 * m_end), dtype=torch.float32, device=dev)
+    d_out = torch.empty((rows, 2 * m_end), dtype=torch.float32, device=dev)
     per_chunk = max(1, int(chunk_samples) // decim)
     for m0 in range(0, max(m_end, 1), per_chunk):
         m1 = min(m_end, m0 + per_chunk)
@@ -473,8 +470,26 @@ def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, code
         else:
             d_iq = torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev) if hi > lo else torch.empty(2, dtype=torch.float32, device=dev)
         # m1 == m0 (an empty capture) still goes through the call: it checks the arguments and writes nothing
-        e.ddc(d_iq, hi - lo, words, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
-              out_stride=m_end)
+        run(d_iq, hi - lo, d_out.data_ptr() + 8 * m0, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1, out_stride=m_end)
+    return d_out
+
+
+def _tune_device(samples, fs, offsets_hz, decim, taps, lead, chunk_samples, codes_format, table, m_end=None):
+    """tune_recording's work -> (device tensor float32 [K][2 * m_end], effective offsets), streamed by _chunk_device.  The phase of a
+    sample follows from its index in the capture, so no chunking changes a bit."""
+    e = get_engine()
+    fs, decim = float(fs), int(decim)
+    effective = None
+
+    def plan():
+        nonlocal effective
+        pairs = [e.ddc_word(f, fs) for f in np.atleast_1d(np.asarray(offsets_hz, np.float64))]
+        words = np.array([p[0] for p in pairs], np.uint64)
+        effective = np.array([p[1] for p in pairs], np.float64)
+        t = e.ddc_default_taps(decim) if taps is None else np.ascontiguousarray(taps, np.float64)
+        return t, len(words), lambda d_iq, n_buf, out, **window: e.ddc(d_iq, n_buf, words, decim, out, taps=t, **window)
+
+    d_out = _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m_end, plan)
     return d_out, effective
 
 
@@ -738,11 +753,9 @@ def bank_offsets(fs, n_chan):
 
 
 def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format, table, m_end=None, entry='pfb'):
-    """channelize_recording's work -> device tensor float32 [n_chan][2 * m_end]: the capture goes up in chunks of about chunk_samples
-    samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place of the one
-    result.  The phase of a sample follows from its index in the capture, so no chunking changes a bit.  entry: 'pfb' (pss_pfb, n_chan a
-    power of two) or 'bank' (pss_bank, n_chan = 2^a 3^b 5^c) — the streaming is the same."""
-    import torch
+    """channelize_recording's work -> (device tensor float32 [n_chan][2 * m_end], decim), streamed by _chunk_device.  The phase of a
+    sample follows from its index in the capture, so no chunking changes a bit.  entry: 'pfb' (pss_pfb, n_chan a power of two) or 'bank'
+    (pss_bank, n_chan = 2^a 3^b 5^c) — the streaming is the same."""
     e = get_engine()
     n_chan = int(n_chan)
     offsets, default_taps, run = {'pfb': (bank_offsets, e.pfb_default_taps, e.pfb), 'bank': (plan_offsets, e.bank_default_taps, e.bank)}[entry]
@@ -750,42 +763,12 @@ def _bank_device(samples, n_chan, decim, taps, lead, chunk_samples, codes_format
     decim = n_chan // 2 if decim is None else int(decim)
     if decim < 1 or decim > n_chan:
         raise ValueError("decim outside [1, n_chan]")
-    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
-        raise ValueError("chunk_samples must be an integer >= 1")
-    if codes_format is not None:
-        iq = _iq_args(codes_format, table)
-        samples = _iq_codes(samples, iq[0])
-        if samples.ndim != 2:
-            raise ValueError("codes: [n, 2]")
-    else:
-        samples = np.ascontiguousarray(samples, np.complex64)
-        if samples.ndim != 1:
-            raise ValueError("samples: a 1-D recording")
-    taps = default_taps(n_chan) if taps is None else np.ascontiguousarray(taps, np.float64)
-    n_taps = len(taps)
-    lead = (n_taps - 1) // 2 if lead is None else int(lead)
-    n = len(samples)
-    n_out = e.lib.pss_ddc_out_len(n, decim)
-    if m_end is None:
-        m_end = n_out
-    dev = f"cuda:{e.device}"
-    d_out = torch.empty((n_chan, 2 * m_end), dtype=torch.float32, device=dev)
-    per_chunk = max(1, int(chunk_samples) // decim)
-    for m0 in range(0, max(m_end, 1), per_chunk):
-        m1 = min(m_end, m0 + per_chunk)
-        lo, hi = max(0, m0 * decim + lead - (n_taps - 1)), min(n, (m1 - 1) * decim + lead + 1)
-        hi = max(hi, lo)
-        if codes_format is not None:
-            d_codes = torch.from_numpy(np.array(samples[lo:hi])).to(dev)
-            d_iq = torch.empty(2 * (hi - lo) + 2, dtype=torch.float32, device=dev)
-            if hi > lo:
-                e.unpack_iq(d_codes, hi - lo, d_iq, codes_format, iq[2])
-        else:
-            d_iq = torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev) if hi > lo else torch.empty(2, dtype=torch.float32, device=dev)
-        # m1 == m0 (an empty capture) still goes through the call: it checks the arguments and writes nothing
-        run(d_iq, hi - lo, n_chan, decim, d_out.data_ptr() + 8 * m0, taps=taps, buf_index0=lo, n_capture=n, lead=lead, m_begin=m0, m_end=m1,
-            out_stride=m_end)
-    return d_out, decim
+
+    def plan():
+        t = default_taps(n_chan) if taps is None else np.ascontiguousarray(taps, np.float64)
+        return t, n_chan, lambda d_iq, n_buf, out, **window: run(d_iq, n_buf, n_chan, decim, out, taps=t, **window)
+
+    return _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m_end, plan), decim
 
 
 def channelize_recording(samples, fs, n_chan, decim=None, taps=None, lead=None, chunk_samples=1 << 22, codes_format=None, table=None):

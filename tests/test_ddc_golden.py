@@ -21,6 +21,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same_bytes, zeros_alike
 import ddc_cases as DC
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
@@ -33,11 +34,6 @@ CSRC = os.path.join(ROOT, "pyspecsdr_amd", "csrc")
 @pytest.fixture(scope="module")
 def g():
     return np.load(os.path.join(HERE, "golden", "ddc.npz"))
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
 
 
 def test_fixture_inputs_are_what_the_makers_give_today(g):
@@ -141,13 +137,6 @@ def test_identity_and_quarter_turn_are_exact():
         assert np.array_equal(y[0], x)                                     # (== on the values: the sign of a zero is not part of the contract)
         turn = np.array([1, -1j, -1, 1j])[(index0 + np.arange(n)) & 3]
         assert np.array_equal(y[1], (x.astype(np.complex128) * turn).astype(np.complex64)), index0
-
-
-def zeros_alike(a):
-    """The bytes with every -0 made +0: what 'byte for byte' means where the sign of a zero is not part of the contract."""
-    v = np.ascontiguousarray(a).view(np.float32).copy()
-    v[v == 0] = 0.0
-    return v.tobytes()
 
 
 def test_the_shape_of_the_call_changes_no_byte():

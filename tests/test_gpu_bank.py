@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same
 import bank_cases as BC
 from gpu_util import engine
 from pyspecsdr_amd import _lib as L
@@ -59,14 +60,6 @@ def test_launch_constants_read_as_restated():
     assert tile_instants(3) == 2728 and tile_instants(192) == 40 and tile_instants(1000) == 8
     for M in SWEEP_M:                                  # the tile fits its LDS image with rows an odd number of slots apart
         assert tile_instants(M) * (M | 1) <= K["TILE_SLOTS"] and tile_instants(M) * M <= 8192, M
-
-
-def same(a, b):
-    """Bit for bit, except that +0 and -0 are the same value."""
-    a, b = np.ascontiguousarray(a, np.complex64).view(np.float32), np.ascontiguousarray(b, np.complex64).view(np.float32)
-    if a.shape != b.shape:
-        return False
-    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))))
 
 
 CANARY = np.float32(-7.25)

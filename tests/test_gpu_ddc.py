@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same
 import ddc_cases as DC
 from gpu_util import engine
 from pyspecsdr_amd import _lib as L
@@ -65,14 +66,6 @@ def test_launch_constants_read_as_restated():
         assert line in src["pss_ddc.hip"], line
     # the tiles the sweep below leans on
     assert tile_outputs(1, 1) == 1792 and tile_outputs(50, 1001) == 112 and tile_outputs(4096, 4097) == 1 and tile_outputs(1, 4097) == 27
-
-
-def same(a, b):
-    """Bit for bit, except that +0 and -0 are the same value."""
-    a, b = np.ascontiguousarray(a, np.complex64).view(np.float32), np.ascontiguousarray(b, np.complex64).view(np.float32)
-    if a.shape != b.shape:
-        return False
-    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))))
 
 
 CANARY = np.float32(-7.25)

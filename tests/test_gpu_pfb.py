@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same
 import pfb_cases as PC
 from gpu_util import engine
 from pyspecsdr_amd import _lib as L
@@ -54,14 +55,6 @@ def test_launch_constants_read_as_restated():
                  "dim3((unsigned)(n_tiles < PFB_GRID_CAP ? n_tiles : PFB_GRID_CAP)), dim3(PFB_T)"):
         assert line in src["pss_pfb.hip"], line
     assert tile_instants(2) == 4096 and tile_instants(64) == 128 and tile_instants(1024) == 8
-
-
-def same(a, b):
-    """Bit for bit, except that +0 and -0 are the same value."""
-    a, b = np.ascontiguousarray(a, np.complex64).view(np.float32), np.ascontiguousarray(b, np.complex64).view(np.float32)
-    if a.shape != b.shape:
-        return False
-    return bool(np.all((a.view(np.uint32) == b.view(np.uint32)) | ((a == 0) & (b == 0)) | (np.isnan(a) & np.isnan(b))))
 
 
 CANARY = np.float32(-7.25)

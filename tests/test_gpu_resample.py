@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same_bytes
 import resample_cases as RC
 from gpu_util import engine
 from pyspecsdr_amd import _lib as L
@@ -33,11 +34,6 @@ def test_launch_constants_read_as_restated():
                  "for (long id = (long)blockIdx.x * RS_T + threadIdx.x; id < G.n_items; id += step) {",
                  "dim3((unsigned)(n_groups < RS_GRID_CAP ? n_groups : RS_GRID_CAP)), dim3(RS_T)", "G.S = p.up * ((64 + p.up - 1) / p.up);"):
         assert line in src, line
-
-
-def same_bytes(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 _TAPS = {}

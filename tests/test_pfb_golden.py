@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same_bytes, zeros_alike
 import pfb_cases as PC
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
@@ -32,18 +33,6 @@ CSRC = os.path.join(ROOT, "pyspecsdr_amd", "csrc")
 @pytest.fixture(scope="module")
 def g():
     return np.load(os.path.join(HERE, "golden", "pfb.npz"))
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-def zeros_alike(a):
-    """The bytes with every -0 made +0: what 'byte for byte' means where the sign of a zero is not part of the contract."""
-    v = np.ascontiguousarray(a).view(np.float32).copy()
-    v[v == 0] = 0.0
-    return v.tobytes()
 
 
 def test_fixture_inputs_are_what_the_makers_give_today(g):

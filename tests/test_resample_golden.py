@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bytes_util import same_bytes
 import resample_cases as RC
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
@@ -22,11 +23,6 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(ROOT, "pyspecsdr_amd", "csrc")
 
 CASES = RC.golden_cases()
-
-
-def same_bytes(a, b):
-    a, b = np.asarray(a), np.asarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
 _TAPS = {}

@@ -22,7 +22,6 @@ and its line are not touched by any of this.
 import os
 import statistics
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -30,35 +29,11 @@ import numpy as np
 import torch
 
 from pyspecsdr_amd.engine import Engine
+from bench_util import kernels, stats, timed
 
 DDC_MAX_TAPS = 4097
 SHAPES = [("cfg 5 capture", 99_999_744, 10e6, 800, 200), ("cfg 5 capture", 99_999_744, 10e6, 800, 400), ("cfg 5 capture", 99_999_744, 10e6, 400, 200),
           ("2.4 MS/s capture", 24_000_000, 2.4e6, 192, 48), ("2.4 MS/s capture", 24_000_000, 2.4e6, 96, 48)]
-
-
-def stats(v):
-    return f"{min(v):.3f} - {max(v):.3f} ms (median {statistics.median(v):.3f}, {len(v)} regions)"
-
-
-def timed(e, fn):
-    e.sync()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    e.sync()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def kernels(e, fn):
-    """The launch's kernels by the context's per-kernel events -> {name: ms}."""
-    e.enable_timing(True)
-    e.kernel_times()
-    fn()
-    e.sync()
-    kt = e.kernel_times()
-    e.enable_timing(False)
-    return {k: sum(v) for k, v in kt.items()}
 
 
 def capture(n):

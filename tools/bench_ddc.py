@@ -11,9 +11,7 @@ against the NFM step on the untuned capture.  Host clock around call + synchroni
 floors are computed here from the shapes.  A record, not a pass condition; bench.py and its line are not touched by any of this.
 """
 import os
-import statistics
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -22,35 +20,12 @@ import torch
 
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
+from bench_util import kernels, stats, timed
 
 REP = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 CUS, CLOCK = 256, 2.4e9          # MI355X: compute units, shader clock the floors are stated at
 FRAME = 4096                     # read-buffer length of the channels' NFM step
 FRAME_WIDE = 32768               # and of the untuned capture's
-
-
-def stats(v):
-    return f"{min(v):.3f} - {max(v):.3f} ms (median {statistics.median(v):.3f}, {len(v)} regions)"
-
-
-def timed(e, fn):
-    e.sync()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    e.sync()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def kernels(e, fn):
-    e.enable_timing(True)
-    e.kernel_times()
-    fn()
-    e.sync()
-    kt = e.kernel_times()
-    e.enable_timing(False)
-    return "  ".join(f"{k}={sum(v):.3f}" for k, v in kt.items()) + " ms"
 
 
 def shape(e, name, n, fs, decim):
@@ -99,7 +74,7 @@ def shape(e, name, n, fs, decim):
     for k, (label, fn) in enumerate(routes):
         print(f"    {label} {stats(t[k])}")
     for label, fn in routes[1:]:
-        print(f"    kernels of {label.strip()}: {kernels(e, fn)}")
+        print(f"    kernels of {label.strip()}: " + "  ".join(f"{k}={v:.3f}" for k, v in kernels(e, fn).items()) + " ms")
     ddc(0, 16)
     e.sync()
     m0 = n_out // 2

@@ -16,7 +16,6 @@ bench.py and its line are not touched by any of this.
 import os
 import statistics
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -25,34 +24,11 @@ import torch
 
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
+from bench_util import kernels, stats, timed
 
 CUS, CLOCK, HBM = 256, 2.4e9, 8e12   # MI355X: compute units, shader clock and memory rate the floors are stated at
 FRAME = 4096                         # read-buffer length of the rows' NFM step
 DDC_MAX_TAPS = 4097
-
-
-def stats(v):
-    return f"{min(v):.3f} - {max(v):.3f} ms (median {statistics.median(v):.3f}, {len(v)} regions)"
-
-
-def timed(e, fn):
-    e.sync()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    e.sync()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
-
-
-def kernels(e, fn):
-    e.enable_timing(True)
-    e.kernel_times()
-    fn()
-    e.sync()
-    kt = e.kernel_times()
-    e.enable_timing(False)
-    return "  ".join(f"{k}={sum(v):.3f}" for k, v in kt.items()) + " ms"
 
 
 def capture(n):
@@ -117,7 +93,7 @@ def shape(e, name, d_iq, n, fs, M, D, rep):
     for k, (label, fn) in enumerate(routes):
         print(f"    {label} {stats(t[k])}")
     for label, fn in routes[1:]:
-        print(f"    kernels of {label.strip()}: {kernels(e, fn)}")
+        print(f"    kernels of {label.strip()}: " + "  ".join(f"{k}={v:.3f}" for k, v in kernels(e, fn).items()) + " ms")
     med = {label.strip(): statistics.median(v) for (label, _), v in zip(routes, t)}
     bank = med[f"pss_pfb, all {M} rows, {len(short)} taps"]
     bar = med[f"pss_ddc K = {M // 8}, {len(short)} taps"]

@@ -17,7 +17,6 @@ Last, 64 outputs of every row from the middle against the host twin.  A record; 
 import os
 import statistics
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -26,26 +25,13 @@ import torch
 
 from pyspecsdr_amd import _lib as L
 from pyspecsdr_amd.engine import Engine
+from bench_util import stats, timed
 
 FRAME = 32768
 SHAPES = [("12.5 kHz plan to NFM", 192, 500_000, np.complex64, 441, 500, L.MODE_NFM, 44100.0),
           ("12.5 kHz plan to AM", 192, 500_000, np.complex64, 441, 1000, L.MODE_AM, 22050.0),
           ("240 kS/s rows to WFM", 16, 500_000, np.complex64, 147, 320, None, 110250.0),
           ("many short rows", 65_536, 10, np.float64, 3969, 4000, None, None)]
-
-
-def stats(v):
-    return f"{min(v):.3f} - {max(v):.3f} ms (median {statistics.median(v):.3f}, {len(v)} regions)"
-
-
-def timed(e, fn):
-    e.sync()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    e.sync()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
 
 
 def rows_on_device(n_rows, n, dtype):

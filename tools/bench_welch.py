@@ -16,7 +16,6 @@ A record; bench.py and its line are not touched by any of this.
 import os
 import statistics
 import sys
-import time
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -24,20 +23,7 @@ import numpy as np
 import torch
 
 from pyspecsdr_amd.engine import Engine
-
-
-def stats(v):
-    return f"{min(v):.3f} - {max(v):.3f} ms (median {statistics.median(v):.3f}, {len(v)} regions)"
-
-
-def timed(e, fn):
-    e.sync()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    fn()
-    e.sync()
-    torch.cuda.synchronize()
-    return (time.perf_counter() - t0) * 1e3
+from bench_util import stats, timed
 
 
 def samples_on_device(n_floats):
