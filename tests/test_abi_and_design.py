@@ -135,18 +135,37 @@ needs_skx = pytest.mark.skipif(not _numpy_on_avx512_skx(), reason="NumPy is not 
 @needs_skx
 def test_designers_equal_scipy_on_sweeps():
     """The library's own designers against SciPy itself (where the test runs): firwin for the NFM / SSB cutoffs at 120 sample rates,
-    scipy.signal.decimate's cheby1(8, 0.05, 0.8 / q) sections and their sosfilt_zi for q = 2 .. 400, butter(5) low / band for the WFM
-    filters at 120 sample rates — every coefficient bit."""
+    scipy.signal.decimate's cheby1(8, 0.05, 0.8 / q) sections and their sosfilt_zi for q = 1 .. 400, butter(5) low / band for the WFM
+    filters at 120 sample rates — every coefficient bit.  With them the channel rates of tests/channel_rate_cases.py (30 001 S/s ..
+    240 kS/s) and the rates at which SciPy raises: the library refuses there with PSS_E_CUTOFF."""
     import ctypes as C
     import scipy.signal as ss
     lib = L.load()
     taps, sos4, zi = np.empty(65), np.empty((4, 6)), np.empty((4, 2))
-    rates = list(np.linspace(240e3, 20e6, 115)) + [250e3, 1.024e6, 2.048e6, 2.4e6, 10e6]
+    import channel_rate_cases as CR
+    channel = sorted({fs for fs, _, _ in CR.NFM_RATES + CR.WFM_RATES} | {30001.0})     # what the channelisers feed the demodulators
+    assert len(channel) == 10 and channel[0] == 30001.0 and channel[-1] == 240000.0
+    rates = list(np.linspace(240e3, 20e6, 115)) + [250e3, 1.024e6, 2.048e6, 2.4e6, 10e6] + channel
     for fs in rates:
         for c in (15000 / (fs / 2), 3000 / fs):
             assert lib.pss_design_firwin(65, c, taps.ctypes.data) == 0
             assert np.array_equal(taps, ss.firwin(65, c)), (fs, c)
-    for q in range(2, 401):
+    for fs, _, _ in CR.SSB_RATES:
+        assert lib.pss_design_firwin(65, 3000 / fs, taps.ctypes.data) == 0
+        assert np.array_equal(taps, ss.firwin(65, 3000 / fs)), fs
+    # the refusals: where SciPy raises ValueError the library returns PSS_E_CUTOFF (firwin's 15 kHz at or above Nyquist, butter's 53 kHz)
+    for fs in CR.NFM_REFUSED:
+        assert fs in (30000.0, 22050.0)
+        with pytest.raises(ValueError):
+            ss.firwin(65, 15000 / (fs / 2))
+        assert lib.pss_design_firwin(65, 15000 / (fs / 2), taps.ctypes.data) == L.PSS_E_CUTOFF, fs
+    for fs in CR.WFM_REFUSED:
+        assert fs == 106000.0
+        with pytest.raises(ValueError):
+            ss.butter(5, [23000 / (fs / 2), 53000 / (fs / 2)], btype="band", output="sos")
+        band = np.zeros((5, 6))
+        assert lib.pss_design_butter_sos(5, 23000 / (fs / 2), 53000 / (fs / 2), band.ctypes.data, None) == L.PSS_E_CUTOFF, fs
+    for q in range(1, 401):             # q = 1: scipy.signal.decimate(x, 1) still filters, with cheby1(8, 0.05, 0.8) (NFM at 37 500 S/s)
         assert lib.pss_design_cheby1_sos(8, 0.05, 0.8 / q, sos4.ctypes.data) == 0
         ref = ss.cheby1(8, 0.05, 0.8 / q, output="sos")
         assert np.array_equal(sos4, ref), q

@@ -300,8 +300,16 @@ def test_chain_hears_each_station_in_its_row_as_the_down_converter_does(chain, g
     e = engine()
     M, D = BC.CHAIN_M, BC.CHAIN_D
     assert chain["fs2"] == 50000.0 and chain["pcm"].shape == (M, 3072, 2)
-    assert same(chain["channels"], Engine.h_bank(chain["x"], M, D))
-    rows = [row for _, row, _ in BC.CHAIN_STATIONS]
+    h_ch = Engine.h_bank(chain["x"], M, D)
+    assert same(chain["channels"], h_ch)
+    # the PCM of all 192 rows against the CPU oracle on the twin's channels (demodulate_signal does not correct NFM buffers; the engine's
+    # own tables at 50 kS/s, q = 2)
+    import oracle_lib as O
+    taps, sos, zi = e.nfm_filters(chain["fs2"])
+    with np.errstate(all="ignore"):
+        want = np.stack(O.map_frames(lambda row: O.pcm16_stereo(O.demod_nfm(row, chain["fs2"], taps, sos, zi)), list(h_ch)))
+    assert np.array_equal(chain["pcm"], want), np.nonzero((chain["pcm"] != want).any(axis=(1, 2)))[0]
+    rows =[row for _, row, _ in BC.CHAIN_STATIONS]
     assert rows == [24, 159] and F.plan_rows(BC.CHAIN_FS, 0.0, [off for off, _, _ in BC.CHAIN_STATIONS], BC.CHAIN_SPACING).tolist() == rows
     peaks = [audio_peak(chain["pcm"][r]) for r in rows]
     assert peaks == [int(b) for b in g["chain_bins"]] == [82, 205], peaks

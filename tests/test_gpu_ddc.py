@@ -288,7 +288,14 @@ def test_chain_equals_the_host_chain_and_finds_both_tones(chain, g):
     h_ch = Engine.h_ddc(chain["x"], chain["words"], DC.CHAIN_D)
     assert same(chain["channels"], h_ch)
     assert np.array_equal(chain["pcm"], e.h_demodulate_batch(L.MODE_NFM, h_ch, chain["fs2"]))
-    peaks = [audio_peak(chain["pcm"][c]) for c in range(3)]
+    # h_demodulate_batch runs the same kernels behind a staging copy: the CPU oracle on the twin's channels is what anchors the PCM
+    # (demodulate_signal does not correct NFM buffers; the engine's own tables at 48 kS/s, q = 2)
+    import oracle_lib as O
+    taps, sos, zi = e.nfm_filters(chain["fs2"])
+    with np.errstate(all="ignore"):
+        want = np.stack([O.pcm16_stereo(O.demod_nfm(row, chain["fs2"], taps, sos, zi)) for row in h_ch])
+    assert np.array_equal(chain["pcm"], want), np.nonzero((chain["pcm"] != want).any(axis=(1, 2)))[0]
+    peaks =[audio_peak(chain["pcm"][c]) for c in range(3)]
     assert peaks[:2] == [int(b) for b in g["chain_bins"]] == [85, 213], peaks
     assert peaks[2] not in (85, 213), peaks        # the untuned channel hears neither station
 

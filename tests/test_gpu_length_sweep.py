@@ -31,6 +31,15 @@ the two others, test_power_db_lengths 1.0 + 0.7 s, test_iq_correction_lengths 1.
 1.1 + 1.0 s and 0.5 + 0.4 s through pss_demod_power, test_nfm_lengths 0.9 / 0.3 s and 0.1 s, test_ssb_lengths 0.84 / 0.34 s and 0.15 s for
 LSB, test_am_lengths 0.7 s, test_wfm_factor_one_lengths 0.7 s and 0.02 s, test_c128_lengths 0.6 s, test_classify_lengths 0.35 s,
 test_nfm_right_extension_across_two_work_items 0.3 s.
+
+The channel rates (tests/channel_rate_cases.py): the same sweeps at the rates the channelisers hand to the demodulators — NFM at 37 500
+(q = 1), 44 100, 48 000, 50 000 (q = 2), 75 000 (q = 3) and 110 250 S/s (q = 5), WFM at 108 000 (q = 4), 110 250, 120 000 (q = 5) and
+240 000 S/s (q = 10), SSB at 22 050 and 50 000 S/s — under the same criteria, then the product's own frame lengths (4096, 32 768 and
+32 770 samples, every one of the n_out outputs) and the rates at which the reference raises.  tests/test_channel_rates_golden.py pins the
+oracle to the reference at these rates.  Measured the same way: the 47 new cases about 12 s together, none above 0.75 s — test_wfm_lengths
+0.6 .. 0.75 s per rate on the small-batch path and 0.18 .. 0.25 s on the two others, test_nfm_lengths 0.3 .. 0.4 s and 0.1 s,
+test_ssb_lengths 0.54 / 0.35 s and 0.15 s for LSB, test_nfm_product_lengths and test_wfm_product_lengths below 0.1 s each,
+test_refused_rates_leave_the_outputs_untouched 0.1 s.
 """
 import numpy as np
 import pytest
@@ -39,6 +48,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+import channel_rate_cases as CR
 import length_cases as LC
 import oracle_lib as O
 from pyspecsdr_amd import _lib as L
@@ -53,6 +63,11 @@ AM_G1 = 13                 # one k_am_grp group of 12 frames plus one
 DEFAULTS = {"small_batch": 1, "nfm_fused": 1, "wfm_fused": 1, "wfm_corr_copy": 0, "ssb_hilbert": 1, "hilbert_exact": 0}
 NFM_PATHS = {"small_batch": {}, "fused": {"small_batch": 0}, "three_kernel": {"small_batch": 0, "nfm_fused": 0}}
 WFM_PATHS = {"small_batch": {}, "fused": {"small_batch": 0}, "plain": {"small_batch": 0, "wfm_fused": 0}}
+# the rates of the existing sweeps, then those the channelisers feed the demodulators (tests/channel_rate_cases.py; q = 1 .. 10)
+NFM_FS = [2.4e6, 250e3] + [fs for fs, _, _ in CR.NFM_RATES]
+WFM_FS = [2.4e6, 250e3] + [fs for fs, _, _ in CR.WFM_RATES]
+SSB_FS = [2.4e6, 48e3] + [fs for fs, _, _ in CR.SSB_RATES]
+FS_IDS = {2.4e6: "2.4M_q108", 250e3: "250k_q11"}
 REDUCE_PARTS = {"1..2199": [n for n in LC.REDUCE_LENGTHS if n < 2200], "chunk_and_group_edges": [n for n in LC.REDUCE_LENGTHS if n >= 2200]}
 
 
@@ -432,11 +447,16 @@ def _compare(S, key, batches, got, want, nf_of, pcm_of, audio_bad=bits_bad):
         S.bad(key, n, "int16 PCM", eq_bad(got[i][1], pcm_of(a)))
 
 
+def _fs_id(fs):
+    return FS_IDS.get(fs) or CR.rate_id(fs)
+
+
 @pytest.mark.parametrize("path", list(NFM_PATHS))
-@pytest.mark.parametrize("fs", [2.4e6, 250e3], ids=["2.4M_q108", "250k_q11"])
+@pytest.mark.parametrize("fs", NFM_FS, ids=_fs_id)
 def test_nfm_lengths(fs, path):
     """demodulate_nfm with the engine's own designed filters on the small-batch array, the fused forward kernel (from n - 1 >= 128; the
-    three-kernel path below) and the three-kernel path: float64 audio bits and int16 PCM of every frame; n = 28 raises ValueError."""
+    three-kernel path below) and the three-kernel path: float64 audio bits and int16 PCM of every frame; n = 28 raises ValueError.
+    At the channel rates q = 1 .. 5: at 37 500 S/s nothing is dropped (n_out = n - 1, cheby1(8, 0.05, 0.8) still runs)."""
     batches = _demod_batches()
     S, key, nf_of = Sweep(), ("demod(NFM)", path, fs), _nf_of(path == "small_batch")
     e = _engine()
@@ -489,7 +509,7 @@ def test_nfm_right_extension_across_two_work_items(path):
 
 
 @pytest.mark.parametrize("path", list(WFM_PATHS))
-@pytest.mark.parametrize("fs", [2.4e6, 250e3], ids=["2.4M_q108", "250k_q11"])
+@pytest.mark.parametrize("fs", WFM_FS, ids=_fs_id)
 def test_wfm_lengths(fs, path):
     """demodulate_wfm on the small-batch array (k_wfm_mrg), the fused forward kernel and the plain kernels; for n <= 160 also
     demodulate_signal (iq_correction first: the correction pre-pass, and option "wfm_corr_copy" = 1, the corrected copy)."""
@@ -545,6 +565,108 @@ def test_wfm_factor_one_lengths(path):
     S.report()
 
 
+# ---- the product's own frame lengths at the channel rates ---------------------------------------------------------------------------------
+PRODUCT_NF = {"small_batch": lambda n: 3, "fused": lambda n: 65 if n == 4096 else 5, "other": lambda n: 5}
+
+
+def _product_batches():
+    """The chain tests' 4096 (65 frames: a full 64-frame tile plus one), the default frame_len 32 768 and 32 770, one past the switch
+    (n - 1) * 8 >= 262144 of both demodulators (5 frames each)."""
+    assert CR.PRODUCT_LENGTHS == [4096, 32768, 32770] and (32768 - 1) * 8 < 262144 <= (32770 - 1) * 8
+    return _batches("product", CR.PRODUCT_LENGTHS, PRODUCT_NF["fused"], LC.fm_frames)
+
+
+def _product_nf(path):
+    return PRODUCT_NF.get(path, PRODUCT_NF["other"])
+
+
+@pytest.mark.parametrize("path", list(NFM_PATHS))
+@pytest.mark.parametrize("fs", CR.PRODUCT_NFM_RATES, ids=CR.rate_id)
+def test_nfm_product_lengths(fs, path):
+    """demodulate_nfm at the frame lengths demodulate_channels / demodulate_bank / monitor_channels cut, at 37 500 S/s (q = 1: 32 769
+    outputs per frame) and 48 000 S/s: all n_out outputs of every frame, float64 audio bits and int16 PCM."""
+    batches = _product_batches()
+    S, key, nf_of = Sweep(), ("demod(NFM)", path + ", product lengths", fs), _product_nf(path)
+    e = _engine()
+    try:
+        taps, sos, zi = e.nfm_filters(fs)
+        want = _refs(("nfm_product", fs), batches, lambda r: O.demod_nfm(r, fs, taps, sos, zi))
+        assert [len(w[0]) for w in want] == [-(-(n - 1) // CR.factor(fs)) for n in CR.PRODUCT_LENGTHS]
+        _options(e, NFM_PATHS[path])
+        try:
+            got = _launch_demod(e, S, key, L.MODE_NFM, fs, batches, nf_of)
+        finally:
+            _restore(e, NFM_PATHS[path])
+    finally:
+        e.close()
+    _compare(S, key, batches, got, want, nf_of, _pcm_mono)
+    S.report()
+
+
+@pytest.mark.parametrize("path", list(WFM_PATHS))
+@pytest.mark.parametrize("fs", CR.PRODUCT_WFM_RATES, ids=CR.rate_id)
+def test_wfm_product_lengths(fs, path):
+    """demodulate_wfm at the same frame lengths, at 110 250 S/s (plan_audio's WFM rate, q = 5) and 240 000 S/s (q = 10): all n_out
+    outputs of every frame, both channels."""
+    batches = _product_batches()
+    S, key, nf_of = Sweep(), ("demod(WFM)", path + ", product lengths", fs), _product_nf(path)
+    e = _engine()
+    try:
+        filt = _wfm_filt(e, fs)
+        want = _refs(("wfm_product", fs), batches, lambda r: O.demod_wfm(r, fs, filt))
+        assert [len(w[0]) for w in want] == [-(-(n - 1) // CR.factor(fs)) for n in CR.PRODUCT_LENGTHS]
+        _options(e, WFM_PATHS[path])
+        try:
+            got = _launch_demod(e, S, key, L.MODE_WFM, fs, batches, nf_of, stereo=True)
+        finally:
+            _restore(e, WFM_PATHS[path])
+    finally:
+        e.close()
+    _compare(S, key, batches, got, want, nf_of, int16_of)
+    S.report()
+
+
+CANARY16, CANARY64 = -12345, -7.25
+
+
+def test_refused_rates_leave_the_outputs_untouched():
+    """Where the reference's SciPy calls raise ValueError the engine raises it too, with the library's reason, on every path and through
+    both entry points, and writes nothing: NFM at 30 000 and 22 050 S/s (firwin's 15 kHz at or above Nyquist), WFM at 106 000 S/s
+    (butter's 53 kHz band edge at Nyquist).  Below 22 050 S/s the decimation factor is 0: demod_out_len is negative and the call is an
+    argument error."""
+    from pyspecsdr_amd.engine import PssError
+    nf, n = 5, 256
+    assert CR.NFM_REFUSED == [30000.0, 22050.0] and CR.WFM_REFUSED == [106000.0]
+    cases = [(L.MODE_NFM, fs, NFM_PATHS, "firwin: invalid cutoff frequency") for fs in CR.NFM_REFUSED]
+    cases += [(L.MODE_WFM, fs, WFM_PATHS, "butter: digital filter critical frequencies must be 0 < Wn < 1") for fs in CR.WFM_REFUSED]
+    e = _engine()
+    try:
+        d_in = torch.from_numpy(_f32(LC.fm_frames(nf, n)).copy()).cuda()
+        d_pcm = torch.full((nf, n, 2), CANARY16, dtype=torch.int16, device="cuda")
+        d_au = torch.full((nf, n, 2), CANARY64, dtype=torch.float64, device="cuda")
+        for mode, fs, paths, reason in cases:
+            assert e.demod_out_len(mode, n, fs) == -(-(n - 1) // CR.factor(fs))          # the length exists; the design does not
+            for path, opts in paths.items():
+                _options(e, opts)
+                try:
+                    for call in ("demod", "demod_signal"):
+                        with pytest.raises(ValueError) as err:
+                            getattr(e, call)(mode, d_in, nf, n, fs, d_pcm, d_au)
+                        assert reason in str(err.value), (mode, fs, path, call, str(err.value))
+                finally:
+                    _restore(e, opts)
+        for mode in (L.MODE_NFM, L.MODE_WFM):
+            for fs in (22049.0, 20000.0, 11025.0):
+                assert e.demod_out_len(mode, n, fs) < 0, (mode, fs)
+                with pytest.raises(PssError) as err:
+                    e.demod(mode, d_in, nf, n, fs, d_pcm, d_au)
+                assert err.value.code == L.PSS_E_ARG, (mode, fs)
+        e.sync()
+        assert bool(torch.all(d_pcm == CANARY16)) and bool(torch.all(d_au == CANARY64))
+    finally:
+        e.close()
+
+
 # ---- AM and SSB --------------------------------------------------------------------------------------------------------------------------
 def _am_ssb_batches(kind, maker):
     return _batches(kind, LC.AM_SSB_LENGTHS, lambda n: AM_G1, maker)
@@ -571,7 +693,7 @@ def _pow2(n):
 
 
 @pytest.mark.parametrize("mode", [L.MODE_USB, L.MODE_LSB], ids=["usb", "lsb"])
-@pytest.mark.parametrize("fs", [2.4e6, 48e3], ids=["2.4M", "48k"])
+@pytest.mark.parametrize("fs", SSB_FS, ids=["2.4M", "48k", "22050", "50k"])
 def test_ssb_lengths(fs, mode):
     """demodulate_ssb from one sample up, 13 frames: the default path (int16 equal to the full oracle at every length; float64 within
     2e-14 where the oracle runs the hilbert() round trip, equal bit for bit elsewhere), option "ssb_hilbert" = 0 (bit for bit against the

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from bytes_util import same_bytes
+from bytes_util import same, same_bytes
 import resample_cases as RC
 from gpu_util import engine
 from pyspecsdr_amd import _lib as L
@@ -244,6 +244,40 @@ def compose(capture, listed, mode, exact):
     return d_pcm.cpu().numpy().reshape(len(listed), n_frames, n_out, 2), rate
 
 
+_TWIN = {}
+
+
+def oracle_pcm(capture, listed, mode):
+    """The exact-rate chain on the host: the twins (h_bank's rows, h_resample) cut into frames, then the CPU oracle with the dispatcher's
+    semantics (demodulate_signal corrects neither NFM nor AM buffers) and the engine's own tables."""
+    import oracle_lib as O
+    from pyspecsdr_amd import formats as F
+    from pyspecsdr_amd.signal_processing import get_engine
+    e = get_engine()
+    M, D = F.plan_bank(FS, SPACING)
+    assert (M, D) == (192, 48)
+    if "bank" not in _TWIN:                                   # (one pass of each for the NFM and the AM case)
+        _TWIN["bank"] = Engine.h_bank(capture, M, D), F.channelize_plan(capture, FS, SPACING)[0]
+    twin, dev = _TWIN["bank"]
+    rate = FS / D
+    rows = F.plan_rows(FS, CENTRE, listed, SPACING)
+    sel = twin[rows]
+    assert same(dev[rows], sel)                               # the device's channels are the twin's (test_gpu_bank's criterion)
+    up, down, rate = F.plan_audio(rate, mode)
+    sel = Engine.h_resample(sel, up, down)
+    n_frames = sel.shape[1] // FRAME
+    frames = np.ascontiguousarray(sel[:, :n_frames * FRAME]).reshape(len(listed) * n_frames, FRAME)
+    with np.errstate(all="ignore"):
+        if mode == "NFM":
+            taps, sos, zi = e.nfm_filters(rate)
+            audio = [O.demod_nfm(f, rate, taps, sos, zi) for f in frames]
+        else:
+            sos = np.empty((5, 6))
+            e.lib.pss_am_bandpass_sos(sos.ctypes.data)
+            audio = [O.demod_am(f, sos) for f in frames]
+    return np.stack([O.pcm16_stereo(a) for a in audio]).reshape(len(listed), n_frames, -1, 2)
+
+
 def test_monitor_channels_at_the_exact_rate(capture):
     from pyspecsdr_amd import formats as F
     listed = [CENTRE + off for off, _ in NFM_STATIONS]
@@ -251,6 +285,7 @@ def test_monitor_channels_at_the_exact_rate(capture):
     assert rate == 44100.0 and rows.tolist() == [2, 189] and pcm.dtype == np.int16 and pcm.shape == (2, 2, 2048, 2)
     want, want_rate = compose(capture, listed, "NFM", True)
     assert want_rate == rate and same_bytes(pcm, want)
+    assert same_bytes(pcm, oracle_pcm(capture, listed, "NFM"))          # 44 100 S/s, q = 2: against the CPU oracle, not the device's own kernels
     for k, (_, tone) in enumerate(NFM_STATIONS):
         there, not_there = round(tone * 2048 / 22050), round(tone * 2048 / 25000)
         assert there != not_there and audio_peak(pcm[k, 1]) == there, (tone, audio_peak(pcm[k, 1]))
@@ -259,6 +294,7 @@ def test_monitor_channels_at_the_exact_rate(capture):
     assert rate == 22050.0 and rows.tolist() == [8] and pcm.shape == (1, 1, FRAME, 2)
     want, want_rate = compose(capture, [CENTRE + off], "AM", True)
     assert want_rate == rate and same_bytes(pcm, want)
+    assert same_bytes(pcm, oracle_pcm(capture, [CENTRE + off], "AM"))   # 22 050 S/s
     there, not_there = round(tone * 2048 / 22050), round(tone * 2048 / 50000)
     assert there != not_there and audio_peak(pcm[0, 0]) == there, audio_peak(pcm[0, 0])
     # the other two entry points take the keyword too
