@@ -819,6 +819,54 @@ int pss_welch(pss_ctx *ctx, const float *d_iq, long n_rows, long n, long row_str
               double scale, double *d_mean, double *d_max);
 int pss_h_welch(const float *iq, long n_rows, long n, long row_stride, int nperseg, int step, const double *win, int detrend, double scale,
                 double *mean, double *max);
+/* ---- RDS for broadcast FM: the station's groups (PI, name, RadioText) from rows of IQ — the hooks extract_rds / demodulate_rds_bpsk that the
+ * reference's demodulate_wfm calls and never defines (signal_processing.py:165-174).  Four stages, the arithmetic of the three new ones
+ * stated once in csrc/pss_rds.h (PARITY.md "RDS"); the device and the host twins agree on every byte, and every output follows from indices
+ * in the ROW, never from how the row was cut.
+ *   rows of IQ at fs --pss_rds_front--> rows at fs / decim --pss_resample (complex64)--> rows at 19 000 S/s (16 samples a bit)
+ *   --pss_rds_bits--> the differentially decoded bits --pss_rds_groups--> the groups whose four blocks pass the check.
+ * pss_rds_plan: decim = min(floor(fs / 19 000), 204) — pss_ddc_default_taps(decim) are then the front's default taps — and up / down =
+ *   19 000 decim / fs reduced, the resampler's factors.  PSS_E_ARG (reason in pss_last_error(NULL), starting "pss_rds: "): an fs that is
+ *   not an integer number of Hz, an fs at or below 120 000, reduced factors outside [1, 4096].
+ * pss_rds_front: d_iq complex64, 8-byte aligned: n_rows rows x_stride samples apart, the buffer holding samples [buf_index0, buf_index0 +
+ *   n_buf) of every row of n_capture samples.  Per sample i >= 1 the float32 polar discriminator d[i] = arctan2 of the float32 product
+ *   x[i] conj(x[i - 1]) (NumPy's routine as pss_decode_mono models it; no gain; d[0] = 0), times pss_ddc's rotor at the word of 57 000 Hz
+ *   and index i of the row, then pss_ddc's filter: output m of row r, y[m] = sum over k of taps[k] z[m decim + lead - k], z zero outside
+ *   the row, goes to complex64 element r out_stride + (m - m_begin) of d_out for m in [m_begin, m_end).  taps: a HOST table (its device
+ *   copy is kept on the context).  A sample's discriminator reads the sample before it: that one must lie in the buffer too.
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_rds_front: "; a refused call writes nothing): fs not above 114 000, n_rows < 1,
+ *   x_stride < n_buf, and pss_ddc's refusals for decim, n_taps, lead, the taps, the buffer, the window, out_stride and the alignment.
+ *   One kernel, k_rds_front (discriminator and mixer once per sample into LDS, float64 tap loop from there).
+ * pss_rds_default_pulse: the matched filter of the standard's biphase symbol at 16 samples a bit, 16 span_bits + 1 taps (span_bits in
+ *   [1, 16]; the receiver's default is 4): two impulses of opposite sign half a bit apart shaped by cos(pi f t_d / 4), |f| <= 2 / t_d, in
+ *   closed form.  *n_pulse is set, pulse (NULL: only the count) is filled.
+ * pss_rds_bits: d_bb complex64 rows of n samples at 19 000 S/s, row_stride samples apart -> d_bits uint8 [n_rows][max_bits] and d_n_bits
+ *   int32 [n_rows] (the true count; bits past max_bits are not stored).  Matched filter (pulse: a HOST table of an odd number of taps,
+ *   at most 257), feed-forward symbol timing per segment of 64 bits smoothed over 9 segments, one fixed rule where the timing offset
+ *   wraps, differential detection without carrier recovery.  Two kernels, k_rds_energy and k_rds_bits; scratch on the context.
+ *   PSS_E_ARG ("pss_rds_bits: "): n_rows < 1, n or max_bits outside [0, 2^30], row_stride < n, a pulse that is not odd, in [1, 257] and
+ *   finite, a null or misaligned pointer.
+ * pss_rds_groups: d_bits [n_rows][max_bits] and d_n_bits as pss_rds_bits left them -> d_groups uint16 [n_rows][max_groups][4] (the four
+ *   information words), d_pos int32 [n_rows][max_groups] (the bit index of the group's first bit), d_n_groups int32 [n_rows] (the true
+ *   count; the first max_groups are kept), in ascending position.  A group is accepted where all four blocks pass the check as A, B,
+ *   C or C' (by the version bit of block 2) and D; there is no error correction.  One kernel, k_rds_groups.  PSS_E_ARG
+ *   ("pss_rds_groups: "): n_rows < 1, max_bits outside [0, 2^30], max_groups < 0, a null or misaligned pointer.
+ * pss_h_rds_front / _bits / _groups: the same on host buffers, pure host code (no context, no GPU; the reason of a refusal:
+ *   pss_last_error(NULL), starting with the twin's own name). */
+int pss_rds_plan(double fs, int *decim, int *up, int *down);
+int pss_rds_front(pss_ctx *ctx, const float *d_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_capture, double fs, int decim,
+                  const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_out, long out_stride);
+int pss_h_rds_front(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_capture, double fs, int decim,
+                    const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_out, long out_stride);
+int pss_rds_default_pulse(int span_bits, double *pulse, int *n_pulse);
+int pss_rds_bits(pss_ctx *ctx, const float *d_bb, long n_rows, long row_stride, long n, const double *pulse, int n_pulse, uint8_t *d_bits,
+                 long max_bits, int32_t *d_n_bits);
+int pss_h_rds_bits(const float *h_bb, long n_rows, long row_stride, long n, const double *pulse, int n_pulse, uint8_t *h_bits, long max_bits,
+                   int32_t *h_n_bits);
+int pss_rds_groups(pss_ctx *ctx, const uint8_t *d_bits, const int32_t *d_n_bits, long n_rows, long max_bits, uint16_t *d_groups, int32_t *d_pos,
+                   int max_groups, int32_t *d_n_groups);
+int pss_h_rds_groups(const uint8_t *h_bits, const int32_t *h_n_bits, long n_rows, long max_bits, uint16_t *h_groups, int32_t *h_pos,
+                     int max_groups, int32_t *h_n_groups);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -195,6 +195,16 @@ _SIGS = {
     "pss_welch_default_window": (C.c_int, [C.c_int, _p]),
     "pss_welch": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_double, _p, _p]),
     "pss_h_welch": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, _p, C.c_int, C.c_double, _p, _p]),
+    "pss_rds_plan": (C.c_int, [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pss_rds_front": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_double, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long,
+                                _p, C.c_long]),
+    "pss_h_rds_front": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_double, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long,
+                                  _p, C.c_long]),
+    "pss_rds_default_pulse": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
+    "pss_rds_bits": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, _p, C.c_int, _p, C.c_long, _p]),
+    "pss_h_rds_bits": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, _p, C.c_int, _p, C.c_long, _p]),
+    "pss_rds_groups": (C.c_int, [_p, _p, _p, C.c_long, C.c_long, _p, _p, C.c_int, _p]),
+    "pss_h_rds_groups": (C.c_int, [_p, _p, C.c_long, C.c_long, _p, _p, C.c_int, _p]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

@@ -35,6 +35,7 @@ UNITS = [
     ("pss_bank.hip", ["-ffp-contract=off"]),   # the channeliser for 2^a 3^b 5^c grids: the same rule
     ("pss_resample.hip", ["-ffp-contract=off"]),   # the rational resampler: SciPy's upfirdn, one multiply and one add per tap
     ("pss_welch.hip", ["-ffp-contract=off"]),   # the capture survey: every fused multiply-add is written as fma
+    ("pss_rds.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the RDS receiver: NumPy's float32 arctan2, then fma chains written as fma
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),
     ("pss_decode.cpp", ["-x", "hip", "-ffp-contract=off"]),   # host only: the decoders' per-message halves

@@ -121,6 +121,8 @@ struct pss_ctx {
     PssDevTable bank_tab;    // pss_bank.hip: twiddles of M, taps, digit reversal
     PssDevTable rs_tab;      // pss_resample.hip: the plan's numbers, then the taps in visit order
     PssDevTable welch_win;   // pss_welch.hip: the caller's window
+    PssDevTable rds_tab;     // pss_rds.hip, pss_rds_front: rotor knots, taps
+    PssDevTable rds_pulse;   // pss_rds.hip, pss_rds_bits: the pulse table
     void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;
@@ -275,6 +277,8 @@ int pss_chain_vals_f32(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft
 int pss_chain_vals_f64(pss_ctx *ctx, const double *d_db, long n_frames, int n_fft, double *d_lo, double *d_hi, int n_halo, int window, int display,
                        int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals);
 bool pss_ssb_fused_supported(int n);
+// NumPy's float32 arctan2 on the host, the statements of pss_device.h's atan2f_svml (pss_mono.hip)
+float pss_h_atan2f_model(float y, float x);
 // NumPy's float64 tan / exp under its AVX512_SKX dispatch (SVML's _ha routines restated, pss_design.cpp)
 double pss_np_tan(double x);
 double pss_np_exp(double x);

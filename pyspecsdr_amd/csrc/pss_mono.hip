@@ -240,6 +240,9 @@ bool lf_args_ok(const double *b, const double *a, int ncoef)
 
 }  // namespace
 
+// the host model of NumPy's float32 arctan2 for the other units' host twins (pss_rds.hip)
+float pss_h_atan2f_model(float y, float x) { return h_atan2f_svml(y, x); }
+
 // scipy.signal.bilinear([1], [tau, 1], fs): with M = 1 its loops leave bprime = [1, 1] and aprime = [1 + t, 1 - t], t = tau * (2 fs) (the
 // products by the binomial coefficients 1.0 and by (-1) ** k are exact), and normalize() divides both by aprime[0].
 extern "C" int pss_design_deemph(double tau, double fs, double b[2], double a[2])

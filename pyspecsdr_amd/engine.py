@@ -1381,6 +1381,118 @@ class Engine:
             return mean[0], (mx[0] if want_max else None)
         return mean, mx
 
+    # -- RDS for broadcast FM: rows of IQ -> groups (pss_rds_*; the arithmetic: csrc/pss_rds.h)
+    @staticmethod
+    def rds_plan(fs, lib=None):
+        """pss_rds_plan -> (decim, up, down): the front's decimation min(fs // 19 000, 204) and the resampler's factors to 19 000 S/s.
+        Host code."""
+        lib = lib or L.load()
+        d, u, w = C.c_int(), C.c_int(), C.c_int()
+        if lib.pss_rds_plan(float(fs), C.byref(d), C.byref(u), C.byref(w)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return d.value, u.value, w.value
+
+    @staticmethod
+    def rds_default_pulse(span_bits=4, lib=None):
+        """pss_rds_default_pulse: the biphase symbol's matched filter at 16 samples a bit, 16 span_bits + 1 float64 taps.  Host code."""
+        return Engine._default_taps(lib, "pss_rds_default_pulse", "rds_default_pulse: span_bits outside [1, 16]", span_bits)
+
+    @staticmethod
+    def _rds_front_args(lib, n_buf, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride):
+        """The defaults of rds_front / h_rds_front: ddc's, without the words."""
+        _, taps, a, b, c, out_stride = Engine._ddc_args(lib, n_buf, np.zeros(1, np.uint64), decim, taps, buf_index0, n_capture, lead, m_begin, m_end,
+                                                        out_stride)
+        return taps, a, b[1], c, out_stride
+
+    def rds_front(self, d_iq, n_rows, n_buf, fs, decim, d_out, taps=None, x_stride=None, buf_index0=0, n_capture=None, lead=None, m_begin=0,
+                  m_end=None, out_stride=None):
+        """d_iq complex64: n_rows rows x_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_capture
+        samples -> d_out complex64: discriminator, 57 kHz mixer and decimating FIR, output m of row r at element r * out_stride +
+        (m - m_begin).  taps, lead and the window: as ddc (default taps: ddc_default_taps(decim))."""
+        taps, a, decim, c, out_stride = self._rds_front_args(self.lib, n_buf, decim, taps, buf_index0, n_capture, lead, m_begin, m_end, out_stride)
+        self._dev(self.lib.pss_rds_front, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), *a, float(fs), decim, _ptr(taps), *c,
+                  _ptr(d_out), out_stride)
+
+    @staticmethod
+    def h_rds_front(iq, fs, decim, taps=None, buf_index0=0, n_capture=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_rds_front on a host array [n_rows][n_buf] or [n_buf] -> complex64 [n_rows][m_end - m_begin] or [m_end - m_begin].  Pure
+        host code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        x = np.asarray(iq, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("iq: a 1-D or 2-D complex array")
+        rows = Engine._as_rows(x)
+        taps, a, decim, c, stride = Engine._rds_front_args(lib, rows.shape[1], decim, taps, buf_index0, n_capture, lead, m_begin, m_end, None)
+        out = np.empty((rows.shape[0], max(stride, 0)), np.complex64)
+        if lib.pss_h_rds_front(_ptr(rows), rows.shape[0], rows.shape[1], *a, float(fs), decim, _ptr(taps), *c, _ptr(out), stride) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out if x.ndim == 2 else out[0]
+
+    @staticmethod
+    def _as_rows(x):
+        """A 1-D array as one row, a 2-D array as it is (an empty one too) -> contiguous [n_rows][n]."""
+        return np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+
+    @staticmethod
+    def _rds_pulse(pulse, lib):
+        return Engine.rds_default_pulse(4, lib) if pulse is None else np.ascontiguousarray(np.atleast_1d(pulse), np.float64)
+
+    def rds_bits(self, d_bb, n_rows, n, d_bits, max_bits, d_n_bits, pulse=None, row_stride=None):
+        """d_bb complex64: n_rows rows of n samples at 19 000 S/s, row_stride samples apart (default n) -> d_bits uint8 [n_rows][max_bits],
+        d_n_bits int32 [n_rows] (the true count).  pulse: host float64 matched filter (default rds_default_pulse())."""
+        pulse = self._rds_pulse(pulse, self.lib)
+        self._dev(self.lib.pss_rds_bits, _ptr(d_bb), int(n_rows), int(n if row_stride is None else row_stride), int(n), _ptr(pulse), len(pulse),
+                  _ptr(d_bits), int(max_bits), _ptr(d_n_bits))
+
+    @staticmethod
+    def rds_max_bits(n):
+        """Room for every bit of a baseband row of n samples at 19 000 S/s: a strobe every 16 samples and one more per 64-bit segment."""
+        return int(n) // 16 + int(n) // 1024 + 2
+
+    @staticmethod
+    def h_rds_bits(bb, pulse=None, max_bits=None, lib=None):
+        """pss_h_rds_bits on a host array [n_rows][n] or [n] -> a list of uint8 bit rows (or one row).  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(bb, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("bb: a 1-D or 2-D complex array")
+        rows = Engine._as_rows(x)
+        pulse = Engine._rds_pulse(pulse, lib)
+        max_bits = Engine.rds_max_bits(rows.shape[1]) if max_bits is None else int(max_bits)
+        bits = np.zeros((rows.shape[0], max(max_bits, 0)), np.uint8)
+        n_bits = np.zeros(rows.shape[0], np.int32)
+        if lib.pss_h_rds_bits(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], _ptr(pulse), len(pulse), _ptr(bits), max_bits, _ptr(n_bits)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        out = [bits[r, :min(int(n_bits[r]), max_bits)] for r in range(rows.shape[0])]
+        return out if x.ndim == 2 else out[0]
+
+    def rds_groups(self, d_bits, d_n_bits, n_rows, max_bits, d_groups, d_pos, max_groups, d_n_groups):
+        """d_bits uint8 [n_rows][max_bits], d_n_bits int32 [n_rows] -> d_groups uint16 [n_rows][max_groups][4], d_pos int32
+        [n_rows][max_groups], d_n_groups int32 [n_rows] (the true count; the first max_groups are kept)."""
+        self._dev(self.lib.pss_rds_groups, _ptr(d_bits), _ptr(d_n_bits), int(n_rows), int(max_bits), _ptr(d_groups), _ptr(d_pos), int(max_groups),
+                  _ptr(d_n_groups))
+
+    @staticmethod
+    def h_rds_groups(bits, n_bits=None, max_groups=None, lib=None):
+        """pss_h_rds_groups on a host bit array [n_rows][max_bits] or [max_bits] (n_bits: the rows' counts, default max_bits) ->
+        (groups uint16 [n_rows][max_groups][4], pos int32 [n_rows][max_groups], n_groups int32 [n_rows]), or one row's.  Pure host code."""
+        lib = lib or L.load()
+        b = np.asarray(bits, np.uint8)
+        if b.ndim not in (1, 2):
+            raise ValueError("bits: a 1-D or 2-D array")
+        rows = Engine._as_rows(b)
+        n_rows, max_bits = rows.shape
+        nb = np.full(n_rows, max_bits, np.int32) if n_bits is None else np.ascontiguousarray(np.atleast_1d(n_bits), np.int32)
+        if nb.shape != (n_rows,):
+            raise ValueError("n_bits: one count per row")
+        max_groups = max_bits // 104 + 1 if max_groups is None else int(max_groups)
+        groups = np.zeros((n_rows, max(max_groups, 0), 4), np.uint16)
+        pos = np.zeros((n_rows, max(max_groups, 0)), np.int32)
+        n_groups = np.zeros(n_rows, np.int32)
+        if lib.pss_h_rds_groups(_ptr(rows), _ptr(nb), n_rows, max_bits, _ptr(groups), _ptr(pos), max_groups, _ptr(n_groups)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return (groups, pos, n_groups) if b.ndim == 2 else (groups[0], pos[0], int(n_groups[0]))
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

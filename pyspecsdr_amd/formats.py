@@ -429,11 +429,12 @@ def decode_mono_recording(samples, fs, frame_len=32768, codes_format=None, table
     return pcm
 
 
-def _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m_end, plan):
+def _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m_end, plan, reach_back=0):
     """The streaming _tune_device and _bank_device share -> device tensor float32 [rows][2 * m_end]: the capture goes up in chunks of about
     chunk_samples samples, each with the halo its outputs' taps reach back and ahead for, and every chunk's outputs land in their place
     of the one result.  plan() -> (taps, rows, run) is asked once the capture is in its form; run(d_iq, n_buf, out_ptr, **window) is the
-    entry point's call with buf_index0, n_capture, lead, m_begin, m_end and out_stride."""
+    entry point's call with buf_index0, n_capture, lead, m_begin, m_end and out_stride.  reach_back: samples in front of the taps' halo that
+    the entry point reads as well (pss_rds_front's discriminator: 1)."""
     import torch
     if int(chunk_samples) != chunk_samples or chunk_samples < 1:
         raise ValueError("chunk_samples must be an integer >= 1")
@@ -460,7 +461,7 @@ def _chunk_device(e, samples, decim, lead, chunk_samples, codes_format, table, m
     per_chunk = max(1, int(chunk_samples) // decim)
     for m0 in range(0, max(m_end, 1), per_chunk):
         m1 = min(m_end, m0 + per_chunk)
-        lo, hi = max(0, m0 * decim + lead - (n_taps - 1)), min(n, (m1 - 1) * decim + lead + 1)
+        lo, hi = max(0, m0 * decim + lead - (n_taps - 1) - reach_back), min(n, (m1 - 1) * decim + lead + 1)
         hi = max(hi, lo)
         if codes_format is not None:
             d_codes = torch.from_numpy(np.array(samples[lo:hi])).to(dev)
@@ -925,6 +926,132 @@ def monitor_channels(samples, fs, center_hz, channels_hz, spacing_hz, mode='NFM'
     rows = plan_rows(fs, center_hz, channels_hz, spacing_hz)
     pcm, decim, rate = _demodulate_rows(samples, fs, n_chan, d if decim is None else decim, mode, frame_len, kw, 'bank', rows=rows)
     return pcm, rows, rate
+
+
+_RDS_RATE = 19000
+
+
+def _rds_char(c):
+    return chr(c) if 0x20 <= c <= 0x7E or 0xA0 <= c <= 0xFF else '?'
+
+
+def rds_decode(groups):
+    """The groups of ONE row (uint16 [n][4], in the order received) -> dict: 'pi' (the most frequent block 1; None without groups), 'pty',
+    'tp' (of the last group), 'group_counts' ({'0A': n, ...}), 'ps' (the eight-character name from groups 0A / 0B, two characters per
+    segment address; None until all four segments have been seen), 'radiotext' (from 2A, four characters per address, and 2B, two;
+    cleared when the A/B flag toggles; up to 0x0D, or to the first character not yet received; None while character 0 is missing).
+    Characters are read as Latin-1 with unprintables as '?' (the standard's own code table is not applied).  Host code, pure Python."""
+    groups = np.asarray(groups, np.uint16).reshape(-1, 4)
+    out = {'pi': None, 'pty': None, 'tp': None, 'group_counts': {}, 'ps': None, 'radiotext': None}
+    if not len(groups):
+        return out
+    pis, counts = np.unique(groups[:, 0], return_counts=True)
+    out['pi'] = int(pis[np.argmax(counts)])
+    ps, rt, flag = [None] * 8, [None] * 64, None
+    for a, b, c, d in ((int(v) for v in g) for g in groups):
+        gtype, version_b = b >> 12, (b >> 11) & 1
+        name = f"{gtype}{'B' if version_b else 'A'}"
+        out['group_counts'][name] = out['group_counts'].get(name, 0) + 1
+        out['tp'], out['pty'] = (b >> 10) & 1, (b >> 5) & 31
+        if gtype == 0:
+            seg = b & 3
+            ps[2 * seg], ps[2 * seg + 1] = d >> 8, d & 255
+        elif gtype == 2:
+            if flag is not None and flag != (b >> 4) & 1:
+                rt = [None] * 64
+            flag = (b >> 4) & 1
+            addr = b & 15
+            chars = [d >> 8, d & 255] if version_b else [c >> 8, c & 255, d >> 8, d & 255]
+            rt[len(chars) * addr:len(chars) * (addr + 1)] = chars
+    if all(v is not None for v in ps):
+        out['ps'] = ''.join(_rds_char(v) for v in ps)
+    text = []
+    for v in rt:
+        if v is None or v == 0x0D:
+            break
+        text.append(_rds_char(v))
+    if rt[0] is not None:
+        out['radiotext'] = ''.join(text)
+    return out
+
+
+def _rds_rows(e, d_iq, n_rows, n, fs, taps=None, pulse=None, d_front=None):
+    """The stages behind the IQ rows on the device -> (groups uint16 [n_rows][max_groups][4], pos int32 [n_rows][max_groups], n_groups
+    int32 [n_rows]) on the host.  d_iq: float32 tensor [n_rows][2 n] at fs, or None with d_front, the front's rows (float32
+    [n_rows][2 m] at fs / decim)."""
+    import torch
+    decim, up, down = e.rds_plan(fs)
+    if d_front is None:
+        m = e.lib.pss_ddc_out_len(n, decim)
+        d_front = torch.empty((n_rows, 2 * m), dtype=torch.float32, device=d_iq.device)
+        e.rds_front(d_iq, n_rows, n, fs, decim, d_front, taps=taps)
+    m = d_front.shape[1] // 2
+    dev = d_front.device
+    n19 = e.resample_out_len(m, up, down)
+    d_bb = torch.empty((n_rows, 2 * n19), dtype=torch.float32, device=dev)
+    e.resample(d_front, np.complex64, n_rows, m, up, down, d_bb)
+    max_bits = e.rds_max_bits(n19)
+    max_groups = max_bits // 104 + 1
+    d_bits = torch.empty((n_rows, max_bits), dtype=torch.uint8, device=dev)
+    d_n_bits = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    e.rds_bits(d_bb, n_rows, n19, d_bits, max_bits, d_n_bits, pulse=pulse)
+    d_groups = torch.zeros((n_rows, max_groups, 4), dtype=torch.int16, device=dev)
+    d_pos = torch.zeros((n_rows, max_groups), dtype=torch.int32, device=dev)
+    d_n_groups = torch.empty(n_rows, dtype=torch.int32, device=dev)
+    e.rds_groups(d_bits, d_n_bits, n_rows, max_bits, d_groups, d_pos, max_groups, d_n_groups)
+    return d_groups.cpu().numpy().view(np.uint16), d_pos.cpu().numpy(), d_n_groups.cpu().numpy()
+
+
+def rds_recording(samples, fs, taps=None, pulse=None, chunk_samples=1 << 22, codes_format=None, table=None):
+    """RDS of one station's capture (the station at 0 Hz of a capture at fs, an integer rate above 120 kS/s) -> rds_decode's dict with
+    'groups' (uint16 [n][4]) and 'pos' (the bit index of each group) added.  On the GPU: discriminator + 57 kHz mixer + decimating FIR
+    (pss_rds_front, streamed in chunks of chunk_samples samples plus their halos; the result does not depend on chunk_samples), the
+    resampler to 19 kS/s, symbol timing and differential detection (pss_rds_bits) and the block check (pss_rds_groups) on the whole row.
+    taps: the front's float64 low-pass table (default firwin(20 decim + 1, 1 / decim)); pulse: the matched filter (default
+    rds_default_pulse()); codes_format / table: as demodulate_recording."""
+    e = get_engine()
+    fs = float(fs)
+    decim = e.rds_plan(fs)[0]
+
+    def plan():
+        t = e.ddc_default_taps(decim) if taps is None else np.ascontiguousarray(taps, np.float64)
+        return t, 1, lambda d_iq, n_buf, out, **window: e.rds_front(d_iq, 1, n_buf, fs, decim, out, taps=t, **window)
+
+    d_front = _chunk_device(e, samples, decim, None, chunk_samples, codes_format, table, None, plan, reach_back=1)
+    groups, pos, n_groups = _rds_rows(e, None, 1, 0, fs, pulse=pulse, d_front=d_front)
+    k = min(int(n_groups[0]), groups.shape[1])
+    out = rds_decode(groups[0, :k])
+    out['groups'], out['pos'] = groups[0, :k].copy(), pos[0, :k].copy()
+    return out
+
+
+def rds_stations(samples, fs, center_hz, spacing_hz=100e3, taps=None, pulse=None, chunk_samples=1 << 22, codes_format=None, table=None):
+    """Which station is on each channel of a capture of the FM band centred on center_hz -> a list of (frequency_hz, pi, ps, radiotext,
+    n_groups), one entry per row of the bank that produced at least one group, in ascending frequency.  The grid goes through the bank
+    (plan_bank(fs, spacing_hz), pss_bank: 100 kHz channels come out at 200 kS/s), then all rows at once through pss_rds_front, the
+    resampler, pss_rds_bits and pss_rds_groups; only the groups come back to the host.  A strong station also decodes in the rows next
+    to its own: adjacent rows that report the same PI are ALL listed, and merging them is the caller's business.  taps: the BANK's
+    table; the default is firwin(20 n_chan + 1, 1.8 / n_chan), a channel 1.8 spacings wide (+-90 kHz on the 100 kHz grid), not
+    bank_default_taps' one spacing: the RDS subcarrier sits 57 kHz either side of the FM carrier, outside a +-50 kHz channel.  pulse,
+    chunk_samples, codes_format, table: as rds_recording."""
+    e = get_engine()
+    n_chan, decim = plan_bank(fs, spacing_hz)
+    rate = float(fs) / decim
+    e.rds_plan(rate)   # refuses a channel rate the receiver does not take before any work is done
+    if taps is None:
+        taps = np.empty(20 * n_chan + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 1.8 / n_chan, taps.ctypes.data) != 0:
+            raise ValueError("rds_stations: the bank's filter design failed")
+    d_rows, _ = _bank_device(samples, n_chan, decim, taps, None, chunk_samples, codes_format, table, entry='bank')
+    groups, _, n_groups = _rds_rows(e, d_rows, n_chan, d_rows.shape[1] // 2, rate, pulse=pulse)
+    freqs = float(center_hz) + plan_offsets(fs, n_chan)
+    out = []
+    for c in np.argsort(freqs):
+        k = min(int(n_groups[c]), groups.shape[1])
+        if k:
+            d = rds_decode(groups[c, :k])
+            out.append((float(freqs[c]), d['pi'], d['ps'], d['radiotext'], k))
+    return out
 
 
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):

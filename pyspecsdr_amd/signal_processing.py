@@ -233,6 +233,49 @@ def demodulate_wfm(samples, sample_rate, target_rate=DEFAULT_SAMPLE_RATE):
     return audio
 
 
+def extract_rds(demod, sample_rate):
+    """The hook the reference's demodulate_wfm calls and never defines (signal_processing.py:165-174): the RDS subcarrier of a REAL
+    discriminator row at sample_rate -> (baseband complex64 at 19 kS/s, 19000): mixed down by 57 kHz, low-pass filtered and decimated
+    (pss_ddc at pss_rds_plan's factor) and resampled to 16 samples a bit (pss_resample).  demodulate_wfm does not call it: its bytes
+    stay the reference's."""
+    import torch
+    e = get_engine()
+    x = np.ascontiguousarray(demod, np.float64).astype(np.float32).astype(np.complex64)
+    if x.ndim != 1:
+        raise ValueError("demod: a 1-D real row")
+    decim, up, down = e.rds_plan(sample_rate)
+    dev = f"cuda:{e.device}"
+    n = len(x)
+    m = e.lib.pss_ddc_out_len(n, decim)
+    n19 = e.resample_out_len(m, up, down)
+    d_x = torch.from_numpy(x.view(np.float32)).to(dev) if n else torch.empty(2, dtype=torch.float32, device=dev)
+    d_mid = torch.empty(max(2 * m, 2), dtype=torch.float32, device=dev)
+    d_bb = torch.empty(max(2 * n19, 2), dtype=torch.float32, device=dev)
+    e.ddc(d_x, n, [e.ddc_word(57000.0, float(sample_rate))[0]], decim, d_mid)
+    e.resample(d_mid, np.complex64, 1, m, up, down, d_bb)
+    return d_bb[:2 * n19].cpu().numpy().view(np.complex64), 19000
+
+
+def demodulate_rds_bpsk(rds_baseband, rds_rate):
+    """The second hook: the RDS baseband at 19 kS/s -> the list of differentially decoded data bits (pss_rds_bits: matched filter,
+    feed-forward symbol timing, differential detection)."""
+    import torch
+    if int(rds_rate) != 19000:
+        raise ValueError("rds_rate must be 19000 (extract_rds' rate: 16 samples a bit)")
+    e = get_engine()
+    x = np.ascontiguousarray(rds_baseband, np.complex64)
+    if x.ndim != 1:
+        raise ValueError("rds_baseband: a 1-D complex row")
+    dev = f"cuda:{e.device}"
+    n = len(x)
+    max_bits = e.rds_max_bits(n)
+    d_x = torch.from_numpy(x.view(np.float32)).to(dev) if n else torch.empty(2, dtype=torch.float32, device=dev)
+    d_bits = torch.zeros(max_bits, dtype=torch.uint8, device=dev)
+    d_n = torch.zeros(1, dtype=torch.int32, device=dev)
+    e.rds_bits(d_x, 1, n, d_bits, max_bits, d_n)
+    return d_bits[:int(d_n.cpu()[0])].cpu().numpy().tolist()
+
+
 def demodulate_am(samples):
     if _is_c128(samples) and len(samples) >= 1:        # float64 np.abs / np.mean, as the reference computes it for such a buffer (no narrowing)
         return get_engine().h_demodulate_am_c128(samples)[0]
