@@ -42,6 +42,45 @@ struct PssDevTable {
     }
 };
 
+// What the streamed entry points (pss_h_stream_*, pss_stream.cpp) keep across calls: the two copy streams, the events of the two buffer
+// sets and the device buffers, created on first use and grow-only (creating and freeing them per capture cost ~2 ms of a 17 ms capture).
+// The three calls use the same slots for the same roles, so a context that alternates between them holds one set of chunk buffers.
+struct PssStreaming {
+    enum Slot {         // a pair is two slots, one per buffer set: ensure(ctx, SLOT + b, ...)
+        IQ = 0,         // the chunk's samples as complex64 (pair)
+        DB = 2,         // its dB rows (pair)
+        PCM = 4,        // its int16 PCM (pair)
+        PLANE_A = 6,    // the view's first byte plane per frame: glyphs / row indices, bar heights, magnitudes, the mask (pair)
+        PLANE_B = 8,    // the second: colours, bar levels (pair)
+        POST = 10,      // the post-processed rows of the chunk in flight
+        EXTREMES = 11,  // [lo | hi] x (halo + frames): the row extremes of the whole capture
+        GRID_A = 12,    // the full screen after a chunk, first plane (pair)
+        GRID_B = 14,    // its second plane (pair)
+        TAIL = 16,      // the last `window` post-processed rows, carried from chunk to chunk (ping-pong pair)
+        CODES = 18,     // the chunk's ADC codes as uploaded (pair; pss_ingest.hip unpacks them into IQ)
+        NUMBERS = 20,   // per frame: range, peak, avg as float64, open and live as bytes (pair)
+        WORK = 22,      // the chunk's live frames gathered, then the index lists of its live and open frames
+        N_SLOTS
+    };
+    hipStream_t up = nullptr, dn = nullptr;   // upload and download stream; compute is the context's own
+    hipEvent_t up_done[2] = {}, cmp_done[2] = {}, dn_done[2] = {};   // per buffer set: uploaded, computed, downloaded
+    void *buf[N_SLOTS] = {};
+    size_t cap[N_SLOTS] = {};
+    int open(pss_ctx *ctx);   // streams and events, on first use
+    int ensure(pss_ctx *ctx, int slot, size_t bytes, void **out);   // *out = the slot's buffer, at least `bytes` long (a grow frees and reallocates)
+    void release()
+    {
+        if (up) hipStreamDestroy(up);
+        if (dn) hipStreamDestroy(dn);
+        for (hipEvent_t *ev : {up_done, cmp_done, dn_done})
+            for (int i = 0; i < 2; i++)
+                if (ev[i]) hipEventDestroy(ev[i]);
+        for (void *b : buf)
+            if (b) hipFree(b);
+        *this = PssStreaming{};
+    }
+};
+
 struct pss_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -81,12 +120,7 @@ struct pss_ctx {
     size_t scratch_win_bytes = 0;
     float *d_hann = nullptr;       // pss_classify: scipy's periodic Hann window (1024, float32) and sum(win * win)
     float hann_sum = 0.0f;
-    // streaming entry points (pss_h_stream_*): copy streams, events and the two device buffer sets, kept across calls
-    // (creating and freeing them per capture cost ~2 ms of a 17 ms capture)
-    hipStream_t st_up = nullptr, st_dn = nullptr;
-    hipEvent_t st_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // up_done[2], cmp_done[2], dn_done[2]
-    void *st_buf[24] = {};         // [0..11]: the chunk buffer sets; [12..15]: per-chunk display grids (two sets x two planes); [16..17]: the last `window` post-processed rows (ping-pong); [18..19]: the chunk's ADC codes as uploaded (the *_codes calls, pss_ingest.hip); [20..23]: pss_h_stream_frames' per-frame numbers (two sets), gathered live frames and index lists (its other buffers are [0..11] and [18..19])
-    size_t st_cap[24] = {};
+    PssStreaming st;               // the streamed entry points' streams, events and chunk buffers (pss_stream.cpp)
     float *d_hann_short = nullptr;  // the same for reads shorter than 1024 samples (window length = read length hann_short_n)
     float hann_short_sum = 0.0f;
     int hann_short_n = 0;

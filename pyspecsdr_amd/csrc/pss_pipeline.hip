@@ -6,6 +6,7 @@
 #include <string>
 
 #include "pss_ctx.h"
+#include "pss_rows.h"
 
 extern "C" int pss_spectrum_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, int n, double fs, float *d_db,
                                 int16_t *d_pcm)
@@ -37,33 +38,13 @@ extern "C" int pss_spectrum_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, 
 // output) or TR = double (pss_frame_pipeline_nfm_f64: the reference's own row type from IQ to cells — compute_fft returns float64 and the
 // caller smooths, clamps and draws float64: these are the reference's cells).
 namespace {
-inline int pipe_spectrum(pss_ctx *ctx, const float *d_iq, long nf, int n, float *d_db) { return pss_spectrum_db(ctx, d_iq, nf, n, d_db); }
-inline int pipe_spectrum(pss_ctx *ctx, const float *d_iq, long nf, int n, double *d_db) { return pss_spectrum_db_f64(ctx, d_iq, nf, n, d_db); }
-inline int pipe_post(pss_ctx *ctx, const float *d_db, long nf, int n, float *d_post, float *lo, float *hi) { return pss_spectrum_post_extremes(ctx, d_db, nf, n, d_post, lo, hi); }
-inline int pipe_post(pss_ctx *ctx, const double *d_db, long nf, int n, double *d_post, double *lo, double *hi) { return pss_spectrum_post_f64(ctx, d_db, nf, n, d_post, lo, hi); }
-inline int pipe_lines(pss_ctx *ctx, int display, const float *d_post, long nf, int len, const float *lo, const float *hi, int n_halo, int window, int disp_h,
+template <class TR>
+inline int pipe_lines(pss_ctx *ctx, int display, const TR *d_post, long nf, int len, const TR *lo, const TR *hi, int n_halo, int window, int disp_h,
                       int disp_w, int8_t *a, int8_t *b)
 {
-    return display == 2 ? pss_gradient_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
-         : display ? pss_persistence_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
-                   : pss_waterfall_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
-}
-inline int pipe_lines(pss_ctx *ctx, int display, const double *d_post, long nf, int len, const double *lo, const double *hi, int n_halo, int window, int disp_h,
-                      int disp_w, int8_t *a, int8_t *b)
-{
-    return display == 2 ? pss_gradient_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
-         : display ? pss_persistence_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
-                   : pss_waterfall_rows_f64(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
-}
-inline int pipe_chain_vals(pss_ctx *ctx, const float *d_db, long nf, int n, float *lo, float *hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                           int8_t *a, int8_t *b, double *vals)
-{
-    return pss_chain_vals_f32(ctx, d_db, nf, n, lo, hi, n_halo, window, display, disp_h, disp_w, a, b, vals);
-}
-inline int pipe_chain_vals(pss_ctx *ctx, const double *d_db, long nf, int n, double *lo, double *hi, int n_halo, int window, int display, int disp_h, int disp_w,
-                           int8_t *a, int8_t *b, double *vals)
-{
-    return pss_chain_vals_f64(ctx, d_db, nf, n, lo, hi, n_halo, window, display, disp_h, disp_w, a, b, vals);
+    return display == 2 ? pss_rows::gradient_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b)
+         : display ? pss_rows::persistence_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_h, disp_w, a)
+                   : pss_rows::waterfall_rows(ctx, d_post, nf, len, lo, hi, n_halo, window, disp_w, a, b);
 }
 }  // namespace
 
@@ -130,7 +111,7 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
                 return pss_spec_post_chain(ctx, d_iq, n_frames, n, d_db32, d_db, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph,
                                            d_colour, d_vals);
         }
-        int q = pipe_spectrum(ctx, d_iq, n_frames, n, d_db);     // compute_fft sees the samples as read (pyspecsdr.py:2275), not the corrected ones
+        int q = pss_rows::spectrum_db(ctx, d_iq, n_frames, n, d_db);     // compute_fft sees the samples as read (pyspecsdr.py:2275), not the corrected ones
         if (q) return q;
         if (d_db32 && n_frames > 0) {
             const long count = n_frames * (long)n;
@@ -141,8 +122,8 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
             q = pss_hip_check(ctx, hipGetLastError(), "k_rows_f64_to_f32 launch");
             if (q) return q;
         }
-        if (d_vals) return pipe_chain_vals(ctx, d_db, n_frames, n, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph, d_colour, d_vals);
-        q = pipe_post(ctx, d_db, n_frames, n, d_post, d_row_lo + n_halo, d_row_hi + n_halo);
+        if (d_vals) return pss_rows::chain_vals(ctx, d_db, n_frames, n, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph, d_colour, d_vals);
+        q = pss_rows::post(ctx, d_db, n_frames, n, d_post, d_row_lo + n_halo, d_row_hi + n_halo);
         if (!q) q = pipe_lines(ctx, display, d_post, n_frames, n - 4, d_row_lo, d_row_hi, n_halo, window, disp_h, disp_w, d_glyph, d_colour);
         return q;
     };

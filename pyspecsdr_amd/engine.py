@@ -700,7 +700,7 @@ class Engine:
         history 30; "persistence": lines = (y,), history 10.  halo: (lo, hi) float32 arrays of the rows preceding the
         capture.  Returns dict(lines=..., pcm=..., row_lo=..., row_hi=..., db=... or None)."""
         assert h_iq.dtype == np.complex64 and h_iq.ndim == 2 and h_iq.flags.c_contiguous
-        return self._stream_display(h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out)
+        return self._stream_display(np.float32, h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, False, out)
 
     def stream_display_nfm_codes(self, h_codes, fs, chunk_frames, fmt, table=None, mode="waterfall", window=None, disp_h=36, disp_w=112,
                                  halo=None, want_db=False, out=None):
@@ -709,44 +709,58 @@ class Engine:
         iq = _iq_args(fmt, table)
         h_codes = _iq_codes(h_codes, iq[0])
         assert h_codes.ndim == 3
-        return self._stream_display(h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out)
+        return self._stream_display(np.float32, h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, False, out)
 
-    def _stream_display(self, h_in, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, out):
+    def _stream_display(self, dtype, h_in, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out):
+        """The pss_h_stream_display_nfm* call for rows of `dtype` (float32 / float64), a capture of complex64 (iq None) or of ADC codes
+        (iq = _iq_args(...)), with the full screens after every chunk or without."""
+        f64 = dtype is np.float64
         nf, n = h_in.shape[:2]
         m = 0 if mode == "waterfall" else 1
         window = (30 if m == 0 else 10) if window is None else int(window)
         n_out = self.demod_out_len(L.MODE_NFM, n, fs)
+        n_chunks = (nf + int(chunk_frames) - 1) // int(chunk_frames) if nf else 0
         # out: a previous call's result dict to write into again (pass arrays from pinned_empty() to keep the downloads
         # asynchronous: a copy into pageable memory is staged by the runtime and blocks the pipeline)
         if out is not None:
             la, lb = (out["lines"] + (None,))[:2]
             pcm, db, lo, hi = out["pcm"], out.get("db"), out["row_lo"], out["row_hi"]
-            assert la.shape == (nf, disp_w) and pcm.shape == (nf, n_out, 2) and len(lo) == nf and len(hi) == nf
+            assert la.shape == (nf, disp_w) and pcm.shape == (nf, n_out, 2) and (not f64 or lo.dtype == np.float64) and len(lo) == nf and len(hi) == nf
         else:
             la = np.empty((nf, disp_w), np.int8)
             lb = np.empty((nf, disp_w), np.int8) if m == 0 else None
             pcm = np.empty((nf, n_out, 2), np.int16)
-            db = np.empty((nf, n), np.float32) if want_db else None
-            lo, hi = np.empty(nf, np.float32), np.empty(nf, np.float32)
+            db = np.empty((nf, n), dtype) if want_db else None
+            lo, hi = np.empty(nf, dtype), np.empty(nf, dtype)
+        ga = np.empty((n_chunks, disp_h, disp_w), np.int8) if grids else None
+        gb = np.empty((n_chunks, disp_h, disp_w), np.int8) if grids and m == 0 else None
         hl = hh = None
         n_halo = 0
         if halo is not None and len(halo[0]):
-            hl, hh = np.ascontiguousarray(halo[0], np.float32), np.ascontiguousarray(halo[1], np.float32)
+            hl, hh = np.ascontiguousarray(halo[0], dtype), np.ascontiguousarray(halo[1], dtype)
             n_halo = len(hl)
-        tail = (nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w, _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db),
-                _ptr(lo), _ptr(hi))
-        if iq is None:
-            self._ck(self.lib.pss_h_stream_display_nfm(self.h, _ptr(h_in), *tail))
+        head = (self.h,) if iq is None else (self.h, iq[0], iq[1], _ptr(iq[2]))
+        head += (_ptr(h_in), nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w)
+        tail = (_ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db), _ptr(lo), _ptr(hi))
+        codes = "" if iq is None else "_codes"
+        if f64:
+            self._ck(getattr(self.lib, f"pss_h_stream_display_nfm{codes}_f64")(*head, *tail, _ptr(ga), _ptr(gb)))
+        elif grids:     # float32 rows with grids: complex64 captures with a fresh history, no dB rows
+            assert iq is None and hl is None and db is None
+            self._ck(self.lib.pss_h_stream_display_nfm_grids(*head, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(lo), _ptr(hi), _ptr(ga), _ptr(gb)))
         else:
-            self._ck(self.lib.pss_h_stream_display_nfm_codes(self.h, iq[0], iq[1], _ptr(iq[2]), _ptr(h_in), *tail))
-        return {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "db": db}
+            self._ck(getattr(self.lib, f"pss_h_stream_display_nfm{codes}")(*head, *tail))
+        res = {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "db": db}
+        if grids:
+            res["grids"] = (ga, gb) if m == 0 else (ga,)
+        return res
 
     def stream_display_nfm_f64(self, h_iq, fs, chunk_frames, mode="waterfall", window=None, disp_h=36, disp_w=112, halo=None, want_db=False,
                                grids=False, out=None):
         """stream_display_nfm with compute_fft's own float64 rows from the transform to the cells: the lines (and, grids=True, the full screen
         after every chunk) the REFERENCE draws from this capture.  halo / row_lo / row_hi / db: float64.  PCIe-bound like the float32 call."""
         assert h_iq.dtype == np.complex64 and h_iq.ndim == 2 and h_iq.flags.c_contiguous
-        return self._stream_display_f64(h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
+        return self._stream_display(np.float64, h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
 
     def stream_display_nfm_codes_f64(self, h_codes, fs, chunk_frames, fmt, table=None, mode="waterfall", window=None, disp_h=36, disp_w=112,
                                      halo=None, want_db=False, grids=False, out=None):
@@ -754,61 +768,16 @@ class Engine:
         iq = _iq_args(fmt, table)
         h_codes = _iq_codes(h_codes, iq[0])
         assert h_codes.ndim == 3
-        return self._stream_display_f64(h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
-
-    def _stream_display_f64(self, h_in, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out):
-        nf, n = h_in.shape[:2]
-        m = 0 if mode == "waterfall" else 1
-        window = (30 if m == 0 else 10) if window is None else int(window)
-        n_out = self.demod_out_len(L.MODE_NFM, n, fs)
-        n_chunks = (nf + int(chunk_frames) - 1) // int(chunk_frames) if nf else 0
-        if out is not None:      # a previous call's dict / arrays from pinned_empty(): downloads into pinned memory stay asynchronous
-            la, lb = (out["lines"] + (None,))[:2]
-            pcm, db, lo, hi = out["pcm"], out.get("db"), out["row_lo"], out["row_hi"]
-            assert la.shape == (nf, disp_w) and pcm.shape == (nf, n_out, 2) and lo.dtype == np.float64 and len(lo) == nf and len(hi) == nf
-        else:
-            la = np.empty((nf, disp_w), np.int8)
-            lb = np.empty((nf, disp_w), np.int8) if m == 0 else None
-            pcm = np.empty((nf, n_out, 2), np.int16)
-            db = np.empty((nf, n), np.float64) if want_db else None
-            lo, hi = np.empty(nf, np.float64), np.empty(nf, np.float64)
-        ga = np.empty((n_chunks, disp_h, disp_w), np.int8) if grids else None
-        gb = np.empty((n_chunks, disp_h, disp_w), np.int8) if grids and m == 0 else None
-        hl = hh = None
-        n_halo = 0
-        if halo is not None and len(halo[0]):
-            hl, hh = np.ascontiguousarray(halo[0], np.float64), np.ascontiguousarray(halo[1], np.float64)
-            n_halo = len(hl)
-        tail = (nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w, _ptr(hl), _ptr(hh), n_halo, _ptr(la), _ptr(lb), _ptr(pcm), _ptr(db),
-                _ptr(lo), _ptr(hi), _ptr(ga), _ptr(gb))
-        if iq is None:
-            self._ck(self.lib.pss_h_stream_display_nfm_f64(self.h, _ptr(h_in), *tail))
-        else:
-            self._ck(self.lib.pss_h_stream_display_nfm_codes_f64(self.h, iq[0], iq[1], _ptr(iq[2]), _ptr(h_in), *tail))
-        out = {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "db": db}
-        if grids:
-            out["grids"] = (ga, gb) if m == 0 else (ga,)
-        return out
+        return self._stream_display(np.float64, h_codes, iq, fs, chunk_frames, mode, window, disp_h, disp_w, halo, want_db, grids, out)
 
     def stream_display_nfm_grids(self, h_iq, fs, chunk_frames, mode="waterfall", window=None, disp_h=36, disp_w=112):
         """stream_display_nfm for a capture with a fresh history, plus the FULL display grid after the last frame of every chunk (what the
         reference's screen shows: every line / trace of the history redrawn with the current extremes).  Returns the stream_display_nfm dict
         + "grids": (glyph, colour) int8 [n_chunks][disp_h][disp_w] for the waterfall, (colour,) for persistence."""
         assert h_iq.dtype == np.complex64 and h_iq.ndim == 2 and h_iq.flags.c_contiguous
-        nf, n = h_iq.shape
-        m = 0 if mode == "waterfall" else 1
-        window = (30 if m == 0 else 10) if window is None else int(window)
-        n_out = self.demod_out_len(L.MODE_NFM, n, fs)
-        n_chunks = (nf + int(chunk_frames) - 1) // int(chunk_frames)
-        la = np.empty((nf, disp_w), np.int8)
-        lb = np.empty((nf, disp_w), np.int8) if m == 0 else None
-        pcm = np.empty((nf, n_out, 2), np.int16)
-        lo, hi = np.empty(nf, np.float32), np.empty(nf, np.float32)
-        ga = np.empty((n_chunks, disp_h, disp_w), np.int8)
-        gb = np.empty((n_chunks, disp_h, disp_w), np.int8) if m == 0 else None
-        self._ck(self.lib.pss_h_stream_display_nfm_grids(self.h, _ptr(h_iq), nf, n, float(fs), int(chunk_frames), m, window, disp_h, disp_w,
-                                                         _ptr(la), _ptr(lb), _ptr(pcm), _ptr(lo), _ptr(hi), _ptr(ga), _ptr(gb)))
-        return {"lines": (la, lb) if m == 0 else (la,), "pcm": pcm, "row_lo": lo, "row_hi": hi, "grids": (ga, gb) if m == 0 else (ga,)}
+        res = self._stream_display(np.float32, h_iq, None, fs, chunk_frames, mode, window, disp_h, disp_w, None, False, True, None)
+        del res["db"]   # this call has no dB rows to offer
+        return res
 
     def stream_spectrum_nfm(self, h_iq, fs, chunk_frames, h_db=None, h_pcm=None):
         """h_iq: complex64 [n_frames, n] host array (pinned for overlap).  Returns (h_db or None, h_pcm)."""
