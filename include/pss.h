@@ -867,6 +867,38 @@ int pss_rds_groups(pss_ctx *ctx, const uint8_t *d_bits, const int32_t *d_n_bits,
                    int max_groups, int32_t *d_n_groups);
 int pss_h_rds_groups(const uint8_t *h_bits, const int32_t *h_n_bits, long n_rows, long max_bits, uint16_t *h_groups, int32_t *h_pos,
                      int max_groups, int32_t *h_n_groups);
+/* ---- ADS-B: the Mode S frames of a 1090 MHz capture — what the reference's command list starts dump1090 for (rtlcoms.json, "Decode Aircraft
+ * Transmissions").  The arithmetic is the project's own, stated once in csrc/pss_adsb.h (PARITY.md "ADS-B"); the device and the host twin
+ * agree on every byte, and every output follows from indices in the CAPTURE, so no chunking changes one.
+ * pss_adsb_plan: spc = fs / 2 000 000, the samples of a 0.5 us chip.  PSS_E_ARG (reason in pss_last_error(NULL), starting "pss_adsb: "): an fs
+ *   for which that is no integer in [1, 8].
+ * pss_adsb_crc: the 24-bit remainder of the first n_bits bits of msg (whole bytes; n_bits in [0, 112]) under the generator 0x1FFF409.  Pure
+ *   host code.  A null msg or an n_bits outside that range: 0xFFFFFFFF.
+ * pss_adsb_frames: d_iq complex64, 8-byte aligned, holding samples [buf_index0, buf_index0 + n_buf) of a capture of n_capture samples.  Every
+ *   start s in [s_begin, s_end) is a candidate: magnitudes re re + im im, chip energies of spc samples, the 16-chip preamble (pulses at chips
+ *   0, 2, 7, 9; the weakest pulse must exceed ratio times the strongest gap), 56 or 112 bits by comparing chip pairs, the remainder, and the
+ *   format's rule: DF 17 / 18 with remainder 0, DF 11 with remainder below 128, DF 0 / 4 / 5 / 16 / 20 / 21 with the remainder in d_icao
+ *   (n_icao ascending unique uint32 values below 2^24 ON THE DEVICE; the order is the caller's to keep).  Of accepted starts less than 2 spc
+ *   apart that slice the same message, the one with the strongest weakest pulse stays (the earlier on a tie).  Records in ascending s:
+ *   d_msg uint8 [max_frames][14] (a short frame zero-padded), d_pos int64 [max_frames] (the capture index of the preamble's first sample),
+ *   d_meta uint32 [max_frames] (n_bits | DF << 16), d_score float32 [max_frames] (the weakest pulse's energy), d_count int32 [1] (the TRUE
+ *   count; nothing is written past max_frames).  The buffer must hold what the window's starts and their possible suppressors read: the
+ *   samples from max(0, s_begin - (2 spc - 1)) to min(n_capture, s_end + 2 spc - 2 + 240 spc).
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_adsb_frames: "; a refused call writes nothing): spc outside [1, 8], a ratio that is
+ *   negative or not finite, a buffer or a window outside the capture, s_end < s_begin, a window above 2^30 starts, a buffer that does not
+ *   cover the window's reach, max_frames < 0, n_icao outside [0, 2^24], a null or misaligned pointer.
+ *   Kernels: k_adsb_detect (the one pass over the capture), then k_adsb_scan, k_adsb_gather, k_adsb_keep, k_adsb_scan, k_adsb_emit over the
+ *   accepted starts only.  Scratch on the context, 2 bytes per start of the largest window it has been given, grow-only and freed by
+ *   pss_destroy (a 2^30-start window keeps 2 GB); the call waits once for the count of accepted starts.
+ * pss_h_adsb_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL)); it also refuses an
+ *   address list that is not ascending, unique and below 2^24. */
+int pss_adsb_plan(double fs, int *spc);
+uint32_t pss_adsb_crc(const uint8_t *msg, int n_bits);
+int pss_adsb_frames(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0, long n_capture, int spc, float ratio, const uint32_t *d_icao,
+                    int n_icao, long s_begin, long s_end, uint8_t *d_msg, int64_t *d_pos, uint32_t *d_meta, float *d_score, int32_t *d_count,
+                    int max_frames);
+int pss_h_adsb_frames(const float *h_iq, long n_buf, long buf_index0, long n_capture, int spc, float ratio, const uint32_t *h_icao, int n_icao,
+                      long s_begin, long s_end, uint8_t *h_msg, int64_t *h_pos, uint32_t *h_meta, float *h_score, int32_t *h_count, int max_frames);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -157,6 +157,11 @@ struct pss_ctx {
     PssDevTable welch_win;   // pss_welch.hip: the caller's window
     PssDevTable rds_tab;     // pss_rds.hip, pss_rds_front: rotor knots, taps
     PssDevTable rds_pulse;   // pss_rds.hip, pss_rds_bits: the pulse table
+    // pss_adsb.hip, grow-only: [0] the tiles' counts, offsets and lists, [1] the accepted starts with their keep flags and ranks;
+    // adsb_pin: 8 pinned bytes the count of accepted starts lands in
+    void *adsb_buf[2] = {};
+    size_t adsb_cap[2] = {};
+    void *adsb_pin = nullptr;
     void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;

@@ -1462,6 +1462,64 @@ class Engine:
             raise ValueError(lib.pss_last_error(None).decode())
         return (groups, pos, n_groups) if b.ndim == 2 else (groups[0], pos[0], int(n_groups[0]))
 
+    # -- ADS-B: a 1090 MHz capture -> the Mode S frames that pass their check (pss_adsb_*; the arithmetic: csrc/pss_adsb.h)
+    @staticmethod
+    def adsb_plan(fs, lib=None):
+        """pss_adsb_plan -> spc, the samples of a 0.5 us chip: fs / 2 000 000, an integer in [1, 8].  Host code."""
+        lib = lib or L.load()
+        spc = C.c_int()
+        if lib.pss_adsb_plan(float(fs), C.byref(spc)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return spc.value
+
+    @staticmethod
+    def adsb_crc(msg, n_bits=None, lib=None):
+        """pss_adsb_crc: the 24-bit remainder of a message (bytes, or a uint8 array) under 0x1FFF409.  n_bits: default every byte.  Host code."""
+        lib = lib or L.load()
+        m = np.ascontiguousarray(np.frombuffer(bytes(msg), np.uint8) if isinstance(msg, (bytes, bytearray)) else msg, np.uint8)
+        n_bits = 8 * len(m) if n_bits is None else int(n_bits)
+        if m.ndim != 1 or n_bits < 0 or n_bits > min(8 * len(m), 112):
+            raise ValueError("adsb_crc: n_bits outside the message, or above 112")
+        return int(lib.pss_adsb_crc(_ptr(m), n_bits))
+
+    def adsb_frames(self, d_iq, n_buf, spc, d_msg, d_pos, d_meta, d_score, d_count, max_frames, ratio=2.0, d_icao=None, n_icao=0, buf_index0=0,
+                    n_capture=None, s_begin=0, s_end=None):
+        """d_iq complex64: samples [buf_index0, buf_index0 + n_buf) of a capture of n_capture samples (default: the buffer is the capture) ->
+        the frames that start in [s_begin, s_end) (default: to the capture's end), ascending: d_msg uint8 [max_frames][14], d_pos int64, d_meta
+        uint32 (n_bits | DF << 16), d_score float32, d_count int32 [1] (the true count).  d_icao: n_icao ascending uint32 addresses ON THE
+        DEVICE, against which the address-overlaid formats are checked."""
+        n_capture = int(buf_index0) + int(n_buf) if n_capture is None else int(n_capture)
+        s_end = n_capture if s_end is None else int(s_end)
+        self._dev(self.lib.pss_adsb_frames, _ptr(d_iq), int(n_buf), int(buf_index0), n_capture, int(spc), float(ratio), _ptr(d_icao), int(n_icao),
+                  int(s_begin), s_end, _ptr(d_msg), _ptr(d_pos), _ptr(d_meta), _ptr(d_score), _ptr(d_count), int(max_frames))
+
+    @staticmethod
+    def h_adsb_frames(iq, spc, ratio=2.0, icao=(), buf_index0=0, n_capture=None, s_begin=0, s_end=None, max_frames=None, lib=None):
+        """pss_h_adsb_frames on a host complex64 array -> (msg uint8 [k][14], pos int64 [k], meta uint32 [k], score float32 [k], count): the
+        first k = min(count, max_frames) records and the true count.  max_frames: default room for every frame the window can hold.  Pure
+        host code."""
+        lib = lib or L.load()
+        x = np.ascontiguousarray(iq, np.complex64)
+        if x.ndim != 1:
+            raise ValueError("iq: a 1-D complex array")
+        n_capture = int(buf_index0) + len(x) if n_capture is None else int(n_capture)
+        s_end = n_capture if s_end is None else int(s_end)
+        a = np.ascontiguousarray(icao, np.uint32).reshape(-1)
+        grow = max_frames is None
+        max_frames = 64 if grow else int(max_frames)
+        while True:
+            room = max(max_frames, 0)
+            msg, pos, meta = np.zeros((room, 14), np.uint8), np.zeros(room, np.int64), np.zeros(room, np.uint32)
+            score, count = np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_adsb_frames(_ptr(x), len(x), int(buf_index0), n_capture, int(spc), float(ratio), _ptr(a) if len(a) else None, len(a),
+                                     int(s_begin), s_end, _ptr(msg), _ptr(pos), _ptr(meta), _ptr(score), _ptr(count), max_frames) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_frames = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return msg[:k], pos[:k], meta[:k], score[:k], int(count[0])
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

@@ -1054,6 +1054,211 @@ def rds_stations(samples, fs, center_hz, spacing_hz=100e3, taps=None, pulse=None
     return out
 
 
+# -- ADS-B: what the frames of pss_adsb_frames say (host code), and a capture end to end
+_ADSB_CHARS = "#ABCDEFGHIJKLMNOPQRSTUVWXYZ##### ###############0123456789######"
+_ADSB_OVERLAID = (0, 4, 5, 16, 20, 21)   # the formats whose parity field carries the address
+
+
+def adsb_decode(msg, n_bits):
+    """One Mode S message (14 bytes as pss_adsb_frames writes them, or the frame's own 7 / 14) -> a dict.  Always 'df' and 'icao' (the AA
+    field of DF 11 / 17 / 18; the remainder of the address-overlaid formats).  DF 17 / 18: 'tc', the type code, and with it
+      1 - 4    'callsign' (the 6-bit table, trailing spaces stripped)
+      9 - 18   'altitude' in feet (None unless the Q bit is set), 'odd' (the CPR format flag), 'cpr_lat', 'cpr_lon' (17 bits each)
+      19       subtypes 1 and 2: 'speed' in knots, 'track' in degrees, 'vertical_rate' in ft/min (None where the field says "no data").
+    Pure Python: no library call but the remainder."""
+    m = bytes(np.asarray(msg, np.uint8).tobytes() if not isinstance(msg, (bytes, bytearray)) else msg)
+    n_bits = int(n_bits)
+    if n_bits not in (56, 112) or len(m) < n_bits // 8:
+        raise ValueError("adsb_decode: n_bits is 56 or 112, and msg holds that many")
+    m = m[:n_bits // 8]
+    df = m[0] >> 3
+    out = {'df': df}
+    if df in (11, 17, 18):
+        out['icao'] = int.from_bytes(m[1:4], 'big')
+    else:
+        from .engine import Engine
+        out['icao'] = Engine.adsb_crc(m, n_bits) if df in _ADSB_OVERLAID else None
+    if df not in (17, 18):
+        return out
+    me = int.from_bytes(m[4:11], 'big')
+    tc = me >> 51
+    out['tc'] = tc
+    if 1 <= tc <= 4:
+        out['callsign'] = "".join(_ADSB_CHARS[(me >> (42 - 6 * k)) & 0x3F] for k in range(8)).rstrip(" ")
+    elif 9 <= tc <= 18:
+        alt = (me >> 36) & 0xFFF
+        out['altitude'] = (((alt & 0xFE0) >> 1) | (alt & 0xF)) * 25 - 1000 if alt & 0x10 else None
+        out['odd'] = (me >> 34) & 1
+        out['cpr_lat'], out['cpr_lon'] = (me >> 17) & 0x1FFFF, me & 0x1FFFF
+    elif tc == 19 and (me >> 48) & 7 in (1, 2):
+        scale = 4 if (me >> 48) & 7 == 2 else 1
+        ew, ns, vr = (me >> 32) & 0x3FF, (me >> 21) & 0x3FF, (me >> 10) & 0x1FF
+        out['speed'] = out['track'] = None
+        if ew and ns:
+            vx = (ew - 1) * scale * (-1 if (me >> 42) & 1 else 1)
+            vy = (ns - 1) * scale * (-1 if (me >> 31) & 1 else 1)
+            out['speed'] = float(np.hypot(vx, vy))
+            out['track'] = float(np.degrees(np.arctan2(vx, vy)) % 360.0)
+        out['vertical_rate'] = (vr - 1) * 64 * (-1 if (me >> 19) & 1 else 1) if vr else None
+    return out
+
+
+def _cpr_nl(lat):
+    """The number of longitude zones at a latitude (the standard's NL function)."""
+    lat = abs(lat)
+    if lat == 0:
+        return 59
+    if lat == 87:
+        return 2
+    if lat > 87:
+        return 1
+    return int(np.floor(2 * np.pi / np.arccos(1 - (1 - np.cos(np.pi / 30)) / np.cos(np.pi / 180 * lat) ** 2)))
+
+
+def adsb_position(even, odd, newest_odd):
+    """The globally unambiguous CPR decode of an even and an odd airborne position, each (cpr_lat, cpr_lon) -> (latitude, longitude) in
+    degrees as float64, or None where the two latitudes fall in different longitude zones.  newest_odd: the odd frame is the later one."""
+    lat_e, lon_e = even[0] / 131072.0, even[1] / 131072.0
+    lat_o, lon_o = odd[0] / 131072.0, odd[1] / 131072.0
+    j = int(np.floor(59 * lat_e - 60 * lat_o + 0.5))
+    la_e, la_o = 360.0 / 60 * (j % 60 + lat_e), 360.0 / 59 * (j % 59 + lat_o)
+    la_e, la_o = (la_e - 360 if la_e >= 270 else la_e), (la_o - 360 if la_o >= 270 else la_o)
+    nl = _cpr_nl(la_e)
+    if nl != _cpr_nl(la_o):
+        return None
+    m = int(np.floor(lon_e * (nl - 1) - lon_o * nl + 0.5))
+    lat, ni, frac = (la_o, max(nl - 1, 1), lon_o) if newest_odd else (la_e, max(nl, 1), lon_e)
+    lon = 360.0 / ni * (m % ni + frac)
+    return lat, (lon - 360 if lon >= 180 else lon)
+
+
+def adsb_tracks(records, fs):
+    """records: the frames in order, each a mapping with 'msg', 'n_bits' and 'pos' (adsb_recording's 'frames') -> one dict per aircraft in
+    order of first appearance: 'icao', 'callsign', 'altitude' and 'velocity' (the last of each, or None), 'frames', 'first' and 'last' (pos / fs,
+    seconds) and 'position': (latitude, longitude) from the newest even and the newest odd position frame where they lie within 10 s of each
+    other and their latitudes fall in the same longitude zone, else None."""
+    fs = float(fs)
+    tracks, cpr = {}, {}
+    for rec in records:
+        d = adsb_decode(rec['msg'], rec['n_bits'])
+        if d['icao'] is None:
+            continue
+        t = int(rec['pos']) / fs
+        tr = tracks.setdefault(d['icao'], {'icao': d['icao'], 'callsign': None, 'altitude': None, 'velocity': None, 'frames': 0, 'first': t,
+                                           'last': t, 'position': None})
+        tr['frames'] += 1
+        tr['last'] = t
+        if 'callsign' in d:
+            tr['callsign'] = d['callsign']
+        if d.get('altitude') is not None:
+            tr['altitude'] = d['altitude']
+        if 'vertical_rate' in d:
+            tr['velocity'] = {k: d[k] for k in ('speed', 'track', 'vertical_rate')}
+        if 'cpr_lat' in d:
+            cpr.setdefault(d['icao'], {})[d['odd']] = (t, (d['cpr_lat'], d['cpr_lon']))
+    for icao, pair in cpr.items():
+        if 0 in pair and 1 in pair and abs(pair[0][0] - pair[1][0]) <= 10.0:
+            tracks[icao]['position'] = adsb_position(pair[0][1], pair[1][1], newest_odd=pair[1][0] > pair[0][0])
+    return list(tracks.values())
+
+
+def _adsb_pass(e, upload, n, spc, ratio, addresses, chunk):
+    """One pass over a capture of n samples -> the records on the host: (msg [k][14], pos, meta, score).  upload(lo, hi) -> a float32 device
+    tensor holding samples [lo, hi).  Each chunk of `chunk` starts goes up with the halo its starts and their suppressors read."""
+    import torch
+    dev = f"cuda:{e.device}"
+    a = np.array(sorted({int(x) for x in addresses}), np.uint32)
+    d_icao = torch.from_numpy(a.view(np.int32)).to(dev) if len(a) else None
+    room = 4096
+    d_msg = torch.empty((room, 14), dtype=torch.uint8, device=dev)
+    d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+    d_meta = torch.empty(room, dtype=torch.int32, device=dev)
+    d_score = torch.empty(room, dtype=torch.float32, device=dev)
+    d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+    parts = []
+    for s0 in range(0, n, chunk):
+        s1 = min(n, s0 + chunk)
+        lo, hi = max(0, s0 - (2 * spc - 1)), min(n, s1 + 2 * spc - 2 + 240 * spc)
+        d_iq = upload(lo, hi)
+        while True:
+            e.adsb_frames(d_iq, hi - lo, spc, d_msg, d_pos, d_meta, d_score, d_count, room, ratio=ratio, d_icao=d_icao, n_icao=len(a), buf_index0=lo,
+                          n_capture=n, s_begin=s0, s_end=s1)
+            k = int(d_count.cpu()[0])
+            if k <= room:
+                break
+            room = k   # the true count: the chunk again with room for it
+            d_msg = torch.empty((room, 14), dtype=torch.uint8, device=dev)
+            d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+            d_meta = torch.empty(room, dtype=torch.int32, device=dev)
+            d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        parts.append((d_msg[:k].cpu().numpy(), d_pos[:k].cpu().numpy(), d_meta[:k].cpu().numpy().view(np.uint32), d_score[:k].cpu().numpy()))
+    if not parts:
+        return np.zeros((0, 14), np.uint8), np.zeros(0, np.int64), np.zeros(0, np.uint32), np.zeros(0, np.float32)
+    return tuple(np.concatenate([p[i] for p in parts]) for i in range(4))
+
+
+def adsb_recording(samples, fs, ratio=2.0, addresses=(), learn=True, chunk_samples=1 << 22, codes_format=None, table=None):
+    """The aircraft of a 1090 MHz capture -> dict(frames=..., tracks=..., fs=...): 'frames' a list of dicts in order of 'pos' (adsb_decode's keys
+    and 'msg' (bytes), 'n_bits', 'pos', 'score'), 'tracks' adsb_tracks(frames, fs), 'fs' the rate the positions count in.
+    At a multiple of 2 MS/s up to 16 MS/s the capture is streamed through pss_adsb_frames in chunks of chunk_samples starts, each with its
+    halo; the result does not depend on chunk_samples.  Another integer rate is first brought to the next multiple of 2 MS/s by pss_resample
+    on the resident complex64 row (2.4 MS/s -> 4 MS/s): such a capture has to fit on the device.
+    addresses: the aircraft whose address-overlaid replies (DF 0 / 4 / 5 / 16 / 20 / 21) are wanted.  learn: a second pass runs with these
+    and every address seen in an accepted DF 11 / 17 / 18 frame of the first, and ITS result is the answer (the capture is read twice).
+    codes_format / table: as rds_recording; codes are widened per chunk on the device."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    chunk = int(chunk_samples)
+    dev = f"cuda:{e.device}"
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+    else:
+        samples = np.ascontiguousarray(samples, np.complex64)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+
+    def from_host(lo, hi):
+        if codes_format is None:
+            return torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev)
+        d_iq = torch.empty(2 * (hi - lo), dtype=torch.float32, device=dev)
+        e.unpack_iq(torch.from_numpy(np.array(samples[lo:hi])).to(dev), hi - lo, d_iq, codes_format, iq[2])
+        return d_iq
+
+    n = len(samples)
+    upload = from_host
+    if fs % 2e6 != 0.0:
+        rate = 2e6 * np.ceil(fs / 2e6)
+        up, down = plan_resample(fs, rate)
+        d_in = from_host(0, n) if n else torch.empty(2, dtype=torch.float32, device=dev)
+        n_out = e.resample_out_len(n, up, down)
+        d_row = torch.empty(2 * max(n_out, 1), dtype=torch.float32, device=dev)
+        if n:
+            e.resample(d_in, np.complex64, 1, n, up, down, d_row)
+        del d_in
+        fs, n = float(rate), n_out
+        upload = lambda lo, hi: d_row[2 * lo:2 * hi]   # noqa: E731  (resident: a chunk is a view)
+    spc = e.adsb_plan(fs)
+    known = {int(a) for a in addresses}
+    rec = _adsb_pass(e, upload, n, spc, ratio, known, chunk)
+    if learn:
+        seen = {int.from_bytes(bytes(m[1:4]), 'big') for m, w in zip(rec[0], rec[2]) if (int(w) >> 16) in (11, 17, 18)}
+        if not seen <= known:
+            rec = _adsb_pass(e, upload, n, spc, ratio, known | seen, chunk)
+    frames = []
+    for m, p, w, sc in zip(*rec):
+        nb = int(w) & 0xFFFF
+        d = adsb_decode(m, nb)
+        d.update(msg=bytes(m[:nb // 8]), n_bits=nb, pos=int(p), score=float(sc))
+        frames.append(d)
+    return dict(frames=frames, tracks=adsb_tracks(frames, fs), fs=fs)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
