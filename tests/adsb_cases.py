@@ -184,13 +184,72 @@ def clean(n, spc, frames):
     return synth(n, spc, [(m, p, 1.0, 0.0) for m, p in frames])
 
 
-def twin_starts(p=41, tail=9):
-    """spc 2, hand-made: only the SECOND sample of every chip carries the frame, so the starts p and p + 1 slice the same message with the
-    same chip energies (x + 0 and 0 + x) -> (capture, p)."""
-    c = chips_of(IDENT)
-    x = np.zeros(p + 2 * len(c) + tail, np.complex64)
-    x[p + 1:p + 1 + 2 * len(c):2] = c
+def same_score_starts(spc, p, msg=IDENT, tail=9):
+    """Hand-made: only the LAST sample of every chip carries the frame, so the starts p .. p + spc - 1 slice the same message with bit-equal
+    chip energies (0 + ... + 0 + x, the x further forward in the sum at every later start) -> (capture, p).  tail >= spc - 1: the last of
+    them still fits the capture."""
+    c = chips_of(msg)
+    x = np.zeros(p + spc * len(c) + tail, np.complex64)
+    x[p + spc - 1:p + spc - 1 + spc * len(c):spc] = c
     return x, p
+
+
+def twin_starts(p=41, tail=9):
+    """spc 2: only the SECOND sample of every chip carries the frame, so the starts p and p + 1 slice the same message with the same chip
+    energies (x + 0 and 0 + x) -> (capture, p)."""
+    return same_score_starts(2, p, IDENT, tail)
+
+
+def overlaid(head_hex, address):
+    """with_parity(head) with the address XORed into its last three bytes: a message whose remainder is the address."""
+    b = bytearray(bytes.fromhex(with_parity(head_hex)))
+    for k in range(3):
+        b[len(b) - 3 + k] ^= (address >> (16 - 8 * k)) & 0xFF
+    return bytes(b).hex().upper()
+
+
+def every_format_capture():
+    """spc 1, no noise: for each DF 0 .. 31 one frame with remainder zero and one with remainder ADDRESS (DF >= 16 long, the others short; the
+    first byte DF << 3 | 5, the bytes behind it a pattern of the DF), odd gaps between them -> (capture, the positions the rules accept
+    with the address list [ADDRESS]: remainder zero of DF 11, 17, 18, remainder ADDRESS of DF 0, 4, 5, 16, 20, 21, in that DF order)."""
+    frames, accepted, pos = [], [], 7
+    for df in range(32):
+        head = bytes([df << 3 | 5] + [(37 * df + 11 * j + 3) & 0xFF for j in range(1, 11 if df >= 16 else 4)]).hex()
+        for k, msg in enumerate((with_parity(head), overlaid(head, ADDRESS))):
+            frames.append((msg, pos))
+            if (k == 0 and df in (11, 17, 18)) or (k == 1 and df in (0, 4, 5, 16, 20, 21)):
+                accepted.append(pos)
+            pos += 16 + 8 * len(msg) + 31 + 2 * ((2 * df + k) % 7)      # the frame (len hex digits: 8 len chips of data), then an odd gap
+    return clean(pos + 40, 1, frames), accepted
+
+
+# ---- captures the CPU and the GPU tests share.  TILE restates DT_S of csrc/pss_adsb.hip (tests/launch_caps.py pins the line).
+TILE = 4096
+
+
+def dense_capture(spc):
+    """Unit noise with three strong frames, near survivors 700, 2500 and TILE - 5 of the first detect tile when ratio is 0 (nearly every
+    start survives then) -> complex64 [TILE + 240 spc + 600]."""
+    n = TILE + 240 * spc + 600
+    return synth(n, spc, [(IDENT, 700, 10.0, 0.2), (ALL_CALL, 2500, 10.0, 0.9), (VELOCITY, TILE - 5, 10.0, 1.7)], seed=[88, spc])
+
+
+TWO_TILE_P = 5000
+TWO_TILE_EXTRA = (1, 7, 8, 9, 15, 16)
+
+
+def two_tile_window_capture():
+    """spc 8, no noise: a long frame at TWO_TILE_P and a short one behind it.  A window that begins at TWO_TILE_P - 4066 - c and ends at
+    TWO_TILE_P (or one later) evaluates TILE + c starts (15 either side): one whole tile and a last one of c starts."""
+    p, spc = TWO_TILE_P, 8
+    return clean(p + 240 * spc + 3000, spc, [(POS_EVEN, p), (ALL_CALL, p + 240 * spc + 100)])
+
+
+def ending_capture(spc, msg):
+    """A frame whose last sample is the capture's last, sample TILE + 4 -> (capture, the frame's position)."""
+    span = spc * (16 + 8 * len(msg))                # len(msg) hex digits: 8 len chips of data
+    p = TILE + 5 - span
+    return clean(p + span, spc, [(msg, p)]), p
 
 
 def windows_capture():

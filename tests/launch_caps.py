@@ -265,3 +265,107 @@ CAPS = {
             "for (long g = (long)blockIdx.x * 4 + (threadIdx.x >> 6); g < n_rows; g += (long)gridDim.x * 4) {",
         ]}),
 }
+
+
+# ---- the receivers (pss_rds.hip, pss_adsb.hip).  Not rows of CAPS: tests/test_gpu_grid_caps.py iterates that table, and these units have
+# their past-the-cap tests in tests/test_gpu_rds.py and tests/test_gpu_adsb.py, which import the numbers below instead of restating them.
+# Every number stands in a pinned line, so a changed cap fails tests/test_launch_caps.py before it can turn those tests into tests of nothing.
+FR_T, FR_GRID_CAP = 1024, 2048            # k_rds_front: (row, tile) pairs
+EN_T, EN_GRID_CAP = 256, 16384            # k_rds_energy: tiles of EN_T / 16 segments of 1024 samples
+BT_T, BT_GRID_CAP = 256, 4096             # k_rds_bits: rows; BT_T segments a pass of its scan
+GR_T, GR_GRID_CAP = 256, 4096             # k_rds_groups: rows
+DT_T, DT_S, DT_GRID_CAP = 1024, 4096, 1024    # k_adsb_detect: tiles of DT_S starts
+SC_T, SC_PER = 1024, 4                    # k_adsb_scan: SC_PER * SC_T counts a step
+LS_T, LS_GRID_CAP = 256, 2048             # k_adsb_gather: tiles; k_adsb_keep, k_adsb_emit: LS_T / 64 accepted starts a workgroup
+
+RDS_SEGMENT = 1024                        # pss_rds.h: SEG_BITS * SPB samples of a row
+FRONT_GRID_CAP = FR_GRID_CAP
+ENERGY_TILE_SEGMENTS = EN_T // 16
+BITS_SCAN_PASS = BT_T
+DETECT_TILE, DETECT_GRID_CAP = DT_S, DT_GRID_CAP
+SCAN_STEP = SC_PER * SC_T
+LIST_PASS = LS_GRID_CAP * (LS_T // 64)    # accepted starts one pass of k_adsb_keep / k_adsb_emit covers
+
+RECEIVER_CAPS = {
+    "rds_front": Cap(
+        "pss_rds_front", "k_rds_front", "(row, tile) pairs", lambda n=None, o=None: FR_GRID_CAP,
+        {"pss_rds.hip": [
+            f"constexpr int FR_T = {FR_T};",
+            f"constexpr long FR_GRID_CAP = {FR_GRID_CAP};",
+            "hipLaunchKernelGGL(k_rds_front, dim3((unsigned)(n_pairs < FR_GRID_CAP ? n_pairs : FR_GRID_CAP)), dim3(FR_T), 0,",
+            "for (long p = blockIdx.x; p < n_pairs; p += gridDim.x) {",
+        ]}),
+    # n samples a row: one tile covers EN_T / SPB segments of a row, and a tile never spans two rows
+    "rds_energy": Cap(
+        "pss_rds_bits", "k_rds_energy", "rows",
+        lambda n, o=None: EN_GRID_CAP // max(1, -(-(-(-n // RDS_SEGMENT)) // ENERGY_TILE_SEGMENTS)),
+        {"pss_rds.hip": [
+            f"constexpr int EN_T = {EN_T};",
+            "constexpr int EN_SEGS = EN_T / SPB;",
+            f"constexpr long EN_GRID_CAP = {EN_GRID_CAP};",
+            "const long tiles_per_row = (n_seg + EN_SEGS - 1) / EN_SEGS, n_tiles = tiles_per_row * n_rows;",
+            "hipLaunchKernelGGL(k_rds_energy, dim3((unsigned)(n_tiles < EN_GRID_CAP ? n_tiles : EN_GRID_CAP)), dim3(EN_T), 0,",
+            "for (long t = blockIdx.x; t < n_tiles; t += gridDim.x) {",
+        ], "pss_rds.h": [
+            "constexpr int SPB = 16;",
+            "constexpr int SEG_BITS = 64, SEG = SEG_BITS * SPB;",
+            "PSS_DDC_HD inline int n_segments(long n) { return (int)((n + SEG - 1) / SEG); }",
+        ]}),
+    "rds_bits": Cap(
+        "pss_rds_bits", "k_rds_bits", "rows", lambda n=None, o=None: BT_GRID_CAP,
+        {"pss_rds.hip": [
+            f"constexpr int BT_T = {BT_T};",
+            f"constexpr long BT_GRID_CAP = {BT_GRID_CAP};",
+            "hipLaunchKernelGGL(k_rds_bits, dim3((unsigned)(n_rows < BT_GRID_CAP ? n_rows : BT_GRID_CAP)), dim3(BT_T), 0,",
+            "for (long row = blockIdx.x; row < n_rows; row += gridDim.x) {\n        const float2 *x = bb + (size_t)row * row_stride;",
+            "for (int s0 = 0; s0 < n_seg; s0 += BT_T) {",
+        ]}),
+    "rds_groups": Cap(
+        "pss_rds_groups", "k_rds_groups", "rows", lambda n=None, o=None: GR_GRID_CAP,
+        {"pss_rds.hip": [
+            f"constexpr int GR_T = {GR_T};",
+            f"constexpr long GR_GRID_CAP = {GR_GRID_CAP};",
+            "hipLaunchKernelGGL(k_rds_groups, dim3((unsigned)(n_rows < GR_GRID_CAP ? n_rows : GR_GRID_CAP)), dim3(GR_T), 0,",
+            "for (long row = blockIdx.x; row < n_rows; row += gridDim.x) {\n        const uint8_t *b = bits + (size_t)row * max_bits;",
+        ]}),
+    "adsb_detect": Cap(
+        "pss_adsb_frames", "k_adsb_detect", "tiles of DT_S starts", lambda n=None, o=None: DT_GRID_CAP,
+        {"pss_adsb.hip": [
+            f"constexpr int DT_T = {DT_T};",
+            f"constexpr int DT_S = {DT_S};",
+            f"constexpr long DT_GRID_CAP = {DT_GRID_CAP};",
+            "const long n_ext = w.e1 - w.e0, n_tiles = (n_ext + DT_S - 1) / DT_S;",
+            "hipLaunchKernelGGL(k_adsb_detect, dim3((unsigned)(n_tiles < DT_GRID_CAP ? n_tiles : DT_GRID_CAP)), dim3(DT_T), 0,",
+            "for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {\n        const long g0 = e0 + tile * DT_S;",
+        ]}),
+    "adsb_scan": Cap(
+        "pss_adsb_frames", "k_adsb_scan<int>, k_adsb_scan<uint8_t>", "counts a step of the one workgroup", lambda n=None, o=None: SC_PER * SC_T,
+        {"pss_adsb.hip": [
+            f"constexpr int SC_T = {SC_T}, SC_PER = {SC_PER};",
+            "for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {",
+            "hipLaunchKernelGGL(k_adsb_scan<int>, dim3(1), dim3(SC_T), 0,",
+            "hipLaunchKernelGGL(k_adsb_scan<uint8_t>, dim3(1), dim3(SC_T), 0,",
+        ]}),
+    "adsb_gather": Cap(
+        "pss_adsb_frames", "k_adsb_gather", "tiles", lambda n=None, o=None: LS_GRID_CAP,
+        {"pss_adsb.hip": [
+            f"constexpr int LS_T = {LS_T};",
+            f"constexpr long LS_GRID_CAP = {LS_GRID_CAP};",
+            "hipLaunchKernelGGL(k_adsb_gather, dim3((unsigned)(n_tiles < LS_GRID_CAP ? n_tiles : LS_GRID_CAP)), dim3(LS_T), 0,",
+            "for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {\n        const int c = tile_count[tile], o = tile_off[tile];",
+        ]}),
+    "adsb_list": Cap(
+        "pss_adsb_frames", "k_adsb_keep, k_adsb_emit", "accepted starts", lambda n=None, o=None: LS_GRID_CAP * (LS_T // 64),
+        {"pss_adsb.hip": [
+            f"constexpr int LS_T = {LS_T};",
+            f"constexpr long LS_GRID_CAP = {LS_GRID_CAP};",
+            "const long wave_blocks = (n_acc + LS_T / 64 - 1) / (LS_T / 64);",
+            "const dim3 wave_grid((unsigned)(wave_blocks < LS_GRID_CAP ? wave_blocks : LS_GRID_CAP));",
+            "hipLaunchKernelGGL(k_adsb_keep, wave_grid, dim3(LS_T), 0,",
+            "hipLaunchKernelGGL(k_adsb_emit, wave_grid, dim3(LS_T), 0,",
+            "const long wave = (long)blockIdx.x * (LS_T / 64) + (threadIdx.x >> 6), n_waves = (long)gridDim.x * (LS_T / 64);\n"
+            "    for (long k = wave; k < n_acc; k += n_waves) {\n        const int a = acc[k];",
+            "const long wave = (long)blockIdx.x * (LS_T / 64) + (threadIdx.x >> 6), n_waves = (long)gridDim.x * (LS_T / 64);\n"
+            "    for (long k = wave; k < n_acc; k += n_waves) {\n        if (!keep[k]) continue;",
+        ]}),
+}

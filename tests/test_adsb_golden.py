@@ -347,3 +347,89 @@ def test_header_alone_runs_clean_under_the_sanitizers(tmp_path):
                     "-fno-sanitize-recover=undefined", "-I", CSRC, os.path.join(HERE, "adsb_host.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "adsb_host: ok" in r.stdout and not r.stderr, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+
+
+# ---- the captures tests/test_gpu_adsb.py sends through the kernels' loops and carries: here the twin is held to the NumPy statement on them
+def test_twin_starts_is_same_score_starts_at_spc_2():
+    c = A.chips_of(A.IDENT)
+    for q, tail in ((41, 9), (4095, 9), (7, 3)):
+        x = np.zeros(q + 2 * len(c) + tail, np.complex64)
+        x[q + 1:q + 1 + 2 * len(c):2] = c
+        for got in (A.twin_starts(q, tail), A.same_score_starts(2, q, tail=tail)):
+            assert got[1] == q and got[0].dtype == np.complex64 and same_bytes(got[0], x)
+
+
+def test_overlaid_has_the_address_as_its_remainder():
+    for head in ("20000B38", "A0000B38AB0D0D11223344"):
+        m = bytes.fromhex(A.overlaid(head, A.ADDRESS))
+        assert A.crc24(m) == A.ADDRESS == E.adsb_crc(m) and m[:-3] == bytes.fromhex(head) and A.crc24(bytes.fromhex(A.with_parity(head))) == 0
+    assert A.overlaid("20000B38", A.ADDRESS) == A.ALT_REPLY
+
+
+def test_every_downlink_format():
+    x, accepted = A.every_format_capture()
+    assert len(accepted) == 9
+    first = (A.ADDRESS + 7 * np.arange(1000)).astype(np.uint32)
+    last = (A.ADDRESS - 7 * np.arange(999, -1, -1)).astype(np.uint32)
+    for icao in ([A.ADDRESS], first, last):
+        msg, pos, meta, score, count = both(x, 1, icao=icao)
+        assert pos.tolist() == accepted and count == 9
+        assert [int(w) >> 16 for w in meta] == list(A.REPORTED_DF) and [int(w) & 0xFFFF for w in meta] == [56, 56, 56, 56, 112, 112, 112, 112, 112]
+        assert [A.crc24(bytes(m[:(int(w) & 0xFFFF) // 8])) for m, w in zip(msg, meta)] == [A.ADDRESS] * 3 + [0, A.ADDRESS, 0, 0, A.ADDRESS, A.ADDRESS]
+    msg, pos, meta, score, count = both(x, 1)
+    assert count == 3 and [int(w) >> 16 for w in meta] == [11, 17, 18] and pos.tolist() == [accepted[3], accepted[5], accepted[6]]
+    assert both(x, 1, icao=first[1:])[4] == 3                       # 999 addresses, none of them the frames'
+
+
+@pytest.mark.parametrize("spc", [2, 4, 8])
+def test_equal_scores_at_every_start_of_a_chip(spc):
+    q = A.TILE - spc // 2                                           # the spc starts lie on both sides of a tile boundary of the kernel
+    x, _ = A.same_score_starts(spc, q)
+    assert both(x, spc)[1].tolist() == [q]
+    for k in range(1, spc):                                         # every later start alone is accepted, with the same score bits
+        alone = both(x[q + k:], spc, s_begin=0, s_end=1)
+        assert alone[4] == 1 and same_bytes(alone[3], both(x, spc)[3])
+    assert both(x, spc, s_begin=q + 1)[4] == 0                      # the earliest start lies outside the window and still drops the others
+    assert both(x, spc, s_begin=q + spc - 1)[4] == 0
+    assert both(x, spc, s_end=q)[4] == 0
+    assert both(x, spc, ratio=0.0)[1].tolist() == [q]
+
+
+@pytest.mark.parametrize("spc", [1, 3, 8])
+@pytest.mark.parametrize("msg", [A.IDENT, A.ALL_CALL], ids=["long", "short"])
+def test_frames_that_end_with_the_capture(spc, msg):
+    x, q = A.ending_capture(spc, msg)
+    assert len(x) == A.TILE + 5
+    assert both(x, spc)[1].tolist() == [q]
+    # one sample shorter: the frame at q no longer fits.  spc 8: the start in front of it slices the same bits out of 7/8 of every chip and fits
+    assert both(x[:-1], spc)[1].tolist() == ([q - 1] if spc == 8 else [])
+
+
+def test_window_of_two_tiles_with_exactly_its_reach():
+    x, q, spc = A.two_tile_window_capture(), A.TWO_TILE_P, 8
+    n = len(x)
+    whole = both(x, spc)
+    assert whole[1].tolist() == [q, q + 240 * spc + 100]
+    for c in A.TWO_TILE_EXTRA:
+        s_begin = q - 4066 - c
+        for s_end, want in ((q, []), (q + 1, [q])):                 # start q - 1 is accepted; q, in the right margin, drops it
+            lo, hi = A.reach(s_begin, s_end, spc, n)
+            assert hi - lo == A.TILE + c + 1919 + (s_end - q)
+            part = both(x[lo:hi], spc, buf_index0=lo, n_capture=n, s_begin=s_begin, s_end=s_end)
+            assert part[1].tolist() == want and part[4] == len(want)
+            inside = (whole[1] >= s_begin) & (whole[1] < s_end)
+            for a, b in zip(part[:4], whole[:4]):
+                assert same_bytes(a, b[inside])
+
+
+@pytest.mark.parametrize("spc", [1, 2, 4, 6, 7, 8])
+def test_dense_survivors(spc):
+    """ratio 0: nearly every start survives its preamble test.  At spc 8 the frame at 700 runs into the one at 2500 (700 + 1920 > 2500) and
+    is not reported at any start."""
+    stats = {}
+    x = A.dense_capture(spc)
+    A.numpy_frames(x, spc, ratio=0.0, stats=stats)
+    assert stats["survivors"] > A.TILE
+    pos = both(x, spc, ratio=0.0)[1]
+    for q in (700,) * (spc < 8) + (2500, A.TILE - 5):
+        assert np.any(np.abs(pos - q) < spc), (q, pos)

@@ -1,7 +1,11 @@
 """The ADS-B kernels (k_adsb_detect, k_adsb_scan, k_adsb_gather, k_adsb_keep, k_adsb_emit) against pss_h_adsb_frames on every
 byte — the messages, pos, the meta word, the score bits and the count — and formats.adsb_recording end to end.  The shapes are the smallest
 at which each path is taken: frames on both sides of a tile boundary, one tile past the grid cap, more survivors in a tile than a wavefront
-holds and more than one pass of the second compaction takes (ratio 0), more accepted frames than one pass of the list kernels, a count above max_frames, windows with exactly their reach.
+holds and more than one pass of the second compaction takes (ratio 0, at every rate that has its own LDS extent), more accepted frames than
+one step of the scan and than one pass of the list kernels, a count above max_frames, windows with exactly their reach, of less than a tile
+and of a tile and a few starts; 4097 tiles, so that a workgroup of the detect kernel walks five and the tiles' counts carry in the scan;
+every downlink format; up to eight starts with one score; frames that end with the capture.  The caps and tile sizes come from
+tests/launch_caps.py, where tests/test_launch_caps.py pins them to the source lines.
 
 A frame spans at most 240 * 8 = 1920 samples and a tile of the detect kernel is 4096 starts, so no frame covers three tiles: the spc 8 case
 below puts one across a boundary and its reach into the tile after."""
@@ -17,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adsb_cases as A
 from bytes_util import same_bytes
 from gpu_util import dev
+from launch_caps import DETECT_GRID_CAP, DETECT_TILE, LIST_PASS, LS_GRID_CAP, SCAN_STEP   # pinned to csrc/pss_adsb.hip by tests/test_launch_caps.py
 from pyspecsdr_amd import formats as F
 from pyspecsdr_amd.engine import Engine
 
@@ -24,10 +29,8 @@ pytestmark = pytest.mark.gpu
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adsb.npz"))
 NAMES = [str(n) for n in GOLD["names"]]
-DETECT_TILE = 4096          # csrc/pss_adsb.hip: DT_S, the starts of a tile
-DETECT_GRID_CAP = 1024      # DT_GRID_CAP
-SCAN_STEP = 4096            # SC_PER * SC_T: the counts k_adsb_scan takes in one step
 SENTINEL = 0xA5
+assert A.TILE == DETECT_TILE
 
 
 @pytest.fixture(scope="module")
@@ -249,3 +252,116 @@ def test_recording_resamples_a_dongle_rate(e):
     got = [(f["msg"].hex().upper(), f["pos"] / out["fs"] * 1e6) for f in out["frames"]]
     assert [g[0] for g in got] == msgs
     assert all(abs(g[1] - t0) <= 0.5 for g, t0 in zip(got, t_us)), got          # within one chip
+
+
+# ---- the loops, carries and reuses that need more tiles, more accepted starts or another rate than the tests above have
+def test_4097_tiles(e):
+    """Workgroup 0 of k_adsb_detect walks tiles 0, 1024, 2048, 3072 and 4096: survivors, none, survivors, none, survivors, so the prefetched
+    registers, ms / surv, wcount and acc_s are reused after a tile that had work.  k_adsb_gather walks tiles 2048 .. a second time, and
+    k_adsb_scan<int> carries into its second step at tile 4096."""
+    S = DETECT_TILE
+    tiles = 4 * DETECT_GRID_CAP + 1
+    assert tiles == SCAN_STEP + 1 and tiles > 2 * LS_GRID_CAP
+    n = (tiles - 1) * S + 600
+    at = [5, 2 * DETECT_GRID_CAP * S + 7, (tiles - 1) * S - 300, (tiles - 1) * S + 3, n - 240]
+    x = np.zeros(n, np.complex64)           # zeros fail the strict preamble test: the twin stays quick
+    for p, m in zip(at, (A.IDENT, A.POS_EVEN, A.VELOCITY, A.POS_ODD, A.IDENT)):
+        x[p:p + 240] = A.chips_of(m)
+    msg, pos, meta, score, count = check(e, x, 1)
+    assert pos.tolist() == at and count == 5
+
+
+def test_more_accepted_starts_than_one_pass_of_the_list_kernels(e):
+    k = LIST_PASS + 5                        # k_adsb_keep and k_adsb_emit: four accepted starts a workgroup, LS_GRID_CAP workgroups
+    at = [3 + 128 * i for i in range(k)]
+    x = A.clean(3 + 128 * k + 5, 1, [(A.ALL_CALL, p) for p in at])
+    want = check(e, x, 1, max_frames=k + 10)
+    assert want[4] == k and want[1].tolist() == at
+    cut = check(e, x, 1, max_frames=LIST_PASS - 2)      # the rank cut falls inside the second pass of k_adsb_emit
+    assert cut[4] == k and cut[1].tolist() == at[:LIST_PASS - 2]
+
+
+@pytest.mark.parametrize("spc", [1, 2, 4, 6, 7, 8])
+def test_dense_survivors_at_every_rate(e, spc):
+    """ratio 0 at every rate: the survivor list fills the aliased ms, the second compaction takes four passes, and at spc 8 the LDS images
+    are at their full size.  At spc 8 the frame at 700 runs into the one at 2500 and is reported at no start (tests/test_adsb_golden.py)."""
+    x = A.dense_capture(spc)
+    assert len(x) == DETECT_TILE + 240 * spc + 600
+    want = check(e, x, spc, ratio=0.0, max_frames=512)
+    ref = A.numpy_frames(x, spc, ratio=0.0, max_frames=512)
+    assert all(same_bytes(w, r) for w, r in zip(want[:4], ref[:4])) and want[4] == ref[4]
+    for q in (700,) * (spc < 8) + (2500, DETECT_TILE - 5):
+        assert np.any(np.abs(want[1] - q) < spc), (q, want[1])
+
+
+def test_window_of_two_tiles_with_exactly_its_reach(e):
+    """A windowed call whose last tile has c starts, from a buffer that ends with the window's reach: the zeros the kernel stages behind
+    it enter no sum that a start of the tile reads (the header comment of k_adsb_detect)."""
+    x, p, spc = A.two_tile_window_capture(), A.TWO_TILE_P, 8
+    n = len(x)
+    whole = check(e, x, spc)
+    assert whole[1].tolist() == [p, p + 240 * spc + 100]
+    for c in A.TWO_TILE_EXTRA:
+        s_begin = p - 4066 - c
+        for s_end, at in ((p, []), (p + 1, [p])):
+            lo, hi = A.reach(s_begin, s_end, spc, n)
+            assert hi - lo == DETECT_TILE + c + 1919 + (s_end - p)
+            part = check(e, x[lo:hi], spc, buf_index0=lo, n_capture=n, s_begin=s_begin, s_end=s_end)
+            assert part[1].tolist() == at and part[4] == len(at), (c, s_end)
+            inside = (whole[1] >= s_begin) & (whole[1] < s_end)
+            for a, b in zip(part[:4], whole[:4]):
+                assert same_bytes(a, b[inside]), (c, s_end)
+
+
+@pytest.mark.parametrize("spc", [1, 3, 8])
+@pytest.mark.parametrize("msg", [A.IDENT, A.ALL_CALL], ids=["long", "short"])
+def test_frames_that_end_with_the_capture(e, spc, msg):
+    x, p = A.ending_capture(spc, msg)        # the capture ends five samples into the second tile
+    assert check(e, x, spc)[1].tolist() == [p]
+    short = check(e, x[:-1], spc)
+    ref = A.numpy_frames(x[:-1], spc)
+    assert all(same_bytes(s, r) for s, r in zip(short[:4], ref[:4])) and short[4] == ref[4]
+    assert p not in short[1].tolist() and short[1].tolist() == ([p - 1] if spc == 8 else [])
+
+
+def test_every_downlink_format(e):
+    x, accepted = A.every_format_capture()
+    first = (A.ADDRESS + 7 * np.arange(1000)).astype(np.uint32)
+    last = (A.ADDRESS - 7 * np.arange(999, -1, -1)).astype(np.uint32)
+    for icao in ([A.ADDRESS], first, last):
+        msg, pos, meta, score, count = check(e, x, 1, icao=icao)
+        assert pos.tolist() == accepted and count == 9 and [int(w) >> 16 for w in meta] == list(A.REPORTED_DF)
+    msg, pos, meta, score, count = check(e, x, 1)
+    assert count == 3 and [int(w) >> 16 for w in meta] == [11, 17, 18]
+    assert check(e, x, 1, icao=first[1:])[4] == 3
+
+
+@pytest.mark.parametrize("spc", [4, 8])
+def test_equal_scores_across_a_tile_boundary(e, spc):
+    """spc starts with bit-equal scores on both sides of a tile boundary: k_adsb_keep walks up to spc - 1 neighbours on either side."""
+    p = DETECT_TILE - spc // 2
+    x, _ = A.same_score_starts(spc, p)
+    assert check(e, x, spc)[1].tolist() == [p]
+    assert check(e, x, spc, s_begin=p + 1)[4] == 0
+    assert check(e, x, spc, s_begin=p + spc - 1)[4] == 0
+    assert check(e, x, spc, s_end=p)[4] == 0
+    assert check(e, x, spc, ratio=0.0)[1].tolist() == [p]
+
+
+def test_one_workgroup_walks_dense_tiles_back_to_back(e):
+    """ratio 0, spc 2: tiles 0, 1024 and 2048 are the first workgroup's, and each holds noise, so every one of them fills the survivor
+    list, acc_s and the wavefront counts behind a tile that filled them too, fuller (4096 survivors, then about 2300, then about 1000):
+    what a tile leaves behind its own count must not reach the next one's list.  Everything between is zero and passes no preamble."""
+    S, cap, spc = DETECT_TILE, DETECT_GRID_CAP, 2
+    n = 2 * cap * S + 1100 + 240 * spc
+    x = np.zeros(n, np.complex64)
+    at = []
+    for k, (lo, hi, p, m) in enumerate(((0, S + 700, 700, A.IDENT), (cap * S - 300, cap * S + 2300, cap * S + 1500, A.ALL_CALL),
+                                        (2 * cap * S + 100, n, 2 * cap * S + 300, A.VELOCITY))):
+        x[lo:hi] = A.synth(hi - lo, spc, [(m, p - lo, 10.0, 0.5 + k)], seed=[89, k])
+        at.append(p)
+    stats = {}
+    A.numpy_frames(x[:S + 240 * spc], spc, ratio=0.0, s_end=S - 2 * spc + 1, stats=stats)
+    assert stats["survivors"] == S                                   # every start of tile 0
+    want = check(e, x, spc, ratio=0.0, max_frames=512)
+    assert set(at) <= set(want[1].tolist())

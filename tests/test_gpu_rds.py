@@ -1,7 +1,9 @@
 """The RDS kernels (k_rds_front, k_rds_energy, k_rds_bits, k_rds_groups) against their host twins on every byte, the chain from IQ on the
 device against the golden groups of tests/golden/rds.npz, and formats.rds_stations on a synthetic capture of the band.  The shapes are
 the smallest at which a kernel takes each of its paths: more than one tile and a partial one, one (row, tile) pair past the grid cap,
-rows around the 1024-sample segments, fewer segments than the smoothing span, the timing wraps, groups at the row's end."""
+rows around the 1024-sample segments, fewer segments than the smoothing span, the timing wraps, groups at the row's end; one row past
+the caps of k_rds_energy, k_rds_bits and k_rds_groups, and a row of more segments than one pass of k_rds_bits' scan.  The caps come from
+tests/launch_caps.py, where tests/test_launch_caps.py pins them to the source lines."""
 import os
 import sys
 
@@ -14,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import rds_cases as R
 from bytes_util import same, same_bytes
 from gpu_util import dev, empty, host
+from launch_caps import BITS_SCAN_PASS, BT_GRID_CAP, EN_GRID_CAP, FRONT_GRID_CAP, GR_GRID_CAP, RDS_SEGMENT, RECEIVER_CAPS   # pinned by tests/test_launch_caps.py
 from pyspecsdr_amd import formats as F
 from pyspecsdr_amd.engine import Engine
 
@@ -21,7 +24,6 @@ pytestmark = pytest.mark.gpu
 
 GOLD = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "rds.npz"))
 NAMES = [str(n) for n in GOLD["names"]]
-FRONT_GRID_CAP = 2048
 
 
 @pytest.fixture(scope="module")
@@ -233,3 +235,73 @@ def test_drop_in_hooks(e):
     groups, _, n = Engine.h_rds_groups(np.array(bits, np.uint8))
     idx = R.find_groups(GOLD["fs240k_plain/groups"], groups[:n])
     assert idx is not None and set(range(1, 7)) <= set(idx)
+
+
+# ---- past the grid caps of k_rds_energy, k_rds_bits and k_rds_groups, and past one pass of k_rds_bits' scan
+def test_bits_one_row_past_each_grid_cap(e):
+    """16 385 rows of two segments: one energy tile a row, so k_rds_energy is one tile past its cap, and every workgroup of k_rds_bits
+    walks four or five rows, resetting its carry for each.  The rows repeat a pool of seven, so a row that took its neighbour's offsets,
+    prefix or carry shows."""
+    rows, n = EN_GRID_CAP + 1, 1100
+    assert RECEIVER_CAPS["rds_energy"].cover(n) == EN_GRID_CAP and rows > 4 * BT_GRID_CAP and RDS_SEGMENT < n <= 2 * RDS_SEGMENT
+    pulse = Engine.rds_default_pulse(1)
+    assert len(pulse) == 17
+    pool = []
+    for name in ("fs240k_plain", "fs400k_fast_clock", "fs250k_slow_wrap"):
+        bb = baseband(name)
+        pool += [bb[:n], bb[3000:3000 + n]]
+    pool.append(capture(n, 7))
+    pool = np.stack(pool)
+    assert len({row.tobytes() for row in pool}) == 7
+    want = Engine.h_rds_bits(pool, pulse=pulse)                      # the twin walks its rows one by one: row r's bits are pool row r % 7's
+    assert len({w.tobytes() for w in want}) > 1 and all(60 <= len(w) <= 70 for w in want)
+    max_bits = Engine.rds_max_bits(n)
+    bits, n_bits = bits_on_device(e, pool[np.arange(rows) % 7], n, pulse=pulse)
+    assert bits.shape == (rows, max_bits)
+    full = np.full((7, max_bits), 7, np.uint8)                       # the sentinel behind n_bits
+    for k, w in enumerate(want):
+        full[k, :len(w)] = w
+    idx = np.arange(rows) % 7
+    assert np.array_equal(n_bits, np.array([len(w) for w in want], np.int32)[idx])
+    bad = np.flatnonzero((bits != full[idx]).any(axis=1))
+    assert len(bad) == 0, bad[:10]
+
+
+def test_bits_more_segments_than_one_pass_of_the_scan(e):
+    """A row of 258 segments (13.8 s of baseband): the strobe counts' prefix carries into a second pass of 256 segments."""
+    n = (BITS_SCAN_PASS + 1) * RDS_SEGMENT + 17
+    bb = baseband("fs240k_plain")
+    long_row = np.tile(bb, -(-(n + 5) // len(bb)))                   # the joins move the timing: wanted
+    for src in (long_row[None, :n], np.stack([long_row[:n], long_row[5:5 + n]])):
+        want = Engine.h_rds_bits(src)
+        assert all(len(w) > 16000 for w in want)
+        bits, n_bits = bits_on_device(e, src, n)
+        for r, w in enumerate(want):
+            assert n_bits[r] == len(w) and np.array_equal(bits[r, :len(w)], w), r
+            assert np.all(bits[r, len(w):] == 7)
+        # and the groups of those bits, from the device's rows as they stand (the sentinels lie behind n_bits)
+        got, pos, n_groups = groups_on_device(e, bits, n_bits, 200)
+        wg, wpos, wn = Engine.h_rds_groups(bits, n_bits, max_groups=200)
+        assert np.array_equal(n_groups, wn) and np.all(wn > 100) and np.all(wn <= 200)
+        for r in range(len(want)):
+            k = int(wn[r])
+            assert np.array_equal(got[r, :k], wg[r, :k]) and np.array_equal(pos[r, :k], wpos[r, :k])
+            assert np.all(got[r, k:] == 0xFFFF) and np.all(pos[r, k:] == -1)
+
+
+def test_groups_one_row_past_the_grid_cap(e):
+    rows, max_bits, max_groups = GR_GRID_CAP + 1, 130, 2
+    stream = R.group_bits(R.station_groups())[:104]
+    r = np.arange(rows)
+    offset, n_bits = r % 23, (104 + r % 27).astype(np.int32)
+    bits = np.zeros((rows, max_bits), np.uint8)
+    for k in range(rows):
+        bits[k, offset[k]:offset[k] + 104] = stream
+    fits = offset + 104 <= n_bits
+    assert fits[-1] and fits[:GR_GRID_CAP].any() and not fits.all()   # the row past the cap holds a group
+    got, pos, n_groups = groups_on_device(e, bits, n_bits, max_groups)
+    wg, wpos, wn = Engine.h_rds_groups(bits, n_bits, max_groups=max_groups)
+    assert np.array_equal(wn, fits.astype(np.int32)) and np.array_equal(n_groups, wn)
+    assert np.array_equal(pos[fits, 0], offset[fits]) and np.array_equal(got[fits, 0], wg[fits, 0])
+    assert np.all(got[fits, 0] == R.station_groups()[0])
+    assert np.all(pos[fits, 1:] == -1) and np.all(pos[~fits] == -1) and np.all(got[fits, 1:] == 0xFFFF) and np.all(got[~fits] == 0xFFFF)

@@ -3,20 +3,40 @@ import os
 
 import pytest
 
-from launch_caps import CAPS
+import launch_caps
+from launch_caps import CAPS, RECEIVER_CAPS
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyspecsdr_amd", "csrc")
 
 
-@pytest.mark.parametrize("name", sorted(CAPS))
-def test_pinned_launch_lines_are_in_the_source(name):
-    row = CAPS[name]
+def pinned(table, which, name):
+    row = table[name]
     for fname, snippets in row.source.items():
         with open(os.path.join(CSRC, fname)) as f:
             src = f.read()
         for s in snippets:
             assert s in src, (f"{row.entry} ({row.kernels}): {fname} no longer reads\n    {s}\n"
-                              f"update tests/launch_caps.py ('{name}') to the new launch grid")
+                              f"update tests/launch_caps.py ({which}'{name}') to the new launch grid")
+
+
+@pytest.mark.parametrize("name", sorted(CAPS))
+def test_pinned_launch_lines_are_in_the_source(name):
+    pinned(CAPS, "", name)
+
+
+@pytest.mark.parametrize("name", sorted(RECEIVER_CAPS))
+def test_pinned_receiver_lines_are_in_the_source(name):
+    """pss_rds.hip and pss_adsb.hip: the constants tests/test_gpu_rds.py and tests/test_gpu_adsb.py import stand in these lines."""
+    pinned(RECEIVER_CAPS, "RECEIVER_CAPS ", name)
+
+
+def test_receiver_caps_at_the_shapes_the_gpu_tests_run():
+    c = launch_caps
+    assert sorted(RECEIVER_CAPS) == ["adsb_detect", "adsb_gather", "adsb_list", "adsb_scan", "rds_bits", "rds_energy", "rds_front", "rds_groups"]
+    assert (c.DETECT_TILE, c.DETECT_GRID_CAP, c.SCAN_STEP, c.LIST_PASS, c.FRONT_GRID_CAP, c.BITS_SCAN_PASS) == (4096, 1024, 4096, 8192, 2048, 256)
+    assert RECEIVER_CAPS["rds_energy"].cover(1100) == 16384 and RECEIVER_CAPS["rds_energy"].cover(257 * 1024 + 17) == 16384 // 17
+    assert RECEIVER_CAPS["adsb_list"].cover() == c.LIST_PASS and RECEIVER_CAPS["adsb_scan"].cover() == c.SCAN_STEP
+    assert RECEIVER_CAPS["adsb_gather"].cover() == 2048 and RECEIVER_CAPS["rds_bits"].cover() == RECEIVER_CAPS["rds_groups"].cover() == 4096
 
 
 def test_caps_at_the_lengths_the_gpu_tests_run():
