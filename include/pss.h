@@ -899,6 +899,53 @@ int pss_adsb_frames(pss_ctx *ctx, const float *d_iq, long n_buf, long buf_index0
                     int max_frames);
 int pss_h_adsb_frames(const float *h_iq, long n_buf, long buf_index0, long n_capture, int spc, float ratio, const uint32_t *h_icao, int n_icao,
                       long s_begin, long s_end, uint8_t *h_msg, int64_t *h_pos, uint32_t *h_meta, float *h_score, int32_t *h_count, int max_frames);
+/* ---- AIS: the ship reports of a marine VHF capture — what the reference's command list starts `rtl_fm -M fm -s 48k | aisdecoder` for
+ * (rtlcoms.json, "Receive AIS").  The arithmetic is the project's own, stated once in csrc/pss_ais.h (PARITY.md "AIS"); the device and the
+ * host twins agree on every byte, and every output follows from indices in the ROW, so no chunking changes one.
+ * pss_ais_plan: the route from a capture at fs to 48 000 S/s: decim = min(fs / 48 000, 204) for pss_ddc, up / down = 48 000 decim / fs reduced
+ *   for pss_resample.  PSS_E_ARG (reason in pss_last_error(NULL), starting "pss_ais: "): an fs that is no integer, below 48 000, or whose
+ *   factors leave [1, 4096].
+ * pss_ais_default_pulse: the post-filter, a Gaussian of BT 0.4 at 5 samples a bit over span_bits bits (in [1, 12]; the receiver's default is
+ *   2), 5 span_bits + 1 taps of sum 1 (an odd span_bits gives an even table, centred between two samples, which pss_ais_front does not
+ *   take).  *n_pulse is set, pulse (NULL: only the count) is filled.
+ * pss_ais_crc: the CRC-16/X.25 of n bytes (reflected 0x8408, init 0xFFFF, final complement: 0x906E for "123456789"; a frame with its two
+ *   check bytes gives 0x0F47, the complement of the register's residue 0xF0B8).  Pure host code.  A null pointer or n < 0: 0xFFFFFFFF.
+ * pss_ais_front: d_iq complex64 rows at 48 000 S/s, x_stride samples apart, 8-byte aligned, holding samples [buf_index0, buf_index0 + n_buf)
+ *   of rows of n_row samples -> d_y float32, sample i of row r at element r * y_stride + (i - i_begin), i in [i_begin, i_end): the float32
+ *   polar discriminator (no gain, d[0] = 0) and the post-filter (pulse: a HOST table of an odd number of taps, at most 65; one float64 fma
+ *   chain per output, zero outside the row).  The buffer must hold the samples from max(0, i_begin - (P - 1) / 2 - 1) to
+ *   min(n_row, i_end + (P - 1) / 2).  One kernel, k_ais_front.
+ *   PSS_E_ARG ("pss_ais_front: "; a refused call writes nothing): n_rows < 1, a buffer or a window outside the row, strides below n_buf or
+ *   the window, a window above 2^30 samples, a pulse that is not odd, in [1, 65] and finite, a buffer that does not cover the window's
+ *   halo, a null or misaligned pointer.
+ * pss_ais_frames: d_y float32 rows at 48 000 S/s (pss_ais_front's, or any FM discriminator's), y_stride samples apart, 4-byte aligned,
+ *   holding samples [buf_index0, buf_index0 + n_buf) of rows of n_row samples.  Every start s in [s_begin, s_end) of every row is a candidate:
+ *   strobes 5 samples apart, a threshold from the eight strobes before the flag, NRZI, the training sequence and the flag, then the HDLC
+ *   walk with bit unstuffing to the closing flag and the CRC-16.  Of accepted starts less than 5 apart in a row that read the same bytes,
+ *   the one whose nearest strobe lies farthest from the threshold stays (the earlier on a tie).  Records in ascending (row, s): d_msg uint8
+ *   [max_frames][128] (zero-padded; byte j holds bits 8 j .. 8 j + 7, the first received the least significant), d_len int32 (bytes, the
+ *   two check bytes included), d_row int32, d_pos int64 (the row index of the flag's first strobe), d_score float32 (that distance),
+ *   d_count int32 [1] (the TRUE count; nothing is written past max_frames).  The buffer must hold the samples from
+ *   max(0, s_begin - 4 - 45) to min(n_row, s_end + 3 + 6221).
+ *   PSS_E_ARG ("pss_ais_frames: "; a refused call writes nothing): n_rows outside [1, 2^20], a buffer or a window outside the row,
+ *   y_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows), a buffer that does not cover the window's reach,
+ *   max_frames < 0, a null or misaligned pointer.
+ *   Kernels: k_ais_detect (the one pass over every start), then k_ais_scan, k_ais_gather, k_ais_walk, k_ais_keep, k_ais_scan, k_ais_emit
+ *   over the survivors of the flag test only.  Scratch on the context, 2 bytes per start of the largest call and 149 bytes per survivor,
+ *   grow-only and freed by pss_destroy; the call waits once for the count of survivors.
+ * pss_h_ais_front / pss_h_ais_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL),
+ *   pss_h_ais_front's starting with its own name, pss_h_ais_frames' with "pss_ais_frames: "). */
+int pss_ais_plan(double fs, int *decim, int *up, int *down);
+int pss_ais_default_pulse(int span_bits, double *pulse, int *n_pulse);
+uint32_t pss_ais_crc(const uint8_t *bytes, long n);
+int pss_ais_front(pss_ctx *ctx, const float *d_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, const double *pulse,
+                  int n_pulse, long i_begin, long i_end, float *d_y, long y_stride);
+int pss_h_ais_front(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, const double *pulse, int n_pulse,
+                    long i_begin, long i_end, float *h_y, long y_stride);
+int pss_ais_frames(pss_ctx *ctx, const float *d_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                   uint8_t *d_msg, int32_t *d_len, int32_t *d_row, int64_t *d_pos, float *d_score, int32_t *d_count, int max_frames);
+int pss_h_ais_frames(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                     uint8_t *h_msg, int32_t *h_len, int32_t *h_row, int64_t *h_pos, float *h_score, int32_t *h_count, int max_frames);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -185,10 +185,12 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->stage) hipFree(ctx->stage);
     for (auto &b : ctx->sq_buf) if (b) hipFree(b);
     if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
-    for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win, &ctx->rds_tab, &ctx->rds_pulse}) t->release();
+    for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win, &ctx->rds_tab, &ctx->rds_pulse, &ctx->ais_pulse}) t->release();
     if (ctx->welch_part) hipFree(ctx->welch_part);
     for (auto &b : ctx->adsb_buf) if (b) hipFree(b);
     if (ctx->adsb_pin) hipHostFree(ctx->adsb_pin);
+    for (auto &b : ctx->ais_buf) if (b) hipFree(b);
+    if (ctx->ais_pin) hipHostFree(ctx->ais_pin);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

@@ -162,6 +162,12 @@ struct pss_ctx {
     void *adsb_buf[2] = {};
     size_t adsb_cap[2] = {};
     void *adsb_pin = nullptr;
+    PssDevTable ais_pulse;   // pss_ais.hip, pss_ais_front: the pulse table
+    // pss_ais.hip, grow-only: [0] the tiles' counts, offsets and lists, [1] the survivors with their payloads, scores, keep flags and ranks;
+    // ais_pin: 8 pinned bytes the count of survivors lands in
+    void *ais_buf[2] = {};
+    size_t ais_cap[2] = {};
+    void *ais_pin = nullptr;
     void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;

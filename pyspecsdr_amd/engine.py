@@ -1520,6 +1520,103 @@ class Engine:
         k = min(int(count[0]), room)
         return msg[:k], pos[:k], meta[:k], score[:k], int(count[0])
 
+    # -- AIS: rows of IQ at 48 kS/s -> the frames that pass their check (pss_ais_*; the arithmetic: csrc/pss_ais.h)
+    @staticmethod
+    def ais_plan(fs, lib=None):
+        """pss_ais_plan -> (decim, up, down): the down-converter's decimation min(fs // 48 000, 204) and the resampler's factors to
+        48 000 S/s.  Host code."""
+        lib = lib or L.load()
+        d, u, w = C.c_int(), C.c_int(), C.c_int()
+        if lib.pss_ais_plan(float(fs), C.byref(d), C.byref(u), C.byref(w)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return d.value, u.value, w.value
+
+    @staticmethod
+    def ais_default_pulse(span_bits=2, lib=None):
+        """pss_ais_default_pulse: a Gaussian of BT 0.4 at 5 samples a bit, 5 span_bits + 1 float64 taps of sum 1.  Host code."""
+        return Engine._default_taps(lib, "pss_ais_default_pulse", "ais_default_pulse: span_bits outside [1, 12]", span_bits)
+
+    @staticmethod
+    def ais_crc(data, lib=None):
+        """pss_ais_crc: the CRC-16/X.25 of bytes (or a uint8 array): 0x906E for b"123456789".  Host code."""
+        lib = lib or L.load()
+        m = np.ascontiguousarray(np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else data, np.uint8)
+        if m.ndim != 1:
+            raise ValueError("ais_crc: a 1-D array of bytes")
+        return int(lib.pss_ais_crc(_ptr(m) if len(m) else _ptr(np.zeros(1, np.uint8)), len(m)))
+
+    @staticmethod
+    def _ais_pulse(pulse, lib):
+        return Engine.ais_default_pulse(2, lib) if pulse is None else np.ascontiguousarray(np.atleast_1d(pulse), np.float64)
+
+    def ais_front(self, d_iq, n_rows, n_buf, d_y, pulse=None, x_stride=None, buf_index0=0, n_row=None, i_begin=0, i_end=None, y_stride=None):
+        """d_iq complex64 at 48 kS/s: n_rows rows x_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of
+        n_row samples (default: the buffer is the row) -> d_y float32: discriminator and post-filter, sample i of row r at element
+        r * y_stride + (i - i_begin), i in [i_begin, i_end) (default: to the row's end; y_stride: default the window).  pulse: host float64
+        table (default ais_default_pulse())."""
+        pulse = self._ais_pulse(pulse, self.lib)
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        self._dev(self.lib.pss_ais_front, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_row,
+                  _ptr(pulse), len(pulse), int(i_begin), i_end, _ptr(d_y), int(i_end - int(i_begin) if y_stride is None else y_stride))
+
+    @staticmethod
+    def h_ais_front(iq, pulse=None, buf_index0=0, n_row=None, i_begin=0, i_end=None, lib=None):
+        """pss_h_ais_front on a host array [n_rows][n_buf] or [n_buf] -> float32 [n_rows][i_end - i_begin] or [i_end - i_begin].  Pure host
+        code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        x = np.asarray(iq, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("iq: a 1-D or 2-D complex array")
+        rows = Engine._as_rows(x)
+        pulse = Engine._ais_pulse(pulse, lib)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        width = i_end - int(i_begin)
+        out = np.empty((rows.shape[0], max(width, 0)), np.float32)
+        if lib.pss_h_ais_front(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, _ptr(pulse), len(pulse), int(i_begin),
+                               i_end, _ptr(out), width) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out if x.ndim == 2 else out[0]
+
+    def ais_frames(self, d_y, n_rows, n_buf, d_msg, d_len, d_row, d_pos, d_score, d_count, max_frames, y_stride=None, buf_index0=0, n_row=None,
+                   s_begin=0, s_end=None):
+        """d_y float32 at 48 kS/s: n_rows rows y_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_row
+        samples (default: the buffer is the row) -> the frames that start in [s_begin, s_end) (default: to the row's end) of every row, ascending
+        in (row, s): d_msg uint8 [max_frames][128], d_len int32 (bytes with the two check bytes), d_row int32, d_pos int64, d_score float32,
+        d_count int32 [1] (the true count)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_ais_frames, _ptr(d_y), int(n_rows), int(n_buf if y_stride is None else y_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, _ptr(d_msg), _ptr(d_len), _ptr(d_row), _ptr(d_pos), _ptr(d_score), _ptr(d_count), int(max_frames))
+
+    @staticmethod
+    def h_ais_frames(y, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_frames=None, lib=None):
+        """pss_h_ais_frames on a host float32 array [n_rows][n_buf] or [n_buf] -> (msg uint8 [k][128], len int32 [k], row int32 [k], pos int64
+        [k], score float32 [k], count): the first k = min(count, max_frames) records and the true count.  max_frames: default room for every
+        frame.  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(y, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("y: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_frames is None
+        max_frames = 64 if grow else int(max_frames)
+        while True:
+            room = max(max_frames, 0)
+            msg, ln, rw = np.zeros((room, 128), np.uint8), np.zeros(room, np.int32), np.zeros(room, np.int32)
+            pos, score, count = np.zeros(room, np.int64), np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_ais_frames(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end, _ptr(msg),
+                                    _ptr(ln), _ptr(rw), _ptr(pos), _ptr(score), _ptr(count), max_frames) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_frames = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return msg[:k], ln[:k], rw[:k], pos[:k], score[:k], int(count[0])
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

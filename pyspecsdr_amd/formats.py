@@ -1259,6 +1259,222 @@ def adsb_recording(samples, fs, ratio=2.0, addresses=(), learn=True, chunk_sampl
     return dict(frames=frames, tracks=adsb_tracks(frames, fs), fs=fs)
 
 
+# -- AIS: what the frames of pss_ais_frames say (host code), and a capture end to end
+_AIS_RATE = 48000
+
+
+def _ais_bytes(msg):
+    return bytes(msg) if isinstance(msg, (bytes, bytearray)) else np.asarray(msg, np.uint8).tobytes()
+
+
+def ais_decode(msg):
+    """One AIS message (the frame's bytes as pss_ais_frames writes them, with or without the two check bytes; message bit p of ITU-R M.1371,
+    0 = the most significant bit of the message id, is bit 7 - p % 8 of byte p // 8) -> a dict.  Always 'type', 'repeat', 'mmsi'.  With them
+      1 / 2 / 3  'status', 'turn' (degrees a minute; None at "not available"), 'speed' (knots), 'accuracy', 'lon', 'lat' (degrees; None at
+                 181 / 91), 'course', 'heading' (degrees), 'second'
+      4          'year' ... 'second', 'accuracy', 'lon', 'lat'
+      5          'imo', 'callsign', 'name', 'ship_type', 'to_bow', 'to_stern', 'to_port', 'to_starboard', 'eta' (month, day, hour, minute),
+                 'draught' (metres), 'destination' (6-bit text: cut at the first '@', trailing spaces stripped)
+      18 / 19    class B: 'speed', 'accuracy', 'lon', 'lat', 'course', 'heading', 'second'; 19 adds 'name', 'ship_type' and the dimensions
+      21         aid to navigation: 'aid_type', 'name', 'accuracy', 'lon', 'lat', the dimensions, 'second', 'off_position'
+      24         'part' 0: 'name'; 1: 'ship_type', 'vendor', 'callsign', the dimensions
+    Any other type, or a message too short for its type: only the three common keys.  Pure Python."""
+    m = _ais_bytes(msg)
+    if len(m) < 5:
+        raise ValueError("ais_decode: a message holds at least 38 bits")
+    word, n_bits = int.from_bytes(m, 'big'), 8 * len(m)
+
+    def u(p, w):
+        if p + w > n_bits:
+            raise IndexError
+        return (word >> (n_bits - p - w)) & ((1 << w) - 1)
+
+    def s(p, w):
+        v = u(p, w)
+        return v - (1 << w) if v >> (w - 1) else v
+
+    def text(p, n_chars):
+        chars = [u(p + 6 * k, 6) for k in range(n_chars)]
+        t = ''.join(chr(c + 64) if c < 32 else chr(c) for c in chars)
+        return t.split('@')[0].rstrip(' ')
+
+    def na(v, code, scale=1.0):
+        return None if v == code else v / scale
+
+    def lonlat(p):
+        lon, lat = s(p, 28), s(p + 28, 27)
+        return (None if lon == 181 * 600000 else lon / 600000.0), (None if lat == 91 * 600000 else lat / 600000.0)
+
+    def dims(p):
+        return dict(to_bow=u(p, 9), to_stern=u(p + 9, 9), to_port=u(p + 18, 6), to_starboard=u(p + 24, 6))
+
+    out = {'type': u(0, 6), 'repeat': u(6, 2), 'mmsi': u(8, 30)}
+    t, d = out['type'], {}
+    try:
+        if t in (1, 2, 3):
+            rot = s(42, 8)
+            d = dict(status=u(38, 4), turn=None if rot == -128 else float(np.sign(rot)) * (rot / 4.733) ** 2, speed=na(u(50, 10), 1023, 10.0),
+                     accuracy=u(60, 1), course=na(u(116, 12), 3600, 10.0), heading=na(u(128, 9), 511), second=u(137, 6))
+            d['lon'], d['lat'] = lonlat(61)
+            if d['heading'] is not None:
+                d['heading'] = int(d['heading'])
+        elif t == 4:
+            d = dict(year=u(38, 14), month=u(52, 4), day=u(56, 5), hour=u(61, 5), minute=u(66, 6), second=u(72, 6), accuracy=u(78, 1))
+            d['lon'], d['lat'] = lonlat(79)
+        elif t == 5:
+            d = dict(imo=u(40, 30), callsign=text(70, 7), name=text(112, 20), ship_type=u(232, 8), **dims(240),
+                     eta=(u(274, 4), u(278, 5), u(283, 5), u(288, 6)), draught=u(294, 8) / 10.0, destination=text(302, 20))
+        elif t in (18, 19):
+            d = dict(speed=na(u(46, 10), 1023, 10.0), accuracy=u(56, 1), course=na(u(112, 12), 3600, 10.0), heading=na(u(124, 9), 511), second=u(133, 6))
+            d['lon'], d['lat'] = lonlat(57)
+            if d['heading'] is not None:
+                d['heading'] = int(d['heading'])
+            if t == 19:
+                d.update(name=text(143, 20), ship_type=u(263, 8), **dims(271))
+        elif t == 21:
+            d = dict(aid_type=u(38, 5), name=text(43, 20), accuracy=u(163, 1), **dims(219), second=u(253, 6), off_position=u(259, 1))
+            d['lon'], d['lat'] = lonlat(164)
+        elif t == 24:
+            d = dict(part=u(38, 2))
+            if d['part'] == 0:
+                d['name'] = text(40, 20)
+            elif d['part'] == 1:
+                d.update(ship_type=u(40, 8), vendor=text(48, 7), callsign=text(90, 7), **dims(132))
+    except IndexError:
+        d = {}
+    out.update(d)
+    return out
+
+
+def ais_nmea(msg, channel='A', seq=0):
+    """The !AIVDM sentences of one message (its bytes WITHOUT the two check bytes) -> a list of str: the payload in 6-bit armour, at most 56
+    characters (336 bits) a sentence, the fill bits on the last one, the XOR checksum behind '*'.  seq: the sequence digit of a message of
+    several sentences (a single sentence leaves the field empty)."""
+    m = _ais_bytes(msg)
+    n_bits = 8 * len(m)
+    fill = (6 - n_bits % 6) % 6
+    word = int.from_bytes(m, 'big') << fill
+    n_chars = (n_bits + fill) // 6
+    chars = []
+    for k in range(n_chars):
+        v = (word >> (6 * (n_chars - 1 - k))) & 63
+        chars.append(chr(v + 48 if v < 40 else v + 56))
+    parts = [''.join(chars[i:i + 56]) for i in range(0, max(n_chars, 1), 56)]
+    out = []
+    for i, part in enumerate(parts):
+        body = "AIVDM,%d,%d,%s,%s,%s,%d" % (len(parts), i + 1, "" if len(parts) == 1 else str(int(seq) % 10), channel, part,
+                                            fill if i == len(parts) - 1 else 0)
+        cs = 0
+        for ch in body:
+            cs ^= ord(ch)
+        out.append("!%s*%02X" % (body, cs))
+    return out
+
+
+def ais_payload(sentences):
+    """ais_nmea backwards: the sentences of ONE message in order -> its bytes (the fill bits dropped).  ValueError on a wrong checksum."""
+    bits, fill = [], 0
+    for sen in sentences:
+        body, _, cs = sen[1:].partition('*')
+        x = 0
+        for ch in body:
+            x ^= ord(ch)
+        if sen[0] != '!' or int(cs, 16) != x:
+            raise ValueError("ais_payload: a wrong checksum")
+        f = body.split(',')
+        for ch in f[5]:
+            v = ord(ch) - 48
+            v = v - 8 if v > 40 else v
+            bits.extend((v >> (5 - k)) & 1 for k in range(6))
+        fill = int(f[6])
+    bits = bits[:len(bits) - fill] if fill else bits
+    return np.packbits(np.array(bits[:len(bits) // 8 * 8], np.uint8)).tobytes()
+
+
+def ais_tracks(records, fs=_AIS_RATE):
+    """records: the frames in order, each a mapping with 'msg' and 'pos' (ais_recording's 'frames') -> one dict per MMSI in order of first
+    appearance: 'mmsi', 'name', 'callsign', 'ship_type', 'position' ((latitude, longitude)), 'speed', 'course' (the last of each, or None),
+    'frames', 'first' and 'last' (pos / fs, seconds)."""
+    fs = float(fs)
+    tracks = {}
+    for rec in records:
+        d = ais_decode(rec['msg'])
+        t = int(rec['pos']) / fs
+        tr = tracks.setdefault(d['mmsi'], {'mmsi': d['mmsi'], 'name': None, 'callsign': None, 'ship_type': None, 'position': None, 'speed': None,
+                                           'course': None, 'frames': 0, 'first': t, 'last': t})
+        tr['frames'] += 1
+        tr['first'], tr['last'] = min(tr['first'], t), max(tr['last'], t)
+        for key in ('name', 'callsign', 'ship_type', 'speed', 'course'):
+            if d.get(key) not in (None, ''):
+                tr[key] = d[key]
+        if d.get('lat') is not None and d.get('lon') is not None:
+            tr['position'] = (d['lat'], d['lon'])
+    return list(tracks.values())
+
+
+def _ais_rows(e, d_y, n_rows, n):
+    """pss_ais_frames on resident rows -> the records on the host: (msg [k][128], len, row, pos, score)."""
+    import torch
+    dev = d_y.device
+    room = 4096
+    while True:
+        d_msg = torch.empty((room, 128), dtype=torch.uint8, device=dev)
+        d_len = torch.empty(room, dtype=torch.int32, device=dev)
+        d_row = torch.empty(room, dtype=torch.int32, device=dev)
+        d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+        d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        e.ais_frames(d_y, n_rows, n, d_msg, d_len, d_row, d_pos, d_score, d_count, room)
+        k = int(d_count.cpu()[0])
+        if k <= room:
+            break
+        room = k   # the true count: again with room for it
+    return tuple(t[:k].cpu().numpy() for t in (d_msg, d_len, d_row, d_pos, d_score))
+
+
+def ais_recording(samples, fs, center_hz=162.0e6, channels_hz=(161.975e6, 162.025e6), taps=None, pulse=None, chunk_samples=1 << 22,
+                  codes_format=None, table=None):
+    """The ships of a marine VHF capture centred on center_hz -> dict(frames=..., tracks=..., nmea=..., fs=48000): 'frames' a list of dicts in
+    order of 'pos' (ais_decode's keys and 'msg' (bytes without the check bytes), 'channel' ('A', 'B', ... by position in channels_hz), 'pos',
+    'score'), 'tracks' ais_tracks(frames), 'nmea' the !AIVDM sentences of every frame in that order, 'fs' the rate the positions count in.
+    On the GPU from the upload to the records: pss_ddc puts the listed channels at 0 Hz at ais_plan(fs)'s decimation (streamed in chunks of
+    chunk_samples samples plus their halos; the result does not depend on chunk_samples), pss_resample brings them to 48 000 S/s where
+    the decimated rate is another one, then pss_ais_front and pss_ais_frames on the resident rows.  taps: the down-converter's float64
+    low-pass (default firwin(20 decim + 1, 25 000 / fs): half-width 12.5 kHz, one channel of the 25 kHz grid); pulse: the post-filter
+    (default ais_default_pulse()); codes_format / table: as demodulate_recording."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    decim, up, down = e.ais_plan(fs)
+    offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+    if offsets.ndim != 1 or not len(offsets) or len(offsets) > 26:
+        raise ValueError("channels_hz: a list of 1 to 26 frequencies")
+    if taps is None:
+        taps = np.empty(20 * decim + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 25000.0 / fs, taps.ctypes.data) != 0:
+            raise ValueError("ais_recording: the down-converter's filter design failed")
+    d_rows, _ = _tune_device(samples, fs, offsets, decim, taps, None, chunk_samples, codes_format, table)
+    k, m = d_rows.shape[0], d_rows.shape[1] // 2
+    if (up, down) != (1, 1):
+        n = e.resample_out_len(m, up, down)
+        d_bb = torch.empty((k, 2 * max(n, 1)), dtype=torch.float32, device=d_rows.device)
+        if m:
+            e.resample(d_rows, np.complex64, k, m, up, down, d_bb)
+        d_rows, m = d_bb[:, :2 * n].contiguous() if n else d_bb[:, :0], n
+    frames = []
+    if m:
+        d_y = torch.empty((k, m), dtype=torch.float32, device=d_rows.device)
+        e.ais_front(d_rows, k, m, d_y, pulse=pulse)
+        for msg, ln, row, pos, score in zip(*_ais_rows(e, d_y, k, m)):
+            body = bytes(msg[:int(ln) - 2])
+            d = ais_decode(body)
+            d.update(msg=body, channel=chr(ord('A') + int(row)), pos=int(pos), score=float(score))
+            frames.append(d)
+    frames.sort(key=lambda f: (f['pos'], f['channel']))
+    nmea = [sen for f in frames for sen in ais_nmea(f['msg'], f['channel'])]
+    return dict(frames=frames, tracks=ais_tracks(frames), nmea=nmea, fs=_AIS_RATE)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
