@@ -91,6 +91,7 @@ struct pss_ctx {
     hipEvent_t ev_in = nullptr, ev_out = nullptr;   // pss_order_after / pss_order_before (created on first use)
     int n_cus = 0;                                  // hipDeviceProp_t::multiProcessorCount
     int fuse_post = 1;              // option "fuse_post" (float64-row pipelines, 1024-point frames): 1 = transform + post-process in ONE kernel (pss_spec_post.h), 0 = two kernels (A/B reference)
+    int post_split = -1;            // option "post_split" (k_spectrum_post's one-round grid, pss_post_split.h): how many groups more the early workgroups take than the late ones; -1 = decided at the launch (equal shares unless an NFM backward pass runs beside the chain: pss_spec_post_chain), >= 0 = forced (sweeps, tests)
     double target_rate = 22050.0;   // demodulate_nfm / _wfm's target_rate (pss_set_target_rate): decimation factor int(fs / target_rate)
     bool wfm_corr_copy = false;     // option "wfm_corr_copy": always materialise the corrected copy of the batch (the round-4 path; A/B reference)
     std::string err;
@@ -316,7 +317,7 @@ int pss_fft_tables(pss_ctx *ctx, int n, const double2 **tw, const double **win);
 bool pss_post_sel_serves(int n_fft, bool f64);
 bool pss_spec_post_serves(const pss_ctx *ctx, int n_fft);
 int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, float *d_db32, double *d_db64, double *d_lo, double *d_hi, int n_halo,
-                        int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals);
+                        int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals, const PssBwdLaunch *beside_bwd = nullptr);
 int pss_chain_vals_f32(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, float *d_lo, float *d_hi, int n_halo, int window, int display,
                        int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals);
 int pss_chain_vals_f64(pss_ctx *ctx, const double *d_db, long n_frames, int n_fft, double *d_lo, double *d_hi, int n_halo, int window, int display,

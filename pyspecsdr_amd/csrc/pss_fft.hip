@@ -1897,8 +1897,20 @@ int pss_chain_vals_f64(pss_ctx *ctx, const double *d_db, long n_frames, int n_ff
 // The fused transform + post-process (pss_spec_post.h) and the lines from its resampled rows: compute_fft -> cells for 1024-point frames without
 // the float64 rows going through HBM.  d_db32 / d_db64: the dB row as float32 and / or float64 (either may be NULL, not both).
 bool pss_spec_post_serves(const pss_ctx *ctx, int n_fft) { return n_fft == 1024 && !ctx->f64_plain; }
+#ifdef PSS_EXP_POST_STAMPS
+static unsigned long long *g_post_stamps = nullptr;   // timing-only build: two stamps per workgroup of the most recent launch
+static long g_post_stamps_wg = 0;
+extern "C" long pss_exp_post_stamps(unsigned long long *h_out, long max_wg)
+{
+    if (!g_post_stamps || hipDeviceSynchronize() != hipSuccess) return -1;
+    const long n = g_post_stamps_wg < max_wg ? g_post_stamps_wg : max_wg;
+    return hipMemcpy(h_out, g_post_stamps, (size_t)n * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost) == hipSuccess ? n : -1;
+}
+#endif
+// beside_bwd: the backward launch of the caller's demodulator that runs beside this chain (NULL: none) — it decides the skew of the grid's two shares.
 int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_fft, float *d_db32, double *d_db64, double *d_lo, double *d_hi,
-                        int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals)
+                        int n_halo, int window, int display, int disp_h, int disp_w, int8_t *d_a, int8_t *d_b, double *d_vals,
+                        const PssBwdLaunch *beside_bwd)
 {
     if (!pss_spec_post_serves(ctx, n_fft) || (!d_db32 && !d_db64)) return pss_fail(ctx, PSS_E_ARG, "fused transform + post-process: 1024-point frames, a row buffer");
     if (n_frames == 0) return PSS_OK;
@@ -1909,13 +1921,48 @@ int pss_spec_post_chain(pss_ctx *ctx, const float *d_iq, long n_frames, int n_ff
     using C = pss_r16::Cfg<2>;
     auto kern = d_db32 ? (d_db64 ? pss_sp::k_spectrum_post<true, true> : pss_sp::k_spectrum_post<true, false>) : pss_sp::k_spectrum_post<false, true>;
     const size_t lds = (size_t)C::FPW * C::EX * sizeof(double2) + (size_t)C::TW2 * sizeof(double2);
-    const long cap = 256L * 2 * 2;       // two 256-thread workgroups per CU (LDS, registers), two rounds
+    const long ncu = ctx->n_cus > 0 ? ctx->n_cus : 256;
+    const long cap = ncu * 2;            // two 256-thread workgroups per CU (LDS, registers), ONE round: a workgroup walks a contiguous range of groups
     if (lds > 64 * 1024) PSS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const long groups = (n_frames + C::FPW - 1) / C::FPW;
+    const long n_wg = groups < cap ? groups : cap;
+    // The two shares (pss_post_split.h).  While a backward pass is resident (one 186-VGPR wavefront of k_nfm_bwd per tile and SIMD) a SIMD has room
+    // for ONE 256-VGPR wavefront of this kernel: workgroups 0 .. ncu - 1 start at once, one per CU, the others about 0.15 ms later as the backward
+    // wavefronts retire (tools/post_stamps.py) — so the early ones take d groups more.  No backward pass beside the chain (pss_spectrum_cells, the
+    // AM / SSB pipelines): equal shares.  Option "post_split" >= 0 forces d.
+    // PSS_POST_SPLIT_D_*: the skew beside a backward pass that fills every SIMD, from the sweeps in profiles/post_split.txt (NOTEBOOK R8-01).
+    // NFM: the bottom of the curve at 65 536 frames (12 .. 20), where the stamps show early and late workgroups ending together.  A longer
+    // backward pass (98 304, 131 072 frames) wants the SAME d, not a multiple: its later wavefronts find the SIMDs taken by this kernel's late
+    // workgroups, so only its first round keeps them out.  A backward pass of fewer wavefronts than SIMDs still holds every CU, for less long
+    // (0.11 ms at a quarter of the SIMDs, 0.16 at all): d follows that time, 0.6 + 0.4 x the filled fraction of D (16 384 .. 49 152 frames).
+    // WFM: 0 — behind k_wfm_fwd no workgroup of this kernel starts early (all 512 within 60 us), and any skew only delays the end.
+    constexpr long PSS_POST_SPLIT_D_NFM = 16, PSS_POST_SPLIT_D_WFM = 0;
+    long d = 0;
+    if (ctx->post_split >= 0) {
+        d = ctx->post_split;
+    } else if (beside_bwd && beside_bwd->flt) {
+        const long simds = ncu * 4;
+        const long bwd_waves = ((beside_bwd->n_frames + 63) / 64) * (beside_bwd->stereo ? 2 : 1);     // k_nfm_bwd: tiles of 64 frames
+        d = (beside_bwd->stereo ? PSS_POST_SPLIT_D_WFM : PSS_POST_SPLIT_D_NFM) * (3 * simds + 2 * (bwd_waves < simds ? bwd_waves : simds)) / (5 * simds);
+    }
+    const PssPostSplit split = pss_post_split_shares(groups, n_wg, ncu, d);
+#ifdef PSS_EXP_POST_STAMPS
+    if (g_post_stamps_wg < n_wg) {
+        if (g_post_stamps) PSS_HIP(ctx, hipFree(g_post_stamps));
+        g_post_stamps = nullptr, g_post_stamps_wg = 0;
+        PSS_HIP(ctx, hipMalloc(&g_post_stamps, (size_t)cap * 2 * sizeof(unsigned long long)));
+        g_post_stamps_wg = cap;
+    }
+#endif
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_spectrum_post");
-    hipLaunchKernelGGL(kern, dim3((unsigned)(groups < cap ? groups : cap)), dim3(256), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db32,
-                       d_db64, tw, win, n_frames, d_lo + n_halo, d_hi + n_halo, d_vals, disp_w);
+#ifdef PSS_EXP_POST_STAMPS
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(256), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db32,
+                       d_db64, tw, win, n_frames, d_lo + n_halo, d_hi + n_halo, d_vals, disp_w, split.n_early, split.share_early, split.share_late, g_post_stamps);
+#else
+    hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(256), lds, PSS_STREAM(ctx), reinterpret_cast<const float2 *>(d_iq), d_db32,
+                       d_db64, tw, win, n_frames, d_lo + n_halo, d_hi + n_halo, d_vals, disp_w, split.n_early, split.share_early, split.share_late);
+#endif
     pss_kernel_end(ctx);
     r = pss_hip_check(ctx, hipGetLastError(), "k_spectrum_post launch");
     if (!r) r = display == 2 ? display_rows<double, 2>(ctx, (const double *)nullptr, n_frames, n_fft - 4, d_lo, d_hi, n_halo, window, 1, disp_w, d_a, d_b, (const double *)nullptr, d_vals)

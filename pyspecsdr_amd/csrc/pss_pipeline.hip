@@ -105,11 +105,12 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
         d_db = reinterpret_cast<TR *>(ctx->scratch_db64);
     }
     // compute_fft of every frame and the display chain behind it, on whichever stream it is queued
+    const PssBwdLaunch *beside_bwd = nullptr;      // the deferred backward launch the chain runs beside (NFM / WFM below): the fused kernel's grid allows for it
     auto spectrum_and_chain = [&]() -> int {
         if constexpr (F64) {
             if (fused)
                 return pss_spec_post_chain(ctx, d_iq, n_frames, n, d_db32, d_db, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_glyph,
-                                           d_colour, d_vals);
+                                           d_colour, d_vals, beside_bwd);
         }
         int q = pss_rows::spectrum_db(ctx, d_iq, n_frames, n, d_db);     // compute_fft sees the samples as read (pyspecsdr.py:2275), not the corrected ones
         if (q) return q;
@@ -157,6 +158,7 @@ static int frame_pipeline_impl(pss_ctx *ctx, int mode, const float *d_iq, long n
     int r = pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, nullptr, &call);
     if (call.bwd.flt) {
         // the side stream ALWAYS waits for the main stream here: the chain reads d_iq and writes d_db / the scratch, all ordered on ctx->stream
+        beside_bwd = &call.bwd;
         if (!r) r = pss_side_fork(ctx);
         if (!r) r = pss_on_side(ctx, spectrum_and_chain);
         const int rb = call.bwd.launch(ctx);       // main stream; launched whatever happened above (the PCM must be produced)

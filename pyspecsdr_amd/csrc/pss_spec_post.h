@@ -13,17 +13,30 @@
 // Included by pss_fft.hip behind pss_fft_r16.h and pss_post.h.
 #pragma once
 
+#include "pss_post_split.h"
+
 namespace pss_sp {
 
 using namespace pss_r16;
 
+// The grid is ONE round of persistent workgroups (two per CU); workgroup b walks the contiguous range of frame groups that
+// pss_post_split_range gives it for (n_early, share_early, share_late), decided by the host (pss_spec_post_chain).
+// -DPSS_EXP_POST_STAMPS (timing only): lane 0 of every workgroup leaves the constant-rate clock (s_memrealtime, 100 MHz) of its first and of its
+// last instruction in stamps[2 b], stamps[2 b + 1] (tools/post_stamps.py reads them).
 // 2: minimum workgroups per CU the register allocation has to allow: two wavefronts per SIMD = at most 256 VGPRs
 template <bool ROW32, bool ROW64>
 __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restrict__ iq, float *__restrict__ db32, double *__restrict__ db64,
                                                        const double2 *__restrict__ tw, const double *__restrict__ win, long n_frames,
                                                        double *__restrict__ row_lo, double *__restrict__ row_hi, double *__restrict__ vals,
-                                                       int disp_w)
+                                                       int disp_w, long n_early, long share_early, long share_late
+#ifdef PSS_EXP_POST_STAMPS
+                                                       , unsigned long long *__restrict__ stamps
+#endif
+)
 {
+#ifdef PSS_EXP_POST_STAMPS
+    if (threadIdx.x == 0) stamps[2 * (size_t)blockIdx.x] = wall_clock64();
+#endif
     using C = Cfg<2>;
     constexpr int R3 = C::R3, T = C::T, N = C::N, FPW = C::FPW;     // 4, 64, 1024, 4
     static_assert(T == 64, "a frame is one wavefront");
@@ -58,15 +71,17 @@ __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restri
 #pragma unroll
         for (int n2 = 0; n2 < 16; n2++) nx[n2] = x[t + T * n2];
     };
-    if ((long)blockIdx.x < groups) fetch(blockIdx.x);
+    long g_first, g_end;
+    pss_post_split_range(groups, (long)gridDim.x, n_early, share_early, share_late, (long)blockIdx.x, &g_first, &g_end);
+    if (g_first < g_end) fetch(g_first);
     int phase = 0;
-    for (long g = blockIdx.x; g < groups; g += gridDim.x) {
+    for (long g = g_first; g < g_end; g++) {
         const long f = g * FPW + fl;
         const bool valid = f < n_frames;                      // wave-uniform
         double2 v[16];
 #pragma unroll
         for (int n2 = 0; n2 < 16; n2++) v[n2] = make_double2((double)nx[n2].x * w[n2], (double)nx[n2].y * w[n2]);
-        if (g + gridDim.x < groups) fetch(g + gridDim.x);
+        if (g + 1 < g_end) fetch(g + 1);
         // row stores through buffer resources over the workgroup's FPW rows (frames past the end fall outside and are dropped): unconditional
         // in the instruction stream, see k_spectrum_r16
         const long f_first = g * FPW;
@@ -119,6 +134,9 @@ __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restri
         }
         frame_sync<true>();                                    // the next frame's stage 1 overwrites the buffer
     }
+#ifdef PSS_EXP_POST_STAMPS
+    if (threadIdx.x == 0) stamps[2 * (size_t)blockIdx.x + 1] = wall_clock64();
+#endif
 }
 
 }  // namespace pss_sp

@@ -8,7 +8,9 @@ k_spectrum_post (pss_spec_post.h), A/B in one process.  Variants:
     two32    pss_frame_pipeline_cells,   fuse_post = 0   (two kernels + conversion pass)
 Outputs compared bit for bit with two64's; ms per step (wall, fenced; three interleaved rounds), the mean launch time of every kernel (HIP
 events, separate pass), and the display half alone (pss_spectrum_cells: no demodulator beside it).
-    python tools/ab_fuse.py [frames] [opt=val ...]      FUSE_VARIANTS=two64,fus32 to choose"""
+    python tools/ab_fuse.py [frames] [opt=val ...]      FUSE_VARIANTS=two64,fus32 to choose; FUSE_MODE=wfm: the WFM step
+FUSE_SWEEP="post_split=0,4,8": instead of the variants against each other, the FIRST variant at every value of that option (three interleaved
+rounds; ms per step and the kernels' mean launch times per value, then the median of the three per value)."""
 import os
 import sys
 import time
@@ -29,6 +31,7 @@ def main():
     nf = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 65536
     n, fs, W = 1024, 2.4e6, 112
     eng = Engine(0, order="none")
+    mode = {"nfm": L.MODE_NFM, "wfm": L.MODE_WFM}[os.environ.get("FUSE_MODE", "nfm")]
     for a in sys.argv[1:]:
         if "=" in a:
             k, v = a.split("=")
@@ -44,7 +47,7 @@ def main():
                        db32=torch.zeros((nf, n), dtype=torch.float32, device=dev) if r32 else None,
                        lo=torch.zeros(nf, dtype=torch.float64, device=dev), hi=torch.zeros(nf, dtype=torch.float64, device=dev),
                        g=torch.zeros((nf, W), dtype=torch.int8, device=dev), c=torch.zeros((nf, W), dtype=torch.int8, device=dev),
-                       pcm=torch.zeros((nf, 10, 2), dtype=torch.int16, device=dev))
+                       pcm=torch.zeros((nf, eng.demod_out_len(mode, n, fs), 2), dtype=torch.int16, device=dev))
     torch.cuda.synchronize()
 
     def call(v, demod=True):
@@ -54,7 +57,9 @@ def main():
         if not demod:
             eng.spectrum_cells(iq, nf, n, b["db32"], b["db64"], b["lo"], b["hi"], W, b["g"], b["c"], window=30)
         elif r32:
-            eng.frame_pipeline_cells(L.MODE_NFM, iq, nf, n, fs, b["db32"], b["db64"], b["lo"], b["hi"], W, b["g"], b["c"], b["pcm"], window=30)
+            eng.frame_pipeline_cells(mode, iq, nf, n, fs, b["db32"], b["db64"], b["lo"], b["hi"], W, b["g"], b["c"], b["pcm"], window=30)
+        elif mode != L.MODE_NFM:
+            eng.frame_pipeline_f64(mode, iq, nf, n, fs, b["db64"], None, b["lo"], b["hi"], W, b["g"], b["c"], b["pcm"], window=30)
         else:
             eng.frame_pipeline_nfm_f64(iq, nf, n, fs, b["db64"], None, b["lo"], b["hi"], W, b["g"], b["c"], b["pcm"])
 
@@ -75,6 +80,32 @@ def main():
         if got["db32"] is not None:
             res["db32"] = bool(np.array_equal(ref["db64"].astype(np.float32), got["db32"]))
         print(f"{v} vs {names[0]}: {res}", flush=True)
+    if os.environ.get("FUSE_SWEEP"):
+        key, _, vals = os.environ["FUSE_SWEEP"].partition("=")
+        vals = [int(x) for x in vals.split(",")]
+        v, seen = names[0], {x: [] for x in vals}
+        for rep in range(3):
+            for x in vals:
+                eng.set_option(key, x)
+                for _ in range(3):
+                    call(v)
+                eng.sync()
+                t = time.perf_counter()
+                for _ in range(20):
+                    call(v)
+                eng.sync()
+                ms = (time.perf_counter() - t) / 20 * 1e3
+                eng.enable_timing(True)
+                for _ in range(5):
+                    call(v)
+                eng.sync()
+                kt = {k: round(sum(y) / len(y), 4) for k, y in eng.kernel_times().items()}
+                eng.enable_timing(False)
+                seen[x].append((ms, kt.get("k_spectrum_post")))
+                print(f"{v} {key}={x:3d}: {ms:.4f} ms/step  {kt}", flush=True)
+        for x in vals:
+            print(f"{v} {key}={x:3d}: median step {sorted(m for m, _ in seen[x])[1]:.4f} ms, k_spectrum_post in the step {sorted(k for _, k in seen[x])[1]:.4f} ms", flush=True)
+        return
     for rep in range(3):
         for v in names:
             for _ in range(3):
