@@ -887,9 +887,9 @@ int pss_h_rds_groups(const uint8_t *h_bits, const int32_t *h_n_bits, long n_rows
  *   PSS_E_ARG (reason in pss_last_error, starting "pss_adsb_frames: "; a refused call writes nothing): spc outside [1, 8], a ratio that is
  *   negative or not finite, a buffer or a window outside the capture, s_end < s_begin, a window above 2^30 starts, a buffer that does not
  *   cover the window's reach, max_frames < 0, n_icao outside [0, 2^24], a null or misaligned pointer.
- *   Kernels: k_adsb_detect (the one pass over the capture), then k_adsb_scan, k_adsb_gather, k_adsb_keep, k_adsb_scan, k_adsb_emit over the
+ *   Kernels: k_adsb_detect (the one pass over the capture), then k_starts_scan, k_starts_gather, k_adsb_keep, k_starts_scan, k_adsb_emit over the
  *   accepted starts only.  Scratch on the context, 2 bytes per start of the largest window it has been given, grow-only and freed by
- *   pss_destroy (a 2^30-start window keeps 2 GB); the call waits once for the count of accepted starts.
+ *   pss_destroy (a 2^30-start window keeps 2 GB), shared with pss_ais_frames; the call waits once for the count of accepted starts.
  * pss_h_adsb_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL)); it also refuses an
  *   address list that is not ascending, unique and below 2^24. */
 int pss_adsb_plan(double fs, int *spc);
@@ -930,8 +930,8 @@ int pss_h_adsb_frames(const float *h_iq, long n_buf, long buf_index0, long n_cap
  *   PSS_E_ARG ("pss_ais_frames: "; a refused call writes nothing): n_rows outside [1, 2^20], a buffer or a window outside the row,
  *   y_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows), a buffer that does not cover the window's reach,
  *   max_frames < 0, a null or misaligned pointer.
- *   Kernels: k_ais_detect (the one pass over every start), then k_ais_scan, k_ais_gather, k_ais_walk, k_ais_keep, k_ais_scan, k_ais_emit
- *   over the survivors of the flag test only.  Scratch on the context, 2 bytes per start of the largest call and 149 bytes per survivor,
+ *   Kernels: k_ais_detect (the one pass over every start), then k_starts_scan, k_starts_gather, k_ais_walk, k_ais_keep, k_starts_scan,
+ *   k_ais_emit over the survivors of the flag test only.  Scratch on the context (the same buffers as pss_adsb_frames' above), 2 bytes per start of the largest call and 149 bytes per survivor,
  *   grow-only and freed by pss_destroy; the call waits once for the count of survivors.
  * pss_h_ais_front / pss_h_ais_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL),
  *   pss_h_ais_front's starting with its own name, pss_h_ais_frames' with "pss_ais_frames: "). */

@@ -1,6 +1,6 @@
 // pss_adsb.h — the arithmetic of the Mode S / ADS-B receiver (what the reference's command list hands to dump1090, rtlcoms.json "Decode
 // Aircraft Transmissions"), stated ONCE for the kernels (pss_adsb.hip: k_adsb_detect, k_adsb_keep, k_adsb_emit), the host twin
-// (pss_h_adsb_frames) and the stand-alone host check (tests/adsb_host.cpp).  The reference has no such arithmetic, so this statement is the
+// (pss_h_adsb_frames; its walk over neighbouring starts is pss_starts.h's) and the stand-alone host check (tests/adsb_host.cpp).  The reference has no such arithmetic, so this statement is the
 // project's own (PARITY.md "ADS-B").  Every output follows from indices in the CAPTURE, never from how the capture was cut.
 //
 //   rate      spc = fs / 2 000 000 samples per 0.5 us chip, an integer in [1, 8].

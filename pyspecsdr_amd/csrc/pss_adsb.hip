@@ -6,9 +6,9 @@
 //                  ends there), ballots and the wavefront counts compact the survivors in ascending order, one wavefront per survivor reads
 //                  the 112 bits out of two ballots and checks them, and the accepted starts of the tile are compacted again into the tile's
 //                  own list.  The next tile's samples are fetched into registers while this one is worked on.
-//   k_adsb_scan    one workgroup: the exclusive prefix of the tiles' counts and their total; later the ranks of the kept starts and the
-//                  true count, from the keep flags.
-//   k_adsb_gather  the tiles' lists, back to back: the ascending list of accepted starts.  No atomics, no cap.
+//   pss_starts.h   k_starts_scan and k_starts_gather, shared with pss_ais.hip: the tiles' counts become offsets and a total, the tiles' lists
+//                  are laid back to back (the ascending list of accepted starts as int offsets from e0: no atomics, no cap), and behind
+//                  the keep pass the same scan ranks the kept starts and writes the true count.
 //   k_adsb_keep    one wavefront per accepted start inside the window: its message and score again from global memory, and those of the
 //                  accepted starts less than 2 spc away (they are its neighbours in the list): the one-record-per-frame rule.
 //   k_adsb_emit    one wavefront per kept start below max_frames: the record.
@@ -23,21 +23,16 @@
 
 #include "pss_adsb.h"
 #include "pss_ctx.h"
+#define PSS_STARTS_KERNELS   // this unit launches the list's kernels
+#include "pss_starts.h"
 
 namespace {
 
 using namespace pss_adsb;
 
-constexpr int DT_T = 1024;                       // threads of a workgroup: 16 wavefronts
-constexpr int DT_WAVES = DT_T / 64;
-constexpr int DT_S = 4096;                       // start positions of a tile
-constexpr long DT_GRID_CAP = 1024;               // workgroups of a launch: tiles past it are walked by a grid-stride loop
 constexpr int DT_B = DT_S + REACH_CHIPS * MAX_SPC;   // sliding sums of a tile: 6016
 constexpr int DT_M = DT_B + MAX_SPC;             // magnitudes under them: 6023, and one of padding
 constexpr int DT_LOADS = (DT_M + DT_T - 1) / DT_T;   // samples a thread brings in for a tile: 6
-constexpr int SC_T = 1024, SC_PER = 4;           // the scan: 4096 counts a step
-constexpr int LS_T = 256;                        // the list kernels
-constexpr long LS_GRID_CAP = 2048;
 
 // The message of two ballots (bit l of b0 = message bit l, bit l of b1 = message bit 64 + l): w0 holds message bits 0 .. 63 from its top
 // bit down, w1 bits 64 .. 111 likewise; a short frame keeps its first 56.  false: the frame does not fit the capture.
@@ -65,7 +60,6 @@ __global__ __launch_bounds__(DT_T) void k_adsb_detect(const float2 *__restrict__
     __shared__ uint8_t acc_s[DT_S];
     __shared__ int wcount[64];
     __shared__ uint32_t pw[LONG_BITS];           // x^k mod the generator
-    static_assert(DT_S / DT_T * DT_WAVES == 64, "one lane per (pass, wavefront) count");
     int *surv = reinterpret_cast<int *>(ms);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -124,27 +118,8 @@ __global__ __launch_bounds__(DT_T) void k_adsb_detect(const float2 *__restrict__
             if (tid == 0) tile_count[tile] = 0;
             continue;
         }
-        // ---- the survivors in ascending order: the 64 counts (pass k, wavefront w) at slot 16 k + w, scanned by every wavefront for itself
-        unsigned long long masks[DT_S / DT_T];
-#pragma unroll
-        for (int k = 0; k < DT_S / DT_T; k++) {
-            masks[k] = __ballot(oks[k]);
-            if (lane == 0) wcount[k * DT_WAVES + wave] = __popcll(masks[k]);
-        }
-        __syncthreads();
-        const int own = wcount[lane];
-        int inc = own;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        const int excl = inc - own;
-        const int total = __shfl(inc, 63);   // the same in every lane
-#pragma unroll
-        for (int k = 0; k < DT_S / DT_T; k++) {
-            const int before = __shfl(excl, k * DT_WAVES + wave);
-            if (oks[k]) surv[before + __popcll(masks[k] & below)] = k * DT_T + tid;
-        }
+        // ---- the survivors in ascending order
+        const int total = tile_slots(oks, wcount, lane, wave, [&](int k, int slot) { surv[slot] = k * DT_T + tid; });
         __syncthreads();
         // ---- one wavefront per survivor: lane l holds bits l and 64 + l
         for (int q = wave; q < total; q += DT_WAVES) {
@@ -181,61 +156,6 @@ __global__ __launch_bounds__(DT_T) void k_adsb_detect(const float2 *__restrict__
         }
         if (tid == 0) tile_count[tile] = n_acc;
         __syncthreads();   // the next tile's staging overwrites the survivors
-    }
-}
-
-// The exclusive prefix of n counts and their total, by one workgroup: SC_PER * SC_T counts a step with a carry, SC_PER consecutive counts a
-// lane, the lanes' sums scanned by shuffles and the wavefronts' through LDS.  The tiles' counts (int32) and the keep flags (bytes) both go
-// through it.
-template <class T>
-__global__ __launch_bounds__(SC_T) void k_adsb_scan(const T *__restrict__ in, int *__restrict__ out, long n, long *__restrict__ total64,
-                                                    int32_t *__restrict__ total32)
-{
-    __shared__ int wsum[SC_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long carry = 0;   // the same in every lane
-    for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {
-        const long k0 = b0 + (long)SC_PER * tid;
-        int v[SC_PER], mine = 0;
-#pragma unroll
-        for (int u = 0; u < SC_PER; u++) {
-            v[u] = k0 + u < n ? (int)in[k0 + u] : 0;
-            mine += v[u];
-        }
-        int inc = mine;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < SC_T / 64; w++) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        __syncthreads();
-        int run = (int)carry + before + inc - mine;
-#pragma unroll
-        for (int u = 0; u < SC_PER; u++) {
-            if (k0 + u < n) out[k0 + u] = run;
-            run += v[u];
-        }
-        carry += all;
-    }
-    if (tid == 0) {
-        if (total64) *total64 = carry;
-        if (total32) *total32 = (int32_t)carry;
-    }
-}
-
-// acc[k] = the k-th accepted start as an offset from e0
-__global__ __launch_bounds__(LS_T) void k_adsb_gather(const int *__restrict__ tile_count, const int *__restrict__ tile_off, const uint16_t *__restrict__ tile_list,
-                                                      long n_tiles, int *__restrict__ acc)
-{
-    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int c = tile_count[tile], o = tile_off[tile];
-        for (int q = threadIdx.x; q < c; q += LS_T) acc[o + q] = (int)(tile * DT_S) + (int)tile_list[(size_t)tile * DT_S + q];
     }
 }
 
@@ -320,11 +240,7 @@ int frames_check(pss_ctx *ctx, const char *who, bool host, const void *iq, long 
     auto off = [](const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (spc < 1 || spc > MAX_SPC) return bad("spc outside [1, 8]");
     if (!std::isfinite(ratio) || ratio < 0.0f) return bad("ratio must be finite and not negative");
-    if (n_capture < 0 || n_capture > (1l << 60)) return bad("n_capture outside [0, 2^60]");
-    if (n_buf < 0 || buf_index0 < 0 || buf_index0 > n_capture || n_buf > n_capture - buf_index0) return bad("the buffer does not lie inside the capture");
-    if (s_end < s_begin) return bad("s_end < s_begin");
-    if (s_begin < 0 || s_end > n_capture) return bad("the window does not lie inside the capture");
-    if (s_end - s_begin > (1l << 30)) return bad("a window of more than 2^30 starts");
+    if (const int r = window_refusals(bad, "capture", n_capture, n_buf, buf_index0, 's', s_begin, s_end, "starts")) return r;
     if (max_frames < 0) return bad("max_frames < 0");
     if (n_icao < 0 || n_icao > (int)MAX_ADDRESS) return bad("n_icao outside [0, 2^24]");
     if (!count || (n_buf > 0 && !iq) || (n_icao > 0 && !icao) || (max_frames > 0 && (!msg || !pos || !meta || !score))) return bad("null buffer");
@@ -376,26 +292,17 @@ extern "C" int pss_h_adsb_frames(const float *h_iq, long n_buf, long buf_index0,
         }
     }
     int total = 0;
-    for (size_t k = 0; k < acc.size(); k++) {
-        const Rec &a = acc[k];
-        if (a.s < s_begin || a.s >= s_end) continue;
-        bool kept = true;
-        // the list ascends: the starts less than 2 spc away are a's neighbours in it
-        size_t q = k;
-        while (q > 0 && a.s - acc[q - 1].s < 2 * (long)spc) q--;
-        for (; q < acc.size() && acc[q].s - a.s < 2 * (long)spc && kept; q++) {
-            const Rec &b = acc[q];
-            if (drops(b.n_bits == a.n_bits && memcmp(b.msg, a.msg, MSG_BYTES) == 0, b.s, b.hi, a.s, a.hi, spc)) kept = false;
-        }
-        if (!kept) continue;
-        if (total < max_frames) {
-            memcpy(h_msg + (size_t)total * MSG_BYTES, a.msg, MSG_BYTES);
-            h_pos[total] = a.s;
-            h_meta[total] = meta_of(a.n_bits, df_of(a.msg));
-            h_score[total] = a.hi;
-        }
-        total++;
-    }
+    keep_starts(acc.data(), acc.size(), s_begin, s_end, 2 * (long)spc,
+        [&](const Rec &b, const Rec &a) { return drops(b.n_bits == a.n_bits && memcmp(b.msg, a.msg, MSG_BYTES) == 0, b.s, b.hi, a.s, a.hi, spc); },
+        [&](const Rec &a) {
+            if (total < max_frames) {
+                memcpy(h_msg + (size_t)total * MSG_BYTES, a.msg, MSG_BYTES);
+                h_pos[total] = a.s;
+                h_meta[total] = meta_of(a.n_bits, df_of(a.msg));
+                h_score[total] = a.hi;
+            }
+            total++;
+        });
     *h_count = total;
     return PSS_OK;
 }
@@ -415,53 +322,32 @@ extern "C" int pss_adsb_frames(pss_ctx *ctx, const float *d_iq, long n_buf, long
     }
     const Reach w = reach_of(s_begin, s_end, spc, n_capture);
     const long n_ext = w.e1 - w.e0, n_tiles = (n_ext + DT_S - 1) / DT_S;
-    // buffer 0: the count of accepted starts, the tiles' counts and offsets, the tiles' lists
-    const size_t o_count = 16, o_off = o_count + sizeof(int) * (size_t)n_tiles, o_list = (o_off + sizeof(int) * (size_t)n_tiles + 15) & ~(size_t)15;
-    r = pss_ensure_buffer(ctx, &ctx->adsb_buf[0], &ctx->adsb_cap[0], o_list + sizeof(uint16_t) * (size_t)n_tiles * DT_S, "pss_adsb_frames tiles");
+    PssStartList &starts = ctx->starts;   // buffer 0: the tiles' counts, offsets and lists
+    PssStartList::Tiles t;
+    r = starts.tiles(ctx, n_tiles, "pss_adsb_frames tiles", t);
     if (r) return r;
-    if (!ctx->adsb_pin) PSS_HIP(ctx, hipHostMalloc(&ctx->adsb_pin, sizeof(long), hipHostMallocDefault));
-    char *b0 = reinterpret_cast<char *>(ctx->adsb_buf[0]);
-    long *d_n_acc = reinterpret_cast<long *>(b0);
-    int *tile_count = reinterpret_cast<int *>(b0 + o_count), *tile_off = reinterpret_cast<int *>(b0 + o_off);
-    uint16_t *tile_list = reinterpret_cast<uint16_t *>(b0 + o_list);
     const float2 *iq = reinterpret_cast<const float2 *>(d_iq);
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_adsb_detect");
     hipLaunchKernelGGL(k_adsb_detect, dim3((unsigned)(n_tiles < DT_GRID_CAP ? n_tiles : DT_GRID_CAP)), dim3(DT_T), 0, PSS_STREAM(ctx), iq, buf_index0,
-                       buf_index0 + n_buf, n_capture, spc, ratio, d_icao, n_icao, w.e0, n_ext, n_tiles, tile_count, tile_list);
+                       buf_index0 + n_buf, n_capture, spc, ratio, d_icao, n_icao, w.e0, n_ext, n_tiles, t.count, t.list);
     pss_kernel_end(ctx);
-    pss_kernel_begin(ctx, "k_adsb_scan");
-    hipLaunchKernelGGL(k_adsb_scan<int>, dim3(1), dim3(SC_T), 0, PSS_STREAM(ctx), tile_count, tile_off, n_tiles, d_n_acc, static_cast<int32_t *>(nullptr));
-    pss_kernel_end(ctx);
-    r = pss_hip_check(ctx, hipGetLastError(), "k_adsb_detect launch");
-    if (r) return r;
-    // the list's length sizes what follows: it reaches the host through 8 pinned bytes and one stream synchronisation, as the gates' counts do
-    PSS_HIP(ctx, hipMemcpyAsync(ctx->adsb_pin, d_n_acc, sizeof(long), hipMemcpyDeviceToHost, PSS_STREAM(ctx)));
-    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));
-    const long n_acc = *reinterpret_cast<const long *>(ctx->adsb_pin);
-    if (n_acc == 0) {
-        PSS_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), PSS_STREAM(ctx)));
-        return PSS_OK;
-    }
+    long n_acc;
+    r = starts.total(ctx, t, n_tiles, "k_adsb_detect launch", d_count, n_acc);
+    if (r || n_acc == 0) return r;
     // buffer 1: the accepted starts, their ranks, their keep flags
     const size_t o_rank = sizeof(int) * (size_t)n_acc, o_keep = 2 * o_rank;
-    r = pss_ensure_buffer(ctx, &ctx->adsb_buf[1], &ctx->adsb_cap[1], o_keep + (size_t)n_acc, "pss_adsb_frames list");
+    r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + (size_t)n_acc, "pss_adsb_frames list");
     if (r) return r;
-    char *b1 = reinterpret_cast<char *>(ctx->adsb_buf[1]);
+    char *b1 = reinterpret_cast<char *>(starts.buf[1]);
     int *acc = reinterpret_cast<int *>(b1), *rank = reinterpret_cast<int *>(b1 + o_rank);
     uint8_t *keep = reinterpret_cast<uint8_t *>(b1 + o_keep);
-    const long wave_blocks = (n_acc + LS_T / 64 - 1) / (LS_T / 64);
-    const dim3 wave_grid((unsigned)(wave_blocks < LS_GRID_CAP ? wave_blocks : LS_GRID_CAP));
-    pss_kernel_begin(ctx, "k_adsb_gather");
-    hipLaunchKernelGGL(k_adsb_gather, dim3((unsigned)(n_tiles < LS_GRID_CAP ? n_tiles : LS_GRID_CAP)), dim3(LS_T), 0, PSS_STREAM(ctx), tile_count, tile_off,
-                       tile_list, n_tiles, acc);
-    pss_kernel_end(ctx);
+    const dim3 wave_grid(PssStartList::list_grid(n_acc, LS_T / 64));
+    starts.gather(ctx, t, n_tiles, acc);   // acc[k] = the k-th accepted start as an offset from e0
     pss_kernel_begin(ctx, "k_adsb_keep");
     hipLaunchKernelGGL(k_adsb_keep, wave_grid, dim3(LS_T), 0, PSS_STREAM(ctx), iq, buf_index0, n_capture, spc, acc, n_acc, w.e0, s_begin, s_end, keep);
     pss_kernel_end(ctx);
-    pss_kernel_begin(ctx, "k_adsb_scan");   // the ranks of the kept starts, and the true count
-    hipLaunchKernelGGL(k_adsb_scan<uint8_t>, dim3(1), dim3(SC_T), 0, PSS_STREAM(ctx), keep, rank, n_acc, static_cast<long *>(nullptr), d_count);
-    pss_kernel_end(ctx);
+    starts.rank(ctx, keep, rank, n_acc, d_count);   // the ranks of the kept starts, and the true count
     if (max_frames > 0) {
         pss_kernel_begin(ctx, "k_adsb_emit");
         hipLaunchKernelGGL(k_adsb_emit, wave_grid, dim3(LS_T), 0, PSS_STREAM(ctx), iq, buf_index0, n_capture, spc, acc, n_acc, w.e0, keep, rank, max_frames, d_msg,

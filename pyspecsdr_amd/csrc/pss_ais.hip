@@ -5,9 +5,9 @@
 //                 once; every lane tests the training sequence and the flag of consecutive starts (17 LDS reads, consecutive lanes on
 //                 consecutive words at every k; a tile without a survivor ends there); ballots and the wavefronts' counts compact the
 //                 survivors in ascending order into the tile's own list.
-//   k_ais_scan    one workgroup: the exclusive prefix of the tiles' counts and their total; later the ranks of the kept starts and the
-//                 true count, from the keep flags.
-//   k_ais_gather  the tiles' lists, back to back: the ascending list of survivors.  No atomics, no cap.
+//   pss_starts.h  k_starts_scan and k_starts_gather, shared with pss_adsb.hip: the tiles' counts become offsets and a total, the tiles'
+//                 lists are laid back to back (the ascending list of survivors as long tile * DT_S + offset: no atomics, no cap), and
+//                 behind the keep pass the same scan ranks the kept starts and writes the true count.
 //   k_ais_walk    one lane per survivor: threshold and score again, then the HDLC walk with its strobes from global memory; the payload
 //                 goes to the survivor's 32 words of scratch.
 //   k_ais_keep    one lane per survivor: the accepted starts less than 5 away in the same row are its neighbours in the list: the
@@ -25,6 +25,8 @@
 #include "pss_ais.h"
 #include "pss_ctx.h"
 #include "pss_device.h"
+#define PSS_STARTS_KERNELS   // this unit launches the list's kernels
+#include "pss_starts.h"
 
 namespace {
 
@@ -86,12 +88,8 @@ int front_check(pss_ctx *ctx, const char *who, const void *iq, long n_rows, long
     auto bad = [&](const char *why) { return pss_fail(ctx, PSS_E_ARG, std::string(who) + ": " + why); };
     auto off = [](const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (n_rows < 1) return bad("n_rows < 1");
-    if (n_row < 0 || n_row > (1l << 60)) return bad("n_row outside [0, 2^60]");
-    if (n_buf < 0 || buf_index0 < 0 || buf_index0 > n_row || n_buf > n_row - buf_index0) return bad("the buffer does not lie inside the row");
+    if (const int r = window_refusals(bad, "row", n_row, n_buf, buf_index0, 'i', i_begin, i_end, "samples")) return r;
     if (x_stride < n_buf) return bad("x_stride < n_buf");
-    if (i_end < i_begin) return bad("i_end < i_begin");
-    if (i_begin < 0 || i_end > n_row) return bad("the window does not lie inside the row");
-    if (i_end - i_begin > (1l << 30)) return bad("a window of more than 2^30 samples");
     if (y_stride < i_end - i_begin) return bad("y_stride < i_end - i_begin");
     const int r = pulse_check(ctx, who, pulse, n_pulse);
     if (r) return r;
@@ -105,14 +103,7 @@ int front_check(pss_ctx *ctx, const char *who, const void *iq, long n_rows, long
 }
 
 // ---- frames -------------------------------------------------------------------------------------------------------------------------------
-constexpr int DT_T = 1024;                       // threads of a workgroup: 16 wavefronts
-constexpr int DT_WAVES = DT_T / 64;
-constexpr int DT_S = 4096;                       // start positions of a tile
-constexpr long DT_GRID_CAP = 1024;               // workgroups of a launch: tiles past it are walked by a grid-stride loop
 constexpr int DT_Y = DT_S + BACK + HEAD;         // samples of a tile: 4176
-constexpr int SC_T = 1024, SC_PER = 4;           // the scan: 4096 counts a step
-constexpr int LS_T = 256;                        // the list kernels
-constexpr long LS_GRID_CAP = 2048;
 constexpr int REC_WORDS = MAX_BYTES / 4;         // a survivor's payload in scratch: 32 words
 
 // where tile `tile` lies: its row and the row index of its first start
@@ -127,10 +118,8 @@ __global__ __launch_bounds__(DT_T) void k_ais_detect(const float *__restrict__ y
 {
     __shared__ float ys[DT_Y];
     __shared__ int wcount[64];
-    static_assert(DT_S / DT_T * DT_WAVES == 64, "one lane per (pass, wavefront) count");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned long long below = (1ull << lane) - 1ull;
     for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         long row, g0;
         tile_at(tile, tpr, e0, row, g0);
@@ -160,87 +149,14 @@ __global__ __launch_bounds__(DT_T) void k_ais_detect(const float *__restrict__ y
             if (tid == 0) tile_count[tile] = 0;
             continue;
         }
-        // ---- the survivors in ascending order: the 64 counts (pass k, wavefront w) at slot 16 k + w, scanned by every wavefront for itself
-        unsigned long long masks[DT_S / DT_T];
-#pragma unroll
-        for (int k = 0; k < DT_S / DT_T; k++) {
-            masks[k] = __ballot(oks[k]);
-            if (lane == 0) wcount[k * DT_WAVES + wave] = __popcll(masks[k]);
-        }
-        __syncthreads();
-        const int own = wcount[lane];
-        int inc = own;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        const int excl = inc - own;
-        const int total = __shfl(inc, 63);   // the same in every lane
-#pragma unroll
-        for (int k = 0; k < DT_S / DT_T; k++) {
-            const int before = __shfl(excl, k * DT_WAVES + wave);
-            if (oks[k]) tile_list[(size_t)tile * DT_S + before + __popcll(masks[k] & below)] = (uint16_t)(k * DT_T + tid);
-        }
+        // ---- the survivors in ascending order into the tile's own list
+        const int total = tile_slots(oks, wcount, lane, wave, [&](int k, size_t slot) { tile_list[(size_t)tile * DT_S + slot] = (uint16_t)(k * DT_T + tid); });
         if (tid == 0) tile_count[tile] = total;
         __syncthreads();   // wcount is read before the next tile with survivors writes it
     }
 }
 
-// The exclusive prefix of n counts and their total, by one workgroup: SC_PER * SC_T counts a step with a carry, SC_PER consecutive counts a
-// lane, the lanes' sums scanned by shuffles and the wavefronts' through LDS.  The tiles' counts (int32) and the keep flags (bytes) both go
-// through it.
-template <class T>
-__global__ __launch_bounds__(SC_T) void k_ais_scan(const T *__restrict__ in, int *__restrict__ out, long n, long *__restrict__ total64,
-                                                   int32_t *__restrict__ total32)
-{
-    __shared__ int wsum[SC_T / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    long carry = 0;   // the same in every lane
-    for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {
-        const long k0 = b0 + (long)SC_PER * tid;
-        int v[SC_PER], mine = 0;
-#pragma unroll
-        for (int u = 0; u < SC_PER; u++) {
-            v[u] = k0 + u < n ? (int)in[k0 + u] : 0;
-            mine += v[u];
-        }
-        int inc = mine;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int t = __shfl_up(inc, d);
-            if (lane >= d) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        int before = 0, all = 0;
-        for (int w = 0; w < SC_T / 64; w++) {
-            if (w < wave) before += wsum[w];
-            all += wsum[w];
-        }
-        __syncthreads();
-        int run = (int)carry + before + inc - mine;
-#pragma unroll
-        for (int u = 0; u < SC_PER; u++) {
-            if (k0 + u < n) out[k0 + u] = run;
-            run += v[u];
-        }
-        carry += all;
-    }
-    if (tid == 0) {
-        if (total64) *total64 = carry;
-        if (total32) *total32 = (int32_t)carry;
-    }
-}
-
 // surv[k] = the k-th survivor as tile * DT_S + its offset in the tile: ascending in (row, s)
-__global__ __launch_bounds__(LS_T) void k_ais_gather(const int *__restrict__ tile_count, const int *__restrict__ tile_off, const uint16_t *__restrict__ tile_list,
-                                                     long n_tiles, long *__restrict__ surv)
-{
-    for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int c = tile_count[tile], o = tile_off[tile];
-        for (int q = threadIdx.x; q < c; q += LS_T) surv[o + q] = tile * DT_S + (long)tile_list[(size_t)tile * DT_S + q];
-    }
-}
-
 __device__ __forceinline__ void start_at(long idx, long tpr, long e0, long &row, long &s)
 {
     long g0;
@@ -342,12 +258,8 @@ int frames_check(pss_ctx *ctx, const char *who, const void *y, long n_rows, long
     auto bad = [&](const char *why) { return pss_fail(ctx, PSS_E_ARG, std::string(who) + ": " + why); };
     auto off = [](const void *p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; };
     if (n_rows < 1 || n_rows > (1l << 20)) return bad("n_rows outside [1, 2^20]");
-    if (n_row < 0 || n_row > (1l << 60)) return bad("n_row outside [0, 2^60]");
-    if (n_buf < 0 || buf_index0 < 0 || buf_index0 > n_row || n_buf > n_row - buf_index0) return bad("the buffer does not lie inside the row");
+    if (const int r = window_refusals(bad, "row", n_row, n_buf, buf_index0, 's', s_begin, s_end, "starts")) return r;
     if (y_stride < n_buf) return bad("y_stride < n_buf");
-    if (s_end < s_begin) return bad("s_end < s_begin");
-    if (s_begin < 0 || s_end > n_row) return bad("the window does not lie inside the row");
-    if (s_end - s_begin > (1l << 30)) return bad("a window of more than 2^30 starts");
     if ((s_end - s_begin + 2 * NEAR) > (1l << 31) / n_rows) return bad("more than 2^31 starts in the rows of one call");
     if (max_frames < 0) return bad("max_frames < 0");
     if (!count || (n_buf > 0 && !y) || (max_frames > 0 && (!msg || !len || !row || !pos || !score))) return bad("null buffer");
@@ -461,27 +373,18 @@ extern "C" int pss_h_ais_frames(const float *h_y, long n_rows, long y_stride, lo
             });
             if (c.len > 0) acc.push_back(c);
         }
-        for (size_t k = 0; k < acc.size(); k++) {
-            const Rec &a = acc[k];
-            if (a.s < s_begin || a.s >= s_end) continue;
-            bool kept = true;
-            // the list ascends: the starts less than 5 away are a's neighbours in it
-            size_t q = k;
-            while (q > 0 && a.s - acc[q - 1].s < NEAR) q--;
-            for (; q < acc.size() && acc[q].s - a.s < NEAR && kept; q++) {
-                const Rec &b = acc[q];
-                if (drops(b.len == a.len && memcmp(b.msg, a.msg, MAX_BYTES) == 0, b.s, b.q, a.s, a.q)) kept = false;
-            }
-            if (!kept) continue;
-            if (total < max_frames) {
-                memcpy(h_msg + (size_t)total * MAX_BYTES, a.msg, MAX_BYTES);
-                h_len[total] = a.len;
-                h_row[total] = (int32_t)row;
-                h_pos[total] = a.s;
-                h_score[total] = a.q;
-            }
-            total++;
-        }
+        keep_starts(acc.data(), acc.size(), s_begin, s_end, NEAR,
+            [&](const Rec &b, const Rec &a) { return drops(b.len == a.len && memcmp(b.msg, a.msg, MAX_BYTES) == 0, b.s, b.q, a.s, a.q); },
+            [&](const Rec &a) {
+                if (total < max_frames) {
+                    memcpy(h_msg + (size_t)total * MAX_BYTES, a.msg, MAX_BYTES);
+                    h_len[total] = a.len;
+                    h_row[total] = (int32_t)row;
+                    h_pos[total] = a.s;
+                    h_score[total] = a.q;
+                }
+                total++;
+            });
     }
     *h_count = total;
     return PSS_OK;
@@ -501,61 +404,39 @@ extern "C" int pss_ais_frames(pss_ctx *ctx, const float *d_y, long n_rows, long 
     }
     const Reach w = reach_of(s_begin, s_end, n_row);
     const long n_ext = w.e1 - w.e0, tpr = (n_ext + DT_S - 1) / DT_S, n_tiles = tpr * n_rows;
-    // buffer 0: the count of survivors, the tiles' counts and offsets, the tiles' lists
-    const size_t o_count = 16, o_off = o_count + sizeof(int) * (size_t)n_tiles, o_list = (o_off + sizeof(int) * (size_t)n_tiles + 15) & ~(size_t)15;
-    r = pss_ensure_buffer(ctx, &ctx->ais_buf[0], &ctx->ais_cap[0], o_list + sizeof(uint16_t) * (size_t)n_tiles * DT_S, "pss_ais_frames tiles");
+    PssStartList &starts = ctx->starts;   // buffer 0: the tiles' counts, offsets and lists
+    PssStartList::Tiles t;
+    r = starts.tiles(ctx, n_tiles, "pss_ais_frames tiles", t);
     if (r) return r;
-    if (!ctx->ais_pin) PSS_HIP(ctx, hipHostMalloc(&ctx->ais_pin, sizeof(long), hipHostMallocDefault));
-    char *b0 = reinterpret_cast<char *>(ctx->ais_buf[0]);
-    long *d_n_surv = reinterpret_cast<long *>(b0);
-    int *tile_count = reinterpret_cast<int *>(b0 + o_count), *tile_off = reinterpret_cast<int *>(b0 + o_off);
-    uint16_t *tile_list = reinterpret_cast<uint16_t *>(b0 + o_list);
     PssTimeScope timed(ctx);
     pss_kernel_begin(ctx, "k_ais_detect");
     hipLaunchKernelGGL(k_ais_detect, dim3((unsigned)(n_tiles < DT_GRID_CAP ? n_tiles : DT_GRID_CAP)), dim3(DT_T), 0, PSS_STREAM(ctx), d_y, y_stride, buf_index0,
-                       buf_index0 + n_buf, n_row, w.e0, n_ext, tpr, n_tiles, tile_count, tile_list);
+                       buf_index0 + n_buf, n_row, w.e0, n_ext, tpr, n_tiles, t.count, t.list);
     pss_kernel_end(ctx);
-    pss_kernel_begin(ctx, "k_ais_scan");
-    hipLaunchKernelGGL(k_ais_scan<int>, dim3(1), dim3(SC_T), 0, PSS_STREAM(ctx), tile_count, tile_off, n_tiles, d_n_surv, static_cast<int32_t *>(nullptr));
-    pss_kernel_end(ctx);
-    r = pss_hip_check(ctx, hipGetLastError(), "k_ais_detect launch");
-    if (r) return r;
-    // the list's length sizes what follows: it reaches the host through 8 pinned bytes and one stream synchronisation
-    PSS_HIP(ctx, hipMemcpyAsync(ctx->ais_pin, d_n_surv, sizeof(long), hipMemcpyDeviceToHost, PSS_STREAM(ctx)));
-    PSS_HIP(ctx, hipStreamSynchronize(PSS_STREAM(ctx)));
-    const long n_surv = *reinterpret_cast<const long *>(ctx->ais_pin);
-    if (n_surv == 0) {
-        PSS_HIP(ctx, hipMemsetAsync(d_count, 0, sizeof(int32_t), PSS_STREAM(ctx)));
-        return PSS_OK;
-    }
+    long n_surv;
+    r = starts.total(ctx, t, n_tiles, "k_ais_detect launch", d_count, n_surv);
+    if (r || n_surv == 0) return r;
     // buffer 1: the survivors, their payload words, lengths, scores and ranks, their keep flags
     const size_t n = (size_t)n_surv;
     const size_t o_words = sizeof(long) * n, o_len = o_words + sizeof(uint32_t) * REC_WORDS * n, o_score = o_len + sizeof(int) * n,
                  o_rank = o_score + sizeof(float) * n, o_keep = o_rank + sizeof(int) * n;
-    r = pss_ensure_buffer(ctx, &ctx->ais_buf[1], &ctx->ais_cap[1], o_keep + n, "pss_ais_frames list");
+    r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + n, "pss_ais_frames list");
     if (r) return r;
-    char *b1 = reinterpret_cast<char *>(ctx->ais_buf[1]);
+    char *b1 = reinterpret_cast<char *>(starts.buf[1]);
     long *surv = reinterpret_cast<long *>(b1);
     uint32_t *words = reinterpret_cast<uint32_t *>(b1 + o_words);
     int *len = reinterpret_cast<int *>(b1 + o_len), *rank = reinterpret_cast<int *>(b1 + o_rank);
     float *score = reinterpret_cast<float *>(b1 + o_score);
     uint8_t *keep = reinterpret_cast<uint8_t *>(b1 + o_keep);
-    const long lane_blocks = (n_surv + LS_T - 1) / LS_T, wave_blocks = (n_surv + LS_T / 64 - 1) / (LS_T / 64);
-    const dim3 lane_grid((unsigned)(lane_blocks < LS_GRID_CAP ? lane_blocks : LS_GRID_CAP));
-    const dim3 wave_grid((unsigned)(wave_blocks < LS_GRID_CAP ? wave_blocks : LS_GRID_CAP));
-    pss_kernel_begin(ctx, "k_ais_gather");
-    hipLaunchKernelGGL(k_ais_gather, dim3((unsigned)(n_tiles < LS_GRID_CAP ? n_tiles : LS_GRID_CAP)), dim3(LS_T), 0, PSS_STREAM(ctx), tile_count, tile_off,
-                       tile_list, n_tiles, surv);
-    pss_kernel_end(ctx);
+    const dim3 lane_grid(PssStartList::list_grid(n_surv, LS_T)), wave_grid(PssStartList::list_grid(n_surv, LS_T / 64));
+    starts.gather(ctx, t, n_tiles, surv);   // surv[k] = the k-th survivor as tile * DT_S + its offset in the tile: ascending in (row, s)
     pss_kernel_begin(ctx, "k_ais_walk");
     hipLaunchKernelGGL(k_ais_walk, lane_grid, dim3(LS_T), 0, PSS_STREAM(ctx), d_y, y_stride, buf_index0, n_row, surv, n_surv, tpr, w.e0, len, score, words);
     pss_kernel_end(ctx);
     pss_kernel_begin(ctx, "k_ais_keep");
     hipLaunchKernelGGL(k_ais_keep, lane_grid, dim3(LS_T), 0, PSS_STREAM(ctx), surv, n_surv, tpr, w.e0, s_begin, s_end, len, score, words, keep);
     pss_kernel_end(ctx);
-    pss_kernel_begin(ctx, "k_ais_scan");   // the ranks of the kept starts, and the true count
-    hipLaunchKernelGGL(k_ais_scan<uint8_t>, dim3(1), dim3(SC_T), 0, PSS_STREAM(ctx), keep, rank, n_surv, static_cast<long *>(nullptr), d_count);
-    pss_kernel_end(ctx);
+    starts.rank(ctx, keep, rank, n_surv, d_count);   // the ranks of the kept starts, and the true count
     if (max_frames > 0) {
         pss_kernel_begin(ctx, "k_ais_emit");
         hipLaunchKernelGGL(k_ais_emit, wave_grid, dim3(LS_T), 0, PSS_STREAM(ctx), surv, n_surv, tpr, w.e0, keep, rank, len, score, words, max_frames, d_msg, d_len,

@@ -187,10 +187,8 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
     for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win, &ctx->rds_tab, &ctx->rds_pulse, &ctx->ais_pulse}) t->release();
     if (ctx->welch_part) hipFree(ctx->welch_part);
-    for (auto &b : ctx->adsb_buf) if (b) hipFree(b);
-    if (ctx->adsb_pin) hipHostFree(ctx->adsb_pin);
-    for (auto &b : ctx->ais_buf) if (b) hipFree(b);
-    if (ctx->ais_pin) hipHostFree(ctx->ais_pin);
+    for (auto &b : ctx->starts.buf) if (b) hipFree(b);
+    if (ctx->starts.pin) hipHostFree(ctx->starts.pin);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/pss.h"
+#include "pss_starts.h"
 
 struct PssNfmFilt {
     double taps[65];
@@ -158,17 +159,10 @@ struct pss_ctx {
     PssDevTable welch_win;   // pss_welch.hip: the caller's window
     PssDevTable rds_tab;     // pss_rds.hip, pss_rds_front: rotor knots, taps
     PssDevTable rds_pulse;   // pss_rds.hip, pss_rds_bits: the pulse table
-    // pss_adsb.hip, grow-only: [0] the tiles' counts, offsets and lists, [1] the accepted starts with their keep flags and ranks;
-    // adsb_pin: 8 pinned bytes the count of accepted starts lands in
-    void *adsb_buf[2] = {};
-    size_t adsb_cap[2] = {};
-    void *adsb_pin = nullptr;
     PssDevTable ais_pulse;   // pss_ais.hip, pss_ais_front: the pulse table
-    // pss_ais.hip, grow-only: [0] the tiles' counts, offsets and lists, [1] the survivors with their payloads, scores, keep flags and ranks;
-    // ais_pin: 8 pinned bytes the count of survivors lands in
-    void *ais_buf[2] = {};
-    size_t ais_cap[2] = {};
-    void *ais_pin = nullptr;
+    // pss_adsb.hip and pss_ais.hip, grow-only, shared as the gates share sq_buf (pss_starts.h): [0] the tiles' counts, offsets and lists,
+    // [1] the listed starts with what the receiver keeps beside them (ADS-B: ranks and keep flags; AIS: payloads, lengths, scores as well)
+    PssStartList starts;
     void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;

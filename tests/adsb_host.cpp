@@ -1,7 +1,8 @@
 // adsb_host.cpp — pss_adsb.h with the host compiler alone (the header must not need HIP), built with -fsanitize=address,undefined and run as
 // a program of its own by tests/test_adsb_golden.py.  It walks the index arithmetic at the capture's ends and the window edges: every
 // accessor checks its index against the capture AND against what reach_of says a window's call may read, the remainder is held against a
-// division written out bit by bit, and the one-record rule against hand-made pairs.  Prints "adsb_host: ok".
+// division written out bit by bit, and the one-record rule against hand-made pairs and, through pss_starts.h's keep_starts (the neighbour
+// loop of pss_h_adsb_frames), against hand-made lists in heap vectors of exactly their size.  Prints "adsb_host: ok".
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "pss_adsb.h"
+#include "pss_starts.h"
 
 using namespace pss_adsb;
 
@@ -185,11 +187,43 @@ static void test_rules()
     CHECK(plan(2e6) == 1 && plan(16e6) == 8 && plan(10e6) == 5 && plan(2.4e6) == 0 && plan(18e6) == 0 && plan(1e6) == 0 && plan(0.0) == 0);
 }
 
+// keep_starts over an ascending list of starts that all carry the same message, spc samples a chip -> the starts it emits, in its order
+struct Start { long s; float hi; };
+static std::vector<long> kept(const std::vector<Start> &list, long s_begin, long s_end, int spc)
+{
+    const std::vector<Start> heap(list.begin(), list.end());   // exactly list.size() records: a read past either end is the sanitizer's
+    std::vector<long> out;
+    pss_starts::keep_starts(
+        heap.data(), heap.size(), s_begin, s_end, 2l * spc, [&](const Start &b, const Start &a) { return drops(true, b.s, b.hi, a.s, a.hi, spc); },
+        [&](const Start &a) { out.push_back(a.s); });
+    return out;
+}
+
+static void test_keep()
+{
+    using L = std::vector<long>;
+    const int spc = 2;   // near = 4
+    CHECK(kept({}, 0, 100, spc) == L{});
+    CHECK(kept({{10, 1.0f}}, 0, 100, spc) == L{10} && kept({{10, 1.0f}}, 10, 11, spc) == L{10});
+    CHECK(kept({{10, 1.0f}}, 11, 100, spc) == L{} && kept({{10, 1.0f}}, 0, 10, spc) == L{});
+    // exactly near apart: no neighbours, both stay; near - 1 apart: the weaker one goes, whichever side it is on
+    CHECK((kept({{10, 2.0f}, {14, 1.0f}}, 0, 100, spc) == L{10, 14}) && (kept({{10, 1.0f}, {14, 2.0f}}, 0, 100, spc) == L{10, 14}));
+    CHECK(kept({{10, 2.0f}, {13, 1.0f}}, 0, 100, spc) == L{10} && kept({{10, 1.0f}, {13, 2.0f}}, 0, 100, spc) == L{13});
+    // the stronger neighbour just outside the window still drops the one inside, and is not emitted itself
+    CHECK(kept({{9, 2.0f}, {10, 1.0f}}, 10, 100, spc) == L{} && kept({{9, 1.0f}, {10, 2.0f}}, 0, 10, spc) == L{});
+    CHECK(kept({{9, 1.0f}, {10, 2.0f}}, 10, 100, spc) == L{10} && kept({{9, 2.0f}, {10, 1.0f}}, 0, 10, spc) == L{9});
+    // equal scores: the earlier start stays
+    CHECK(kept({{10, 1.0f}, {11, 1.0f}}, 0, 100, spc) == L{10} && kept({{10, 1.0f}, {11, 1.0f}, {12, 1.0f}, {13, 1.0f}, {14, 1.0f}}, 0, 100, spc) == L{10});
+    // a chain: each start is judged against every accepted neighbour, whatever that neighbour's own fate (12 goes to 14, and still drops 10)
+    CHECK((kept({{10, 1.0f}, {12, 2.0f}, {14, 3.0f}, {30, 1.0f}}, 0, 100, spc) == L{14, 30}));
+}
+
 int main()
 {
     test_crc();
     test_edges();
     test_rules();
+    test_keep();
     printf("adsb_host: ok\n");
     return 0;
 }

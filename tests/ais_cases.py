@@ -20,7 +20,7 @@ LAST_K = 1244                  # 8 + 1030 appended + 205 dropped + 2 closing - 1
 REACH = SPB * LAST_K + 1       # 6221
 TRAINING = 24
 FLAG = (0, 1, 1, 1, 1, 1, 1, 0)
-TILE = 4096                    # k_ais_detect's tile, FRONT_TILE k_ais_front's (tests/ais_caps.py pins them)
+TILE = 4096                    # k_ais_detect's tile, FRONT_TILE k_ais_front's (tests/ais_caps.py pins them, the first through tests/launch_caps.py)
 FRONT_TILE = 2048
 
 # the published position report: type 1, MMSI 477553000, under way ... longitude -122.345833, latitude 47.582833

@@ -1,6 +1,7 @@
 // ais_host.cpp — pss_ais.h with the host compiler alone (no HIP), as a program of its own under AddressSanitizer and UBSan
 // (tests/test_ais_golden.py builds and runs it).  Every row lives in a heap buffer of exactly its size, so a strobe read outside the row is
-// an error the sanitizer reports.
+// an error the sanitizer reports.  The one-record rule runs through pss_starts.h's keep_starts (the neighbour loop of pss_h_ais_frames) over
+// hand-made lists, each in a heap vector of exactly its size as well.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "pss_ais.h"
+#include "pss_starts.h"
 
 using namespace pss_ais;
 
@@ -88,8 +90,36 @@ static std::vector<Rec> frames(const std::vector<float> &y)
     return out;
 }
 
+// keep_starts over an ascending list of starts of one row that all carry the same frame -> the starts it emits, in its order
+struct Start { long s; float q; };
+static std::vector<long> kept(const std::vector<Start> &list, long s_begin, long s_end)
+{
+    const std::vector<Start> heap(list.begin(), list.end());   // exactly list.size() records
+    std::vector<long> out;
+    pss_starts::keep_starts(
+        heap.data(), heap.size(), s_begin, s_end, NEAR, [](const Start &b, const Start &a) { return drops(true, b.s, b.q, a.s, a.q); },
+        [&](const Start &a) { out.push_back(a.s); });
+    return out;
+}
+
 int main()
 {
+    // the neighbour rule over lists: NEAR = 5
+    {
+        using L = std::vector<long>;
+        CHECK(NEAR == 5 && kept({}, 0, 100) == L{});
+        CHECK(kept({{50, 1.0f}}, 0, 100) == L{50} && kept({{50, 1.0f}}, 50, 51) == L{50} && kept({{50, 1.0f}}, 51, 100) == L{} && kept({{50, 1.0f}}, 0, 50) == L{});
+        // exactly NEAR apart: both stay; NEAR - 1 apart: the weaker one goes, whichever side it is on
+        CHECK((kept({{50, 2.0f}, {55, 1.0f}}, 0, 100) == L{50, 55}) && (kept({{50, 1.0f}, {55, 2.0f}}, 0, 100) == L{50, 55}));
+        CHECK(kept({{50, 2.0f}, {54, 1.0f}}, 0, 100) == L{50} && kept({{50, 1.0f}, {54, 2.0f}}, 0, 100) == L{54});
+        // the stronger neighbour just outside the window still drops the one inside, and is not emitted itself
+        CHECK(kept({{49, 2.0f}, {50, 1.0f}}, 50, 100) == L{} && kept({{49, 1.0f}, {50, 2.0f}}, 0, 50) == L{});
+        CHECK(kept({{49, 1.0f}, {50, 2.0f}}, 50, 100) == L{50} && kept({{49, 2.0f}, {50, 1.0f}}, 0, 50) == L{49});
+        // equal scores: the earlier start stays
+        CHECK(kept({{50, 1.0f}, {51, 1.0f}}, 0, 100) == L{50} && kept({{50, 1.0f}, {51, 1.0f}, {52, 1.0f}, {53, 1.0f}, {54, 1.0f}, {55, 1.0f}}, 0, 100) == L{50});
+        // a neighbour drops a start whatever its own fate: 53 goes to 56, and still drops 50
+        CHECK((kept({{50, 1.0f}, {53, 2.0f}, {56, 3.0f}, {90, 1.0f}}, 0, 100) == L{56, 90}));
+    }
     // the check value and the residue
     const uint8_t digits[] = "123456789";
     CHECK((crc_reg(digits, 9) ^ 0xFFFFu) == 0x906Eu);

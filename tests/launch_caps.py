@@ -267,16 +267,18 @@ CAPS = {
 }
 
 
-# ---- the receivers (pss_rds.hip, pss_adsb.hip).  Not rows of CAPS: tests/test_gpu_grid_caps.py iterates that table, and these units have
-# their past-the-cap tests in tests/test_gpu_rds.py and tests/test_gpu_adsb.py, which import the numbers below instead of restating them.
-# Every number stands in a pinned line, so a changed cap fails tests/test_launch_caps.py before it can turn those tests into tests of nothing.
+# ---- the receivers (pss_rds.hip, pss_adsb.hip, and the start list pss_adsb.hip shares with pss_ais.hip: pss_starts.h).  Not rows of CAPS:
+# tests/test_gpu_grid_caps.py iterates that table, and these units have their past-the-cap tests in tests/test_gpu_rds.py,
+# tests/test_gpu_adsb.py and tests/test_gpu_ais.py, which import the numbers below (the last through tests/ais_caps.py) instead of restating
+# them.  Every number stands in a pinned line, so a changed cap fails tests/test_launch_caps.py before it can turn those tests into tests of
+# nothing.
 FR_T, FR_GRID_CAP = 1024, 2048            # k_rds_front: (row, tile) pairs
 EN_T, EN_GRID_CAP = 256, 16384            # k_rds_energy: tiles of EN_T / 16 segments of 1024 samples
 BT_T, BT_GRID_CAP = 256, 4096             # k_rds_bits: rows; BT_T segments a pass of its scan
 GR_T, GR_GRID_CAP = 256, 4096             # k_rds_groups: rows
-DT_T, DT_S, DT_GRID_CAP = 1024, 4096, 1024    # k_adsb_detect: tiles of DT_S starts
-SC_T, SC_PER = 1024, 4                    # k_adsb_scan: SC_PER * SC_T counts a step
-LS_T, LS_GRID_CAP = 256, 2048             # k_adsb_gather: tiles; k_adsb_keep, k_adsb_emit: LS_T / 64 accepted starts a workgroup
+DT_T, DT_S, DT_GRID_CAP = 1024, 4096, 1024    # k_adsb_detect, k_ais_detect: tiles of DT_S starts
+SC_T, SC_PER = 1024, 4                    # k_starts_scan: SC_PER * SC_T counts a step
+LS_T, LS_GRID_CAP = 256, 2048             # k_starts_gather: tiles; k_adsb_keep, k_adsb_emit: LS_T / 64 accepted starts a workgroup
 
 RDS_SEGMENT = 1024                        # pss_rds.h: SEG_BITS * SPB samples of a row
 FRONT_GRID_CAP = FR_GRID_CAP
@@ -330,37 +332,41 @@ RECEIVER_CAPS = {
         ]}),
     "adsb_detect": Cap(
         "pss_adsb_frames", "k_adsb_detect", "tiles of DT_S starts", lambda n=None, o=None: DT_GRID_CAP,
-        {"pss_adsb.hip": [
+        {"pss_starts.h": [
             f"constexpr int DT_T = {DT_T};",
             f"constexpr int DT_S = {DT_S};",
             f"constexpr long DT_GRID_CAP = {DT_GRID_CAP};",
+        ], "pss_adsb.hip": [
             "const long n_ext = w.e1 - w.e0, n_tiles = (n_ext + DT_S - 1) / DT_S;",
             "hipLaunchKernelGGL(k_adsb_detect, dim3((unsigned)(n_tiles < DT_GRID_CAP ? n_tiles : DT_GRID_CAP)), dim3(DT_T), 0,",
             "for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {\n        const long g0 = e0 + tile * DT_S;",
         ]}),
-    "adsb_scan": Cap(
-        "pss_adsb_frames", "k_adsb_scan<int>, k_adsb_scan<uint8_t>", "counts a step of the one workgroup", lambda n=None, o=None: SC_PER * SC_T,
-        {"pss_adsb.hip": [
+    "starts_scan": Cap(
+        "pss_adsb_frames, pss_ais_frames", "k_starts_scan<int>, k_starts_scan<uint8_t>", "counts a step of the one workgroup",
+        lambda n=None, o=None: SC_PER * SC_T,
+        {"pss_starts.h": [
             f"constexpr int SC_T = {SC_T}, SC_PER = {SC_PER};",
             "for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {",
-            "hipLaunchKernelGGL(k_adsb_scan<int>, dim3(1), dim3(SC_T), 0,",
-            "hipLaunchKernelGGL(k_adsb_scan<uint8_t>, dim3(1), dim3(SC_T), 0,",
+            "hipLaunchKernelGGL(k_starts_scan<int>, dim3(1), dim3(SC_T), 0,",
+            "hipLaunchKernelGGL(k_starts_scan<uint8_t>, dim3(1), dim3(SC_T), 0,",
         ]}),
-    "adsb_gather": Cap(
-        "pss_adsb_frames", "k_adsb_gather", "tiles", lambda n=None, o=None: LS_GRID_CAP,
-        {"pss_adsb.hip": [
+    "starts_gather": Cap(
+        "pss_adsb_frames, pss_ais_frames", "k_starts_gather<int>, k_starts_gather<long>", "tiles", lambda n=None, o=None: LS_GRID_CAP,
+        {"pss_starts.h": [
             f"constexpr int LS_T = {LS_T};",
             f"constexpr long LS_GRID_CAP = {LS_GRID_CAP};",
-            "hipLaunchKernelGGL(k_adsb_gather, dim3((unsigned)(n_tiles < LS_GRID_CAP ? n_tiles : LS_GRID_CAP)), dim3(LS_T), 0,",
+            "hipLaunchKernelGGL(k_starts_gather<I>, dim3((unsigned)(n_tiles < LS_GRID_CAP ? n_tiles : LS_GRID_CAP)), dim3(LS_T), 0,",
             "for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {\n        const int c = tile_count[tile], o = tile_off[tile];",
         ]}),
     "adsb_list": Cap(
         "pss_adsb_frames", "k_adsb_keep, k_adsb_emit", "accepted starts", lambda n=None, o=None: LS_GRID_CAP * (LS_T // 64),
-        {"pss_adsb.hip": [
+        {"pss_starts.h": [
             f"constexpr int LS_T = {LS_T};",
             f"constexpr long LS_GRID_CAP = {LS_GRID_CAP};",
-            "const long wave_blocks = (n_acc + LS_T / 64 - 1) / (LS_T / 64);",
-            "const dim3 wave_grid((unsigned)(wave_blocks < LS_GRID_CAP ? wave_blocks : LS_GRID_CAP));",
+            "const long blocks = (n + per - 1) / per;",
+            "return (unsigned)(blocks < pss_starts::LS_GRID_CAP ? blocks : pss_starts::LS_GRID_CAP);",
+        ], "pss_adsb.hip": [
+            "const dim3 wave_grid(PssStartList::list_grid(n_acc, LS_T / 64));",
             "hipLaunchKernelGGL(k_adsb_keep, wave_grid, dim3(LS_T), 0,",
             "hipLaunchKernelGGL(k_adsb_emit, wave_grid, dim3(LS_T), 0,",
             "const long wave = (long)blockIdx.x * (LS_T / 64) + (threadIdx.x >> 6), n_waves = (long)gridDim.x * (LS_T / 64);\n"

@@ -1,11 +1,14 @@
-"""tests/ais_caps.py against pyspecsdr_amd/csrc/pss_ais.hip: the constants tests/test_gpu_ais.py imports stand in these source lines — no GPU."""
+"""tests/ais_caps.py against pyspecsdr_amd/csrc/pss_ais.hip and pss_starts.h: the constants tests/test_gpu_ais.py imports stand in these
+source lines — no GPU."""
 import os
 import re
 
 import ais_caps as C
 import ais_cases as A
+import launch_caps as L
 
-SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyspecsdr_amd", "csrc", "pss_ais.hip")
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyspecsdr_amd", "csrc")
+SRC = os.path.join(CSRC, "pss_ais.hip")
 
 
 def test_pinned_lines_are_in_the_source():
@@ -21,7 +24,23 @@ def test_pinned_lines_are_in_the_source():
         assert lines.count(line) == 1, line
 
 
+def test_the_shared_constants_are_pinned_in_the_start_list_header():
+    """The tile, the detect grid cap, the scan step and the list kernels' threads and grid cap: one line each in pss_starts.h, and
+    pss_ais.hip takes them from there (it states none of them itself)."""
+    shared = [ln.strip() for ln in open(os.path.join(CSRC, "pss_starts.h")).read().splitlines()]
+    pinned = [s for row in C.SHARED_ROWS for s in L.RECEIVER_CAPS[row].source["pss_starts.h"]]
+    for line in (f"constexpr int DT_T = {L.DT_T};", f"constexpr int DT_S = {L.DT_S};", f"constexpr long DT_GRID_CAP = {L.DT_GRID_CAP};",
+                 f"constexpr int SC_T = {L.SC_T}, SC_PER = {L.SC_PER};", f"constexpr int LS_T = {L.LS_T};", f"constexpr long LS_GRID_CAP = {L.LS_GRID_CAP};",
+                 "for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {"):
+        assert line in pinned, line
+        assert sum(ln.startswith(line) for ln in shared) == 1, line
+    ais = open(SRC).read()
+    assert '#include "pss_starts.h"' in ais
+    for name in ("DT_T", "DT_S", "DT_GRID_CAP", "SC_T", "SC_PER", "LS_T", "LS_GRID_CAP"):
+        assert not re.search(rf"constexpr \w+ [^;]*\b{name} =", ais), name
+
+
 def test_the_cases_module_agrees():
     assert (A.TILE, A.FRONT_TILE) == (C.TILE, C.FRONT_TILE)
-    assert C.LIST_PASS == 524288 and C.SCAN_STEP == 4096 and sorted(C.PINS) == ["DETECT_GRID_CAP", "DETECT_THREADS", "FRONT_GRID_CAP", "FRONT_THREADS",
-                                                                               "FRONT_TILE", "LIST_GRID_CAP", "LIST_THREADS", "SCAN_STEP", "TILE"]
+    assert (C.TILE, C.DETECT_GRID_CAP, C.LIST_PASS, C.SCAN_STEP) == (4096, 1024, 524288, 4096)
+    assert sorted(C.PINS) == ["FRONT_GRID_CAP", "FRONT_THREADS", "FRONT_TILE"]

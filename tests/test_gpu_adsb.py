@@ -1,4 +1,4 @@
-"""The ADS-B kernels (k_adsb_detect, k_adsb_scan, k_adsb_gather, k_adsb_keep, k_adsb_emit) against pss_h_adsb_frames on every
+"""The ADS-B kernels (k_adsb_detect, pss_starts.h's k_starts_scan and k_starts_gather, k_adsb_keep, k_adsb_emit) against pss_h_adsb_frames on every
 byte — the messages, pos, the meta word, the score bits and the count — and formats.adsb_recording end to end.  The shapes are the smallest
 at which each path is taken: frames on both sides of a tile boundary, one tile past the grid cap, more survivors in a tile than a wavefront
 holds and more than one pass of the second compaction takes (ratio 0, at every rate that has its own LDS extent), more accepted frames than
@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import adsb_cases as A
 from bytes_util import same_bytes
 from gpu_util import dev
-from launch_caps import DETECT_GRID_CAP, DETECT_TILE, LIST_PASS, LS_GRID_CAP, SCAN_STEP   # pinned to csrc/pss_adsb.hip by tests/test_launch_caps.py
+from launch_caps import DETECT_GRID_CAP, DETECT_TILE, LIST_PASS, LS_GRID_CAP, SCAN_STEP   # pinned to csrc/pss_starts.h and pss_adsb.hip by tests/test_launch_caps.py
 from pyspecsdr_amd import formats as F
 from pyspecsdr_amd.engine import Engine
 
@@ -163,7 +163,7 @@ def test_more_than_64_frames_and_a_count_above_max_frames(e):
 
 
 def test_more_kept_frames_than_one_step_of_the_scan(e):
-    k = SCAN_STEP + 104                       # short frames back to back: the ranks carry over from one step of k_adsb_scan to the next
+    k = SCAN_STEP + 104                       # short frames back to back: the ranks carry over from one step of k_starts_scan to the next
     x = A.clean(3 + 128 * k + 5, 1, [(A.ALL_CALL, 3 + 128 * i) for i in range(k)])
     want = check(e, x, 1, max_frames=k + 10)
     assert want[4] == k and want[1].tolist() == [3 + 128 * i for i in range(k)]
@@ -257,8 +257,8 @@ def test_recording_resamples_a_dongle_rate(e):
 # ---- the loops, carries and reuses that need more tiles, more accepted starts or another rate than the tests above have
 def test_4097_tiles(e):
     """Workgroup 0 of k_adsb_detect walks tiles 0, 1024, 2048, 3072 and 4096: survivors, none, survivors, none, survivors, so the prefetched
-    registers, ms / surv, wcount and acc_s are reused after a tile that had work.  k_adsb_gather walks tiles 2048 .. a second time, and
-    k_adsb_scan<int> carries into its second step at tile 4096."""
+    registers, ms / surv, wcount and acc_s are reused after a tile that had work.  k_starts_gather walks tiles 2048 .. a second time, and
+    k_starts_scan<int> carries into its second step at tile 4096."""
     S = DETECT_TILE
     tiles = 4 * DETECT_GRID_CAP + 1
     assert tiles == SCAN_STEP + 1 and tiles > 2 * LS_GRID_CAP

@@ -1,11 +1,11 @@
-"""The AIS kernels (k_ais_front; k_ais_detect, k_ais_scan, k_ais_gather, k_ais_walk, k_ais_keep, k_ais_emit) against pss_h_ais_front and
+"""The AIS kernels (k_ais_front; k_ais_detect, pss_starts.h's k_starts_scan and k_starts_gather, k_ais_walk, k_ais_keep, k_ais_emit) against pss_h_ais_front and
 pss_h_ais_frames on every byte of every output, and formats.ais_recording end to end.  Buffers lie between NaNs, rows are strided with NaNs
 in the gaps, and a sentinel sits behind max_frames and behind each row's window.  The shapes are the smallest at which each path is taken:
 row lengths around the pulse's half-width and the front's tile, one tile past each grid cap, flags on both sides of a tile boundary, a
 1024-bit frame across two of them, more survivors in a tile than a wavefront holds and more than one pass of the list kernels takes, more
 accepted frames than one step of the scan, more tiles than one step of the scan, a count above max_frames, equal scores, rows that must
 not run into each other, windows with exactly their reach.  The caps and tile sizes come from tests/ais_caps.py, where
-tests/test_ais_caps.py pins them to the source lines."""
+tests/test_ais_caps.py and, for the start list shared with ADS-B, tests/test_launch_caps.py pin them to the source lines."""
 import os
 import re
 import sys
@@ -17,7 +17,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_cases as A
-from ais_caps import DETECT_GRID_CAP, FRONT_GRID_CAP, FRONT_TILE, LIST_PASS, SCAN_STEP, TILE, WAVE   # pinned to csrc/pss_ais.hip by tests/test_ais_caps.py
+from ais_caps import DETECT_GRID_CAP, FRONT_GRID_CAP, FRONT_TILE, LIST_PASS, SCAN_STEP, TILE, WAVE   # pinned to csrc/pss_ais.hip and pss_starts.h by tests/test_ais_caps.py
 from bytes_util import same_bytes
 from gpu_util import dev
 from pyspecsdr_amd import formats as F

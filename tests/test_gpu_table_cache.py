@@ -1,7 +1,8 @@
 """The cached device tables of the channel family (pss_table_sync, csrc/pss_api.cpp): every member through four calls on one context —
 a small table A, A again (nothing to upload), a table B with more bytes (the buffer regrows and the old pointer dies), A once more (an
 upload into the larger buffer) — each result against the host twin of the same call.  The shapes are the smallest with a whole tile and
-a partial one.  Nothing here counts uploads: a stale or a torn table shows in the outputs."""
+a partial one.  Nothing here counts uploads: a stale or a torn table shows in the outputs.  The last test is about the one start list
+(csrc/pss_starts.h) behind pss_adsb_frames and pss_ais_frames: the two in turn on one context, its buffers regrown and reused."""
 import os
 import sys
 
@@ -11,6 +12,8 @@ import pytest
 torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import adsb_cases as ADSB
+import ais_cases as AIS
 import welch_bounds as WB
 import welch_cases as WC
 from bytes_util import same, same_bytes
@@ -129,3 +132,72 @@ def test_welch(e):
             f = max(WB.fraction(mean[r], h_mean[r], b_mean), WB.fraction(mx[r], h_max[r], b_max))
             print(f"call {call} ({k}), row {r}: fraction of the twin bound {f:.4f}")
             assert f <= 1.0, (call, k, r, f)
+
+
+# ---- the start list that pss_adsb_frames and pss_ais_frames share -------------------------------------------------------------------------
+TILE = 4096
+assert ADSB.TILE == TILE and AIS.TILE == TILE
+
+
+def adsb_capture():
+    """spc 2, two tiles plus a frame's reach: a frame in the first tile, one across the tile boundary, one that starts in the third tile
+    and ends a sample before the capture does."""
+    spc = 2
+    n = 2 * TILE + 241 * spc
+    at = [100, TILE - 200, 2 * TILE + 1]
+    frames = [(m, p, 10.0, 0.3 * k) for k, (m, p) in enumerate(zip((ADSB.IDENT, ADSB.POS_EVEN, ADSB.VELOCITY), at))]
+    return ADSB.synth(n, spc, frames, seed=[94, 1]), spc, at
+
+
+def ais_rows(n_rows):
+    """Rows of two tiles plus a start's reach at 48 kS/s through the front's twin, one burst a row: the first flag a few samples in front of
+    the tile boundary, the others further on."""
+    n = 2 * TILE + AIS.REACH
+    at = [TILE - AIS.SPB * (AIS.TRAINING + 1), 6000, 300][:n_rows]
+    x = np.stack([AIS.synth(n, [(AIS.with_crc(AIS.SHIPS[k]), a, 1.0, 150.0 * k)], snr_db=20.0, seed=[94, 2, k]) for k, a in enumerate(at)])
+    return Engine.h_ais_front(x)
+
+
+def adsb_on_device(e, d_iq, n, spc, room, **window):
+    out = [torch.full((room, 14), 0xA5, dtype=torch.uint8, device="cuda"), torch.full((room,), -7, dtype=torch.int64, device="cuda"),
+           torch.full((room,), -7, dtype=torch.int32, device="cuda"), torch.full((room,), -7.0, dtype=torch.float32, device="cuda")]
+    d_count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    e.adsb_frames(d_iq, n, spc, *out, d_count, room, **window)
+    e.sync()
+    count = int(host(d_count)[0])
+    return [host(t)[:min(count, room)] for t in out], count
+
+
+def ais_on_device(e, y, room):
+    out = [torch.full((room, 128), 0xA5, dtype=torch.uint8, device="cuda"), torch.full((room,), -7, dtype=torch.int32, device="cuda"),
+           torch.full((room,), -7, dtype=torch.int32, device="cuda"), torch.full((room,), -7, dtype=torch.int64, device="cuda"),
+           torch.full((room,), -7.0, dtype=torch.float32, device="cuda")]
+    d_count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+    e.ais_frames(dev(y), y.shape[0], y.shape[1], *out, d_count, room)
+    e.sync()
+    count = int(host(d_count)[0])
+    return [host(t)[:min(count, room)] for t in out], count
+
+
+def test_adsb_and_ais_alternating_on_one_start_list(e):
+    """pss_adsb_frames (3 tiles: the list's buffers are made), pss_ais_frames on two rows (8 tiles: they grow), pss_adsb_frames through a
+    smaller window (1 tile: reused as they are, the other receiver's bytes still in them), pss_ais_frames on three rows (12 tiles: they grow
+    again) — every field and the count of each call against its host twin."""
+    room = 8
+    x, spc, at = adsb_capture()
+    d_iq = dev(x)
+    rows = ais_rows(3)
+    for call, window in ((0, {}), (2, {"s_begin": TILE - 1000, "s_end": TILE + 1000})):
+        want = Engine.h_adsb_frames(x, spc, max_frames=room, **window)
+        assert want[1].tolist() == (at if call == 0 else at[1:2]) and want[4] == len(want[1]), (call, want[1], want[4])
+        got, count = adsb_on_device(e, d_iq, len(x), spc, room, **window)
+        assert count == want[4], (call, count, want[4])
+        for g, w, what in zip(got, want[:4], ("msg", "pos", "meta", "score")):
+            assert same_bytes(g.view(w.dtype), w), (call, what, g, w)
+        y = rows[:2] if call == 0 else rows
+        want = Engine.h_ais_frames(y, max_frames=room)
+        assert want[2].tolist() == list(range(len(y))) and want[5] == len(y), (call, want[2], want[5])   # one burst a row, and nothing else
+        got, count = ais_on_device(e, y, room)
+        assert count == want[5], (call + 1, count, want[5])
+        for g, w, what in zip(got, want[:5], ("msg", "len", "row", "pos", "score")):
+            assert same_bytes(g, w), (call + 1, what, g, w)

@@ -9,13 +9,13 @@ from launch_caps import CAPS, RECEIVER_CAPS
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyspecsdr_amd", "csrc")
 
 
-def pinned(table, which, name):
+def pinned(table, which, name, once=False):
     row = table[name]
     for fname, snippets in row.source.items():
         with open(os.path.join(CSRC, fname)) as f:
             src = f.read()
         for s in snippets:
-            assert s in src, (f"{row.entry} ({row.kernels}): {fname} no longer reads\n    {s}\n"
+            assert src.count(s) == 1 if once else s in src, (f"{row.entry} ({row.kernels}): {fname} no longer reads\n    {s}\n"
                               f"update tests/launch_caps.py ({which}'{name}') to the new launch grid")
 
 
@@ -26,17 +26,18 @@ def test_pinned_launch_lines_are_in_the_source(name):
 
 @pytest.mark.parametrize("name", sorted(RECEIVER_CAPS))
 def test_pinned_receiver_lines_are_in_the_source(name):
-    """pss_rds.hip and pss_adsb.hip: the constants tests/test_gpu_rds.py and tests/test_gpu_adsb.py import stand in these lines."""
-    pinned(RECEIVER_CAPS, "RECEIVER_CAPS ", name)
+    """pss_rds.hip, pss_adsb.hip and pss_starts.h: the constants tests/test_gpu_rds.py, tests/test_gpu_adsb.py and (through tests/ais_caps.py)
+    tests/test_gpu_ais.py import stand in these lines, each exactly once in its file."""
+    pinned(RECEIVER_CAPS, "RECEIVER_CAPS ", name, once=True)
 
 
 def test_receiver_caps_at_the_shapes_the_gpu_tests_run():
     c = launch_caps
-    assert sorted(RECEIVER_CAPS) == ["adsb_detect", "adsb_gather", "adsb_list", "adsb_scan", "rds_bits", "rds_energy", "rds_front", "rds_groups"]
+    assert sorted(RECEIVER_CAPS) == ["adsb_detect", "adsb_list", "rds_bits", "rds_energy", "rds_front", "rds_groups", "starts_gather", "starts_scan"]
     assert (c.DETECT_TILE, c.DETECT_GRID_CAP, c.SCAN_STEP, c.LIST_PASS, c.FRONT_GRID_CAP, c.BITS_SCAN_PASS) == (4096, 1024, 4096, 8192, 2048, 256)
     assert RECEIVER_CAPS["rds_energy"].cover(1100) == 16384 and RECEIVER_CAPS["rds_energy"].cover(257 * 1024 + 17) == 16384 // 17
-    assert RECEIVER_CAPS["adsb_list"].cover() == c.LIST_PASS and RECEIVER_CAPS["adsb_scan"].cover() == c.SCAN_STEP
-    assert RECEIVER_CAPS["adsb_gather"].cover() == 2048 and RECEIVER_CAPS["rds_bits"].cover() == RECEIVER_CAPS["rds_groups"].cover() == 4096
+    assert RECEIVER_CAPS["adsb_list"].cover() == c.LIST_PASS and RECEIVER_CAPS["starts_scan"].cover() == c.SCAN_STEP
+    assert RECEIVER_CAPS["starts_gather"].cover() == 2048 and RECEIVER_CAPS["rds_bits"].cover() == RECEIVER_CAPS["rds_groups"].cover() == 4096
 
 
 def test_caps_at_the_lengths_the_gpu_tests_run():
