@@ -914,7 +914,8 @@ int pss_h_adsb_frames(const float *h_iq, long n_buf, long buf_index0, long n_cap
  *   of rows of n_row samples -> d_y float32, sample i of row r at element r * y_stride + (i - i_begin), i in [i_begin, i_end): the float32
  *   polar discriminator (no gain, d[0] = 0) and the post-filter (pulse: a HOST table of an odd number of taps, at most 65; one float64 fma
  *   chain per output, zero outside the row).  The buffer must hold the samples from max(0, i_begin - (P - 1) / 2 - 1) to
- *   min(n_row, i_end + (P - 1) / 2).  One kernel, k_ais_front.
+ *   min(n_row, i_end + (P - 1) / 2).  One kernel, k_ais_front.  It reads no rate: rows at any rate go through it with a pulse for that rate
+ *   (the POCSAG receiver below feeds it rows at 38 400 S/s and a boxcar).
  *   PSS_E_ARG ("pss_ais_front: "; a refused call writes nothing): n_rows < 1, a buffer or a window outside the row, strides below n_buf or
  *   the window, a window above 2^30 samples, a pulse that is not odd, in [1, 65] and finite, a buffer that does not cover the window's
  *   halo, a null or misaligned pointer.
@@ -946,6 +947,50 @@ int pss_ais_frames(pss_ctx *ctx, const float *d_y, long n_rows, long y_stride, l
                    uint8_t *d_msg, int32_t *d_len, int32_t *d_row, int64_t *d_pos, float *d_score, int32_t *d_count, int max_frames);
 int pss_h_ais_frames(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
                      uint8_t *h_msg, int32_t *h_len, int32_t *h_row, int64_t *h_pos, float *h_score, int32_t *h_count, int max_frames);
+/* ---- POCSAG: the pager messages of a VHF capture — what the reference's command list starts `rtl_fm ... | multimon-ng -a POCSAG1200` for
+ * (rtlcoms.json, "Decode Pager", "Monitor Pager traffic").  The arithmetic is the project's own, stated once in csrc/pss_pocsag.h (PARITY.md
+ * "POCSAG"); the device and the host twin agree on every byte, and every output follows from indices in the ROW, so no chunking changes one.
+ * The rows run at 38 400 S/s: spb = 75, 32 and 16 samples a bit at 512, 1200 and 2400 bit/s.  The front is pss_ais_front above (it reads no
+ * rate) with pss_pocsag_default_pulse's boxcar.
+ * pss_pocsag_plan: the route from a capture at fs to 38 400 S/s: decim = min(fs / 38 400, 204) for pss_ddc, up / down = 38 400 decim / fs
+ *   reduced for pss_resample.  PSS_E_ARG (reason in pss_last_error(NULL), starting "pss_pocsag: "): an fs that is no integer, below 38 400,
+ *   or whose factors leave [1, 4096].
+ * pss_pocsag_default_pulse: the post-filter of a rate of spb samples a bit (in [2, 128]): P = the largest odd number <= min(spb, 65) taps
+ *   of 1.0 / P.  *n_pulse is set, pulse (NULL: only the count) is filled.
+ * pss_pocsag_codeword: the 32-bit codeword of 21 data bits (bits above them ignored): the data in bits 31 .. 11, the BCH(31,21) check bits
+ *   of the generator 0x769 in 10 .. 1, even parity in bit 0.  0x7CD215D8 >> 11 gives the sync word, 0x7A89C197 >> 11 the idle word.  Host only.
+ * pss_pocsag_check: the receiver's check of one codeword: the bits fixed (0, 1 or 2, at most fix, in [0, 2]) with the corrected codeword in
+ *   *fixed (nullable), or -1 with 0 there: uncorrectable.  Errors of weight 1 and 2 in bits 31 .. 1 by their syndrome, bit 0 by the parity.
+ *   Host only.
+ * pss_pocsag_batches: d_y float32 rows at 38 400 S/s, y_stride samples apart, 4-byte aligned, holding samples [buf_index0, buf_index0 +
+ *   n_buf) of rows of n_row samples.  Every start s in [s_begin, s_end) of every row with s + 543 spb < n_row is a candidate: strobes spb
+ *   samples apart, a threshold from the mean of the sync word's own 32 strobes, at most sync_errors (in [0, 2]) mismatches against
+ *   0x7CD215D8 or its complement (an inverted channel), then the batch's 16 codewords through the check above with the caller's fix; a
+ *   batch with more than max_bad (in [0, 16]) uncorrectable codewords is rejected.  Of accepted starts less than spb apart in a row that
+ *   read the same 16 codewords, the one whose nearest sync strobe lies farthest from the threshold stays (the earlier on a tie).  Records
+ *   in ascending (row, s): d_cw uint32 [max_batches][16] (corrected; 0 where uncorrectable), d_fix uint8 [max_batches][16] (0, 1, 2, or 255),
+ *   d_row int32, d_pos int64 (the row index of the sync word's first strobe), d_meta uint32 (sync mismatches | inverted << 8 | n_bad << 16 |
+ *   total fixed bits << 24), d_score float32 (that distance), d_count int32 [1] (the TRUE count; nothing is written past max_batches).  The
+ *   buffer must hold the samples from max(0, s_begin - (spb - 1)) to min(n_row, s_end + spb - 2 + 543 spb + 1).
+ *   PSS_E_ARG ("pss_pocsag_batches: "; a refused call writes nothing): n_rows outside [1, 2^20], spb, sync_errors, fix or max_bad outside
+ *   their ranges, a buffer or a window outside the row, y_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows),
+ *   a buffer that does not cover the window's reach, max_batches < 0, a null or misaligned pointer.
+ *   Kernels: k_pocsag_detect (the one pass over every start), then k_starts_scan, k_starts_gather, k_pocsag_walk, k_pocsag_keep,
+ *   k_starts_scan, k_pocsag_emit over the survivors of the sync test only (about spb of them per batch).  Scratch on the context (the same
+ *   buffers as pss_adsb_frames' and pss_ais_frames'), 2 bytes per start of the largest call and 102 bytes per survivor, grow-only and freed
+ *   by pss_destroy; the call waits once for the count of survivors.
+ * pss_h_pocsag_batches: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL), starting
+ *   "pss_pocsag_batches: "). */
+int pss_pocsag_plan(double fs, int *decim, int *up, int *down);
+int pss_pocsag_default_pulse(int spb, double *pulse, int *n_pulse);
+uint32_t pss_pocsag_codeword(uint32_t data21);
+int pss_pocsag_check(uint32_t cw, int fix, uint32_t *fixed);
+int pss_pocsag_batches(pss_ctx *ctx, const float *d_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                       int spb, int sync_errors, int fix, int max_bad, uint32_t *d_cw, uint8_t *d_fix, int32_t *d_row, int64_t *d_pos, uint32_t *d_meta,
+                       float *d_score, int32_t *d_count, int max_batches);
+int pss_h_pocsag_batches(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, int spb,
+                         int sync_errors, int fix, int max_bad, uint32_t *h_cw, uint8_t *h_fix, int32_t *h_row, int64_t *h_pos, uint32_t *h_meta,
+                         float *h_score, int32_t *h_count, int max_batches);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -216,6 +216,14 @@ _SIGS = {
     "pss_h_ais_front": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
     "pss_ais_frames": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, _p, _p, _p, _p, _p, C.c_int]),
     "pss_h_ais_frames": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_pocsag_plan": (C.c_int, [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pss_pocsag_default_pulse": (C.c_int, [C.c_int, _p, C.POINTER(C.c_int)]),
+    "pss_pocsag_codeword": (C.c_uint32, [C.c_uint32]),
+    "pss_pocsag_check": (C.c_int, [C.c_uint32, C.c_int, C.POINTER(C.c_uint32)]),
+    "pss_pocsag_batches": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _p, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_h_pocsag_batches": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _p, _p, _p, _p, _p, _p, _p, C.c_int]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

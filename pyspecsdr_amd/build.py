@@ -38,6 +38,7 @@ UNITS = [
     ("pss_rds.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the RDS receiver: NumPy's float32 arctan2, then fma chains written as fma
     ("pss_adsb.hip", ["-ffp-contract=off"]),   # the Mode S receiver: float32 products and sums one by one, strict comparisons
     ("pss_ais.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the AIS receiver: NumPy's float32 arctan2, one fma chain, strict comparisons
+    ("pss_pocsag.hip", ["-ffp-contract=off"]),   # the POCSAG receiver: float32 sums one by one, strict comparisons, integer BCH arithmetic
     ("pss_api.cpp", ["-x", "hip"]),
     ("pss_stream.cpp", ["-x", "hip"]),                        # host only: the streamed captures' chunk loop
     ("pss_design.cpp", ["-x", "hip", "-ffp-contract=off"]),

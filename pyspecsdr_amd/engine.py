@@ -1617,6 +1617,80 @@ class Engine:
         k = min(int(count[0]), room)
         return msg[:k], ln[:k], rw[:k], pos[:k], score[:k], int(count[0])
 
+    # -- POCSAG: float32 discriminator rows at 38.4 kS/s -> the batches whose codewords pass their check (pss_pocsag_*; the arithmetic:
+    #    csrc/pss_pocsag.h).  The front is ais_front with pocsag_default_pulse(spb).
+    POCSAG_RATE = 38400
+    POCSAG_SYNC, POCSAG_IDLE = 0x7CD215D8, 0x7A89C197
+
+    @staticmethod
+    def pocsag_plan(fs, lib=None):
+        """pss_pocsag_plan -> (decim, up, down): the down-converter's decimation min(fs // 38 400, 204) and the resampler's factors to
+        38 400 S/s.  Host code."""
+        lib = lib or L.load()
+        d, u, w = C.c_int(), C.c_int(), C.c_int()
+        if lib.pss_pocsag_plan(float(fs), C.byref(d), C.byref(u), C.byref(w)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return d.value, u.value, w.value
+
+    @staticmethod
+    def pocsag_default_pulse(spb, lib=None):
+        """pss_pocsag_default_pulse: a boxcar of the largest odd number of taps <= min(spb, 65), each 1 / P (float64).  Host code."""
+        return Engine._default_taps(lib, "pss_pocsag_default_pulse", "pocsag_default_pulse: spb outside [2, 128]", spb)
+
+    @staticmethod
+    def pocsag_codeword(data21, lib=None):
+        """pss_pocsag_codeword: the 32-bit codeword of 21 data bits (BCH(31,21) and even parity).  Host code."""
+        lib = lib or L.load()
+        return int(lib.pss_pocsag_codeword(int(data21) & 0x1FFFFF))
+
+    @staticmethod
+    def pocsag_check(cw, fix=2, lib=None):
+        """pss_pocsag_check -> (bits fixed, corrected codeword), or (-1, 0): uncorrectable within `fix` bits.  Host code."""
+        lib = lib or L.load()
+        out = C.c_uint32()
+        n = int(lib.pss_pocsag_check(int(cw) & 0xFFFFFFFF, int(fix), C.byref(out)))
+        return n, int(out.value)
+
+    def pocsag_batches(self, d_y, n_rows, n_buf, spb, d_cw, d_fix, d_row, d_pos, d_meta, d_score, d_count, max_batches, sync_errors=2, fix=2, max_bad=0,
+                       y_stride=None, buf_index0=0, n_row=None, s_begin=0, s_end=None):
+        """d_y float32 at 38.4 kS/s: n_rows rows y_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_row
+        samples (default: the buffer is the row) -> the batches whose sync word starts in [s_begin, s_end) (default: to the row's end) of every
+        row, ascending in (row, s): d_cw uint32 [max_batches][16], d_fix uint8 [max_batches][16], d_row int32, d_pos int64, d_meta uint32 (sync
+        mismatches | inverted << 8 | n_bad << 16 | fixed bits << 24), d_score float32, d_count int32 [1] (the true count)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_pocsag_batches, _ptr(d_y), int(n_rows), int(n_buf if y_stride is None else y_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, int(spb), int(sync_errors), int(fix), int(max_bad), _ptr(d_cw), _ptr(d_fix), _ptr(d_row), _ptr(d_pos), _ptr(d_meta),
+                  _ptr(d_score), _ptr(d_count), int(max_batches))
+
+    @staticmethod
+    def h_pocsag_batches(y, spb, sync_errors=2, fix=2, max_bad=0, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_batches=None, lib=None):
+        """pss_h_pocsag_batches on a host float32 array [n_rows][n_buf] or [n_buf] -> (cw uint32 [k][16], fix uint8 [k][16], row int32 [k], pos
+        int64 [k], meta uint32 [k], score float32 [k], count): the first k = min(count, max_batches) records and the true count.  max_batches:
+        default room for every batch.  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(y, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("y: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_batches is None
+        max_batches = 64 if grow else int(max_batches)
+        while True:
+            room = max(max_batches, 0)
+            cw, fx, rw = np.zeros((room, 16), np.uint32), np.zeros((room, 16), np.uint8), np.zeros(room, np.int32)
+            pos, meta, score, count = np.zeros(room, np.int64), np.zeros(room, np.uint32), np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_pocsag_batches(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end, int(spb),
+                                        int(sync_errors), int(fix), int(max_bad), _ptr(cw), _ptr(fx), _ptr(rw), _ptr(pos), _ptr(meta), _ptr(score),
+                                        _ptr(count), max_batches) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_batches = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return cw[:k], fx[:k], rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

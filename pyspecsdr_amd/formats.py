@@ -1475,6 +1475,209 @@ def ais_recording(samples, fs, center_hz=162.0e6, channels_hz=(161.975e6, 162.02
     return dict(frames=frames, tracks=ais_tracks(frames), nmea=nmea, fs=_AIS_RATE)
 
 
+_POCSAG_RATE = 38400
+_POCSAG_IDLE = 0x7A89C197
+_POCSAG_NUMERIC = "0123456789*U -)("
+_POCSAG_KEYS = ('cw', 'fix', 'row', 'pos', 'meta', 'score')
+
+
+def pocsag_records(cw, fix, row, pos, meta, score):
+    """The arrays of pss_pocsag_batches / Engine.h_pocsag_batches -> one dict per batch: 'cw' (16 ints), 'fix' (16 ints), 'row', 'pos', 'meta',
+    'score', and meta's fields 'sync_errors', 'inverted', 'n_bad', 'fixed'."""
+    out = []
+    for c, f, r, p, m, q in zip(cw, fix, row, pos, meta, score):
+        m = int(m)
+        out.append(dict(cw=[int(v) for v in c], fix=[int(v) for v in f], row=int(r), pos=int(p), meta=m, score=float(q), sync_errors=m & 0xFF,
+                        inverted=bool((m >> 8) & 1), n_bad=(m >> 16) & 0xFF, fixed=m >> 24))
+    return out
+
+
+def _pocsag_text(bits):
+    """A message's data bits in the order received -> (numeric, alpha): every group's first bit is its least significant."""
+    numeric = "".join(_POCSAG_NUMERIC[sum(b << i for i, b in enumerate(bits[k:k + 4]))] for k in range(0, len(bits) - 3, 4))
+    codes = [sum(b << i for i, b in enumerate(bits[k:k + 7])) for k in range(0, len(bits) - 6, 7)]
+    while codes and codes[-1] in (0, 3, 4):   # NUL, ETX, EOT: the fill behind the text
+        codes.pop()
+    alpha = "".join(chr(c) if 32 <= c < 127 else "?" for c in codes)
+    return numeric, alpha
+
+
+def pocsag_messages(records, spb, stats=None):
+    """records: batches of ONE rate (pocsag_records' dicts; any order) -> the messages, in order of (row, pos), each a dict: 'ric' (the 18
+    address bits << 3 | the frame the address word stood in), 'function' (0 .. 3), 'numeric' and 'alpha' (both readings of the data bits),
+    'bits' (how many data bits), 'pos' (the row index of the address word's first strobe), 'row', 'baud', 'fixed' (bits corrected in its
+    codewords), 'damaged' (closed by an uncorrectable codeword).
+    1. Among a row's records less than spb apart the one with the smallest (n_bad, fixed bits, -score, pos) stays.
+    2. Batch B continues A iff same row, same polarity and 2 |pos_B - pos_A - 544 spb| <= spb.
+    3. Along a chain a codeword with bit 31 = 0 that is not the idle word 0x7A89C197 opens a message, codewords with bit 31 = 1 append
+       their 20 data bits, an address word, an idle word or the chain's end closes it, an uncorrectable word closes it with damaged=True;
+       data words with no open message are counted: stats['orphans'] where a dict is handed in."""
+    spb = int(spb)
+    key = lambda r: (r['n_bad'], r['fixed'], -r['score'], r['pos'])
+    recs = sorted(records, key=lambda r: (r['row'], r['pos']))
+    kept = []
+    for i, a in enumerate(recs):
+        best = True
+        for step in (-1, 1):
+            j = i + step
+            while best and 0 <= j < len(recs) and recs[j]['row'] == a['row'] and abs(recs[j]['pos'] - a['pos']) < spb:
+                best = not key(recs[j]) < key(a)
+                j += step
+        if best:
+            kept.append(a)
+    follows, has_prev = {}, set()
+    for i, a in enumerate(kept):
+        for j in range(i + 1, len(kept)):
+            b = kept[j]
+            if b['row'] != a['row'] or 2 * (b['pos'] - a['pos'] - 544 * spb) > spb:
+                break
+            if j not in has_prev and b['inverted'] == a['inverted'] and 2 * abs(b['pos'] - a['pos'] - 544 * spb) <= spb:
+                follows[i] = j
+                has_prev.add(j)
+                break
+    baud = _POCSAG_RATE // spb if _POCSAG_RATE % spb == 0 else _POCSAG_RATE / spb
+    messages, orphans = [], 0
+    for head in range(len(kept)):
+        if head in has_prev:
+            continue
+        cur, i = None, head
+
+        def close(damaged=False):
+            nonlocal cur
+            if cur is not None:
+                bits = cur.pop('_bits')
+                numeric, alpha = _pocsag_text(bits)
+                cur.update(numeric=numeric, alpha=alpha, bits=len(bits), damaged=damaged)
+                messages.append(cur)
+            cur = None
+
+        while i is not None:
+            rec = kept[i]
+            for j, (cw, fx) in enumerate(zip(rec['cw'], rec['fix'])):
+                if fx == 255:
+                    close(damaged=True)
+                elif cw == _POCSAG_IDLE:
+                    close()
+                elif not cw >> 31:
+                    close()
+                    cur = dict(ric=((cw >> 13) & 0x3FFFF) << 3 | j // 2, function=(cw >> 11) & 3, pos=rec['pos'] + (32 + 32 * j) * spb, row=rec['row'],
+                               baud=baud, fixed=fx, _bits=[])
+                elif cur is None:
+                    orphans += 1
+                else:
+                    cur['_bits'].extend((cw >> k) & 1 for k in range(30, 10, -1))
+                    cur['fixed'] += fx
+            i = follows.get(i)
+        close()
+    if stats is not None:
+        stats['orphans'] = stats.get('orphans', 0) + orphans
+    messages.sort(key=lambda m: (m['row'], m['pos']))
+    return messages
+
+
+def pocsag_lines(messages):
+    """multimon-ng's lines: `POCSAG1200: Address: 1234567  Function: 3  Alpha:   text`; the numeric reading for function 0, the alpha
+    reading otherwise, neither for a message without data."""
+    out = []
+    for m in messages:
+        line = f"POCSAG{m['baud']}: Address: {m['ric']:7d}  Function: {m['function']}"
+        if m['bits']:
+            line += "  Numeric: " + m['numeric'] if m['function'] == 0 else "  Alpha:   " + m['alpha']
+        out.append(line)
+    return out
+
+
+def _pocsag_batches(e, d_y, n_rows, n, spb, sync_errors, fix, max_bad):
+    """pss_pocsag_batches on resident rows -> the records on the host (pocsag_records)."""
+    import torch
+    dev = d_y.device
+    room = 4096
+    while True:
+        d_cw = torch.empty((room, 16), dtype=torch.int32, device=dev)
+        d_fix = torch.empty((room, 16), dtype=torch.uint8, device=dev)
+        d_row = torch.empty(room, dtype=torch.int32, device=dev)
+        d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+        d_meta = torch.empty(room, dtype=torch.int32, device=dev)
+        d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        e.pocsag_batches(d_y, n_rows, n, spb, d_cw, d_fix, d_row, d_pos, d_meta, d_score, d_count, room, sync_errors=sync_errors, fix=fix, max_bad=max_bad)
+        k = int(d_count.cpu()[0])
+        if k <= room:
+            break
+        room = k   # the true count: again with room for it
+    cw, fx, row, pos, meta, score = (t[:k].cpu().numpy() for t in (d_cw, d_fix, d_row, d_pos, d_meta, d_score))
+    return pocsag_records(cw.view(np.uint32), fx, row, pos, meta.view(np.uint32), score)
+
+
+def pocsag_rows(rows, bauds=(512, 1200, 2400), sync_errors=2, fix=2, max_bad=0):
+    """rows: complex64 rows at 38 400 S/s — a host array [k][n] or [n], or a resident device tensor float32 [k][2 n] — -> (messages,
+    batches): pss_ais_front with pocsag_default_pulse's boxcar and pss_pocsag_batches once per rate on the resident rows, then
+    pocsag_messages.  messages in order of (pos, row); batches: pocsag_records' dicts with 'baud'.  Rows from channelize_plan / pss_bank
+    come here after pss_resample (50 kS/s -> 96 / 125)."""
+    import torch
+    e = get_engine()
+    if isinstance(rows, torch.Tensor):
+        d_rows = rows
+    else:
+        x = np.asarray(rows, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("rows: a 1-D or 2-D complex array")
+        x = np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+        d_rows = torch.from_numpy(x.view(np.float32)).to(f"cuda:{e.device}")
+    if d_rows.dim() != 2 or d_rows.dtype != torch.float32 or d_rows.shape[1] % 2 or not d_rows.is_contiguous():
+        raise ValueError("rows: a contiguous device tensor float32 [k][2 n]")
+    k, n = d_rows.shape[0], d_rows.shape[1] // 2
+    messages, batches = [], []
+    if not k or not n:
+        return messages, batches
+    d_y = torch.empty((k, n), dtype=torch.float32, device=d_rows.device)
+    for baud in bauds:
+        spb = _POCSAG_RATE // int(baud)
+        if spb * int(baud) != _POCSAG_RATE or not 2 <= spb <= 128:
+            raise ValueError("bauds: rates that divide 38 400 into 2 to 128 samples a bit")
+        e.ais_front(d_rows, k, n, d_y, pulse=e.pocsag_default_pulse(spb))
+        recs = _pocsag_batches(e, d_y, k, n, spb, sync_errors, fix, max_bad)
+        messages += pocsag_messages(recs, spb)
+        for r in recs:
+            r['baud'] = int(baud)
+        batches += recs
+    messages.sort(key=lambda m: (m['pos'], m['row'], m['baud']))
+    batches.sort(key=lambda r: (r['pos'], r['row'], r['baud']))
+    return messages, batches
+
+
+def pocsag_recording(samples, fs, center_hz, channels_hz, bauds=(512, 1200, 2400), taps=None, chunk_samples=1 << 22, codes_format=None, table=None,
+                     sync_errors=2, fix=2, max_bad=0):
+    """The pager messages of a capture centred on center_hz -> dict(messages=..., lines=..., batches=..., fs=38400): 'messages'
+    pocsag_messages' dicts in order of 'pos' ('row' is the channel's position in channels_hz), 'lines' pocsag_lines(messages), 'batches' the
+    receiver's records, 'fs' the rate the positions count in.  On the GPU from the upload to the records: pss_ddc puts the listed
+    channels at 0 Hz at pocsag_plan(fs)'s decimation (streamed in chunks of chunk_samples samples plus their halos; the result does not
+    depend on chunk_samples), pss_resample brings them to 38 400 S/s where the decimated rate is another one, then pocsag_rows.  taps: the
+    down-converter's float64 low-pass (default firwin(20 decim + 1, 12 500 / fs): half-width 6.25 kHz, one channel of the 12.5 kHz grid);
+    codes_format / table: as demodulate_recording."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    decim, up, down = e.pocsag_plan(fs)
+    offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+    if offsets.ndim != 1 or not len(offsets):
+        raise ValueError("channels_hz: a list of frequencies")
+    if taps is None:
+        taps = np.empty(20 * decim + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 12500.0 / fs, taps.ctypes.data) != 0:
+            raise ValueError("pocsag_recording: the down-converter's filter design failed")
+    d_rows, _ = _tune_device(samples, fs, offsets, decim, taps, None, chunk_samples, codes_format, table)
+    k, m = d_rows.shape[0], d_rows.shape[1] // 2
+    if (up, down) != (1, 1):
+        n = e.resample_out_len(m, up, down)
+        d_bb = torch.empty((k, 2 * max(n, 1)), dtype=torch.float32, device=d_rows.device)
+        if m:
+            e.resample(d_rows, np.complex64, k, m, up, down, d_bb)
+        d_rows, m = d_bb[:, :2 * n].contiguous() if n else d_bb[:, :0], n
+    messages, batches = pocsag_rows(d_rows.contiguous(), bauds, sync_errors, fix, max_bad) if m else ([], [])
+    return dict(messages=messages, lines=pocsag_lines(messages), batches=batches, fs=_POCSAG_RATE)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
