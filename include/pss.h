@@ -991,6 +991,64 @@ int pss_pocsag_batches(pss_ctx *ctx, const float *d_y, long n_rows, long y_strid
 int pss_h_pocsag_batches(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, int spb,
                          int sync_errors, int fix, int max_bad, uint32_t *h_cw, uint8_t *h_fix, int32_t *h_row, int64_t *h_pos, uint32_t *h_meta,
                          float *h_score, int32_t *h_count, int max_batches);
+/* ---- NOAA APT: the weather-satellite image of a 137 MHz capture — what the reference's command list starts `rtl_fm -f 137.62M -M fm -s 60k ...
+ * | sox ... && wxtoimg` for (rtlcoms.json, "Capture NOAA in .wav"; the band is pyspecconst.py's NOAA_SAT preset).  The arithmetic is the
+ * project's own, stated once in csrc/pss_apt.h (PARITY.md "APT"); the device and the host twins agree on every byte, and every output follows
+ * from indices in the ROW, so windows of a row concatenate to the whole row's bytes.  The rows run at 62 400 S/s (15 samples a word, 26 a
+ * cycle of the 2400 Hz subcarrier), the envelope at 12 480 S/s (3 samples a word, 6240 a line of 2080 words).
+ *   rows of IQ at 62 400 S/s --pss_apt_front--> the envelope --pss_apt_syncs--> the line starts found; the caller fits a grid through them
+ *   (formats.apt_grid) --pss_apt_lines--> float32 [n_lines][2080] words.
+ * pss_apt_plan: the route from a capture at fs to 62 400 S/s: decim = min(fs / 62 400, 204) for pss_ddc, up / down = 62 400 decim / fs
+ *   reduced for pss_resample.  PSS_E_ARG (reason in pss_last_error(NULL), starting "pss_apt: "): an fs that is no integer, below 62 400, or
+ *   whose factors leave [1, 4096].
+ * pss_apt_default_taps: the front's low-pass, scipy.signal.firwin(79, 1 / 15) bit for bit: 2080 Hz at 62 400 S/s.  *n_taps is set (79),
+ *   taps (NULL: only the count) is filled.
+ * pss_apt_front: d_iq complex64, 8-byte aligned: n_rows rows x_stride samples apart, the buffer holding samples [buf_index0, buf_index0 +
+ *   n_buf) of every row of n_row samples.  Per sample i >= 1 the float32 polar discriminator of pss_rds_front (no gain; d[0] = 0), times
+ *   pss_ddc's rotor at the word of 2400 Hz and index i of the row, then pss_ddc's filter in float64, y[m] = sum over k of taps[k]
+ *   z[m decim + lead - k], z zero outside the row, and the magnitude: env[m] = (float) sqrt(fma(re, re, im im)) goes to float32 element
+ *   r env_stride + (m - m_begin) of d_env (4-byte aligned) for m in [m_begin, m_end).  The complex baseband is never stored.  taps: a HOST
+ *   table (its device copy is kept on the context).  The receiver passes fs = 62 400 and decim = 5.
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_apt_front: "; a refused call writes nothing): fs not above 4800, n_rows < 1,
+ *   x_stride < n_buf, and pss_ddc's refusals for decim, n_taps, lead, the taps, the buffer, the window, env_stride and the alignment.
+ *   One kernel, k_apt_front (discriminator and mixer once per sample into LDS, float64 tap loop from there, one float32 store an output).
+ * pss_apt_syncs: d_env float32 rows e_stride samples apart, 4-byte aligned, holding samples [buf_index0, buf_index0 + n_buf) of rows of n_row
+ *   envelope samples.  Every start s in [s_begin, s_end) of every row with s + 116 < n_row is a candidate: strobes e[k] = env[s + 3 k + 1],
+ *   k = 0 .. 38; a threshold from the mean of e[4 .. 31], the pulse train's own 14 high and 14 low words; at most sync_errors (in [0, 4]) of
+ *   the 39 bits e[k] > thr differ from sync A (000011001100110011001100110011000000000).  A NaN strobe compares false; a NaN or infinite
+ *   threshold leaves 14 mismatches, never accepted.  score = (the sum of the 14 high strobes - the sum of the 14 low ones) / 14.  Of accepted
+ *   starts less than 3120 apart in a row, the one with the fewest mismatches stays, then the highest score, then the earliest.  Records in
+ *   ascending (row, s): d_row int32, d_pos int64 (the first envelope sample of sync A's first word), d_meta uint32 (the mismatches),
+ *   d_score float32, d_count int32 [1] (the TRUE count; nothing is written past max_syncs).  The buffer must hold the samples from
+ *   max(0, s_begin - 3119) to min(n_row, s_end + 3118 + 117); starts outside the window still count as neighbours.
+ *   PSS_E_ARG ("pss_apt_syncs: "; a refused call writes nothing): n_rows outside [1, 2^20], sync_errors outside [0, 4], a buffer or a window
+ *   outside the row, e_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows), a buffer that does not cover the
+ *   window's reach, max_syncs < 0, a null or misaligned pointer.
+ *   Kernels: k_apt_detect (the one pass over every start), then k_starts_scan, k_starts_gather, k_apt_score, k_apt_keep, k_starts_scan,
+ *   k_apt_emit over the survivors of the sync test only (two or three per line).  Scratch on the context (the same buffers as
+ *   pss_adsb_frames', pss_ais_frames' and pss_pocsag_batches'), 2 bytes per start of the largest call and 18 bytes per survivor, grow-only
+ *   and freed by pss_destroy; the call waits once for the count of survivors.
+ * pss_apt_lines: d_env float32 [n_rows] rows of n_row samples, e_stride apart; line l is cut at d_line_pos[l] (int64, ANY value: the caller
+ *   may ask for lines whose sync was not found) of row d_line_row[l] (int32): d_words float32 element l words_stride + j = env[p + 3 j + 1],
+ *   j = 0 .. 2079, +0 where that sample lies outside the row and for a row index outside [0, n_rows).  One kernel, k_apt_lines (a workgroup
+ *   a line).  PSS_E_ARG ("pss_apt_lines: "; a refused call writes nothing): n_rows outside [1, 2^20], n_row outside [0, 2^60],
+ *   e_stride < n_row, n_lines outside [0, 2^24], words_stride < 2080, a null or misaligned pointer.
+ * pss_h_apt_front / _syncs / _lines: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL),
+ *   pss_h_apt_front's starting with its own name, the others' with "pss_apt_syncs: " and "pss_apt_lines: "). */
+int pss_apt_plan(double fs, int *decim, int *up, int *down);
+int pss_apt_default_taps(double *taps, int *n_taps);
+int pss_apt_front(pss_ctx *ctx, const float *d_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, double fs, int decim,
+                  const double *taps, int n_taps, int lead, long m_begin, long m_end, float *d_env, long env_stride);
+int pss_h_apt_front(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, double fs, int decim,
+                    const double *taps, int n_taps, int lead, long m_begin, long m_end, float *h_env, long env_stride);
+int pss_apt_syncs(pss_ctx *ctx, const float *d_env, long n_rows, long e_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                  int sync_errors, int32_t *d_row, int64_t *d_pos, uint32_t *d_meta, float *d_score, int32_t *d_count, int max_syncs);
+int pss_h_apt_syncs(const float *h_env, long n_rows, long e_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                    int sync_errors, int32_t *h_row, int64_t *h_pos, uint32_t *h_meta, float *h_score, int32_t *h_count, int max_syncs);
+int pss_apt_lines(pss_ctx *ctx, const float *d_env, long n_rows, long e_stride, long n_row, const int32_t *d_line_row, const int64_t *d_line_pos,
+                  long n_lines, float *d_words, long words_stride);
+int pss_h_apt_lines(const float *h_env, long n_rows, long e_stride, long n_row, const int32_t *h_line_row, const int64_t *h_line_pos, long n_lines,
+                    float *h_words, long words_stride);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -224,6 +224,16 @@ _SIGS = {
                                      _p, _p, _p, _p, _p, _p, _p, C.c_int]),
     "pss_h_pocsag_batches": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _p, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_apt_plan": (C.c_int, [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pss_apt_default_taps": (C.c_int, [_p, C.POINTER(C.c_int)]),
+    "pss_apt_front": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_double, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long,
+                                _p, C.c_long]),
+    "pss_h_apt_front": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_double, C.c_int, _p, C.c_int, C.c_int, C.c_long, C.c_long,
+                                  _p, C.c_long]),
+    "pss_apt_syncs": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_h_apt_syncs": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_apt_lines": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, _p, _p, C.c_long, _p, C.c_long]),
+    "pss_h_apt_lines": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, _p, _p, C.c_long, _p, C.c_long]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

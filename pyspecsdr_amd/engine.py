@@ -1691,6 +1691,118 @@ class Engine:
         k = min(int(count[0]), room)
         return cw[:k], fx[:k], rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
 
+    # -- NOAA APT: complex64 rows at 62.4 kS/s -> the envelope, the line starts, the lines' words (pss_apt_*; the arithmetic: csrc/pss_apt.h)
+    APT_RATE = 62400
+    APT_ENV_RATE = 12480
+    APT_DECIM = 5
+    APT_LINE_WORDS, APT_LINE_ENV = 2080, 6240
+
+    @staticmethod
+    def apt_plan(fs, lib=None):
+        """pss_apt_plan -> (decim, up, down): the down-converter's decimation min(fs // 62 400, 204) and the resampler's factors to
+        62 400 S/s.  Host code."""
+        lib = lib or L.load()
+        d, u, w = C.c_int(), C.c_int(), C.c_int()
+        if lib.pss_apt_plan(float(fs), C.byref(d), C.byref(u), C.byref(w)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return d.value, u.value, w.value
+
+    @staticmethod
+    def apt_default_taps(lib=None):
+        """pss_apt_default_taps: the front's low-pass, scipy.signal.firwin(79, 1 / 15) bit for bit (float64).  Host code."""
+        return Engine._default_taps(lib, "pss_apt_default_taps", "apt_default_taps")
+
+    @staticmethod
+    def _apt_front_args(lib, n_buf, decim, taps, buf_index0, n_row, lead, m_begin, m_end, env_stride):
+        """The defaults of apt_front / h_apt_front: ddc's, without the words, and the receiver's own taps."""
+        taps = Engine.apt_default_taps(lib) if taps is None else taps
+        return Engine._rds_front_args(lib, n_buf, decim, taps, buf_index0, n_row, lead, m_begin, m_end, env_stride)
+
+    def apt_front(self, d_iq, n_rows, n_buf, d_env, fs=APT_RATE, decim=APT_DECIM, taps=None, x_stride=None, buf_index0=0, n_row=None, lead=None,
+                  m_begin=0, m_end=None, env_stride=None):
+        """d_iq complex64: n_rows rows x_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_row
+        samples -> d_env float32: discriminator, 2400 Hz mixer, decimating FIR and magnitude, output m of row r at element r * env_stride +
+        (m - m_begin).  taps (default apt_default_taps()), lead and the window: as ddc."""
+        taps, a, decim, c, env_stride = self._apt_front_args(self.lib, n_buf, decim, taps, buf_index0, n_row, lead, m_begin, m_end, env_stride)
+        self._dev(self.lib.pss_apt_front, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), *a, float(fs), decim, _ptr(taps), *c,
+                  _ptr(d_env), env_stride)
+
+    @staticmethod
+    def h_apt_front(iq, fs=APT_RATE, decim=APT_DECIM, taps=None, buf_index0=0, n_row=None, lead=None, m_begin=0, m_end=None, lib=None):
+        """pss_h_apt_front on a host array [n_rows][n_buf] or [n_buf] -> float32 [n_rows][m_end - m_begin] or [m_end - m_begin].  Pure host
+        code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        x = np.asarray(iq, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("iq: a 1-D or 2-D complex array")
+        rows = Engine._as_rows(x)
+        taps, a, decim, c, stride = Engine._apt_front_args(lib, rows.shape[1], decim, taps, buf_index0, n_row, lead, m_begin, m_end, None)
+        out = np.empty((rows.shape[0], max(stride, 0)), np.float32)
+        if lib.pss_h_apt_front(_ptr(rows), rows.shape[0], rows.shape[1], *a, float(fs), decim, _ptr(taps), *c, _ptr(out), stride) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out if x.ndim == 2 else out[0]
+
+    def apt_syncs(self, d_env, n_rows, n_buf, d_row, d_pos, d_meta, d_score, d_count, max_syncs, sync_errors=2, e_stride=None, buf_index0=0,
+                  n_row=None, s_begin=0, s_end=None):
+        """d_env float32 at 12.48 kS/s: n_rows rows e_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of
+        n_row samples (default: the buffer is the row) -> the line starts in [s_begin, s_end) (default: to the row's end) of every row,
+        ascending in (row, s): d_row int32, d_pos int64, d_meta uint32 (mismatches), d_score float32, d_count int32 [1] (the true count)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_apt_syncs, _ptr(d_env), int(n_rows), int(n_buf if e_stride is None else e_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, int(sync_errors), _ptr(d_row), _ptr(d_pos), _ptr(d_meta), _ptr(d_score), _ptr(d_count), int(max_syncs))
+
+    @staticmethod
+    def h_apt_syncs(env, sync_errors=2, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_syncs=None, lib=None):
+        """pss_h_apt_syncs on a host float32 array [n_rows][n_buf] or [n_buf] -> (row int32 [k], pos int64 [k], meta uint32 [k], score
+        float32 [k], count): the first k = min(count, max_syncs) records and the true count.  max_syncs: default room for every record.
+        Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(env, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("env: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_syncs is None
+        max_syncs = 64 if grow else int(max_syncs)
+        while True:
+            room = max(max_syncs, 0)
+            rw, pos = np.zeros(room, np.int32), np.zeros(room, np.int64)
+            meta, score, count = np.zeros(room, np.uint32), np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_apt_syncs(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end,
+                                   int(sync_errors), _ptr(rw), _ptr(pos), _ptr(meta), _ptr(score), _ptr(count), max_syncs) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_syncs = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
+
+    def apt_lines(self, d_env, n_rows, n_row, d_line_row, d_line_pos, n_lines, d_words, e_stride=None, words_stride=None):
+        """d_env float32 [n_rows] rows of n_row samples, e_stride apart (default n_row); d_line_row int32 and d_line_pos int64 [n_lines] ->
+        d_words float32, word j of line l at element l * words_stride (default 2080) + j: env[pos + 3 j + 1], +0 outside the row."""
+        self._dev(self.lib.pss_apt_lines, _ptr(d_env), int(n_rows), int(n_row if e_stride is None else e_stride), int(n_row), _ptr(d_line_row),
+                  _ptr(d_line_pos), int(n_lines), _ptr(d_words), int(self.APT_LINE_WORDS if words_stride is None else words_stride))
+
+    @staticmethod
+    def h_apt_lines(env, line_row, line_pos, lib=None):
+        """pss_h_apt_lines on a host float32 array [n_rows][n_row] or [n_row] -> float32 [n_lines][2080].  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(env, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("env: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        lr = np.ascontiguousarray(np.atleast_1d(line_row), np.int32)
+        lp = np.ascontiguousarray(np.atleast_1d(line_pos), np.int64)
+        if lr.shape != lp.shape or lr.ndim != 1:
+            raise ValueError("line_row and line_pos: 1-D lists of one length")
+        words = np.zeros((len(lp), Engine.APT_LINE_WORDS), np.float32)
+        if lib.pss_h_apt_lines(_ptr(rows), max(rows.shape[0], 1), rows.shape[1], rows.shape[1], _ptr(lr), _ptr(lp), len(lp), _ptr(words),
+                               Engine.APT_LINE_WORDS) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return words
+
     def afsk_bits(self, d_audio, n_rows, n, fs, d_bits, sos1200=None, sos2200=None):
         c = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         s1, s2 = c(sos1200), c(sos2200)

@@ -1678,6 +1678,316 @@ def pocsag_recording(samples, fs, center_hz, channels_hz, bauds=(512, 1200, 2400
     return dict(messages=messages, lines=pocsag_lines(messages), batches=batches, fs=_POCSAG_RATE)
 
 
+# ---- NOAA APT: the image of a 137 MHz capture (the arithmetic of the three device stages: csrc/pss_apt.h)
+_APT_RATE = 62400
+_APT_ENV_RATE = 12480
+_APT_LINE_WORDS, _APT_LINE_ENV = 2080, 6240
+_APT_IMAGE_A, _APT_TELEMETRY_A, _APT_HALF = 86, 995, 1040        # the first word of image A and of telemetry A; channel B: + 1040
+_APT_IMAGE_WORDS, _APT_TELEMETRY_WORDS = 909, 45
+_APT_WEDGES = (31.0, 63.0, 95.0, 127.0, 159.0, 191.0, 224.0, 255.0, 0.0)   # wedges 1 .. 9 of 255
+_APT_CHANNEL_IDS = ('1', '2', '3A', '4', '5', '3B')                          # wedge 16 equals wedge 1 .. 6
+_APT_TUNE_BLOCK = 1024                                                       # row samples of a block mean of the discriminator
+
+
+def apt_grid(pos, meta, score, n_env):
+    """The lines' positions from one row's sync records (apt_syncs': pos ascending) -> (line_pos int64 [n], found bool [n]).  The longest
+    chain of records in which each spacing lies within +-3 of a multiple (>= 1) of 6240 is taken; position is fitted against line number by
+    least squares in float64; every line number, negative ones included, whose 6240 samples at floor(fit + 0.5) lie in [0, n_env) is
+    returned in ascending order, with found = a record of the chain carries that number.  Ties: of chains of one length the one with the
+    fewest mismatches in total wins, then the highest total score, then the one whose last record is the earliest; a record's predecessor
+    is chosen by the same order, then the earliest.  No record: no line.  One record: spacing 6240."""
+    pos = np.asarray(pos, np.int64).ravel()
+    meta = np.asarray(meta, np.int64).ravel()
+    score = np.asarray(score, np.float64).ravel()
+    n = len(pos)
+    if not n:
+        return np.zeros(0, np.int64), np.zeros(0, bool)
+    if np.any(np.diff(pos) <= 0):
+        raise ValueError("apt_grid: pos must ascend")
+    # (blen, bmis, bsc)[i] = (length, -mismatches, score) of the best chain that ends at record i; prev[i] its predecessor
+    blen, bmis, bsc = np.ones(n, np.int64), -meta.copy(), score.copy()
+    prev = np.full(n, -1, np.int64)
+    for i in range(1, n):
+        d = pos[i] - pos[:i]
+        k = (d + _APT_LINE_ENV // 2) // _APT_LINE_ENV
+        idx = np.flatnonzero((k >= 1) & (np.abs(d - k * _APT_LINE_ENV) <= 3))
+        if len(idx):
+            j = idx[np.lexsort((-idx, bsc[idx], bmis[idx], blen[idx]))[-1]]   # the best predecessor, the earliest on a tie
+            blen[i], bmis[i], bsc[i], prev[i] = blen[j] + 1, bmis[j] - meta[i], bsc[j] + score[i], j
+    end = int(np.lexsort((-np.arange(n), bsc, bmis, blen))[-1])
+    chain = []
+    while end >= 0:
+        chain.append(end)
+        end = int(prev[end])
+    chain = chain[::-1]
+    p = pos[chain].astype(np.float64)
+    num = np.zeros(len(chain), np.int64)
+    for q in range(1, len(chain)):
+        num[q] = num[q - 1] + (int(pos[chain[q]] - pos[chain[q - 1]]) + _APT_LINE_ENV // 2) // _APT_LINE_ENV
+    if len(chain) == 1:
+        a, b = float(p[0]), float(_APT_LINE_ENV)
+    else:
+        x = num.astype(np.float64)
+        xm, pm = x.mean(), p.mean()
+        b = float(((x - xm) * (p - pm)).sum() / ((x - xm) ** 2).sum())
+        a = float(pm - b * xm)
+    k_lo, k_hi = int(np.floor(-a / b)) - 2, int(np.ceil((n_env - a) / b)) + 2
+    ks = np.arange(k_lo, k_hi + 1, dtype=np.int64)
+    lp = np.floor(a + b * ks.astype(np.float64) + 0.5).astype(np.int64)
+    ok = (lp >= 0) & (lp + _APT_LINE_ENV <= int(n_env))
+    return lp[ok], np.isin(ks[ok], num)
+
+
+def apt_telemetry(words):
+    """words float [n][2080] -> (channel A, channel B), each None where n < 128 or dict(levels float64 [16] (the wedges' means of the raw
+    words), channel ('1', '2', '3A', '4', '5', '3B': the wedge among 1 .. 6 nearest to wedge 16, the first on a tie), gain, offset (255-scale
+    value = gain * word + offset, the least-squares line through the lines of wedges 1 .. 9), phase (the line at which a 128-line frame
+    starts, in [0, 128))).  A line's telemetry value is the mean of the inner 37 of the field's 45 words (the front's filter smears the
+    outer ones).  The phase is the one at which those values correlate best with the staircase 31, 63, 95, 127, 159, 191, 224, 255, 0 of
+    wedges 1 .. 9 (the smallest such phase on a tie)."""
+    w = np.asarray(words, np.float64)
+    if w.ndim != 2 or w.shape[1] != _APT_LINE_WORDS:
+        raise ValueError("words: [n][2080]")
+    n = w.shape[0]
+    out = []
+    stair = np.asarray(_APT_WEDGES)
+    for c in range(2):
+        if n < 128:
+            out.append(None)
+            continue
+        first = _APT_TELEMETRY_A + c * _APT_HALF
+        t = w[:, first + 4:first + _APT_TELEMETRY_WORDS - 4].mean(axis=1)
+        lines = np.arange(n)
+        best, best_phase = -np.inf, 0
+        for phase in range(128):
+            wedge = ((lines - phase) % 128) // 8
+            m = wedge < 9
+            x, y = stair[wedge[m]], t[m]
+            xs, ys = x - x.mean(), y - y.mean()
+            den = np.sqrt((xs * xs).sum() * (ys * ys).sum())
+            r = (xs * ys).sum() / den if den > 0 else -np.inf
+            if r > best:
+                best, best_phase = r, phase
+        wedge = ((lines - best_phase) % 128) // 8
+        m = wedge < 9
+        x, y = stair[wedge[m]], t[m]
+        ys = y - y.mean()
+        var = (ys * ys).sum()
+        gain = float(((x - x.mean()) * ys).sum() / var) if var > 0 else 0.0
+        offset = float(x.mean() - gain * y.mean())
+        levels = np.array([t[wedge == k].mean() if np.any(wedge == k) else np.nan for k in range(16)])
+        ident = int(np.argmin(np.abs(levels[:6] - levels[15])))
+        out.append(dict(levels=levels, channel=_APT_CHANNEL_IDS[ident], gain=gain, offset=offset, phase=best_phase))
+    return tuple(out)
+
+
+def apt_image(words, lo_pct=1, hi_pct=99, telemetry=None):
+    """words float [n][2080] -> uint8 [n][2080].  Without telemetry: the lo_pct-th percentile of the finite words goes to 0 and the
+    hi_pct-th to 255.  telemetry (apt_telemetry's pair): each half of the line (1040 words) is scaled by its own channel's staircase, value
+    = gain * word + offset; a half whose channel is None falls back to the percentiles.  Values are rounded half up and clipped; a word
+    that is not finite gives 0."""
+    w = np.asarray(words, np.float64)
+    if w.ndim != 2 or w.shape[1] != _APT_LINE_WORDS:
+        raise ValueError("words: [n][2080]")
+    fin = np.isfinite(w)
+    if fin.any():
+        lo, hi = np.percentile(w[fin], [lo_pct, hi_pct])
+    else:
+        lo, hi = 0.0, 1.0
+    g = 255.0 / (hi - lo) if hi > lo else 0.0
+    v = (w - lo) * g
+    if telemetry is not None:
+        for c in range(2):
+            if telemetry[c] is not None:
+                half = slice(c * _APT_HALF, (c + 1) * _APT_HALF)
+                v[:, half] = w[:, half] * telemetry[c]['gain'] + telemetry[c]['offset']
+    v = np.where(fin, v, 0.0)
+    return np.clip(np.floor(v + 0.5), 0, 255).astype(np.uint8)
+
+
+def apt_channels(img):
+    """[n][2080] -> (image A, image B), the two 909-column images."""
+    img = np.asarray(img)
+    if img.ndim != 2 or img.shape[1] != _APT_LINE_WORDS:
+        raise ValueError("img: [n][2080]")
+    a, b = _APT_IMAGE_A, _APT_IMAGE_A + _APT_HALF
+    return img[:, a:a + _APT_IMAGE_WORDS], img[:, b:b + _APT_IMAGE_WORDS]
+
+
+def write_pgm(path, img):
+    """uint8 [h][w] -> a binary PGM (P5, maxval 255)."""
+    img = np.ascontiguousarray(img)
+    if img.ndim != 2 or img.dtype != np.uint8:
+        raise ValueError("img: uint8 [h][w]")
+    with open(path, 'wb') as f:
+        f.write(b"P5\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(img.tobytes())
+
+
+def apt_offset(block_means):
+    """The carrier's offset from 0 Hz of one row at 62 400 S/s, in Hz, from the means of its discriminator over blocks of 1024 samples
+    (float32 [n_blocks], rad a sample): the median of the inner blocks (the first and the last see the row's ends), in float64, times
+    62 400 / 2 pi.  The subcarrier has no mean over a block (39.4 cycles), a click of the discriminator spoils one block and the median
+    passes it by.  Fewer than three blocks, or a median that is not finite: 0.0, and the row is left as it is."""
+    m = np.asarray(block_means, np.float64).ravel()[1:-1]
+    if not len(m):
+        return 0.0
+    hz = float(np.median(m)) * _APT_RATE / (2.0 * np.pi)
+    return hz if np.isfinite(hz) else 0.0
+
+
+def _apt_tune_taps():
+    """(the discriminator alone out of pss_ais_front, the block mean for pss_resample, the bare mixer for pss_ddc)"""
+    return np.array([1.0]), np.full(_APT_TUNE_BLOCK + 1, 1.0 / (_APT_TUNE_BLOCK + 1)), np.array([1.0])
+
+
+def _apt_results(n_rows, n_env, records, lines, offsets=None):
+    """The host half of apt_rows: records = (row, pos, meta, score) of all rows; lines(line_row, line_pos) -> words [n][2080]."""
+    row, pos, meta, score = records
+    grids = []
+    for r in range(n_rows):
+        m = row == r
+        grids.append(apt_grid(pos[m], meta[m], score[m], n_env))
+    line_row = np.concatenate([np.full(len(g[0]), r, np.int32) for r, g in enumerate(grids)]) if grids else np.zeros(0, np.int32)
+    line_pos = np.concatenate([g[0] for g in grids]) if grids else np.zeros(0, np.int64)
+    words = lines(line_row, line_pos)
+    out = []
+    for r, (lp, found) in enumerate(grids):
+        m = row == r
+        w = words[line_row == r]
+        tel = apt_telemetry(w)
+        out.append(dict(words=w, image=apt_image(w, telemetry=tel), found=found, pos=lp,
+                        syncs=[dict(pos=int(p), mismatches=int(e), score=float(q)) for p, e, q in zip(pos[m], meta[m], score[m])], telemetry=tel,
+                        offset_hz=0.0 if offsets is None else float(offsets[r])))
+    return out
+
+
+def _apt_host_rows(rows):
+    x = np.asarray(rows, np.complex64)
+    if x.ndim not in (1, 2):
+        raise ValueError("rows: a 1-D or 2-D complex array")
+    return np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+
+
+def h_apt_rows(rows, sync_errors=2, taps=None, tune=True):
+    """apt_rows through the host twins (pss_h_ais_front, pss_h_resample, pss_h_ddc, pss_h_apt_front, pss_h_apt_syncs, pss_h_apt_lines): no
+    GPU, the same bytes."""
+    from .engine import Engine
+    x = _apt_host_rows(rows)
+    if not x.shape[0] or not x.shape[1]:
+        return [dict(words=np.zeros((0, _APT_LINE_WORDS), np.float32), image=np.zeros((0, _APT_LINE_WORDS), np.uint8), found=np.zeros(0, bool),
+                     pos=np.zeros(0, np.int64), syncs=[], telemetry=(None, None), offset_hz=0.0) for _ in range(x.shape[0])]
+    offsets = np.zeros(x.shape[0])
+    if tune:
+        one, box, mix = _apt_tune_taps()
+        means = Engine.h_resample(Engine.h_ais_front(x, pulse=one), 1, _APT_TUNE_BLOCK, taps=box)
+        offsets = np.array([apt_offset(m) for m in means])
+        if offsets.any():
+            x = x.copy()
+            for r in np.flatnonzero(offsets):
+                x[r] = Engine.h_ddc(x[r], [Engine.ddc_word(offsets[r], _APT_RATE)[0]], 1, taps=mix)[0]
+    env = Engine.h_apt_front(x, taps=taps)
+    rw, pos, meta, score, _ = Engine.h_apt_syncs(env, sync_errors=sync_errors)
+    return _apt_results(x.shape[0], env.shape[1], (rw, pos, meta, score), lambda lr, lp: Engine.h_apt_lines(env, lr, lp), offsets)
+
+
+def apt_rows(rows, sync_errors=2, taps=None, tune=True):
+    """rows: complex64 rows at 62 400 S/s — a host array [k][n] or [n], or a resident device tensor float32 [k][2 n] — -> a list per row of
+    dict(words float32 [lines][2080], image uint8 [lines][2080], found bool [lines], pos int64 [lines], syncs, telemetry): pss_apt_front
+    (taps: default apt_default_taps()), pss_apt_syncs, apt_grid on the host (a few records a row), pss_apt_lines at the grid's positions —
+    the lines whose sync was not found included — then apt_telemetry and apt_image.  'syncs': the receiver's records of the row as dicts
+    (pos, mismatches, score); positions count envelope samples at 12 480 S/s.
+    tune: in front of all that each row's carrier is put at 0 Hz, with kernels the library has: the discriminator alone (pss_ais_front
+    with the pulse [1.0]), its means over blocks of 1024 samples (pss_resample, float32, 1 / 1024 with a boxcar), apt_offset on the host
+    (a few hundred numbers a row), and the mixer alone (pss_ddc at decimation 1 with the tap [1.0]); 'offset_hz' is what was taken out.  A
+    carrier off by f leaves the constant 2 pi f / 62 400 in the discriminator, the front's mixer moves it to 2400 Hz, where the default
+    low-pass still passes 0.29 of it, and it beats against the envelope (3 kHz: the image's correlation with what was sent falls from 0.97
+    to 0.92).  tune=False: the rows as they are."""
+    import torch
+    e = get_engine()
+    if isinstance(rows, torch.Tensor):
+        d_rows = rows
+    else:
+        d_rows = torch.from_numpy(_apt_host_rows(rows).view(np.float32)).to(f"cuda:{e.device}")
+    if d_rows.dim() != 2 or d_rows.dtype != torch.float32 or d_rows.shape[1] % 2 or not d_rows.is_contiguous():
+        raise ValueError("rows: a contiguous device tensor float32 [k][2 n]")
+    k, n = d_rows.shape[0], d_rows.shape[1] // 2
+    if not k or not n:
+        return h_apt_rows(np.zeros((k, 0), np.complex64))
+    dev = d_rows.device
+    offsets = np.zeros(k)
+    if tune:
+        one, box, mix = _apt_tune_taps()
+        d_disc = torch.empty((k, n), dtype=torch.float32, device=dev)
+        e.ais_front(d_rows, k, n, d_disc, pulse=one)
+        n_blocks = e.resample_out_len(n, 1, _APT_TUNE_BLOCK)
+        d_means = torch.empty((k, n_blocks), dtype=torch.float32, device=dev)
+        e.resample(d_disc, np.float32, k, n, 1, _APT_TUNE_BLOCK, d_means, taps=box)
+        offsets = np.array([apt_offset(m) for m in d_means.cpu().numpy()])
+        del d_disc
+        if offsets.any():
+            d_tuned = d_rows.clone()
+            for r in np.flatnonzero(offsets):
+                e.ddc(d_rows[r], n, np.array([e.ddc_word(offsets[r], _APT_RATE)[0]], np.uint64), 1, d_tuned[r], taps=mix)
+            d_rows = d_tuned
+    n_env = -(-n // e.APT_DECIM)
+    d_env = torch.empty((k, n_env), dtype=torch.float32, device=dev)
+    e.apt_front(d_rows, k, n, d_env, taps=taps)
+    room = 4096
+    while True:
+        d_row = torch.empty(room, dtype=torch.int32, device=dev)
+        d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+        d_meta = torch.empty(room, dtype=torch.int32, device=dev)
+        d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        e.apt_syncs(d_env, k, n_env, d_row, d_pos, d_meta, d_score, d_count, room, sync_errors=sync_errors)
+        c = int(d_count.cpu()[0])
+        if c <= room:
+            break
+        room = c   # the true count: again with room for it
+    records = tuple(t[:c].cpu().numpy() for t in (d_row, d_pos, d_meta, d_score))
+
+    def lines(line_row, line_pos):
+        if not len(line_pos):
+            return np.zeros((0, _APT_LINE_WORDS), np.float32)
+        d_words = torch.empty((len(line_pos), _APT_LINE_WORDS), dtype=torch.float32, device=dev)
+        e.apt_lines(d_env, k, n_env, torch.from_numpy(line_row).to(dev), torch.from_numpy(line_pos).to(dev), len(line_pos), d_words)
+        return d_words.cpu().numpy()
+
+    return _apt_results(k, n_env, records, lines, offsets)
+
+
+def apt_recording(samples, fs, center_hz, channels_hz=(137.62e6,), taps=None, front_taps=None, sync_errors=2, chunk_samples=1 << 22,
+                  codes_format=None, table=None, tune=True):
+    """The weather-satellite images of a capture centred on center_hz -> dict(rows=apt_rows' list, one entry per channel of channels_hz,
+    fs=12480: the rate the positions count in).  On the GPU from the upload to the words: pss_ddc puts the listed channels at 0 Hz at
+    apt_plan(fs)'s decimation (streamed in chunks of chunk_samples samples plus their halos; the result does not depend on
+    chunk_samples), pss_resample brings them to 62 400 S/s where the decimated rate is another one, then apt_rows (front_taps: its taps;
+    tune: its carrier step).
+    taps: the down-converter's float64 low-pass (default firwin(20 decim + 1, 40 000 / fs): half-width 20 kHz, the reference's NOAA_SAT
+    bandwidth); codes_format / table: as demodulate_recording."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    decim, up, down = e.apt_plan(fs)
+    offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+    if offsets.ndim != 1 or not len(offsets):
+        raise ValueError("channels_hz: a list of frequencies")
+    if taps is None:
+        taps = np.empty(20 * decim + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 40000.0 / fs, taps.ctypes.data) != 0:
+            raise ValueError("apt_recording: the down-converter's filter design failed")
+    d_rows, _ = _tune_device(samples, fs, offsets, decim, taps, None, chunk_samples, codes_format, table)
+    k, m = d_rows.shape[0], d_rows.shape[1] // 2
+    if (up, down) != (1, 1):
+        n = e.resample_out_len(m, up, down)
+        d_bb = torch.empty((k, 2 * max(n, 1)), dtype=torch.float32, device=d_rows.device)
+        if m:
+            e.resample(d_rows, np.complex64, k, m, up, down, d_bb)
+        d_rows, m = d_bb[:, :2 * n].contiguous() if n else d_bb[:, :0], n
+    return dict(rows=apt_rows(d_rows.contiguous(), sync_errors, front_taps, tune), fs=_APT_ENV_RATE)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:

@@ -1,0 +1,51 @@
+"""tests/apt_caps.py against pyspecsdr_amd/csrc/pss_apt.hip, pss_apt.h, pss_ddc.h and pss_starts.h: the constants tests/test_gpu_apt.py
+imports stand in these source lines — no GPU."""
+import os
+import re
+
+import apt_caps as C
+import apt_cases as A
+import launch_caps as L
+
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "pyspecsdr_amd", "csrc")
+SRC = os.path.join(CSRC, "pss_apt.hip")
+
+
+def test_pinned_lines_are_in_the_source():
+    lines = [ln.strip() for ln in open(SRC).read().splitlines()]
+    for name, (value, line) in C.PINS.items():
+        assert lines.count(line) == 1, (name, line)
+        assert re.search(r"= %d;|: %d$" % (value, value), line), (name, value)
+    assert C.PINS["DETECT_LDS"][0] == L.DT_S + C.REACH - 1
+    assert "static_assert(AD_Y == 4212, \"the detect tile's LDS\");" in lines
+    for line in C.LINES:
+        assert lines.count(line) == 1, line
+    header = [ln.strip() for ln in open(os.path.join(CSRC, "pss_apt.h")).read().splitlines()]
+    for line in C.HEADER_LINES:
+        assert header.count(line) == 1, line
+    ddc = open(os.path.join(CSRC, "pss_ddc.h")).read()
+    for line in (f"constexpr int STAGE_CAP = {C.STAGE_CAP};", f"constexpr int PART_CAP = {C.PART_CAP};", f"constexpr int B = {C.BLOCK};"):
+        assert line in ddc, line
+    assert (C.front_tile(5, 79), C.front_tile(5, 1), C.front_tile(1, 4097), C.front_tile(4096, 4097)) == (896, 1637, 27, 1)
+
+
+def test_the_shared_constants_are_pinned_in_the_start_list_header():
+    """The tile, the detect grid cap, the scan step and the list kernels' threads and grid cap: one line each in pss_starts.h, and
+    pss_apt.hip takes them from there (it states none of them itself)."""
+    shared = [ln.strip() for ln in open(os.path.join(CSRC, "pss_starts.h")).read().splitlines()]
+    pinned = [s for row in C.SHARED_ROWS for s in L.RECEIVER_CAPS[row].source["pss_starts.h"]]
+    for line in (f"constexpr int DT_T = {L.DT_T};", f"constexpr int DT_S = {L.DT_S};", f"constexpr long DT_GRID_CAP = {L.DT_GRID_CAP};",
+                 f"constexpr int SC_T = {L.SC_T}, SC_PER = {L.SC_PER};", f"constexpr int LS_T = {L.LS_T};", f"constexpr long LS_GRID_CAP = {L.LS_GRID_CAP};",
+                 "for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {"):
+        assert line in pinned, line
+        assert sum(ln.startswith(line) for ln in shared) == 1, line
+    src = open(SRC).read()
+    assert '#include "pss_starts.h"' in src
+    for name in ("DT_T", "DT_S", "DT_GRID_CAP", "SC_T", "SC_PER", "LS_T", "LS_GRID_CAP"):
+        assert not re.search(rf"constexpr \w+ [^;]*\b{name} =", src), name
+
+
+def test_the_cases_module_agrees():
+    assert A.TILE == C.TILE and (A.REACH, A.NEAR, A.LINE_ENV, A.LINE_WORDS) == (C.REACH, C.NEAR, C.LINE_ENV, C.LINE_WORDS)
+    assert (C.TILE, C.DETECT_GRID_CAP, C.LANE_PASS, C.SCAN_STEP, C.FRONT_GRID_CAP, C.LINES_GRID_CAP) == (4096, 1024, 524288, 4096, 2048, 1024)
+    assert sorted(C.PINS) == ["DETECT_LDS", "FRONT_GRID_CAP", "FRONT_THREADS", "LINES_GRID_CAP", "LINES_THREADS"]
