@@ -17,6 +17,12 @@ LAUNCHES = (
     "hipLaunchKernelGGL(k_ais_front, dim3((unsigned)(n_pairs < FR_GRID_CAP ? n_pairs : FR_GRID_CAP)), dim3(FR_T), 0, PSS_STREAM(ctx),",
     "hipLaunchKernelGGL(k_ais_detect, dim3((unsigned)(n_tiles < DT_GRID_CAP ? n_tiles : DT_GRID_CAP)), dim3(DT_T), 0, PSS_STREAM(ctx), d_y, y_stride, buf_index0,",
     "const dim3 lane_grid(PssStartList::list_grid(n_surv, LS_T)), wave_grid(PssStartList::list_grid(n_surv, LS_T / 64));",
+    # the detect workgroup's way past a tile without survivors, tile_at's division, buffer 1's layout
+    "if (__syncthreads_count(any) == 0) {",
+    "row = tile / tpr;",
+    "const size_t o_words = sizeof(long) * n, o_len = o_words + sizeof(uint32_t) * REC_WORDS * n, o_score = o_len + sizeof(int) * n,",
+    "o_rank = o_score + sizeof(float) * n, o_keep = o_rank + sizeof(int) * n;",
+    "r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + n, \"pss_ais_frames list\");",
 )
 # RECEIVER_CAPS rows of tests/launch_caps.py whose pss_starts.h lines state the shared constants
 SHARED_ROWS = ("adsb_detect", "starts_scan", "starts_gather", "adsb_list")
@@ -24,4 +30,6 @@ SHARED_ROWS = ("adsb_detect", "starts_scan", "starts_gather", "adsb_list")
 FRONT_TILE, FRONT_GRID_CAP = PINS["FRONT_TILE"][0], PINS["FRONT_GRID_CAP"][0]
 TILE, DETECT_GRID_CAP, SCAN_STEP = L.DETECT_TILE, L.DETECT_GRID_CAP, L.SCAN_STEP
 LIST_PASS = L.LS_T * L.LS_GRID_CAP          # survivors one pass of a lane-per-survivor kernel covers: 524 288
+GATHER_GRID_CAP = L.GATHER_GRID_CAP         # tiles one pass of k_starts_gather covers: 2048
+LIST_BYTES = 8 + 4 * 32 + 4 + 4 + 4 + 1     # buffer 1 of the start list, a survivor: the start, 32 record words, length, score, rank, keep
 WAVE = 64

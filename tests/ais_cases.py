@@ -313,3 +313,28 @@ def dense_row(n_patterns, period=80):
         y[at + SPB * np.arange(16)] = lv
         starts.append(at + 8 * SPB)
     return y, starts
+
+
+# ---- the shapes tests/test_gpu_ais.py and tests/test_gpu_start_list.py share (the caps are the callers': tests/ais_caps.py) ----------------------
+SHORT_FRAME = with_crc(SHIPS[0][:4] + bytes([0]))             # 56 bits: the shortest frame
+SHORT_N = 50 + SPB * (len(burst_bits(SHORT_FRAME)) - 1) + 1    # a row of one tile: a burst that starts at 49 ends with it
+
+
+def carrying(n_rows, grid_cap):
+    """The rows of a batch of one-tile rows that carry a record: those of every other round of a detect grid of grid_cap workgroups, and
+    the last.  A workgroup then meets tiles with, without, with, without survivors, and workgroup 0 a fifth that has them."""
+    return [r for r in range(n_rows) if (r // grid_cap) % 2 == 0 or r == n_rows - 1]
+
+
+def short_start(r):
+    return flag_start((3 * r) % 50)
+
+
+def short_rows(n_rows, grid_cap, dense=False):
+    """float32 [n_rows][SHORT_N], one tile a row.  Plain: the shortest burst, its first strobe at (3 r) % 50, in the carrying rows, zeros
+    elsewhere.  dense: that burst with every level held all five samples in EVERY row: five survivors a row, the earliest stays."""
+    y = np.zeros((n_rows, SHORT_N), np.float32)
+    bits = burst_bits(SHORT_FRAME)
+    for r in (range(n_rows) if dense else carrying(n_rows, grid_cap)):
+        y[r] = direct_y(SHORT_N, [(bits, (3 * r) % 50)], hold=SPB if dense else 1)
+    return y

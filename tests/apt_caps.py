@@ -27,6 +27,23 @@ LINES = (
     "hipLaunchKernelGGL(k_apt_emit, lane_grid, dim3(LS_T), 0, PSS_STREAM(ctx), surv, n_surv, tpr, w.e0, keep, rank, mism, score, max_syncs, d_row, d_pos, d_meta,",
     "hipLaunchKernelGGL(k_apt_lines, dim3((unsigned)(n_lines < LN_GRID_CAP ? n_lines : LN_GRID_CAP)), dim3(LN_T), 0, PSS_STREAM(ctx), d_env, n_rows, e_stride, n_row,",
     "for (long l = blockIdx.x; l < n_lines; l += gridDim.x) {",
+    # the detect workgroup's way past a tile without survivors, tile_at's division, the rank cut, buffer 1's layout
+    "if (__syncthreads_count(any) == 0) {",
+    "row = tile / tpr;",
+    "if (r >= max_syncs) continue;",
+    "const size_t o_score = sizeof(long) * n, o_rank = o_score + sizeof(float) * n, o_mism = o_rank + sizeof(int) * n, o_keep = o_mism + n;",
+    "r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + n, \"pss_apt_syncs list\");",
+    # the front's own staging and task walk
+    "const int q0 = tid / L, r0 = tid - q0 * L, dq = FR_T / L, dr = FR_T - dq * L;",
+    "const int pos = r * ROW + q;",
+    "const int G = (cnt + 63) >> 6;",
+    "for (int t = wave; t < n_tasks; t += FR_WAVES) {",
+)
+# pss_ddc.h's lines behind front_tile
+DDC_LINES = (
+    "inline int tile_row(int M, int D, int T) { return (M - 1 + (T + D - 1) / D) | 1; }",
+    "int M = PART_CAP / n_blocks(T);",
+    "while (M > 1 && (long)D * tile_row(M, D, T) > STAGE_CAP) M--;",
 )
 # the header's lines the figures follow from
 HEADER_LINES = (
@@ -39,6 +56,9 @@ SHARED_ROWS = ("adsb_detect", "starts_scan", "starts_gather", "adsb_list")
 
 TILE, DETECT_GRID_CAP, SCAN_STEP = L.DETECT_TILE, L.DETECT_GRID_CAP, L.SCAN_STEP
 LANE_PASS = L.LS_T * L.LS_GRID_CAP          # survivors one pass of the lane-per-survivor kernels (k_apt_score, k_apt_keep, k_apt_emit) covers: 524 288
+GATHER_GRID_CAP = L.GATHER_GRID_CAP         # tiles one pass of k_starts_gather covers: 2048
+LIST_BYTES = 8 + 4 + 4 + 1 + 1              # buffer 1 of the start list, a survivor: the start, its score, rank, mismatches and keep flag
+FRONT_WAVES = PINS["FRONT_THREADS"][0] // 64
 FRONT_GRID_CAP = PINS["FRONT_GRID_CAP"][0]
 LINES_GRID_CAP = PINS["LINES_GRID_CAP"][0]
 WAVE = 64

@@ -208,3 +208,71 @@ def sync_env(n, starts, high=1.0, low=0.2, pattern=SYNC_A, base=None, full=False
     for s in starts:
         e[s:s + len(w)] = w[:max(0, n - s)]
     return e
+
+
+# ---- the shapes tests/test_gpu_apt.py, tests/test_gpu_start_list.py and tests/test_apt_shapes.py share (the caps are the callers': tests/apt_caps.py) ----
+SHORT_N = 300                 # a row of one tile: 184 starts
+
+
+def carrying(n_rows, grid_cap):
+    """The rows of a batch of one-tile rows that carry a record: those of every other round of a detect grid of grid_cap workgroups, and
+    the last.  A workgroup then meets tiles with, without, with, without survivors, and workgroup 0 a fifth that has them."""
+    return [r for r in range(n_rows) if (r // grid_cap) % 2 == 0 or r == n_rows - 1]
+
+
+def short_start(r, dense=False):
+    """Where row r's record lies.  dense: the sync's three samples a word are all high, so the starts one sample either side score the same
+    and the earliest stays."""
+    s = (7 * r) % 183
+    return max(s - 1, 0) if dense else s
+
+
+def short_rows(n_rows, grid_cap, dense=False):
+    """float32 [n_rows][300] for the detect grid's tile reuse, the counts' carry and the gather's second pass: one tile a row.  Plain: a
+    sync at (7 r) % 183 in the carrying rows, 0.2 elsewhere (sync_errors 0: one survivor a sync).  dense: a full sync in EVERY row
+    (sync_errors 4: nine survivors a sync where the row holds them all), so every tile has survivors and every row one record."""
+    env = np.full((n_rows, SHORT_N), 0.2, np.float32)
+    for r in (range(n_rows) if dense else carrying(n_rows, grid_cap)):
+        env[r] = sync_env(SHORT_N, [(7 * r) % 183], full=dense)
+    return env
+
+
+def round_sample(n_rows, grid_cap):
+    """The rows a CPU test restates: the first, the last, and the first, a middle and the last row of every round of the detect grid."""
+    rows = {0, n_rows - 1}
+    for r0 in range(0, n_rows, grid_cap):
+        r1 = min(r0 + grid_cap, n_rows)
+        rows |= {r0, (r0 + r1) // 2, r1 - 1}
+    return sorted(rows)
+
+
+def dense_train(n_tiles, strong):
+    """float32 [n_tiles * TILE - 1000]: full syncs back to back (nine survivors a sync at sync_errors 4, equal scores: each is dropped by
+    the one before it), a quiet stretch behind tile 5, and a sync of three times the height at every start in `strong`."""
+    n = n_tiles * TILE - 1000
+    unit = sync_env(REACH, [0], full=True)
+    env = np.tile(unit, n // REACH + 1)[:n].copy()
+    env[5 * TILE:5 * TILE + 3 * NEAR] = 0.2
+    for s in strong:
+        env[s:s + REACH] = sync_env(REACH, [0], high=3.0)
+    return env
+
+
+GRID_DECIMS = (1, 2, 3, 5, 8, 13, 64, 100, 1000, 4096)
+GRID_TAPS = (1, 2, 63, 64, 65, 128, 129, 1000, 4097)
+
+
+def grid_case(decim, n_taps, tile):
+    """k_apt_front's grid point (decim, n_taps), `tile` = its outputs a tile: (the first decim (2 tile + 3) samples of the noisy case's
+    row: two whole tiles and one of three outputs; seeded taps)."""
+    x = case_row("noise_10db_3khz_40ppm")[:decim * (2 * tile + 3)]
+    assert len(x) == decim * (2 * tile + 3)
+    taps = np.random.default_rng([decim, n_taps]).standard_normal(n_taps) / np.sqrt(n_taps)
+    return x, taps
+
+
+def halo(m0, m1, decim, n_taps, n):
+    """The samples [lo, hi) of a row of n that the outputs [m0, m1) need at the default lead: the taps' span and the discriminator's one
+    sample before it."""
+    lead = (n_taps - 1) // 2
+    return max(0, m0 * decim + lead - (n_taps - 1) - 1), min(n, (m1 - 1) * decim + lead + 1)

@@ -287,6 +287,8 @@ BITS_SCAN_PASS = BT_T
 DETECT_TILE, DETECT_GRID_CAP = DT_S, DT_GRID_CAP
 SCAN_STEP = SC_PER * SC_T
 LIST_PASS = LS_GRID_CAP * (LS_T // 64)    # accepted starts one pass of k_adsb_keep / k_adsb_emit covers
+GATHER_GRID_CAP = LS_GRID_CAP             # tiles one pass of k_starts_gather covers
+ADSB_LIST_BYTES = 4 + 4 + 1               # buffer 1 of the start list, a listed start of pss_adsb_frames: the start, its rank, its keep flag
 
 RECEIVER_CAPS = {
     "rds_front": Cap(
@@ -347,6 +349,8 @@ RECEIVER_CAPS = {
         {"pss_starts.h": [
             f"constexpr int SC_T = {SC_T}, SC_PER = {SC_PER};",
             "for (long b0 = 0; b0 < n; b0 += (long)SC_PER * SC_T) {",
+            "int run = (int)carry + before + inc - mine;",
+            "carry += all;",
             "hipLaunchKernelGGL(k_starts_scan<int>, dim3(1), dim3(SC_T), 0,",
             "hipLaunchKernelGGL(k_starts_scan<uint8_t>, dim3(1), dim3(SC_T), 0,",
         ]}),
@@ -367,6 +371,8 @@ RECEIVER_CAPS = {
             "return (unsigned)(blocks < pss_starts::LS_GRID_CAP ? blocks : pss_starts::LS_GRID_CAP);",
         ], "pss_adsb.hip": [
             "const dim3 wave_grid(PssStartList::list_grid(n_acc, LS_T / 64));",
+            "const size_t o_rank = sizeof(int) * (size_t)n_acc, o_keep = 2 * o_rank;",
+            "r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + (size_t)n_acc, \"pss_adsb_frames list\");",
             "hipLaunchKernelGGL(k_adsb_keep, wave_grid, dim3(LS_T), 0,",
             "hipLaunchKernelGGL(k_adsb_emit, wave_grid, dim3(LS_T), 0,",
             "const long wave = (long)blockIdx.x * (LS_T / 64) + (threadIdx.x >> 6), n_waves = (long)gridDim.x * (LS_T / 64);\n"

@@ -19,6 +19,13 @@ LINES = (
     "hipLaunchKernelGGL(k_pocsag_emit, wave_grid, dim3(LS_T), 0, PSS_STREAM(ctx), surv, n_surv, tpr, w.e0, keep, rank, cw, fixb, meta, score, max_batches, d_cw,",
     "for (long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {",
     "const long n_ext = w.e1 - w.e0, tpr = (n_ext + DT_S - 1) / DT_S, n_tiles = tpr * n_rows;",
+    # the detect workgroup's way past a tile without survivors, tile_at's division, the rank cut, buffer 1's layout
+    "if (__syncthreads_count(any) == 0) {",
+    "row = tile / tpr;",
+    "if (r >= max_batches) continue;",
+    "const size_t o_cw = sizeof(long) * n, o_meta = o_cw + sizeof(uint32_t) * N_CW * n, o_score = o_meta + sizeof(uint32_t) * n,",
+    "o_rank = o_score + sizeof(float) * n, o_fix = o_rank + sizeof(int) * n, o_ok = o_fix + (size_t)N_CW * n, o_keep = o_ok + n;",
+    "r = pss_ensure_buffer(ctx, &starts.buf[1], &starts.cap[1], o_keep + n, \"pss_pocsag_batches list\");",
 )
 # the header's lines the LDS figure follows from
 HEADER_LINES = (
@@ -31,5 +38,7 @@ SHARED_ROWS = ("adsb_detect", "starts_scan", "starts_gather", "adsb_list")
 TILE, DETECT_GRID_CAP, SCAN_STEP = L.DETECT_TILE, L.DETECT_GRID_CAP, L.SCAN_STEP
 LANE_PASS = L.LS_T * L.LS_GRID_CAP          # survivors one pass of the lane-per-survivor kernel (k_pocsag_keep) covers: 524 288
 WAVE_PASS = (L.LS_T // 64) * L.LS_GRID_CAP  # survivors one pass of the wavefront-per-survivor kernels (k_pocsag_walk, k_pocsag_emit) covers: 8192
+GATHER_GRID_CAP = L.GATHER_GRID_CAP         # tiles one pass of k_starts_gather covers: 2048
+LIST_BYTES = 8 + 4 * 16 + 4 + 4 + 4 + 16 + 1 + 1   # buffer 1 of the start list, a survivor: the start, 16 codewords, meta, score, rank, 16 fix bytes, ok, keep
 WAVE = 64
 MAX_SPB = 128

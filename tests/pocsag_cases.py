@@ -313,3 +313,44 @@ def numpy_batches(y, spb, sync_errors=2, fix=2, max_bad=0, buf_index0=0, n_row=N
     return (np.array([o[3] for o in out], np.uint32).reshape(k, 16), np.array([o[4] for o in out], np.uint8).reshape(k, 16),
             np.array([o[0] for o in out], np.int32), np.array([o[1] for o in out], np.int64), np.array([o[5] for o in out], np.uint32),
             np.array([o[2] for o in out], np.float32), count)
+
+
+# ---- the shapes tests/test_gpu_pocsag.py, tests/test_gpu_start_list.py and tests/test_pocsag_shapes.py share (the caps are the callers': tests/pocsag_caps.py) ----
+SHORT_SPB = 2
+SHORT_N = 60 + LAST_K * SHORT_SPB + 1      # a row of one tile: 61 starts
+
+
+def sync_train(n_words, hold=2):
+    """Back-to-back sync words at 2 samples a bit: each is a sync word followed by 16 codewords (the sync word is one), so with hold = 2
+    two starts survive per 64 samples and both are accepted with the same words; the earlier stays."""
+    bits = word_bits(SYNC) * n_words
+    n = 2 * len(bits) + 7
+    return direct_y(n, [(bits, 3)], 2, hold=hold), [3 + 64 * k for k in range(n_words - 16)]
+
+
+def carrying(n_rows, grid_cap):
+    """The rows of a batch of one-tile rows that carry a record: those of every other round of a detect grid of grid_cap workgroups, and
+    the last.  A workgroup then meets tiles with, without, with, without survivors, and workgroup 0 a fifth that has them."""
+    return [r for r in range(n_rows) if (r // grid_cap) % 2 == 0 or r == n_rows - 1]
+
+
+def short_start(r):
+    return (5 * r) % 60
+
+
+def short_rows(n_rows, grid_cap, dense=False):
+    """float32 [n_rows][1147] at 2 samples a bit, one tile a row.  Plain: a batch at (5 r) % 60 in the carrying rows, zeros elsewhere.
+    dense: a batch with every level held both samples in EVERY row: two survivors a row, the earlier stays."""
+    y = np.zeros((n_rows, SHORT_N), np.float32)
+    for r in (range(n_rows) if dense else carrying(n_rows, grid_cap)):
+        y[r] = batch_row(SHORT_SPB, short_start(r), SHORT_N, hold=SHORT_SPB if dense else 1)
+    return y
+
+
+def round_sample(n_rows, grid_cap):
+    """The rows a CPU test restates: the first, the last, and the first, a middle and the last row of every round of the detect grid."""
+    rows = {0, n_rows - 1}
+    for r0 in range(0, n_rows, grid_cap):
+        r1 = min(r0 + grid_cap, n_rows)
+        rows |= {r0, (r0 + r1) // 2, r1 - 1}
+    return sorted(rows)

@@ -43,4 +43,5 @@ def test_the_shared_constants_are_pinned_in_the_start_list_header():
 def test_the_cases_module_agrees():
     assert (A.TILE, A.FRONT_TILE) == (C.TILE, C.FRONT_TILE)
     assert (C.TILE, C.DETECT_GRID_CAP, C.LIST_PASS, C.SCAN_STEP) == (4096, 1024, 524288, 4096)
+    assert (C.GATHER_GRID_CAP, C.LIST_BYTES) == (2048, 149)
     assert sorted(C.PINS) == ["FRONT_GRID_CAP", "FRONT_THREADS", "FRONT_TILE"]

@@ -26,6 +26,9 @@ def test_pinned_lines_are_in_the_source():
     ddc = open(os.path.join(CSRC, "pss_ddc.h")).read()
     for line in (f"constexpr int STAGE_CAP = {C.STAGE_CAP};", f"constexpr int PART_CAP = {C.PART_CAP};", f"constexpr int B = {C.BLOCK};"):
         assert line in ddc, line
+    ddc_lines = [ln.strip() for ln in ddc.splitlines()]
+    for line in C.DDC_LINES:
+        assert ddc_lines.count(line) == 1, line
     assert (C.front_tile(5, 79), C.front_tile(5, 1), C.front_tile(1, 4097), C.front_tile(4096, 4097)) == (896, 1637, 27, 1)
 
 
@@ -48,4 +51,5 @@ def test_the_shared_constants_are_pinned_in_the_start_list_header():
 def test_the_cases_module_agrees():
     assert A.TILE == C.TILE and (A.REACH, A.NEAR, A.LINE_ENV, A.LINE_WORDS) == (C.REACH, C.NEAR, C.LINE_ENV, C.LINE_WORDS)
     assert (C.TILE, C.DETECT_GRID_CAP, C.LANE_PASS, C.SCAN_STEP, C.FRONT_GRID_CAP, C.LINES_GRID_CAP) == (4096, 1024, 524288, 4096, 2048, 1024)
+    assert (C.GATHER_GRID_CAP, C.LIST_BYTES, C.FRONT_WAVES) == (2048, 18, 16)
     assert sorted(C.PINS) == ["DETECT_LDS", "FRONT_GRID_CAP", "FRONT_THREADS", "LINES_GRID_CAP", "LINES_THREADS"]

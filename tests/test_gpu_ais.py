@@ -4,7 +4,8 @@ in the gaps, and a sentinel sits behind max_frames and behind each row's window.
 row lengths around the pulse's half-width and the front's tile, one tile past each grid cap, flags on both sides of a tile boundary, a
 1024-bit frame across two of them, more survivors in a tile than a wavefront holds and more than one pass of the list kernels takes, more
 accepted frames than one step of the scan, more tiles than one step of the scan, a count above max_frames, equal scores, rows that must
-not run into each other, windows with exactly their reach.  The caps and tile sizes come from tests/ais_caps.py, where
+not run into each other, windows with exactly their reach, 4097 one-tile rows whose detect workgroups alternate tiles with and without
+survivors.  The caps and tile sizes come from tests/ais_caps.py, where
 tests/test_ais_caps.py and, for the start list shared with ADS-B, tests/test_launch_caps.py pin them to the source lines."""
 import os
 import re
@@ -17,7 +18,7 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ais_cases as A
-from ais_caps import DETECT_GRID_CAP, FRONT_GRID_CAP, FRONT_TILE, LIST_PASS, SCAN_STEP, TILE, WAVE   # pinned to csrc/pss_ais.hip and pss_starts.h by tests/test_ais_caps.py
+from ais_caps import DETECT_GRID_CAP, FRONT_GRID_CAP, FRONT_TILE, GATHER_GRID_CAP, LIST_PASS, SCAN_STEP, TILE, WAVE   # pinned to csrc/pss_ais.hip and pss_starts.h by tests/test_ais_caps.py
 from bytes_util import same_bytes
 from gpu_util import dev
 from pyspecsdr_amd import formats as F
@@ -209,6 +210,24 @@ def test_more_tiles_than_a_scan_step(e):
     starts = [300, TILE * SCAN_STEP - 1, TILE * SCAN_STEP + 40]
     y = row_with([(good, s - 5 * A.TRAINING) for s in starts], n)
     assert check(e, y)[3].tolist() == starts
+
+
+@pytest.mark.parametrize("dense", [False, True])
+def test_thousands_of_one_tile_rows_and_workgroups_that_alternate_tiles_with_and_without_survivors(e, dense):
+    """SCAN_STEP + 1 rows of one short burst's length: tpr == 1, one tile past a step of the counts' scan and two passes of the gather's
+    grid.  Plain: the rows of every other round of the detect grid carry the burst, so every workgroup meets tiles with, without, with,
+    without survivors and workgroup 0 a fifth with them.  dense: five survivors in every tile."""
+    R = SCAN_STEP + 1
+    assert R > GATHER_GRID_CAP and R > 4 * DETECT_GRID_CAP and A.SHORT_N <= TILE
+    y = A.short_rows(R, DETECT_GRID_CAP, dense)
+    rows = list(range(R)) if dense else A.carrying(R, DETECT_GRID_CAP)
+    full = check(e, y, max_frames=R + 10)
+    assert full[5] == len(rows) == (R if dense else 2 * DETECT_GRID_CAP + 1)
+    assert full[2].tolist() == rows and full[3].tolist() == [A.short_start(r) for r in rows]
+    assert set(frames_of(full)) == {A.SHORT_FRAME}
+    assert check(e, y, max_frames=0)[5] == len(rows)
+    cut = check(e, y, max_frames=len(rows) // 2 + 3)
+    assert cut[5] == len(rows) and cut[2].tolist() == rows[:len(rows) // 2 + 3]
 
 
 def interleaved(n_per_phase, frames=None):

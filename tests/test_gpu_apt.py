@@ -5,7 +5,10 @@ at which each path is taken: 1, 79 and 4097 taps, the lead at both ends, windows
 tile) pair past the front's grid cap; syncs on both sides of a tile boundary and across it, more survivors in a tile than a wavefront holds,
 more survivors than one pass of the lane kernels and more tiles than the detect grid (one case), rows that must not run into each other,
 sync_errors 0 and 4, the row's last candidate, a count above max_syncs, windows with exactly their reach; lines at negative positions and
-past the end, 0, 1 and one line past the gather's grid cap, unsorted positions, mixed rows.  The caps and tile sizes come from
+past the end, 0, 1 and one line past the gather's grid cap, unsorted positions, mixed rows.  Shapes (tests/test_apt_shapes.py runs the
+same arrays on the CPU): the front over a grid of ten decimations and nine tap counts and windows on three strided rows; 4097 one-tile rows
+(the counts' scan carries, the gather's grid walks twice, detect workgroups alternate tiles with and without survivors); a rank cut past
+one pass of the lane kernels.  The caps and tile sizes come from
 tests/apt_caps.py, where tests/test_apt_caps.py and, for the start list, tests/test_launch_caps.py pin them to the source lines."""
 import os
 import re
@@ -18,7 +21,8 @@ torch = pytest.importorskip("torch")
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import apt_cases as A
-from apt_caps import DETECT_GRID_CAP, FRONT_GRID_CAP, LANE_PASS, LINES_GRID_CAP, NEAR, REACH, TILE, WAVE, front_tile   # pinned by tests/test_apt_caps.py
+from apt_caps import (BLOCK, DETECT_GRID_CAP, FRONT_GRID_CAP, FRONT_WAVES, GATHER_GRID_CAP, LANE_PASS, LINES_GRID_CAP, NEAR, REACH, SCAN_STEP, TILE, WAVE,
+                      front_tile)   # pinned by tests/test_apt_caps.py
 from bytes_util import same_bytes
 from gpu_util import dev
 from pyspecsdr_amd import formats as F
@@ -130,6 +134,45 @@ def test_front_one_pair_past_the_grid_cap(e):
     front_check(e, x)                                               # three tiles of one row, the last of three outputs
 
 
+@pytest.mark.parametrize("decim", A.GRID_DECIMS)
+def test_front_grid_of_decimations_and_tap_counts(e, decim):
+    """Two whole tiles and one of three outputs at every tap count of the grid: 1, 2 and 3 tap blocks at every decimation, the tile that
+    STAGE_CAP shrinks (decim 13 to 1000 with few taps), groups of 64 outputs that are no multiple of the workgroup's wavefronts beside many
+    blocks."""
+    for n_taps in A.GRID_TAPS:
+        m = front_tile(decim, n_taps)
+        x, taps = A.grid_case(decim, n_taps, m)
+        assert -(-len(x) // decim) == 2 * m + 3
+        front_check(e, x, decim=decim, taps=taps)
+
+
+def test_the_front_grid_reaches_the_shapes_it_is_there_for():
+    """(no device work) What the grid's points are, from the tile's own figures: block counts 1, 2, 3 at decimations other than 5; a tile
+    cut by STAGE_CAP below its PART_CAP share; a count of 64-output groups that is no multiple of the wavefronts with more than 16 blocks."""
+    shapes = {(d, t): (front_tile(d, t), -(-t // BLOCK)) for d in A.GRID_DECIMS for t in A.GRID_TAPS}
+    for d in A.GRID_DECIMS:
+        assert {shapes[d, t][1] for t in A.GRID_TAPS} >= {1, 2, 3}
+    from apt_caps import PART_CAP
+    assert all(shapes[d, 1][0] < PART_CAP for d in (13, 64, 100, 1000)) and shapes[1, 1][0] == PART_CAP
+    assert any(nb > FRONT_WAVES and -(-m // 64) % FRONT_WAVES for (m, nb) in shapes.values())
+
+
+@pytest.mark.parametrize("decim,n_taps", [(5, 79), (8, 65)])
+def test_front_windows_of_three_rows_with_exactly_their_halo(e, decim, n_taps):
+    """The window test again with three different rows 3 NaNs apart: row * x_stride is not 0 where lo > 0."""
+    from scipy.signal import firwin
+    taps = firwin(n_taps, 1.0 / (3 * decim))
+    rows = np.stack([A.case_row(name)[:30000] for name in sorted(A.CASES)])
+    n = rows.shape[1]
+    whole = Engine.h_apt_front(rows, decim=decim, taps=taps)
+    n_m = whole.shape[1]
+    assert n_m == -(-n // decim) and not same_bytes(whole[0], whole[1]) and not same_bytes(whole[1], whole[2])
+    for m0, m1 in ((0, 1), (17, 18), (100, n_m - 2000), (front_tile(decim, n_taps) - 1, front_tile(decim, n_taps) + 1), (n_m - 10, n_m)):
+        lo, hi = A.halo(m0, m1, decim, n_taps, n)
+        got = front_on_device(e, rows[:, lo:hi], decim=decim, taps=taps, buf_index0=lo, n_row=n, m_begin=m0, m_end=m1, gap=3)
+        assert same_bytes(got, whole[:, m0:m1]), (m0, m1)
+
+
 # ---- syncs ------------------------------------------------------------------------------------------------------------------------------------
 def syncs_on_device(e, env, sync_errors=2, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_syncs=None, gap=3):
     env = np.asarray(env, np.float32)
@@ -233,6 +276,48 @@ def test_more_survivors_than_one_pass_and_more_tiles_than_the_detect_grid(e):
     # on the host over a stretch and scale
     s, _, _ = A.candidates(env[20 * TILE:21 * TILE + REACH], 4)
     assert len(s) * (n // TILE - 4) > LANE_PASS
+
+
+@pytest.mark.parametrize("dense", [False, True])
+def test_thousands_of_one_tile_rows_the_counts_carry_and_the_gathers_second_pass(e, dense):
+    """SCAN_STEP + 1 rows of 300 samples: tpr == 1, one tile past a step of the counts' scan and two passes of the gather's grid.  Plain:
+    the rows of every other round of the detect grid carry one sync, so every workgroup meets tiles with, without, with, without survivors
+    and workgroup 0 a fifth with them; the carry into the last tile is 2048.  dense: nine survivors in every tile: the carry is 36 000."""
+    R = SCAN_STEP + 1
+    assert R > GATHER_GRID_CAP and R > 4 * DETECT_GRID_CAP
+    env = A.short_rows(R, DETECT_GRID_CAP, dense)
+    rows = list(range(R)) if dense else A.carrying(R, DETECT_GRID_CAP)
+    se = 4 if dense else 0
+    full = check(e, env, se, max_syncs=R + 10)
+    assert full[4] == len(rows) == (R if dense else 2 * DETECT_GRID_CAP + 1)
+    assert full[0].tolist() == rows and full[1].tolist() == [A.short_start(r, dense) for r in rows]
+    assert check(e, env, se, max_syncs=0)[4] == len(rows)
+    cut = check(e, env, se, max_syncs=len(rows) // 2 + 3)
+    assert cut[4] == len(rows) and cut[0].tolist() == rows[:len(rows) // 2 + 3]
+
+
+def test_the_rank_cut_falls_past_one_pass_of_the_lane_kernels(e):
+    """The 1709-tile train with two strong syncs whose survivor indices lie past LANE_PASS: max_syncs cuts the second of them, then neither,
+    then both."""
+    n_tiles = 1709
+    strong = [1500 * TILE + 7, 1680 * TILE + 11, 1700 * TILE + 5]
+    env = A.dense_train(n_tiles, strong)
+    s, _, _ = A.candidates(env[20 * TILE:21 * TILE + REACH], 4)
+    assert len(s) * (1680 - 4) > LANE_PASS                            # the survivors in front of the last two, counted over a stretch
+    d_env = dev(env)
+    whole = Engine.h_apt_syncs(env, sync_errors=4, max_syncs=64)
+    assert whole[4] == len(whole[1]) and whole[1].tolist()[-3:] == strong
+    for room in (whole[4] - 1, whole[4], whole[4] - 2):
+        out = [torch.full((room + 3,), -7, dtype=dt, device="cuda") for dt in (torch.int32, torch.int64, torch.int32, torch.float32)]
+        d_count = torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        e.apt_syncs(d_env, 1, len(env), *out, d_count, room, sync_errors=4)
+        e.sync()
+        assert int(d_count.cpu()[0]) == whole[4]
+        k = min(room, whole[4])
+        for t, w, what in zip(out, whole[:4], WHAT):
+            got = t.cpu().numpy()
+            assert same_bytes(got[:k].view(w.dtype), w[:k]), (room, what)
+            assert np.all(got[k:] == -7), (room, what)
 
 
 def test_rows_do_not_run_into_each_other_the_last_candidate_and_max_syncs(e):

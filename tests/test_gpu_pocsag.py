@@ -4,7 +4,9 @@ with NaNs in the gaps, and a sentinel sits behind max_batches.  The shapes are t
 128 samples a bit, sync words on both sides of a tile boundary and across it, one tile past the detect grid cap, more survivors in a tile
 than a wavefront holds and more than one pass of each list kernel takes, more accepted batches than one step of the scan, a count above
 max_batches, equal scores, rows that must not run into each other, both polarities, every fix / sync_errors / max_bad boundary, windows
-with exactly their reach.  The caps and tile sizes come from tests/pocsag_caps.py, where tests/test_pocsag_caps.py and, for the start list,
+with exactly their reach; 4097 one-tile rows (the counts' scan carries, the gather's grid walks twice, detect workgroups alternate tiles
+with and without survivors) and a rank cut past one pass of the wavefront kernels (tests/test_pocsag_shapes.py runs the same arrays on
+the CPU).  The caps and tile sizes come from tests/pocsag_caps.py, where tests/test_pocsag_caps.py and, for the start list,
 tests/test_launch_caps.py pin them to the source lines."""
 import os
 import re
@@ -19,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import pocsag_cases as P
 from bytes_util import same_bytes
 from gpu_util import dev
-from pocsag_caps import DETECT_GRID_CAP, LANE_PASS, SCAN_STEP, TILE, WAVE, WAVE_PASS   # pinned by tests/test_pocsag_caps.py
+from pocsag_caps import DETECT_GRID_CAP, GATHER_GRID_CAP, LANE_PASS, SCAN_STEP, TILE, WAVE, WAVE_PASS   # pinned by tests/test_pocsag_caps.py
 from pyspecsdr_amd import formats as F
 from pyspecsdr_amd.engine import Engine
 
@@ -123,12 +125,7 @@ def test_sync_words_on_both_sides_of_a_tile_boundary_and_across_it(e):
             assert check(e, y, spb)[3].tolist() == [s], (spb, s)
 
 
-def sync_train(n_words, hold=2):
-    """Back-to-back sync words at 2 samples a bit: each is a sync word followed by 16 codewords (the sync word is one), so with hold = 2
-    two starts survive per 64 samples and both are accepted with the same words; the earlier stays."""
-    bits = P.word_bits(P.SYNC) * n_words
-    n = 2 * len(bits) + 7
-    return P.direct_y(n, [(bits, 3)], 2, hold=hold), [3 + 64 * k for k in range(n_words - 16)]
+sync_train = P.sync_train       # (the CPU tests of tests/test_pocsag_shapes.py use the same rows)
 
 
 def test_more_survivors_in_a_tile_than_a_wavefront_holds_and_more_than_a_wave_pass(e):
@@ -151,6 +148,35 @@ def test_more_survivors_than_one_pass_of_the_lane_kernel_and_one_tile_past_the_d
     assert 2 * len(starts) > LANE_PASS and len(y) > TILE * (DETECT_GRID_CAP + 1)
     r = check(e, y, 2, max_batches=50)
     assert r[6] == len(starts) and r[3].tolist() == starts[:50]
+
+
+def test_the_rank_cut_falls_past_one_pass_of_the_wave_kernels(e):
+    """The sync train of the test above: survivors come two a kept start, so record k is survivor 2 k, and max_batches just past
+    WAVE_PASS / 2 cuts in the second pass of k_pocsag_emit's loop."""
+    y, starts = sync_train(WAVE_PASS // 2 + 40)
+    for max_batches in (WAVE_PASS // 2 + 10, WAVE_PASS // 2 + 11, WAVE_PASS // 2 + 9):
+        assert 2 * (max_batches - 1) > WAVE_PASS and 2 * max_batches > WAVE_PASS and max_batches < len(starts)
+        cut = check(e, y, 2, max_batches=max_batches)
+        assert cut[6] == len(starts) and cut[3].tolist() == starts[:max_batches]
+
+
+@pytest.mark.parametrize("dense", [False, True])
+def test_thousands_of_one_tile_rows_the_counts_carry_and_the_gathers_second_pass(e, dense):
+    """SCAN_STEP + 1 rows of 1147 samples at 2 samples a bit: tpr == 1, one tile past a step of the counts' scan and two passes of the
+    gather's grid.  Plain: the rows of every other round of the detect grid carry one batch, so every workgroup meets tiles with, without,
+    with, without survivors and workgroup 0 a fifth with them; the carry into the last tile is 2048.  dense: two survivors in every tile:
+    the carry is 8192."""
+    R = SCAN_STEP + 1
+    assert R > GATHER_GRID_CAP and R > 4 * DETECT_GRID_CAP
+    y = P.short_rows(R, DETECT_GRID_CAP, dense)
+    rows = list(range(R)) if dense else P.carrying(R, DETECT_GRID_CAP)
+    full = check(e, y, P.SHORT_SPB, max_batches=R + 10)
+    assert full[6] == len(rows) == (R if dense else 2 * DETECT_GRID_CAP + 1)
+    assert full[2].tolist() == rows and full[3].tolist() == [P.short_start(r) for r in rows]
+    assert all(w.tolist() == P.WORDS for w in full[0][[0, len(rows) // 2, -1]]) and not full[1].any()
+    assert check(e, y, P.SHORT_SPB, max_batches=0)[6] == len(rows)
+    cut = check(e, y, P.SHORT_SPB, max_batches=len(rows) // 2 + 3)
+    assert cut[6] == len(rows) and cut[2].tolist() == rows[:len(rows) // 2 + 3]
 
 
 def test_one_tile_past_the_detect_grid_cap(e):

@@ -37,6 +37,7 @@ def test_receiver_caps_at_the_shapes_the_gpu_tests_run():
     assert (c.DETECT_TILE, c.DETECT_GRID_CAP, c.SCAN_STEP, c.LIST_PASS, c.FRONT_GRID_CAP, c.BITS_SCAN_PASS) == (4096, 1024, 4096, 8192, 2048, 256)
     assert RECEIVER_CAPS["rds_energy"].cover(1100) == 16384 and RECEIVER_CAPS["rds_energy"].cover(257 * 1024 + 17) == 16384 // 17
     assert RECEIVER_CAPS["adsb_list"].cover() == c.LIST_PASS and RECEIVER_CAPS["starts_scan"].cover() == c.SCAN_STEP
+    assert (c.GATHER_GRID_CAP, c.ADSB_LIST_BYTES) == (2048, 9)
     assert RECEIVER_CAPS["starts_gather"].cover() == 2048 and RECEIVER_CAPS["rds_bits"].cover() == RECEIVER_CAPS["rds_groups"].cover() == 4096
 
 

@@ -43,4 +43,5 @@ def test_the_shared_constants_are_pinned_in_the_start_list_header():
 def test_the_cases_module_agrees():
     assert P.TILE == C.TILE
     assert (C.TILE, C.DETECT_GRID_CAP, C.LANE_PASS, C.WAVE_PASS, C.SCAN_STEP) == (4096, 1024, 524288, 8192, 4096)
+    assert (C.GATHER_GRID_CAP, C.LIST_BYTES) == (2048, 102)
     assert sorted(C.PINS) == ["DETECT_LDS"]
