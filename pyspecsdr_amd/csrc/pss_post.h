@@ -131,6 +131,15 @@ __device__ __forceinline__ K row_reduce(K v, unsigned long long *red, int wave, 
     return s;
 }
 
+// The guess brackets of the compacting selects, half-widths in dB around the row's mean, tried in this order.  The first is sized to CAP = 64 CPL
+// candidates: +-0.5 dB holds 136 of a benchmark row's 1020 keys on average (more than 128 on 7 rows in 10: a wasted compaction sweep, a halving
+// sweep and a second compaction), +-0.35 dB holds 95 (more than 128 on 2 rows in 1000) and rank k on 99 rows in 100; a miss costs the next rung.
+// 0.35 is the width with the fewest full-row sweeps per row over the row families of tools/bracket_ladder.py, 2.03 instead of 3.41 on the
+// benchmark's rows (profiles/bracket_ladder.txt).  select_kth (rows of several wavefronts, and the rows the compaction gives up on) has no
+// candidate buffer to fit and keeps the two wide rungs.
+constexpr int N_BRACKETS = 3;
+__device__ __forceinline__ float bracket_db(int attempt) { return attempt == 0 ? 0.35f : attempt == 1 ? 0.5f : 2.0f; }
+
 // number of keys of the row below `trial`.  The per-lane count is accumulated on the vector unit (v_cmp + v_addc per
 // element) and reduced once: counting each register slot with ballot + s_bcnt1 + s_add instead put 2 scalar instructions
 // per element on the CU's single scalar unit and made the kernel scalar-issue bound (measured: 0.23 ms at 65536 x 1024).
@@ -178,8 +187,8 @@ __device__ __forceinline__ K select_kth(const K (&key)[EPL], unsigned k, unsigne
     if (mn == mx) { next = mn; below = 0; upto = n_valid; return mn; }   // a constant row (n_valid >= 2 wherever next is used)
     if (have_guess && mx != PAD) {
 #pragma unroll 1
-        for (int attempt = 0; attempt < 2; attempt++) {
-            const float d = attempt ? 2.0f : 0.5f;
+        for (int attempt = 1; attempt < N_BRACKETS; attempt++) {
+            const float d = bracket_db(attempt);
             K lo = enc(-d), hi = enc(d);
             lo = lo < mn ? mn : lo;
             hi = hi > mx ? mx : hi;
@@ -317,7 +326,7 @@ __device__ __forceinline__ void select_kth64(const unsigned (&kh)[EPL], const un
 // The row's extreme keys come from v_min_f64 / v_max_f64 over the smoothed values (the caller reduces them before the search) — valid
 // because this path is only taken for rows without a NaN (the row's mean, `guess`, is a sum over every element).
 // Every result is decided by exact counts, as in select_kth; returns false — v1 / v2 untouched, only the idle staging buffer written — when the
-// row does not fit the scheme (NaN or infinite mean, rank k outside both brackets, more than 64 CPL keys sharing one high word): the caller then
+// row does not fit the scheme (NaN or infinite mean, rank k outside every bracket, more than 64 CPL keys sharing one high word): the caller then
 // runs select_kth64.
 #ifndef PSS_POST_CPL
 #define PSS_POST_CPL 2       // candidates per lane after the compaction (3 / 4: measured no faster, NOTEBOOK R6-14)
@@ -394,8 +403,8 @@ __device__ __forceinline__ bool select_kth64_compact(const unsigned (&kh)[EPL], 
     int phase = 0;
     auto join = [](unsigned h, unsigned l) { return ((K)h << 32) | l; };
 #pragma unroll 1
-    for (int attempt = 0; attempt < 2; attempt++) {
-        const float d = attempt ? 2.0f : 0.5f;
+    for (int attempt = 0; attempt < N_BRACKETS; attempt++) {
+        const float d = bracket_db(attempt);
         // (finite values: high words below 0xfff00000, so hi + 1 cannot wrap and the padding keys — all ones — are never counted)
         // wave-uniform by construction; said so (v_readfirstlane), the search's 64-bit bracket arithmetic below runs on the scalar unit instead of
         // as a dependent chain of a dozen vector instructions per pass
@@ -496,8 +505,8 @@ __device__ __forceinline__ bool select_kth32_compact(const unsigned (&key)[EPL],
     if (!(guess - guess == 0.0f)) return false;               // NaN or infinite mean
     int phase = 0;
 #pragma unroll 1
-    for (int attempt = 0; attempt < 2; attempt++) {
-        const float d = attempt ? 2.0f : 0.5f;
+    for (int attempt = 0; attempt < N_BRACKETS; attempt++) {
+        const float d = bracket_db(attempt);
         // (finite values: keys below 0xff800000, so hi + 1 cannot wrap and the padding keys are never inside a bracket)
         unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)f2ord(guess - d));
         unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)f2ord(guess + d));
@@ -644,6 +653,15 @@ struct StagedRow {
     __device__ __forceinline__ T operator[](int e) const { return buf[(e / EPL) * PostCfg<EPL, T>::S + (e % EPL)]; }
 };
 
+// the SMOOTHED float64 row in the staging layout, clamped below `thr` where it is read: max(s, thr) by v_max_f64 is the maximum of the ordered
+// images for operands without a NaN (-0 < +0 in both), which is what post_row_staged's clamp of a whole row stores
+template <int EPL>
+struct ClampedStagedRow {
+    const double *buf;
+    double thr;
+    __device__ __forceinline__ double operator[](int e) const { return vmax_f64(buf[(e / EPL) * PostCfg<EPL, double>::S + (e % EPL)], thr); }
+};
+
 // One row, staged in LDS in the per-thread-consecutive layout (element e at buf[(e / EPL) * S + e % EPL]) and already
 // synchronised: 5-tap smoothing, median, clamp, the clamped row out through the same staging buffer (coalesced 16-byte
 // stores to out4), the row's finite extremes.  slot[j]: LDS slot of the 16-byte chunk j * T + t.  Ends with a row_sync
@@ -656,7 +674,16 @@ struct StagedRow {
 // reads disp_w values per row instead of the row (k_disp_vals_win).
 // TR = float: the float32 rows of pss_spectrum_db (sums in float64, rounded once); TR = double: the reference's own row type throughout
 // (np.median of a row with a NaN is NaN and clamps nothing).
-template <int EPL, int W, bool FULL, class TR>
+// READ_CLAMP (float64 rows of one wavefront that are NOT written: out4 == nullptr; the fused kernel): the clamped row is not formed at all.
+// Its only reader is interp_at — two elements per display column, 224 of 1020 —, so the 16 smoothed doubles of a lane go back over the lane's
+// raw values as they are (every lane of the wavefront has read its window by then) and the two values a column reads are clamped there
+// (ClampedStagedRow): 4 v_max_f64 per lane instead of a 64-bit compare, two selects and the decoding of 16 keys.  A row whose threshold is the
+// lowest image (a NaN in the row, or a NaN median) clamps nothing: its smoothed row is read as it is — the bits the clamp loop stores for it.
+// (The last lane's padding slots store their sums — formed from the unwritten halo stride: garbage — into elements m .. m + 3 of the staged row as
+// well; interp_at reads no element beyond m - 1.)
+// The compaction's candidates then live behind the row's 64 lane strides (buf + 64 S: the halo stride, which only padding reads, and what follows;
+// the caller provides room for m keys from there).
+template <int EPL, int W, bool FULL, class TR, bool READ_CLAMP = false>
 __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostCfg<EPL, TR>::Q], int t, int m, unsigned long long *red, int wave,
                                                 int lane, int &phase, float4 *out4, TR *row_lo, TR *row_hi, long f, TR *row_thr = nullptr,
                                                 double *vals = nullptr, int disp_w = 0)
@@ -667,6 +694,7 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
     constexpr int T = 64 * W, S = PC::S, Q = PC::Q, CH = PC::CH;
     constexpr int PAD_FROM = FULL ? EPL - 4 : 0;
     constexpr bool F64 = sizeof(TR) == 8;
+    static_assert(!READ_CLAMP || (F64 && W == 1), "READ_CLAMP: float64 rows of one wavefront");
     const int mq = m / CH;                       // whole 16-byte chunks of the output row (m % CH == 0: m = N - 4, N % 4 == 0)
     const int nv = m - t * EPL;                  // this thread's slots r < nv hold elements of the smoothed row
     // EPL consecutive elements + the next thread's first four (the 5-tap window of the last four outputs)
@@ -677,6 +705,7 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
     float fmin32 = INFINITY, fmax32 = -INFINITY; // (float32 rows: the same)
     {
         double xd[EPL + 4];
+        double smv[READ_CLAMP ? EPL : 1];
 #pragma unroll
         for (int i = 0; i < Q + PC::TAILQ; i++) {
             const float4 v = *reinterpret_cast<const float4 *>(buf + (i < Q ? t * S + CH * i : (t + 1) * S + CH * (i - Q)));
@@ -701,6 +730,7 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
             if constexpr (F64) { kh[r] = (unsigned)(kk0 >> 32); kl[r] = (unsigned)kk0; }
             else key[r] = kk0;
             lsum += pad ? 0.0f : (float)sm;
+            if constexpr (READ_CLAMP) smv[r] = (double)sm;
             if constexpr (!F64 && W == 1) {
                 if (FULL && r < PAD_FROM) { fmin32 = vmin_f32(fmin32, (float)sm); fmax32 = vmax_f32(fmax32, (float)sm); }
                 else { fmin32 = vmin_f32(fmin32, pad ? INFINITY : (float)sm); fmax32 = vmax_f32(fmax32, pad ? -INFINITY : (float)sm); }
@@ -709,6 +739,11 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
                 if (FULL && r < PAD_FROM) { dmin = vmin_f64(dmin, (double)sm); dmax = vmax_f64(dmax, (double)sm); }
                 else { dmin = vmin_f64(dmin, pad ? (double)INFINITY : (double)sm); dmax = vmax_f64(dmax, pad ? -(double)INFINITY : (double)sm); }
             }
+        }
+        if constexpr (READ_CLAMP) {
+            wave_lds_sync();                     // every lane's window reads (its neighbour's first four values among them) come before the stores
+#pragma unroll
+            for (int i = 0; i < Q; i++) *reinterpret_cast<double2 *>(buf + t * S + CH * i) = make_double2(smv[CH * i], smv[CH * i + 1]);
         }
     }
     // the row's mean: where the median search starts looking (select_kth; a hint only, never part of a result)
@@ -723,7 +758,7 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
             // (the row's extreme keys first: two wave-uniform results instead of two per-lane doubles kept across the search)
             mn = wave_extreme_key_f64<true>(dmin);
             mx = wave_extreme_key_f64<false>(dmax);
-            done = select_kth64_compact<EPL, PSS_POST_CPL>(kh, kl, k1, v1, v2, reinterpret_cast<K *>(buf), lane, guess);
+            done = select_kth64_compact<EPL, PSS_POST_CPL>(kh, kl, k1, v1, v2, reinterpret_cast<K *>(READ_CLAMP ? buf + T * S : buf), lane, guess);
         }
 #endif
         if (!done) select_kth64<EPL, W, PAD_FROM>(kh, kl, k1, (unsigned)m, v1, v2, mn, mx, red, wave, lane, phase, guess);
@@ -757,7 +792,17 @@ __device__ __forceinline__ void post_row_staged(TR *buf, const int (&slot)[PostC
     }
     if (row_thr && t == 0) row_thr[f] = O::dec(thr);
     row_sync<W == 1>();                      // every thread has read its input window
-    if (out4 || vals) {
+    if constexpr (READ_CLAMP) {
+        if (vals) {
+            if (thr == 0) {                      // (wave-uniform) nothing to clamp: a NaN in the row or a NaN median
+                const StagedRow<EPL, TR> row{buf};
+                for (int x = t; x < disp_w; x += T) vals[(size_t)f * disp_w + x] = interp_at(row, m, disp_w, x);
+            } else {
+                const ClampedStagedRow<EPL> row{buf, O::dec(thr)};
+                for (int x = t; x < disp_w; x += T) vals[(size_t)f * disp_w + x] = interp_at(row, m, disp_w, x);
+            }
+        }
+    } else if (out4 || vals) {
 #pragma unroll
         for (int i = 0; i < Q; i++) {
             TR o[CH];

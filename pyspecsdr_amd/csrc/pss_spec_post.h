@@ -6,8 +6,9 @@
 // Why: as two kernels (k_spectrum_r16<D64> -> k_post_sel<double>) the float64 rows are written (8 bytes per bin) and read straight back: 1.07 GB of
 // the step's 3.7 GB at 65 536 x 1024.  A frame of 1024 points IS one wavefront in both kernels (16 values per lane), so the row can stay where it
 // is: the 16 float64 dB values of a lane go through the frame's (then idle) exchange buffer into k_post_sel's per-thread-consecutive layout and
-// pss_post::post_row_staged runs on them unchanged — the same smoothing, the same select on the keys' high words, the same clamp, extremes and
-// np.interp: the same bits.  What reaches HBM per frame: the dB row ONCE — float32 (db32: compute_fft's float64 value rounded once, the
+// pss_post::post_row_staged runs on them — the same smoothing, the same select on the keys' high words, the same extremes and np.interp; the
+// clamp is applied to the two smoothed values a display column reads (READ_CLAMP: the clamped row itself is never formed): the same bits.
+// What reaches HBM per frame: the dB row ONCE — float32 (db32: compute_fft's float64 value rounded once, the
 // 1e-4-relative contract of the spectrum output: 4 bytes per bin) and / or float64 (db64: the reference's own row type) —, 16 bytes of
 // extremes and disp_w float64 resampled values.
 // Included by pss_fft.hip behind pss_fft_r16.h and pss_post.h.
@@ -43,6 +44,10 @@ __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restri
     constexpr int EPL = 16;
     using PC = pss_post::PostCfg<EPL, double>;
     static_assert((size_t)(T + 1) * PC::S * sizeof(double) <= (size_t)C::EX * sizeof(double2), "the staged row fits the frame's exchange buffer");
+    // READ_CLAMP keeps the smoothed row in the 64 lane strides (64 * 18 * 8 = 9216 bytes) while the select compacts its candidates — up to all
+    // N - 4 = 1020 keys of a constant row, 8160 bytes — behind them: 17 376 of the buffer's 17 408 bytes
+    static_assert((size_t)T * PC::S * sizeof(double) + (size_t)(N - 4) * sizeof(unsigned long long) <= (size_t)C::EX * sizeof(double2),
+                  "the smoothed row and a whole row of candidates fit the frame's exchange buffer side by side");
     extern __shared__ __align__(16) unsigned char smem[];
     double2 *ex_all = reinterpret_cast<double2 *>(smem);
     double2 *tw2 = ex_all + (size_t)FPW * C::EX;
@@ -130,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void k_spectrum_post(const float2 *__restri
             int slot[PC::Q];
 #pragma unroll
             for (int j = 0; j < PC::Q; j++) slot[j] = 0;       // (only used for materialised post-processed rows: none here)
-            pss_post::post_row_staged<EPL, 1, true, double>(stage, slot, t, N - 4, nullptr, fl, t, phase, nullptr, row_lo, row_hi, f, nullptr, vals, disp_w);
+            pss_post::post_row_staged<EPL, 1, true, double, true>(stage, slot, t, N - 4, nullptr, fl, t, phase, nullptr, row_lo, row_hi, f, nullptr, vals, disp_w);
         }
         frame_sync<true>();                                    // the next frame's stage 1 overwrites the buffer
     }
