@@ -116,6 +116,26 @@ int pss_get_nfm_filters(pss_ctx *ctx, double fs, double *taps65, double *sos4x6,
 int pss_get_ssb_taps(pss_ctx *ctx, double fs, double *taps65);
 
 /* ---- batched device entry points --------------------------------------------------------------- */
+/* Pointer alignment.  A caller does not have to hand these entry points whole allocations: a capture resident on the device may be cut
+ * into frames at any sample (d_capture + 2 * k floats), a float32 row may lie inside a larger grid, a PCM ring may be written at a running
+ * offset.  A device pointer is valid when it is aligned to ONE RECORD of its documented layout:
+ *     complex64 samples (d_iq, d_out_iq)            one sample            8 bytes
+ *     float32 values (dB rows, extremes, power ...)  one value             4
+ *     float64 values, complex128 (re, im) values     one float64           8
+ *     int16 PCM [n_out][2]                           one [L, R] pair       4
+ *     int32 / uint32 values (indices, counts, masks) one value             4
+ *     int8 / uint8 grids, lines, bits, flags         one byte              1
+ * Every entry point from here to pss_lfilter, and pss_afsk_bits, pss_np_f32 and pss_row_normalise further down, SERVES such a pointer
+ * with the bytes it produces for a 256-byte-aligned one: where a kernel moves 8 or 16 bytes per lane on a caller's buffer it does so
+ * with plain address arithmetic on the pointer as given (or aligns itself, as k_vector_masks does), and no atomic operation is ever made
+ * on a caller's buffer.  A pointer BELOW its record's alignment (a d_pcm at 2 bytes, a float32 row at 2, a d_iq at 4) is refused before
+ * anything is launched: PSS_E_ARG, "<entry point>: <argument> must be <n>-byte aligned", outputs untouched.  Either way a call touches
+ * no byte outside its documented buffers and never writes its inputs.  (Serving a float32 row or a PCM pointer 4 bytes off a 16-byte boundary
+ * relies on MEASURED behaviour of gfx950 under the driver's default memory configuration — multi-dword vector-memory accesses need dword
+ * alignment only —, not on an architectural guarantee: a port re-runs tests/test_gpu_views_of_buffers.py.)  PARITY.md ("Views of buffers") lists every access wider than its
+ * buffer's record with file and line; tests/test_gpu_views_of_buffers.py runs every entry point one record off, between guard bands.
+ * The units further down that take strides and capture offsets (pss_ddc .. pss_apt_lines, pss_unpack_iq, pss_live_frames,
+ * pss_demod_gated, pss_decode_mono) state their own alignment rules where they are declared. */
 /* compute_fft (signal_processing.py:243-264) for n_frames frames: Hamming window, n_fft-point FFT (float64
  * butterflies), fftshift, 10*log10(|X|^2 + 1e-10).  d_db: float32 [n_frames][n_fft].
  * n_fft: a power of two in [16, 1048576] (register / LDS radix-16 kernels), or any other length in [2, 524288]

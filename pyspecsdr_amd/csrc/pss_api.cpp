@@ -18,6 +18,14 @@ int pss_fail(pss_ctx *ctx, int code, const std::string &msg)
     return code;
 }
 
+int pss_ptrs_aligned(pss_ctx *ctx, const char *entry, std::initializer_list<PssPtr> ptrs)
+{
+    for (const PssPtr &a : ptrs)
+        if (reinterpret_cast<uintptr_t>(a.p) & (a.align - 1))
+            return pss_fail(ctx, PSS_E_ARG, std::string(entry) + ": " + a.name + " must be " + std::to_string(a.align) + "-byte aligned");
+    return PSS_OK;
+}
+
 int pss_hip_check(pss_ctx *ctx, hipError_t e, const char *what)
 {
     if (e == hipSuccess) return PSS_OK;

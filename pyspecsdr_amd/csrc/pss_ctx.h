@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -211,6 +213,18 @@ using PssStreamScope = PssScoped<hipStream_t>;
 
 int pss_fail(pss_ctx *ctx, int code, const std::string &msg);
 int pss_hip_check(pss_ctx *ctx, hipError_t e, const char *what);
+// The core entry points' pointer contract (include/pss.h, "pointer alignment"): a device pointer is valid when it is aligned to one record
+// of its buffer (complex64 sample 8, float32 4, float64 / complex128 value 8, int16 [L, R] pair 4, int32 4); anything below that is refused
+// here, before the first launch, with a message that names the argument.  A null pointer passes (whether it may be null is the entry
+// point's own rule).  Which wider accesses the kernels make on such pointers, and why they are served: PARITY.md, "Views of buffers".
+struct PssPtr { const void *p; unsigned align; const char *name; };
+int pss_ptrs_aligned(pss_ctx *ctx, const char *entry, std::initializer_list<PssPtr> ptrs);
+#define PSS_P(x, bytes) PssPtr{(x), (bytes), #x}
+#define PSS_ALIGNED(ctx, entry, ...)                                      \
+    do {                                                                  \
+        int _a = pss_ptrs_aligned((ctx), (entry), {__VA_ARGS__});         \
+        if (_a) return _a;                                                \
+    } while (0)
 int pss_ensure_scratch(pss_ctx *ctx, size_t bytes);
 int pss_ensure_buffer(pss_ctx *ctx, void **buf, size_t *cap, size_t bytes, const char *what);
 // Make t's device copy hold the `bytes` bytes at `img`: nothing where the mirror already equals them, otherwise an upload on the context's

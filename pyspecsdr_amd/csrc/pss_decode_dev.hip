@@ -391,6 +391,7 @@ extern "C" int pss_morse_text(pss_ctx *ctx, const int32_t *d_rise, const int32_t
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || cap < 0 || text_cap < 0 || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_morse_text: bad argument (n_frames, cap, text_cap >= 0, fs > 0)");
+    PSS_ALIGNED(ctx, "pss_morse_text", PSS_P(d_rise, 4), PSS_P(d_fall, 4), PSS_P(d_counts, 4), PSS_P(d_text_len, 4), PSS_P(d_timing, 8), PSS_P(d_pulses, 4));
     if (n_frames == 0) return PSS_OK;
     if (!d_counts || !d_text_len || !d_timing || !d_pulses || (cap > 0 && (!d_rise || !d_fall)) || (text_cap > 0 && !d_text))
         return pss_fail(ctx, PSS_E_ARG, "pss_morse_text: null buffer");
@@ -406,6 +407,7 @@ extern "C" int pss_ax25_frames(pss_ctx *ctx, const uint8_t *d_bits, long n_rows,
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || n_bits < 0 || out_cap < 0) return pss_fail(ctx, PSS_E_ARG, "pss_ax25_frames: bad argument (n_rows, n_bits, out_cap >= 0)");
+    PSS_ALIGNED(ctx, "pss_ax25_frames", PSS_P(d_out_len, 4));
     if (n_rows == 0) return PSS_OK;
     if (!d_out_len || (n_bits > 0 && !d_bits) || (out_cap > 0 && !d_out)) return pss_fail(ctx, PSS_E_ARG, "pss_ax25_frames: null buffer");
     const long groups = (n_rows + 3) / 4;
@@ -421,6 +423,7 @@ extern "C" int pss_real_normalise(pss_ctx *ctx, const float *d_iq, long n_rows, 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || n < 0 || (n_rows > 0 && n > 0 && (!d_iq || !d_audio))) return pss_fail(ctx, PSS_E_ARG, "pss_real_normalise: bad argument");
+    PSS_ALIGNED(ctx, "pss_real_normalise", PSS_P(d_iq, 8), PSS_P(d_audio, 8));
     if (n_rows == 0 || n == 0) return PSS_OK;
     pss_kernel_begin(ctx, "k_real_normalise");
     hipLaunchKernelGGL(k_real_normalise, dim3((unsigned)(n_rows < RN_GRID_MAX ? n_rows : RN_GRID_MAX)), dim3(256), 0, PSS_STREAM(ctx),
@@ -439,6 +442,8 @@ extern "C" int pss_decode_morse_batch(pss_ctx *ctx, const float *d_iq, long n_fr
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || cap < 0 || text_cap < 0 || !(fs > 0.0))
         return pss_fail(ctx, PSS_E_ARG, "pss_decode_morse_batch: bad argument (n_frames, cap, text_cap >= 0, n >= 1, fs > 0)");
+    PSS_ALIGNED(ctx, "pss_decode_morse_batch", PSS_P(d_iq, 8), PSS_P(d_rise, 4), PSS_P(d_fall, 4), PSS_P(d_counts, 4), PSS_P(d_text_len, 4), PSS_P(d_timing, 8),
+                PSS_P(d_pulses, 4));
     if (n_frames == 0) return PSS_OK;
     PssTimeScope timed(ctx);
     int r = pss_morse_edges(ctx, d_iq, n_frames, n, threshold_db, cap, d_rise, d_fall, d_counts);
@@ -453,6 +458,7 @@ extern "C" int pss_decode_aprs_batch(pss_ctx *ctx, const float *d_iq, long n_row
     PSS_GUARD(ctx);
     if (n_rows < 0 || n < 0 || out_cap < 0 || !(fs >= 1200.0))
         return pss_fail(ctx, PSS_E_ARG, "pss_decode_aprs_batch: bad argument (n_rows, n, out_cap >= 0, fs >= 1200)");
+    PSS_ALIGNED(ctx, "pss_decode_aprs_batch", PSS_P(d_iq, 8), PSS_P(d_audio, 8), PSS_P(d_out_len, 4));
     if (n_rows == 0) return PSS_OK;
     PssTimeScope timed(ctx);
     int r = pss_real_normalise(ctx, d_iq, n_rows, n, d_audio);

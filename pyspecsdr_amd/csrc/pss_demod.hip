@@ -2286,6 +2286,7 @@ extern "C" int pss_iq_correction(pss_ctx *ctx, const float *d_iq, long n_frames,
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n <= 0 || (n_frames > 0 && (!d_iq || (!d_out_iq && !d_raw)))) return pss_fail(ctx, PSS_E_ARG, "pss_iq_correction: bad argument");
+    PSS_ALIGNED(ctx, "pss_iq_correction", PSS_P(d_iq, 8), PSS_P(d_out_iq, 8), PSS_P(d_raw, 4));
     if (n_frames == 0) return PSS_OK;
     return iq_correction_launch(ctx, d_iq, n_frames, n, d_out_iq, d_raw, nullptr);
 }
@@ -2321,6 +2322,7 @@ extern "C" int pss_power_db(pss_ctx *ctx, const float *d_iq, long n_frames, int 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n < 1 || n_frames < 0 || (n_frames > 0 && (!d_iq || !d_power))) return pss_fail(ctx, PSS_E_ARG, "bad power arguments");
+    PSS_ALIGNED(ctx, "pss_power_db", PSS_P(d_iq, 8), PSS_P(d_power, 4));
     if (n_frames == 0) return PSS_OK;
     PssTimeScope timed(ctx);
     int r = launch_pairwise<float>(ctx, k_pairwise<0, false>, k_pairwise<0, true>, "k_pairwise launch", d_iq, n_frames, n, d_power, (float *)nullptr);
@@ -2332,6 +2334,7 @@ extern "C" int pss_agc_steps(pss_ctx *ctx, const float *d_power, long n, int sta
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_power || !d_idx_out || n < 0 || n_gains < 1) return pss_fail(ctx, PSS_E_ARG, "bad agc arguments");
+    PSS_ALIGNED(ctx, "pss_agc_steps", PSS_P(d_power, 4), PSS_P(d_idx_out, 4));
     if (n == 0) return PSS_OK;
     pss_kernel_begin(ctx, "k_agc");
     hipLaunchKernelGGL(k_agc, dim3(1), dim3(AGC_T), 0, PSS_STREAM(ctx), d_power, n, start_idx, n_gains, d_idx_out);
@@ -2791,6 +2794,7 @@ extern "C" int pss_demod(pss_ctx *ctx, int mode, const float *d_iq, long n_frame
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_demod", PSS_P(d_iq, 8), PSS_P(d_pcm, 4), PSS_P(d_audio, 8));
     return pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, nullptr);
 }
 
@@ -2800,6 +2804,7 @@ extern "C" int pss_demod_signal(pss_ctx *ctx, int mode, const float *d_iq, long 
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_demod_signal", PSS_P(d_iq, 8), PSS_P(d_pcm, 4), PSS_P(d_audio, 8));
     PssDemodCall call;
     call.correct = mode == PSS_MODE_WFM && n_frames > 0;
     return pss_demod_run(ctx, mode, PssIq{d_iq}, n_frames, n, fs, d_pcm, d_audio, &call);
@@ -2814,6 +2819,7 @@ extern "C" int pss_demod_power(pss_ctx *ctx, int mode, const float *d_iq, long n
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_power && n_frames > 0) return pss_fail(ctx, PSS_E_ARG, "pss_demod_power: d_power is null");
+    PSS_ALIGNED(ctx, "pss_demod_power", PSS_P(d_iq, 8), PSS_P(d_pcm, 4), PSS_P(d_audio, 8), PSS_P(d_power, 4));
     PssDemodCall call;
     if (mode == PSS_MODE_AM && n_frames > 0 && n >= 1 && d_iq) {
         call.d_power = d_power;
@@ -2830,6 +2836,7 @@ extern "C" int pss_sosfilt(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_x || !d_y || !sos || n_rows < 0 || n < 0 || nsec < 1 || nsec > 8) return pss_fail(ctx, PSS_E_ARG, "pss_sosfilt: bad argument");
+    PSS_ALIGNED(ctx, "pss_sosfilt", PSS_P(d_x, 8), PSS_P(d_y, 8));
     if (n_rows == 0 || n == 0) return PSS_OK;
     SosArg a;
     a.nsec = nsec;
@@ -2935,6 +2942,7 @@ extern "C" int pss_demod_am_c128(pss_ctx *ctx, const double *d_iq, long n_frames
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || (n_frames > 0 && (!d_iq || (!d_pcm && !d_audio)))) return pss_fail(ctx, PSS_E_ARG, "pss_demod_am_c128: bad argument");
+    PSS_ALIGNED(ctx, "pss_demod_am_c128", PSS_P(d_iq, 8), PSS_P(d_pcm, 4), PSS_P(d_audio, 8));
     if (n_frames == 0) return PSS_OK;
     const size_t rows = align256((size_t)n_frames * n * sizeof(double));
     int r = pss_ensure_scratch(ctx, 2 * rows);
@@ -2966,6 +2974,7 @@ extern "C" int pss_demod_ssb_c128(pss_ctx *ctx, int lower, const double *d_iq, l
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || (n_frames > 0 && (!d_iq || (!d_pcm && !d_audio)))) return pss_fail(ctx, PSS_E_ARG, "pss_demod_ssb_c128: bad argument");
+    PSS_ALIGNED(ctx, "pss_demod_ssb_c128", PSS_P(d_iq, 8), PSS_P(d_pcm, 4), PSS_P(d_audio, 8));
     return pss_demod_run(ctx, lower ? PSS_MODE_LSB : PSS_MODE_USB, PssIq{nullptr, d_iq}, n_frames, n, fs, d_pcm, d_audio, nullptr);
 }
 
@@ -2977,6 +2986,7 @@ extern "C" int pss_mean_power_c128(pss_ctx *ctx, const double *d_iq, long n_fram
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || (n_frames > 0 && (!d_iq || !d_power))) return pss_fail(ctx, PSS_E_ARG, "pss_mean_power_c128: bad argument");
+    PSS_ALIGNED(ctx, "pss_mean_power_c128", PSS_P(d_iq, 8), PSS_P(d_power, 8));
     if (n_frames == 0) return PSS_OK;
     int r = pss_ensure_scratch(ctx, align256((size_t)n_frames * n * sizeof(double)));
     if (r) return r;
@@ -3000,6 +3010,7 @@ extern "C" int pss_morse_edges(pss_ctx *ctx, const float *d_iq, long n_frames, i
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || n < 1 || cap < 0) return pss_fail(ctx, PSS_E_ARG, "pss_morse_edges: bad argument");
+    PSS_ALIGNED(ctx, "pss_morse_edges", PSS_P(d_iq, 8), PSS_P(d_rise, 4), PSS_P(d_fall, 4), PSS_P(d_counts, 4));
     if (n_frames == 0) return PSS_OK;
     if (!d_iq || !d_counts || (cap > 0 && (!d_rise || !d_fall))) return pss_fail(ctx, PSS_E_ARG, "pss_morse_edges: null buffer");
     const long g = n_frames < 16384 ? n_frames : 16384;
@@ -3078,6 +3089,7 @@ extern "C" int pss_classify(pss_ctx *ctx, const float *d_iq, long n_frames, int 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_classify: bad argument");
+    PSS_ALIGNED(ctx, "pss_classify", PSS_P(d_iq, 8), PSS_P(d_label, 4), PSS_P(d_bw, 8), PSS_P(d_mi, 4), PSS_P(d_flat, 4), PSS_P(d_psd, 4));
     if (n < 1) return pss_fail(ctx, PSS_E_ARG, "pss_classify: empty read (welch raises on it)");
     if (n_frames == 0) return PSS_OK;
     if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_classify: null input");
@@ -3115,6 +3127,7 @@ extern "C" int pss_classify_gated(pss_ctx *ctx, const float *d_iq, long n_frames
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || !(fs > 0.0) || n_idx < 0 || n_idx > n_frames) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: n_idx outside [0, n_frames] or a bad argument");
+    PSS_ALIGNED(ctx, "pss_classify_gated", PSS_P(d_iq, 8), PSS_P(d_idx, 4), PSS_P(d_label, 4), PSS_P(d_bw, 8), PSS_P(d_mi, 4), PSS_P(d_flat, 4), PSS_P(d_psd, 4));
     if (n < 1) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: empty read (welch raises on it)");
     if (n_idx == 0) return PSS_OK;                  // no detection: nothing is launched, the outputs stay as they are
     if (!d_iq) return pss_fail(ctx, PSS_E_ARG, "pss_classify_gated: null input");
@@ -3147,6 +3160,7 @@ extern "C" int pss_afsk_bits(pss_ctx *ctx, const double *d_audio, long n_rows, i
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || n < 0 || !(fs >= 1200.0)) return pss_fail(ctx, PSS_E_ARG, "pss_afsk_bits: bad argument");
+    PSS_ALIGNED(ctx, "pss_afsk_bits", PSS_P(d_audio, 8));
     double t1[48], t2[48];
     if (!sos1200 || !sos2200) {  // design butter(5) band-passes as bandpass_filter does (signal_processing.py:41)
         const double nyq = fs / 2.0;
@@ -3194,6 +3208,7 @@ extern "C" int pss_np_f32(pss_ctx *ctx, int op, const float *d_a, const float *d
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (op < PSS_NP_ARCTAN2 || op > PSS_NP_ABS || n < 0) return pss_fail(ctx, PSS_E_ARG, "pss_np_f32: bad argument");
+    PSS_ALIGNED(ctx, "pss_np_f32", PSS_P(d_a, 4), PSS_P(d_b, 4), PSS_P(d_out, 4));
     if (n == 0) return PSS_OK;
     if (!d_a || !d_out || (op != PSS_NP_LOG10 && !d_b)) return pss_fail(ctx, PSS_E_ARG, "pss_np_f32: null pointer");
     const long blocks = (n + 255) / 256;
@@ -3208,6 +3223,7 @@ extern "C" int pss_row_normalise(pss_ctx *ctx, const double *d_x, long n_rows, i
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || n < 0 || (n_rows > 0 && n > 0 && (!d_x || !d_y))) return pss_fail(ctx, PSS_E_ARG, "pss_row_normalise: bad argument");
+    PSS_ALIGNED(ctx, "pss_row_normalise", PSS_P(d_x, 8), PSS_P(d_y, 8));
     if (n_rows == 0 || n == 0) return PSS_OK;
     pss_kernel_begin(ctx, "k_row_normalise");
     hipLaunchKernelGGL(k_row_normalise, dim3((unsigned)(n_rows < 8192 ? n_rows : 8192)), dim3(256), 0, PSS_STREAM(ctx), d_x, d_y, n, n_rows);

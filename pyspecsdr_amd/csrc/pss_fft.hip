@@ -1465,6 +1465,7 @@ extern "C" int pss_hilbert(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || (n_rows > 0 && (!d_x || !d_analytic))) return pss_fail(ctx, PSS_E_ARG, "pss_hilbert: bad argument");
+    PSS_ALIGNED(ctx, "pss_hilbert", PSS_P(d_x, 8), PSS_P(d_analytic, 8));
     PssTimeScope timed(ctx);
     const int r = pss_hilbert_rows(ctx, d_x, n_rows, n, d_analytic, 0, nullptr, nullptr);
     return r;
@@ -1484,6 +1485,7 @@ extern "C" int pss_spectrum_db(pss_ctx *ctx, const float *d_iq, long n_frames, i
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_db && n_frames > 0) return pss_fail(ctx, PSS_E_ARG, "d_db is null");
+    PSS_ALIGNED(ctx, "pss_spectrum_db", PSS_P(d_iq, 8), PSS_P(d_db, 4));
     if (n_fft == 1) {
         if (n_frames < 0 || (n_frames > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "null iq / negative n_frames");
         if (n_frames == 0) return PSS_OK;
@@ -1506,6 +1508,7 @@ extern "C" int pss_spectrum_db_f64(pss_ctx *ctx, const float *d_iq, long n_frame
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || (n_frames > 0 && (!d_iq || !d_db))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_db_f64: null buffer / negative n_frames");
+    PSS_ALIGNED(ctx, "pss_spectrum_db_f64", PSS_P(d_iq, 8), PSS_P(d_db, 8));
     if (n_fft < 16 || n_fft > 65536 || (n_fft & (n_fft - 1)))
         return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_db_f64: n_fft must be a power of two in [16, 65536]");
     if (n_frames == 0) return PSS_OK;
@@ -1546,6 +1549,7 @@ extern "C" int pss_spectrum_db_c128(pss_ctx *ctx, const double *d_iq, long n_fra
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || (n_frames > 0 && (!d_iq || !d_db))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_db_c128: null buffer / negative n_frames");
+    PSS_ALIGNED(ctx, "pss_spectrum_db_c128", PSS_P(d_iq, 8), PSS_P(d_db, 8));
     if (n_fft < 16 || n_fft > 65536 || (n_fft & (n_fft - 1)))
         return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_db_c128: n_fft must be a power of two in [16, 65536]");
     if (n_frames == 0) return PSS_OK;
@@ -1591,6 +1595,7 @@ extern "C" int pss_scan(pss_ctx *ctx, const float *d_iq, long n_slices, int n_ff
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_peak) return pss_fail(ctx, PSS_E_ARG, "d_peak is null");
+    PSS_ALIGNED(ctx, "pss_scan", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_peak, 4), PSS_P(d_bw, 8), PSS_P(d_count, 4));
     if (n_slices > 0 && d_iq && n_fft >= 2 && !(is_pow2(n_fft) && n_fft >= 16 && n_fft <= 16384)) {
         const float *rows;
         int r = scan_rows(ctx, d_iq, n_slices, n_fft, d_db, &rows);
@@ -1606,6 +1611,7 @@ extern "C" int pss_scan_threshold(pss_ctx *ctx, const float *d_iq, long n_slices
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_slices < 0 || n < 2 || (n_slices > 0 && !d_iq)) return pss_fail(ctx, PSS_E_ARG, "pss_scan_threshold: bad argument");
+    PSS_ALIGNED(ctx, "pss_scan_threshold", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_peak, 4), PSS_P(d_bw, 8), PSS_P(d_count, 4));
     if (n_slices == 0) return PSS_OK;
     const float *rows;
     int r = scan_rows(ctx, d_iq, n_slices, n, d_db, &rows);
@@ -1781,6 +1787,7 @@ extern "C" int pss_spectrum_db_post(pss_ctx *ctx, const float *d_iq, long n_fram
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames < 0 || (n_frames > 0 && (!d_iq || !d_db || !d_post))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_db_post: null buffer");
+    PSS_ALIGNED(ctx, "pss_spectrum_db_post", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     if ((d_row_lo == nullptr) != (d_row_hi == nullptr)) return pss_fail(ctx, PSS_E_ARG, "row extremes: pass both arrays or neither");
     if (n_frames == 0) return PSS_OK;
     int r = pss_spectrum_db(ctx, d_iq, n_frames, n_fft, d_db);
@@ -1792,6 +1799,7 @@ extern "C" int pss_spectrum_post(pss_ctx *ctx, const float *d_db, long n_frames,
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_spectrum_post", PSS_P(d_db, 4), PSS_P(d_post, 4));
     return spectrum_post(ctx, d_db, n_frames, n_fft, d_post, nullptr, nullptr);
 }
 
@@ -1801,6 +1809,7 @@ extern "C" int pss_spectrum_post_extremes(pss_ctx *ctx, const float *d_db, long 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames > 0 && (!d_row_lo || !d_row_hi)) return pss_fail(ctx, PSS_E_ARG, "null row-extremes array");
+    PSS_ALIGNED(ctx, "pss_spectrum_post_extremes", PSS_P(d_db, 4), PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return spectrum_post(ctx, d_db, n_frames, n_fft, d_post, d_row_lo, d_row_hi);
 }
 
@@ -1808,12 +1817,14 @@ extern "C" int pss_row_extremes(pss_ctx *ctx, const float *d_rows, long n_rows, 
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_row_extremes", PSS_P(d_rows, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return row_extremes<float>(ctx, d_rows, n_rows, len, d_row_lo, d_row_hi);
 }
 extern "C" int pss_row_extremes_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, double *d_row_lo, double *d_row_hi)
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_row_extremes_f64", PSS_P(d_rows, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     return row_extremes<double>(ctx, d_rows, n_rows, len, d_row_lo, d_row_hi);
 }
 
@@ -1823,6 +1834,7 @@ extern "C" int pss_spectrum_post_f64(pss_ctx *ctx, const double *d_db, long n_fr
     PSS_GUARD(ctx);
     if (n_frames < 0 || n_fft < 5 || (n_frames > 0 && (!d_db || !d_post))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_f64: bad argument");
     if ((d_row_lo == nullptr) != (d_row_hi == nullptr)) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_f64: row_lo and row_hi go together");
+    PSS_ALIGNED(ctx, "pss_spectrum_post_f64", PSS_P(d_db, 8), PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     if (n_frames == 0) return PSS_OK;
     if (!ctx->f64_plain && n_fft >= 8 && post_sel_serves(n_fft, true)) {   // the register select on 64-bit keys (option "f64_plain" = 1: the radix-select kernel below)
         PssTimeScope timed(ctx);
@@ -1846,6 +1858,7 @@ extern "C" int pss_spectrum_post_thresholds(pss_ctx *ctx, const float *d_db, lon
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames > 0 && (!d_row_thr || !d_row_lo || !d_row_hi)) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_post_thresholds: null buffer");
+    PSS_ALIGNED(ctx, "pss_spectrum_post_thresholds", PSS_P(d_db, 4), PSS_P(d_row_thr, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return spectrum_post(ctx, d_db, n_frames, n_fft, nullptr, d_row_lo, d_row_hi, d_row_thr);
 }
 extern "C" int pss_waterfall_rows_db(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, const float *d_row_thr, const float *d_row_lo,
@@ -1854,6 +1867,7 @@ extern "C" int pss_waterfall_rows_db(pss_ctx *ctx, const float *d_db, long n_fra
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames > 0 && !d_row_thr) return pss_fail(ctx, PSS_E_ARG, "pss_waterfall_rows_db: null thresholds");
+    PSS_ALIGNED(ctx, "pss_waterfall_rows_db", PSS_P(d_db, 4), PSS_P(d_row_thr, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return display_rows<float, 0>(ctx, d_db, n_frames, n_fft - 4, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour, d_row_thr);
 }
 extern "C" int pss_persistence_rows_db(pss_ctx *ctx, const float *d_db, long n_frames, int n_fft, const float *d_row_thr,
@@ -1862,6 +1876,7 @@ extern "C" int pss_persistence_rows_db(pss_ctx *ctx, const float *d_db, long n_f
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_frames > 0 && !d_row_thr) return pss_fail(ctx, PSS_E_ARG, "pss_persistence_rows_db: null thresholds");
+    PSS_ALIGNED(ctx, "pss_persistence_rows_db", PSS_P(d_db, 4), PSS_P(d_row_thr, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return display_rows<float, 1>(ctx, d_db, n_frames, n_fft - 4, d_row_lo, d_row_hi, n_halo, window, disp_h, disp_w, d_y, nullptr, d_row_thr);
 }
 
@@ -1976,6 +1991,7 @@ extern "C" int pss_waterfall_rows(pss_ctx *ctx, const float *d_post, long n_fram
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_waterfall_rows", PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return display_rows<float, 0>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
 }
 extern "C" int pss_waterfall_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
@@ -1983,6 +1999,7 @@ extern "C" int pss_waterfall_rows_f64(pss_ctx *ctx, const double *d_post, long n
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_waterfall_rows_f64", PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     return display_rows<double, 0>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
 }
 // the gradient view's newest line per frame (draw_gradient_waterfall, pyspecsdr.py:1640-1716): pss_waterfall_rows' arguments, another quantiser
@@ -1991,6 +2008,7 @@ extern "C" int pss_gradient_rows(pss_ctx *ctx, const float *d_post, long n_frame
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_gradient_rows", PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return display_rows<float, 2>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
 }
 extern "C" int pss_gradient_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
@@ -1998,6 +2016,7 @@ extern "C" int pss_gradient_rows_f64(pss_ctx *ctx, const double *d_post, long n_
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_gradient_rows_f64", PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     return display_rows<double, 2>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, 1, disp_w, d_glyph, d_colour);
 }
 extern "C" int pss_persistence_rows(pss_ctx *ctx, const float *d_post, long n_frames, int len, const float *d_row_lo,
@@ -2005,6 +2024,7 @@ extern "C" int pss_persistence_rows(pss_ctx *ctx, const float *d_post, long n_fr
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_persistence_rows", PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4));
     return display_rows<float, 1>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, disp_h, disp_w, d_y, nullptr);
 }
 extern "C" int pss_persistence_rows_f64(pss_ctx *ctx, const double *d_post, long n_frames, int len, const double *d_row_lo,
@@ -2012,6 +2032,7 @@ extern "C" int pss_persistence_rows_f64(pss_ctx *ctx, const double *d_post, long
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_persistence_rows_f64", PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     return display_rows<double, 1>(ctx, d_post, n_frames, len, d_row_lo, d_row_hi, n_halo, window, disp_h, disp_w, d_y, nullptr);
 }
 
@@ -2022,6 +2043,7 @@ extern "C" int pss_waterfall_cells(pss_ctx *ctx, const float *d_rows, int n_rows
     PSS_GUARD(ctx);
     if (!d_rows || !d_glyph || !d_colour || n_rows < 1 || len < 2 || disp_h < 1 || disp_w < 1)
         return pss_fail(ctx, PSS_E_ARG, "bad waterfall arguments");
+    PSS_ALIGNED(ctx, "pss_waterfall_cells", PSS_P(d_rows, 4));
     pss_kernel_begin(ctx, "k_cells");
     hipLaunchKernelGGL((k_cells<float, 0>), dim3(1), dim3(1024), 0, PSS_STREAM(ctx), d_rows, n_rows, len, disp_h, disp_w,
                        d_glyph, d_colour, 0, n_rows);
@@ -2036,6 +2058,7 @@ extern "C" int pss_persistence_cells(pss_ctx *ctx, const float *d_rows, int n_ro
     PSS_GUARD(ctx);
     if (!d_rows || !d_colour || n_rows < 1 || len < 2 || disp_h < 1 || disp_w < 1)
         return pss_fail(ctx, PSS_E_ARG, "bad persistence arguments");
+    PSS_ALIGNED(ctx, "pss_persistence_cells", PSS_P(d_rows, 4));
     pss_kernel_begin(ctx, "k_cells");
     hipLaunchKernelGGL((k_cells<float, 1>), dim3(1), dim3(1024), 0, PSS_STREAM(ctx), d_rows, n_rows, len, disp_h, disp_w,
                        (int8_t *)nullptr, d_colour, 0, n_rows);
@@ -2064,12 +2087,16 @@ static int launch_spectrogram(pss_ctx *ctx, const T *d_rows, long n_rows, int le
 extern "C" int pss_spectrogram_cells(pss_ctx *ctx, const float *d_rows, long n_rows, int len, int disp_h, int disp_w,
                                      int8_t *d_glyph, int8_t *d_colour, double *d_range)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_spectrogram_cells", PSS_P(d_rows, 4), PSS_P(d_range, 8));
     return launch_spectrogram<float>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_glyph, d_colour, d_range);
 }
 
 extern "C" int pss_spectrogram_cells_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_h, int disp_w,
                                          int8_t *d_glyph, int8_t *d_colour, double *d_range)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_spectrogram_cells_f64", PSS_P(d_rows, 8), PSS_P(d_range, 8));
     return launch_spectrogram<double>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_glyph, d_colour, d_range);
 }
 
@@ -2128,6 +2155,7 @@ extern "C" int pss_spectrum_bars(pss_ctx *ctx, const float *d_rows, long n_rows,
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_spectrum_bars", PSS_P(d_rows, 4), PSS_P(d_range, 8));
     return spectrum_bars<float>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
 }
 extern "C" int pss_spectrum_bars_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_h, int disp_w, int8_t *d_height, int8_t *d_level,
@@ -2135,6 +2163,7 @@ extern "C" int pss_spectrum_bars_f64(pss_ctx *ctx, const double *d_rows, long n_
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_spectrum_bars_f64", PSS_P(d_rows, 8), PSS_P(d_range, 8));
     return spectrum_bars<double>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_height, d_level, d_range);
 }
 
@@ -2189,6 +2218,7 @@ extern "C" int pss_vector_cells(pss_ctx *ctx, const float *d_iq, int n, int max_
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (!d_iq || !d_grid || n < 0 || max_h < 1 || max_w < 1) return pss_fail(ctx, PSS_E_ARG, "bad vector-display arguments");
+    PSS_ALIGNED(ctx, "pss_vector_cells", PSS_P(d_iq, 8));
     PSS_HIP(ctx, hipMemsetAsync(d_grid, 0, (size_t)max_h * max_w, PSS_STREAM(ctx)));
     if (n == 0) return PSS_OK;
     pss_kernel_begin(ctx, "k_vector");
@@ -2215,11 +2245,15 @@ static int launch_gradient(pss_ctx *ctx, const T *d_rows, int n_rows, int len, i
 extern "C" int pss_gradient_cells(pss_ctx *ctx, const float *d_rows, int n_rows, int len, int disp_h, int disp_w,
                                   int8_t *d_glyph, int8_t *d_colour)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_gradient_cells", PSS_P(d_rows, 4));
     return launch_gradient<float>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_glyph, d_colour);
 }
 extern "C" int pss_gradient_cells_f64(pss_ctx *ctx, const double *d_rows, int n_rows, int len, int disp_h, int disp_w,
                                       int8_t *d_glyph, int8_t *d_colour)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_gradient_cells_f64", PSS_P(d_rows, 8));
     return launch_gradient<double>(ctx, d_rows, n_rows, len, disp_h, disp_w, d_glyph, d_colour);
 }
 
@@ -2240,10 +2274,14 @@ static int launch_surface(pss_ctx *ctx, const T *d_row, int len, int max_h, int 
 }
 extern "C" int pss_surface_cells(pss_ctx *ctx, const float *d_row, int len, int max_h, int max_w, int8_t *d_colour)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_surface_cells", PSS_P(d_row, 4));
     return launch_surface<float>(ctx, d_row, len, max_h, max_w, d_colour);
 }
 extern "C" int pss_surface_cells_f64(pss_ctx *ctx, const double *d_row, int len, int max_h, int max_w, int8_t *d_colour)
 {
+    if (!ctx) return PSS_E_ARG;
+    PSS_ALIGNED(ctx, "pss_surface_cells_f64", PSS_P(d_row, 8));
     return launch_surface<double>(ctx, d_row, len, max_h, max_w, d_colour);
 }
 
@@ -2296,12 +2334,14 @@ extern "C" int pss_surface_mags(pss_ctx *ctx, const float *d_rows, long n_rows, 
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_surface_mags", PSS_P(d_rows, 4), PSS_P(d_range, 8));
     return surface_mags<float>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
 }
 extern "C" int pss_surface_mags_f64(pss_ctx *ctx, const double *d_rows, long n_rows, int len, int disp_w, int8_t *d_mag, double *d_range)
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_surface_mags_f64", PSS_P(d_rows, 8), PSS_P(d_range, 8));
     return surface_mags<double>(ctx, d_rows, n_rows, len, disp_w, d_mag, d_range);
 }
 
@@ -2348,6 +2388,7 @@ extern "C" int pss_vector_masks(pss_ctx *ctx, const float *d_iq, long n_frames, 
     const long words = ((long)max_w + 31) / 32;
     if (n_frames < 0 || n < 0 || max_h < 1 || max_w < 1 || (long)max_h * words > MASK_MAX_WORDS || (n_frames > 0 && (!d_iq || !d_mask)))
         return pss_fail(ctx, PSS_E_ARG, "pss_vector_masks: bad argument (counts >= 0, max_h >= 1, max_w >= 1, max_h * ((max_w + 31) / 32) <= 16384, non-null buffers)");
+    PSS_ALIGNED(ctx, "pss_vector_masks", PSS_P(d_iq, 8), PSS_P(d_mask, 4));
     if (n_frames == 0) return PSS_OK;
     const size_t mask_bytes = (size_t)max_h * words * sizeof(uint32_t);
     PssTimeScope timed(ctx);
@@ -2370,6 +2411,7 @@ extern "C" int pss_masks_cells(pss_ctx *ctx, const uint32_t *d_mask, long n_fram
     PSS_GUARD(ctx);
     if (!masks_cells_args_ok(d_mask, n_frames, max_h, max_w, d_grid))
         return pss_fail(ctx, PSS_E_ARG, "pss_masks_cells: bad argument (max_h >= 1, max_w >= 1, n_frames >= 0, non-null buffers)");
+    PSS_ALIGNED(ctx, "pss_masks_cells", PSS_P(d_mask, 4));
     if (n_frames == 0) return PSS_OK;
     const long total = n_frames * max_h * max_w, blocks = (total + 255) / 256;
     pss_kernel_begin(ctx, "k_masks_cells");
@@ -2395,6 +2437,7 @@ extern "C" int pss_waterfall_cells_f64(pss_ctx *ctx, const double *d_rows, int n
     PSS_GUARD(ctx);
     if (!d_rows || !d_glyph || !d_colour || n_rows < 1 || len < 2 || disp_h < 1 || disp_w < 1)
         return pss_fail(ctx, PSS_E_ARG, "bad waterfall arguments");
+    PSS_ALIGNED(ctx, "pss_waterfall_cells_f64", PSS_P(d_rows, 8));
     pss_kernel_begin(ctx, "k_cells");
     hipLaunchKernelGGL((k_cells<double, 0>), dim3(1), dim3(1024), 0, PSS_STREAM(ctx), d_rows, n_rows, len, disp_h, disp_w,
                        d_glyph, d_colour, 0, n_rows);
@@ -2409,6 +2452,7 @@ extern "C" int pss_persistence_cells_f64(pss_ctx *ctx, const double *d_rows, int
     PSS_GUARD(ctx);
     if (!d_rows || !d_colour || n_rows < 1 || len < 2 || disp_h < 1 || disp_w < 1)
         return pss_fail(ctx, PSS_E_ARG, "bad persistence arguments");
+    PSS_ALIGNED(ctx, "pss_persistence_cells_f64", PSS_P(d_rows, 8));
     pss_kernel_begin(ctx, "k_cells");
     hipLaunchKernelGGL((k_cells<double, 1>), dim3(1), dim3(1024), 0, PSS_STREAM(ctx), d_rows, n_rows, len, disp_h, disp_w,
                        (int8_t *)nullptr, d_colour, 0, n_rows);
@@ -2452,6 +2496,7 @@ extern "C" int pss_ring_push(pss_ring *r, const float *d_row)
 {
     if (!r || !d_row) return PSS_E_ARG;
     PSS_GUARD(r->ctx);
+    PSS_ALIGNED(r->ctx, "pss_ring_push", PSS_P(d_row, 4));
     int slot;
     if (r->count < r->cap) slot = (r->head + r->count++) % r->cap;
     else { slot = r->head; r->head = (r->head + 1) % r->cap; }  // history.pop(0)

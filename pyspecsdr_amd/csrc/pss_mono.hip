@@ -344,6 +344,7 @@ extern "C" int pss_lfilter(pss_ctx *ctx, const double *d_x, long n_rows, int n, 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || n < 0 || !lf_args_ok(b, a, ncoef)) return pss_fail(ctx, PSS_E_ARG, "pss_lfilter: bad argument");
+    PSS_ALIGNED(ctx, "pss_lfilter", PSS_P(d_x, 8), PSS_P(d_y, 8));
     if (n_rows == 0 || n == 0) return PSS_OK;
     if (!d_x || !d_y) return pss_fail(ctx, PSS_E_ARG, "pss_lfilter: null buffer");
     LfArg c = {};

@@ -13,6 +13,7 @@ extern "C" int pss_spectrum_nfm(pss_ctx *ctx, const float *d_iq, long n_frames, 
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_spectrum_nfm", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_pcm, 4));
     // The backward IIR pass runs one wavefront per SIMD and is latency-bound; the spectrum kernel (HBM-bound, high
     // occupancy) is launched on a side stream right behind the forward kernel so that the two share the machine
     // (pss_side_*).  Only the fused large-batch NFM path honours PSS_FORK_AFTER_FWD, and reports it in `forked`.
@@ -181,6 +182,7 @@ extern "C" int pss_frame_pipeline_nfm_f64(pss_ctx *ctx, const float *d_iq, long 
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_nfm_f64: n must be a power of two in [16, 65536]");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_nfm_f64", PSS_P(d_iq, 8), PSS_P(d_db, 8), PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8), PSS_P(d_pcm, 4));
     return frame_pipeline<double>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, 0, 0, disp_w, d_glyph,
                                   d_colour, d_pcm);
 }
@@ -194,6 +196,7 @@ extern "C" int pss_frame_pipeline_f64(pss_ctx *ctx, int mode, const float *d_iq,
     PSS_GUARD(ctx);
     if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
     if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_f64: n must be a power of two in [16, 65536]");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_f64", PSS_P(d_iq, 8), PSS_P(d_db, 8), PSS_P(d_post, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8), PSS_P(d_pcm, 4));
     return frame_pipeline<double>(ctx, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
                                   d_line_b, d_pcm);
 }
@@ -209,6 +212,7 @@ extern "C" int pss_frame_pipeline_cells(pss_ctx *ctx, int mode, const float *d_i
     if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
     if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_cells: n must be a power of two in [16, 65536]");
     if (n_frames > 0 && !d_db32) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_cells: d_db32 is null");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_cells", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8), PSS_P(d_pcm, 4));
     return frame_pipeline<double>(ctx, mode, d_iq, n_frames, n, fs, d_db64, nullptr, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
                                   d_line_b, d_pcm, d_db32);
 }
@@ -221,6 +225,7 @@ extern "C" int pss_spectrum_cells(pss_ctx *ctx, const float *d_iq, long n_frames
     PSS_GUARD(ctx);
     if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_cells: n must be a power of two in [16, 65536]");
     if (n_frames > 0 && !d_db32 && !d_db64) return pss_fail(ctx, PSS_E_ARG, "pss_spectrum_cells: no row buffer");
+    PSS_ALIGNED(ctx, "pss_spectrum_cells", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8));
     return frame_pipeline<double>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, 0.0, d_db64, nullptr, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w,
                                   d_line_a, d_line_b, nullptr, d_db32, false);
 }
@@ -280,6 +285,7 @@ extern "C" int pss_frame_pipeline_bars(pss_ctx *ctx, int mode, const float *d_iq
     PSS_GUARD(ctx);
     if (n_frames < 0 || disp_h < 1 || disp_h > 127 || disp_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: bad frame count or display geometry");
     if (n_frames > 0 && (!d_height || !d_level)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_bars: null buffer");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_bars", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_post, 8), PSS_P(d_range, 8), PSS_P(d_pcm, 4));
     return view_pipeline(ctx, "pss_frame_pipeline_bars", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *post) {
         return pss_spectrum_bars_f64(ctx, post, n_frames, n - 4, disp_h, disp_w, d_height, d_level, d_range);
     });
@@ -294,6 +300,7 @@ extern "C" int pss_frame_pipeline_surface(pss_ctx *ctx, int mode, const float *d
     PSS_GUARD(ctx);
     if (n_frames < 0 || disp_w < 2) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_surface: bad frame count or display width");
     if (n_frames > 0 && !d_mag) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_surface: null buffer");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_surface", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_post, 8), PSS_P(d_range, 8), PSS_P(d_pcm, 4));
     return view_pipeline(ctx, "pss_frame_pipeline_surface", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *post) {
         return pss_surface_mags_f64(ctx, post, n_frames, n - 4, disp_w, d_mag, d_range);
     });
@@ -308,6 +315,7 @@ extern "C" int pss_frame_pipeline_vector(pss_ctx *ctx, int mode, const float *d_
     PSS_GUARD(ctx);
     if (n_frames < 0 || max_h < 1 || max_w < 1) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_vector: bad frame count or screen size");
     if (n_frames > 0 && !d_mask) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_vector: null buffer");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_vector", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_post, 8), PSS_P(d_mask, 4), PSS_P(d_pcm, 4));
     return view_pipeline(ctx, "pss_frame_pipeline_vector", mode, d_iq, n_frames, n, fs, d_db32, d_db64, d_post, d_pcm, [&](const double *) {
         return pss_vector_masks(ctx, d_iq, n_frames, n, max_h, max_w, d_mask);
     });
@@ -319,6 +327,7 @@ extern "C" int pss_frame_pipeline_nfm(pss_ctx *ctx, const float *d_iq, long n_fr
 {
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_nfm", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4), PSS_P(d_pcm, 4));
     return frame_pipeline<float>(ctx, PSS_MODE_NFM, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, 0, 0, disp_w, d_glyph,
                                  d_colour, d_pcm);
 }
@@ -330,6 +339,7 @@ extern "C" int pss_frame_pipeline(pss_ctx *ctx, int mode, const float *d_iq, lon
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (mode < PSS_MODE_NFM || mode > PSS_MODE_WFM) return pss_fail(ctx, PSS_E_ARG, "unknown demodulation mode");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_post, 4), PSS_P(d_row_lo, 4), PSS_P(d_row_hi, 4), PSS_P(d_pcm, 4));
     return frame_pipeline<float>(ctx, mode, d_iq, n_frames, n, fs, d_db, d_post, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a,
                                  d_line_b, d_pcm);
 }

@@ -41,6 +41,7 @@ extern "C" int pss_row_meter_f64(pss_ctx *ctx, const double *d_rows, long n_rows
     if (!ctx) return PSS_E_ARG;
     PSS_GUARD(ctx);
     if (n_rows < 0 || len < 1 || (!d_peak && !d_avg) || (n_rows > 0 && !d_rows)) return pss_fail(ctx, PSS_E_ARG, "pss_row_meter_f64: bad argument");
+    PSS_ALIGNED(ctx, "pss_row_meter_f64", PSS_P(d_rows, 8), PSS_P(d_peak, 8), PSS_P(d_avg, 8));
     if (n_rows == 0) return PSS_OK;
     MeterPlans pl{};
     pl.n_full = len > CHUNK ? len / CHUNK : 0;
@@ -86,6 +87,7 @@ extern "C" int pss_squelch_gate(pss_ctx *ctx, const double *d_peak, long n_frame
     PSS_GUARD(ctx);
     if (!gate_args_ok(n_frames, every, phase) || (n_frames > 0 && !d_peak))
         return pss_fail(ctx, PSS_E_ARG, "pss_squelch_gate: every < 0, phase outside [0, every), a frame count outside [0, 2^31) or a null peak array");
+    PSS_ALIGNED(ctx, "pss_squelch_gate", PSS_P(d_peak, 8), PSS_P(d_open_idx, 4));
     if (n_frames == 0) {
         if (n_open) *n_open = 0;
         if (held_out) *held_out = held_in;
@@ -237,6 +239,8 @@ extern "C" int pss_frame_pipeline_squelch(pss_ctx *ctx, int mode, const float *d
     if (!gate_args_ok(n_frames, every, phase)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: every < 0 or phase outside [0, every)");
     if (n < 16 || n > 65536 || (n & (n - 1))) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: n must be a power of two in [16, 65536]");
     if (n_frames > 0 && (!d_db32 || !d_peak || !d_pcm)) return pss_fail(ctx, PSS_E_ARG, "pss_frame_pipeline_squelch: null buffer");
+    PSS_ALIGNED(ctx, "pss_frame_pipeline_squelch", PSS_P(d_iq, 8), PSS_P(d_db32, 4), PSS_P(d_db64, 8), PSS_P(d_row_lo, 8), PSS_P(d_row_hi, 8), PSS_P(d_pcm, 4), PSS_P(d_peak, 8),
+                PSS_P(d_avg, 8));
     if (n_frames == 0) {
         const int r0 = pss_spectrum_cells(ctx, d_iq, 0, n, d_db32, d_db64, d_row_lo, d_row_hi, n_halo, window, display, disp_h, disp_w, d_line_a, d_line_b);
         if (r0) return r0;
@@ -289,6 +293,7 @@ extern "C" int pss_scan_gate(pss_ctx *ctx, const float *d_peak, const double *d_
     PSS_GUARD(ctx);
     if (n_slices < 0 || n_slices > INT32_MAX || (n_slices > 0 && (!d_peak || !d_bw)))
         return pss_fail(ctx, PSS_E_ARG, "pss_scan_gate: a slice count outside [0, 2^31) or a null peak / bandwidth array");
+    PSS_ALIGNED(ctx, "pss_scan_gate", PSS_P(d_peak, 4), PSS_P(d_bw, 8), PSS_P(d_hit_idx, 4));
     if (n_slices == 0) {
         if (n_hit) *n_hit = 0;
         return PSS_OK;
@@ -335,6 +340,8 @@ extern "C" int pss_sweep_report(pss_ctx *ctx, int kind, const float *d_iq, long 
     if (kind != PSS_SWEEP_INLINE && kind != PSS_SWEEP_DRIVER) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: unknown sweep kind");
     if (n_slices < 0 || n_slices > INT32_MAX || !(fs > 0.0)) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: a slice count outside [0, 2^31) or fs <= 0");
     if (n_slices > 0 && (!d_iq || !d_peak || !d_bw || !d_hit_idx)) return pss_fail(ctx, PSS_E_ARG, "pss_sweep_report: null d_iq / d_peak / d_bw / d_hit_idx");
+    PSS_ALIGNED(ctx, "pss_sweep_report", PSS_P(d_iq, 8), PSS_P(d_db, 4), PSS_P(d_peak, 4), PSS_P(d_bw, 8), PSS_P(d_count, 4), PSS_P(d_hit_idx, 4), PSS_P(d_label, 4),
+                PSS_P(d_cls_bw, 8), PSS_P(d_mi, 4), PSS_P(d_flat, 4));
     if (n_slices == 0) {
         if (n_hit) *n_hit = 0;
         return PSS_OK;
