@@ -1069,6 +1069,80 @@ int pss_apt_lines(pss_ctx *ctx, const float *d_env, long n_rows, long e_stride, 
                   long n_lines, float *d_words, long words_stride);
 int pss_h_apt_lines(const float *h_env, long n_rows, long e_stride, long n_row, const int32_t *h_line_row, const int64_t *h_line_pos, long n_lines,
                     float *h_words, long words_stride);
+/* ---- OOK devices: the sensor and remote messages of a 433 MHz capture — what the reference's command list starts `rtl_433 -f {freq}M` for
+ * (rtlcoms.json, "Decode smart devices").  The arithmetic is the project's own, stated once in csrc/pss_ook.h (PARITY.md "OOK"); the device
+ * and the host twins agree on every byte, and every output follows from indices in the ROW, so no chunking or windowing changes one.  There is
+ * no word to look for: the device turns a row into the edges of its keyed envelope, cuts them into messages at long gaps and slices each
+ * message into bits under the caller's timing (what rtl_433 -X 'n=..,m=OOK_PPM,s=..,l=..,g=..' takes; formats.ook_spec turns the string into
+ * these arguments).  Samples and sample counts only: microseconds live in formats.  Rows are complex64, 8-byte aligned, x_stride samples
+ * apart, the buffer holding samples [buf_index0, buf_index0 + n_buf) of every row of n_row samples; samples before index 0 count as 0 + 0j.
+ * (dev_*: pointers into device memory; the pss_h_ twins take the same arrays on the host.)
+ *   m[n] = fl32(fl32(re re) + fl32(im im)); e[n] = fl32((m[n - P + 1] + ... + m[n] in float64, in that order from +0.0) / P), P in [1, 65].
+ * pss_ook_envelope: e[n] for n in [i_begin, i_end) of every row to float32 element r env_stride + (n - i_begin) of dev_env (4-byte aligned).
+ *   A stage dump for tests and for the trace; the receiver does not go through it.  The buffer must hold [max(0, i_begin - P + 1), i_end).
+ *   One kernel, k_ook_envelope.
+ * pss_ook_levels: block b of a row is samples [4096 b, 4096 b + 4096); its mean is the float64 sum of its m in ascending order from +0.0,
+ *   divided by 4096, and goes to float64 element r means_stride + (b - b_begin) of dev_means (8-byte aligned) for the whole blocks b in
+ *   [b_begin, b_end), which must lie inside the row and the buffer.  The caller turns the means into the thresholds (formats.ook_levels: hi
+ *   and lo as multiples of the lower quartile of a row's block means).  One kernel, k_ook_levels: 8 bytes read a sample, 8 written a block.
+ * pss_ook_messages: sample n is decisive if e[n] >= hi (high) or e[n] < lo (low), a NaN neither; on(n) holds iff the last decisive sample
+ *   d <= n exists, is high, and n - d <= R (R in [0, 4096]; hi >= lo > 0); on(-1) is off and so is everything past the row's end.  A rise at
+ *   n: on(n) && !on(n - 1); a fall: the reverse; a pulse still on at the row's last sample falls at n_row (flag OPEN).  A pulse is a rise
+ *   with the row's next fall, its gap the distance from that fall to the next rise.  A rise at pos starts a message if no fall lies in
+ *   [pos - gap_limit, pos) (gap_limit in [1, 2^20]); the message is that pulse and the following ones up to and including the first whose gap
+ *   exceeds gap_limit.  Edges at or past pos + span (span in [1, 2^24]) are not read: a pulse whose fall is not read is dropped with all
+ *   later ones (LONG), and so is the 1025th pulse (MANY).  The slicer (mode; tol >= 0; the classes short, long and a non-zero sync more than
+ *   2 tol apart) turns widths into bits, MSB first, at most 256 (FULL), every bit flipped where invert is 1:
+ *     PSS_OOK_PWM  each pulse's width: within tol of short -> 1, of long -> 0, of sync -> nothing, else one odd symbol.
+ *     PSS_OOK_PPM  each pulse's gap, the message's last pulse excluded: short -> 0, long -> 1, sync -> nothing, else one odd symbol.
+ *     PSS_OOK_MC   Manchester: pulses and gaps in time order, the last pulse's gap excluded, are 1 half-bit within tol of short and 2 within
+ *                  tol of 2 short; the first that is neither ends the list and counts as one odd.  Bit i is the pair of half-bit levels
+ *                  (h[2 i + phase], h[2 i + phase + 1]) while inside the list, phase in {0, 1}: (1, 0) -> 1, (0, 1) -> 0, equal -> one odd.
+ *   Reported iff n_bits >= min_bits (in [0, 256]) and n_odd <= max_odd (in [0, 2047]), for the messages whose pos lies in [s_begin, s_end) of
+ *   every row, in ascending (row, pos): dev_bits uint8 [max_msgs][32], dev_n_bits int32, dev_row int32, dev_pos int64 (the first rise), dev_span int32
+ *   (from the first rise to the last fall of a pulse kept), dev_meta uint32 (pulses kept in bits 0 .. 10, min(n_odd, 2047) in bits 11 .. 21,
+ *   PSS_OOK_OPEN / _LONG / _MANY / _FULL above them), dev_count int32 [1] (the TRUE count; nothing is written past max_msgs).  The buffer must
+ *   hold [max(0, s_begin - before), min(n_row, s_end + after)) with pss_ook_halo's before = gap_limit + R + P and after = span.
+ *   PSS_E_ARG (reason in pss_last_error, starting "pss_ook_messages: "; a refused call writes nothing): a buffer or a window outside the
+ *   row, s_end < s_begin, a window above 2^30 starts (2^31 edge positions over all rows), n_rows outside [1, 2^20], x_stride < n_buf, P, R,
+ *   the thresholds, gap_limit, span, mode, tol, short, long, sync, phase, invert, min_bits or max_odd outside their ranges, classes not more
+ *   than 2 tol apart, max_msgs < 0, a buffer that does not cover the window's reach, a null or misaligned pointer.
+ *   Kernels: k_ook_detect (the one pass over every sample: m to LDS once per tile of 4096 edge positions, e from there, a workgroup max-scan
+ *   of the last decisive sample, the edges compacted; e never reaches memory), then k_starts_scan, k_starts_gather, k_ook_heads,
+ *   k_starts_scan, k_ook_list, k_ook_walk, k_starts_scan, k_ook_emit over the edges only.  Scratch on the context (the same buffers as the
+ *   other receivers'), grow-only and freed by pss_destroy: 2 bytes per edge position of the largest call and 1 per 4096, 25 bytes per edge
+ *   and 53 per possible message (every other edge and one more a row: a row's listed edges may end on a rise); the call waits once for
+ *   the count of edges.
+ * pss_ook_halo: the reach of a window: *before = gap_limit + R + P samples back from s_begin, *after = span samples on from s_end.
+ *   PSS_E_ARG ("pss_ook_halo: "): an argument outside its range, a null pointer.  Host only.
+ * pss_h_ook_envelope / _levels / _messages: the same on host buffers, pure host code (no context, no GPU; the reason:
+ *   pss_last_error(NULL), starting with the device entry's name). */
+#define PSS_OOK_PWM 0
+#define PSS_OOK_PPM 1
+#define PSS_OOK_MC 2
+#define PSS_OOK_MAX_PULSES 1024
+#define PSS_OOK_MAX_BITS 256
+#define PSS_OOK_OPEN (1u << 22)
+#define PSS_OOK_LONG (1u << 23)
+#define PSS_OOK_MANY (1u << 24)
+#define PSS_OOK_FULL (1u << 25)
+int pss_ook_halo(int P, int R, long gap_limit, long span, long *before, long *after);
+int pss_ook_envelope(pss_ctx *ctx, const float *dev_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, int P, long i_begin,
+                     long i_end, float *dev_env, long env_stride);
+int pss_h_ook_envelope(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, int P, long i_begin, long i_end,
+                       float *h_env, long env_stride);
+int pss_ook_levels(pss_ctx *ctx, const float *dev_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, long b_begin, long b_end,
+                   double *dev_means, long means_stride);
+int pss_h_ook_levels(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, long b_begin, long b_end,
+                     double *h_means, long means_stride);
+int pss_ook_messages(pss_ctx *ctx, const float *dev_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                     int P, float hi, float lo, int R, long gap_limit, long span, int mode, int w_short, int w_long, int w_sync, int tol, int phase,
+                     int invert, int min_bits, int max_odd, uint8_t *dev_bits, int32_t *dev_n_bits, int32_t *dev_row, int64_t *dev_pos, int32_t *dev_span,
+                     uint32_t *dev_meta, int32_t *dev_count, int max_msgs);
+int pss_h_ook_messages(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, int P,
+                       float hi, float lo, int R, long gap_limit, long span, int mode, int w_short, int w_long, int w_sync, int tol, int phase,
+                       int invert, int min_bits, int max_odd, uint8_t *h_bits, int32_t *h_n_bits, int32_t *h_row, int64_t *h_pos, int32_t *h_span,
+                       uint32_t *h_meta, int32_t *h_count, int max_msgs);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -234,6 +234,17 @@ _SIGS = {
     "pss_h_apt_syncs": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, _p, _p, _p, _p, _p, C.c_int]),
     "pss_apt_lines": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, _p, _p, C.c_long, _p, C.c_long]),
     "pss_h_apt_lines": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, _p, _p, C.c_long, _p, C.c_long]),
+    "pss_ook_halo": (C.c_int, [C.c_int, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "pss_ook_envelope": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_h_ook_envelope": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_ook_levels": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_h_ook_levels": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_ook_messages": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int,
+                                   C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   _p, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_h_ook_messages": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int,
+                                     C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     _p, _p, _p, _p, _p, _p, _p, C.c_int]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

@@ -197,6 +197,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->welch_part) hipFree(ctx->welch_part);
     for (auto &b : ctx->starts.buf) if (b) hipFree(b);
     if (ctx->starts.pin) hipHostFree(ctx->starts.pin);
+    if (ctx->ook_first) hipFree(ctx->ook_first);
     hipEventDestroy(ctx->ev0);
     hipEventDestroy(ctx->ev1);
     hipStreamSynchronize(ctx->stream2);

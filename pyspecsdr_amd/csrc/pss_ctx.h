@@ -166,6 +166,8 @@ struct pss_ctx {
     // pss_adsb.hip and pss_ais.hip, grow-only, shared as the gates share sq_buf (pss_starts.h): [0] the tiles' counts, offsets and lists,
     // [1] the listed starts with what the receiver keeps beside them (ADS-B: ranks and keep flags; AIS: payloads, lengths, scores as well)
     PssStartList starts;
+    void *ook_first = nullptr;    // pss_ook.hip: a byte per detect tile, the polarity of its first edge, grow-only
+    size_t ook_first_bytes = 0;
     void *welch_part = nullptr;   // pss_welch.hip: the block partials, grow-only
     size_t welch_part_bytes = 0;
     bool timing = false;

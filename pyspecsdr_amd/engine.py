@@ -1691,6 +1691,111 @@ class Engine:
         k = min(int(count[0]), room)
         return cw[:k], fx[:k], rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
 
+    # -- OOK devices: complex64 rows -> the envelope (a stage dump), the block means the thresholds come from, the sliced messages
+    #    (pss_ook_*; the arithmetic: csrc/pss_ook.h).  spec: formats.ook_spec's dict, every length in samples.
+    OOK_PWM, OOK_PPM, OOK_MC = 0, 1, 2
+    OOK_OPEN, OOK_LONG, OOK_MANY, OOK_FULL = 1 << 22, 1 << 23, 1 << 24, 1 << 25
+    OOK_MAX_PULSES, OOK_MAX_BITS, OOK_BLOCK = 1024, 256, 4096
+
+    @staticmethod
+    def ook_halo(P, R, gap_limit, span, lib=None):
+        """pss_ook_halo -> (before, after): the samples a window of ook_messages reads back from s_begin and on from s_end.  Host code."""
+        lib = lib or L.load()
+        b, a = C.c_long(), C.c_long()
+        if lib.pss_ook_halo(int(P), int(R), int(gap_limit), int(span), C.byref(b), C.byref(a)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return b.value, a.value
+
+    @staticmethod
+    def _ook_spec_args(spec):
+        return (int(spec['gap_limit']), int(spec['span']), int(spec['mode']), int(spec['short']), int(spec.get('long', 0)), int(spec.get('sync', 0)),
+                int(spec['tol']), int(spec.get('phase', 0)), int(spec.get('invert', 0)), int(spec.get('min_bits', 0)), int(spec.get('max_odd', 0)))
+
+    def ook_envelope(self, d_iq, n_rows, n_buf, d_env, P=9, x_stride=None, buf_index0=0, n_row=None, i_begin=0, i_end=None, env_stride=None):
+        """d_iq complex64: n_rows rows x_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_row samples
+        (default: the buffer is the row) -> d_env float32 [n_rows][env_stride]: the envelope of the samples [i_begin, i_end)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        self._dev(self.lib.pss_ook_envelope, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_row, int(P),
+                  int(i_begin), i_end, _ptr(d_env), int(i_end - int(i_begin) if env_stride is None else env_stride))
+
+    def ook_levels(self, d_iq, n_rows, n_buf, d_means, x_stride=None, buf_index0=0, n_row=None, b_begin=0, b_end=None, means_stride=None):
+        """-> d_means float64 [n_rows][means_stride]: the mean of m over the whole blocks [b_begin, b_end) of 4096 samples (default: every
+        whole block of the row)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        b_end = n_row // self.OOK_BLOCK if b_end is None else int(b_end)
+        self._dev(self.lib.pss_ook_levels, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_row,
+                  int(b_begin), b_end, _ptr(d_means), int(b_end - int(b_begin) if means_stride is None else means_stride))
+
+    def ook_messages(self, d_iq, n_rows, n_buf, hi, lo, spec, d_bits, d_n_bits, d_row, d_pos, d_span, d_meta, d_count, max_msgs, P=9, R=64, x_stride=None,
+                     buf_index0=0, n_row=None, s_begin=0, s_end=None):
+        """-> the messages whose first rise lies in [s_begin, s_end) (default: to the row's end) of every row, ascending in (row, pos): d_bits
+        uint8 [max_msgs][32], d_n_bits int32, d_row int32, d_pos int64, d_span int32, d_meta uint32 (pulses | n_odd << 11 | flags), d_count
+        int32 [1] (the true count)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_ook_messages, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, int(P), float(hi), float(lo), int(R), *self._ook_spec_args(spec), _ptr(d_bits), _ptr(d_n_bits), _ptr(d_row),
+                  _ptr(d_pos), _ptr(d_span), _ptr(d_meta), _ptr(d_count), int(max_msgs))
+
+    @staticmethod
+    def _ook_rows(iq):
+        x = np.asarray(iq, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("iq: a 1-D or 2-D complex64 array")
+        return Engine._as_rows(x)
+
+    @staticmethod
+    def h_ook_envelope(iq, P=9, buf_index0=0, n_row=None, i_begin=0, i_end=None, lib=None):
+        """pss_h_ook_envelope on a host complex64 array [n_rows][n_buf] or [n_buf] -> float32 [n_rows][i_end - i_begin].  Pure host code."""
+        lib = lib or L.load()
+        rows = Engine._ook_rows(iq)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        env = np.zeros((rows.shape[0], max(i_end - int(i_begin), 0)), np.float32)
+        if lib.pss_h_ook_envelope(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(P), int(i_begin), i_end, _ptr(env),
+                                  env.shape[1]) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return env
+
+    @staticmethod
+    def h_ook_levels(iq, buf_index0=0, n_row=None, b_begin=0, b_end=None, lib=None):
+        """pss_h_ook_levels on a host complex64 array -> float64 [n_rows][b_end - b_begin].  Pure host code."""
+        lib = lib or L.load()
+        rows = Engine._ook_rows(iq)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        b_end = n_row // Engine.OOK_BLOCK if b_end is None else int(b_end)
+        means = np.zeros((rows.shape[0], max(b_end - int(b_begin), 0)), np.float64)
+        if lib.pss_h_ook_levels(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(b_begin), b_end, _ptr(means),
+                                means.shape[1]) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return means
+
+    @staticmethod
+    def h_ook_messages(iq, hi, lo, spec, P=9, R=64, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_msgs=None, lib=None):
+        """pss_h_ook_messages on a host complex64 array [n_rows][n_buf] or [n_buf] -> (bits uint8 [k][32], n_bits int32 [k], row int32 [k], pos
+        int64 [k], span int32 [k], meta uint32 [k], count): the first k = min(count, max_msgs) records and the true count.  max_msgs: default
+        room for every message.  Pure host code."""
+        lib = lib or L.load()
+        rows = Engine._ook_rows(iq)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_msgs is None
+        max_msgs = 64 if grow else int(max_msgs)
+        while True:
+            room = max(max_msgs, 0)
+            bits, nb, rw = np.zeros((room, 32), np.uint8), np.zeros(room, np.int32), np.zeros(room, np.int32)
+            pos, sp, meta, count = np.zeros(room, np.int64), np.zeros(room, np.int32), np.zeros(room, np.uint32), np.zeros(1, np.int32)
+            if lib.pss_h_ook_messages(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end, int(P), float(hi),
+                                      float(lo), int(R), *Engine._ook_spec_args(spec), _ptr(bits), _ptr(nb), _ptr(rw), _ptr(pos), _ptr(sp), _ptr(meta),
+                                      _ptr(count), max_msgs) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_msgs = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return bits[:k], nb[:k], rw[:k], pos[:k], sp[:k], meta[:k], int(count[0])
+
     # -- NOAA APT: complex64 rows at 62.4 kS/s -> the envelope, the line starts, the lines' words (pss_apt_*; the arithmetic: csrc/pss_apt.h)
     APT_RATE = 62400
     APT_ENV_RATE = 12480

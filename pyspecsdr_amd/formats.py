@@ -1678,6 +1678,313 @@ def pocsag_recording(samples, fs, center_hz, channels_hz, bauds=(512, 1200, 2400
     return dict(messages=messages, lines=pocsag_lines(messages), batches=batches, fs=_POCSAG_RATE)
 
 
+# ---- OOK devices: the sensor and remote messages of a 433 MHz capture (the arithmetic of the device stages: csrc/pss_ook.h)
+_OOK_MODES = {'OOK_PWM': 0, 'OOK_PPM': 1, 'OOK_MC_ZEROBIT': 2}
+_OOK_FLAGS = ((1 << 22, 'OPEN'), (1 << 23, 'LONG'), (1 << 24, 'MANY'), (1 << 25, 'FULL'))
+_OOK_BLOCK = 4096
+_OOK_US = {'s': 'short', 'l': 'long', 'y': 'sync', 'g': 'gap_limit', 't': 'tol', 'r': 'reset'}
+# the project's own statement of two common device families, as the flex strings `rtl_433 -X` takes
+OOK_DEVICES = {
+    'nexus': "n=nexus,m=OOK_PPM,s=1000,l=2000,g=3000,r=5000,bits>=36",
+    'ev1527': "n=ev1527,m=OOK_PWM,s=352,l=1056,g=2400,t=160,r=12000,bits>=24",
+}
+
+
+def ook_spec(text, fs):
+    """rtl_433's flex string -> the C arguments in samples at fs, as a dict: 'name', 'mode', 'short', 'long', 'sync', 'gap_limit', 'tol',
+    'reset', 'span', 'phase', 'invert', 'min_bits', 'max_odd'.  Keys: n= name; m= OOK_PWM | OOK_PPM | OOK_MC_ZEROBIT; s= short, l= long,
+    y= sync, g= gap limit, t= tolerance (default a quarter of s), r= reset (default four gap limits), all in microseconds and converted as
+    int(round(us fs / 1e6)); bits>= the fewest bits of a message; invert.  An unknown key is refused by name.  span (the samples a message
+    may cover) is 512 of the longer symbol and a gap limit; OOK_MC_ZEROBIT reads the first pulse as the second half of a leading 0, so
+    phase = 1."""
+    fs = float(fs)
+    us = {}
+    spec = dict(name='', mode=None, sync=0, phase=0, invert=0, min_bits=0, max_odd=0)
+    for item in str(text).split(','):
+        item = item.strip()
+        if not item:
+            continue
+        if item == 'invert':
+            spec['invert'] = 1
+            continue
+        if item.startswith('bits>='):
+            spec['min_bits'] = int(item[6:])
+            continue
+        key, eq, value = item.partition('=')
+        key = key.strip()
+        if not eq or key not in ('n', 'm') + tuple(_OOK_US):
+            raise ValueError(f"ook_spec: unknown key {key!r}")
+        if key == 'n':
+            spec['name'] = value.strip()
+        elif key == 'm':
+            if value.strip() not in _OOK_MODES:
+                raise ValueError(f"ook_spec: unknown modulation {value.strip()!r}")
+            spec['mode'] = _OOK_MODES[value.strip()]
+        else:
+            us[_OOK_US[key]] = float(value)
+    if spec['mode'] is None or 'short' not in us:
+        raise ValueError("ook_spec: m= and s= are needed")
+    if spec['mode'] != 2 and 'long' not in us:
+        raise ValueError("ook_spec: l= is needed")
+    us.setdefault('long', 2.0 * us['short'] if spec['mode'] == 2 else 0.0)
+    us.setdefault('gap_limit', 2.0 * max(us['short'], us['long']))
+    us.setdefault('tol', us['short'] / 4.0)
+    us.setdefault('reset', 4.0 * us['gap_limit'])
+    for key, value in us.items():
+        spec[key] = int(round(value * fs / 1e6))
+    spec['span'] = min(1 << 24, max(1, 512 * max(spec['long'], 2 * spec['short']) + spec['gap_limit']))
+    if spec['mode'] == 2:
+        spec['phase'] = 1
+    return spec
+
+
+def ook_levels(block_means, hi_ratio=8.0, lo_ratio=4.0, quantile=0.25):
+    """The block means of ONE row (pss_ook_levels) -> (hi, lo) float32: floor = the element at index int(len quantile) of the sorted means
+    (len // 4: the lower quartile, which keyed traffic under a quarter of the time does not move), hi = fl32(hi_ratio floor),
+    lo = fl32(lo_ratio floor)."""
+    m = np.sort(np.asarray(block_means, np.float64).ravel())
+    if not len(m):
+        raise ValueError("ook_levels: no whole block of 4096 samples")
+    floor = m[min(len(m) - 1, int(len(m) * float(quantile)))]
+    return np.float32(float(hi_ratio) * floor), np.float32(float(lo_ratio) * floor)
+
+
+def ook_records(bits, n_bits, row, pos, span, meta):
+    """The arrays of pss_ook_messages / Engine.h_ook_messages -> one dict per record: 'bits' (a list of 0 / 1), 'n_bits', 'row', 'pos', 'span',
+    'n_pulses', 'n_odd', 'flags' (names of OPEN / LONG / MANY / FULL), 'hex'."""
+    out = []
+    for b, n, r, p, s, w in zip(bits, n_bits, row, pos, span, meta):
+        n, w = int(n), int(w)
+        out.append(dict(bits=np.unpackbits(np.asarray(b, np.uint8))[:n].tolist(), n_bits=n, row=int(r), pos=int(p), span=int(s), n_pulses=w & 0x7FF,
+                        n_odd=(w >> 11) & 0x7FF, flags=[name for mask, name in _OOK_FLAGS if w & mask], hex=bytes(b[:(n + 7) // 8]).hex()))
+    return out
+
+
+def ook_messages(records, fs, reset_us):
+    """records of ONE spec (ook_records' dicts) -> the messages in order of (row, pos): a record with the row and the bits of the message before
+    it whose start lies within reset_us of that copy's end is a repeat of it.  Each: 'row', 'pos', 'time' (s), 'bits', 'n_bits', 'hex',
+    'count', 'span' (first rise of the first copy to last fall of the last)."""
+    reset = int(round(float(reset_us) * float(fs) / 1e6))
+    out = []
+    for r in sorted(records, key=lambda r: (r['row'], r['pos'])):
+        m = out[-1] if out else None
+        if m and m['row'] == r['row'] and m['bits'] == r['bits'] and r['pos'] - (m['pos'] + m['span']) <= reset:
+            m['count'] += 1
+            m['span'] = r['pos'] + r['span'] - m['pos']
+        else:
+            out.append(dict(row=r['row'], pos=r['pos'], time=r['pos'] / float(fs), bits=list(r['bits']), n_bits=r['n_bits'], hex=r['hex'], count=1,
+                            span=r['span']))
+    return out
+
+
+def _ook_field(bits, a, b):
+    return int("".join(map(str, bits[a:b])), 2)
+
+
+def ook_decode(name, bits):
+    """The fields of a message of one of OOK_DEVICES' layouts -> dict with 'model': nexus (36 bits: id 8 | battery 1 | 0 | channel 2 |
+    temperature 12, two's complement, tenths of a degree C | 1111 | humidity 8) and ev1527 (24 bits: id 20 | buttons 4).  Anything else,
+    and a message that does not fit its layout, is reported as hex."""
+    bits = [int(b) & 1 for b in bits]
+    if name == 'nexus' and len(bits) == 36 and bits[9] == 0 and bits[24:28] == [1, 1, 1, 1]:
+        t = _ook_field(bits, 12, 24)
+        return dict(model='nexus', id=_ook_field(bits, 0, 8), battery_ok=bits[8], channel=_ook_field(bits, 10, 12) + 1,
+                    temperature_c=(t - 4096 if t & 0x800 else t) / 10.0, humidity=_ook_field(bits, 28, 36))
+    if name == 'ev1527' and len(bits) == 24:
+        return dict(model='ev1527', id=_ook_field(bits, 0, 20), buttons=_ook_field(bits, 20, 24))
+    pad = bits + [0] * (-len(bits) % 8)
+    return dict(model=name, n_bits=len(bits), hex=bytes(_ook_field(pad, k, k + 8) for k in range(0, len(pad), 8)).hex())
+
+
+def ook_lines(messages):
+    """One text line a message (ook_rows' dicts with 'name' and 'fields')."""
+    out = []
+    for m in messages:
+        f = m['fields']
+        if f['model'] == 'nexus' and 'id' in f:
+            text = (f"id {f['id']} channel {f['channel']} battery {'ok' if f['battery_ok'] else 'low'} temperature {f['temperature_c']:.1f} C "
+                    f"humidity {f['humidity']} %")
+        elif f['model'] == 'ev1527' and 'id' in f:
+            text = f"id {f['id']:05x} buttons {f['buttons']:04b}"
+        else:
+            text = f"{f['n_bits']} bits {f['hex']}"
+        out.append(f"{m['time']:10.4f} s  row {m['row']}  {m['name']}: {text}  x{m['count']}")
+    return out
+
+
+def _ook_specs(specs, fs):
+    items = specs.items() if isinstance(specs, dict) else [(None, s) for s in specs]
+    out = []
+    for name, s in items:
+        s = dict(s) if isinstance(s, dict) else ook_spec(s, fs)
+        if name is not None and not s.get('name'):
+            s['name'] = name
+        out.append(s)
+    return out
+
+
+def _ook_result(specs, per_spec, fs, levels):
+    """per_spec[i]: spec i's records of every row -> the recording entries' dict."""
+    records, messages = [], []
+    for s, recs in zip(specs, per_spec):
+        for m in ook_messages(recs, fs, s['reset'] * 1e6 / float(fs)):
+            m.update(name=s['name'], fields=ook_decode(s['name'], m['bits']))
+            messages.append(m)
+        records += [dict(r, name=s['name']) for r in recs]
+    messages.sort(key=lambda m: (m['pos'], m['row'], m['name']))
+    return dict(messages=messages, lines=ook_lines(messages), records=records, levels=levels, fs=float(fs))
+
+
+def _ook_host_rows(rows):
+    x = np.asarray(rows, np.complex64)
+    if x.ndim not in (1, 2):
+        raise ValueError("rows: a 1-D or 2-D complex array")
+    return np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+
+
+def h_ook_rows(rows, fs, specs=OOK_DEVICES, P=9, R=64, hi_ratio=8.0, lo_ratio=4.0, quantile=0.25):
+    """ook_rows on the host twins (pss_h_ook_levels, pss_h_ook_messages): no GPU."""
+    from .engine import Engine
+    x = _ook_host_rows(rows)
+    specs = _ook_specs(specs, fs)
+    per_spec, levels = [[] for _ in specs], []
+    for k in range(len(x)):
+        if x.shape[1] < _OOK_BLOCK:
+            levels.append(None)
+            continue
+        hi, lo = ook_levels(Engine.h_ook_levels(x[k])[0], hi_ratio, lo_ratio, quantile)
+        levels.append((float(hi), float(lo)))
+        for i, s in enumerate(specs):
+            recs = ook_records(*Engine.h_ook_messages(x[k], hi, lo, s, P=P, R=R)[:6])
+            per_spec[i] += [dict(r, row=k) for r in recs]
+    return _ook_result(specs, per_spec, fs, levels)
+
+
+def _ook_call(e, ptr, n_buf, hi, lo, spec, P, R, out, **window):
+    """pss_ook_messages on one resident row -> (records on the host, out): out holds the device arrays and grows to the true count."""
+    import torch
+    dev = f"cuda:{e.device}"
+    while True:
+        if out.get('room', 0) == 0 or out.get('grow'):
+            room = out['room'] = max(out.get('grow', 0), 4096)
+            out.pop('grow', None)
+            out['t'] = (torch.empty((room, 32), dtype=torch.uint8, device=dev), torch.empty(room, dtype=torch.int32, device=dev),
+                        torch.empty(room, dtype=torch.int32, device=dev), torch.empty(room, dtype=torch.int64, device=dev),
+                        torch.empty(room, dtype=torch.int32, device=dev), torch.empty(room, dtype=torch.int32, device=dev),
+                        torch.zeros(1, dtype=torch.int32, device=dev))
+        t = out['t']
+        e.ook_messages(ptr, 1, n_buf, hi, lo, spec, *t, out['room'], P=P, R=R, **window)
+        k = int(t[6].cpu()[0])
+        if k <= out['room']:
+            break
+        out['grow'] = k   # the true count: again with room for it
+    bits, nb, row, pos, span, meta = (a[:k].cpu().numpy() for a in t[:6])
+    return ook_records(bits, nb, row, pos, span, meta.view(np.uint32))
+
+
+def ook_rows(rows, fs, specs=OOK_DEVICES, P=9, R=64, hi_ratio=8.0, lo_ratio=4.0, quantile=0.25):
+    """rows: complex64 rows at fs — a host array [k][n] or [n], or a resident device tensor float32 [k][2 n] (pss_ddc's, pss_pfb's, pss_bank's
+    output) — -> dict(messages, lines, records, levels, fs): per row the block means once (pss_ook_levels) and from them its thresholds
+    (ook_levels), then pss_ook_messages once per spec on the resident row.  specs: OOK_DEVICES' kind, a dict or a list of flex strings or of
+    ook_spec's dicts.  'records': ook_records' dicts with 'name', per spec in order of (row, pos); 'messages': the repeats joined
+    (ook_messages), with 'name' and 'fields' (ook_decode), in order of (pos, row, name); 'lines': ook_lines; 'levels': (hi, lo) per row,
+    None for a row shorter than one block, which reports nothing."""
+    import torch
+    e = get_engine()
+    if isinstance(rows, torch.Tensor):
+        d_rows = rows
+    else:
+        d_rows = torch.from_numpy(_ook_host_rows(rows).view(np.float32)).to(f"cuda:{e.device}")
+    if d_rows.dim() != 2 or d_rows.dtype != torch.float32 or d_rows.shape[1] % 2 or not d_rows.is_contiguous():
+        raise ValueError("rows: a contiguous device tensor float32 [k][2 n]")
+    k, n = d_rows.shape[0], d_rows.shape[1] // 2
+    specs = _ook_specs(specs, fs)
+    per_spec, levels, out = [[] for _ in specs], [], {}
+    nb = n // _OOK_BLOCK
+    if nb and k:
+        d_means = torch.empty((k, nb), dtype=torch.float64, device=d_rows.device)
+        e.ook_levels(d_rows, k, n, d_means)
+        means = d_means.cpu().numpy()
+    for r in range(k):
+        if not nb:
+            levels.append(None)
+            continue
+        hi, lo = ook_levels(means[r], hi_ratio, lo_ratio, quantile)
+        levels.append((float(hi), float(lo)))
+        for i, s in enumerate(specs):
+            recs = _ook_call(e, d_rows.data_ptr() + 8 * n * r, n, hi, lo, s, P, R, out)
+            per_spec[i] += [dict(rec, row=r) for rec in recs]
+    return _ook_result(specs, per_spec, fs, levels)
+
+
+def ook_recording(samples, fs, specs=OOK_DEVICES, center_hz=None, channels_hz=None, decim=1, taps=None, chunk_samples=1 << 22, codes_format=None,
+                  table=None, P=9, R=64, hi_ratio=8.0, lo_ratio=4.0, quantile=0.25):
+    """The OOK devices of a capture -> ook_rows' dict; 'fs' is the rate the positions count in.  Without channels_hz the capture is the row: it
+    is streamed twice in chunks of chunk_samples samples, once through pss_ook_levels (whole blocks) and once, each chunk with the halo
+    pss_ook_halo states for the widest spec, through pss_ook_messages per spec.  With channels_hz (and center_hz) pss_ddc first puts the
+    listed channels at 0 Hz at fs / decim (taps: its float64 low-pass, default firwin(20 decim + 1, 1 / decim)), streamed by the shared
+    chunk loop, and ook_rows reads the resident rows ('row' is the channel's position in channels_hz).  The result does not depend on
+    chunk_samples.  Every chunk goes up with `span` samples of halo behind it (about a second for OOK_DEVICES' timings), so chunks well
+    above the widest span are the intended use: a chunk of one tile re-reads its halo 64-fold.  codes_format / table: as
+    demodulate_recording; codes are widened per chunk on the device."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    if channels_hz is not None:
+        if center_hz is None:
+            raise ValueError("ook_recording: channels_hz needs center_hz")
+        offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+        if offsets.ndim != 1 or not len(offsets):
+            raise ValueError("channels_hz: a list of frequencies")
+        d_rows, _ = _tune_device(samples, fs, offsets, int(decim), taps, None, chunk_samples, codes_format, table)
+        return ook_rows(d_rows.contiguous(), fs / int(decim), specs, P, R, hi_ratio, lo_ratio, quantile)
+    if int(chunk_samples) != chunk_samples or chunk_samples < 1:
+        raise ValueError("chunk_samples must be an integer >= 1")
+    dev = f"cuda:{e.device}"
+    if codes_format is not None:
+        iq = _iq_args(codes_format, table)
+        samples = _iq_codes(samples, iq[0])
+        if samples.ndim != 2:
+            raise ValueError("codes: [n, 2]")
+    else:
+        samples = np.ascontiguousarray(samples, np.complex64)
+        if samples.ndim != 1:
+            raise ValueError("samples: a 1-D recording")
+
+    def upload(lo, hi):
+        if codes_format is None:
+            return torch.from_numpy(samples[lo:hi].view(np.float32)).to(dev)
+        d_iq = torch.empty(2 * (hi - lo), dtype=torch.float32, device=dev)
+        e.unpack_iq(torch.from_numpy(np.array(samples[lo:hi])).to(dev), hi - lo, d_iq, codes_format, iq[2])
+        return d_iq
+
+    n = len(samples)
+    specs = _ook_specs(specs, fs)
+    per_spec = [[] for _ in specs]
+    nb = n // _OOK_BLOCK
+    if not nb:
+        return _ook_result(specs, per_spec, fs, [None])
+    step = max(1, int(chunk_samples) // _OOK_BLOCK)
+    means = np.empty(nb, np.float64)
+    for b0 in range(0, nb, step):
+        b1 = min(nb, b0 + step)
+        d_means = torch.empty((1, b1 - b0), dtype=torch.float64, device=dev)
+        e.ook_levels(upload(b0 * _OOK_BLOCK, b1 * _OOK_BLOCK), 1, (b1 - b0) * _OOK_BLOCK, d_means, buf_index0=b0 * _OOK_BLOCK, n_row=n, b_begin=b0, b_end=b1)
+        means[b0:b1] = d_means.cpu().numpy()[0]
+    hi, lo = ook_levels(means, hi_ratio, lo_ratio, quantile)
+    halos = [e.ook_halo(P, R, s['gap_limit'], s['span']) for s in specs]
+    before, after = max(h[0] for h in halos), max(h[1] for h in halos)
+    out = {}
+    chunk = int(chunk_samples)
+    for s0 in range(0, n, chunk):
+        s1 = min(n, s0 + chunk)
+        b_lo, b_hi = max(0, s0 - before), min(n, s1 + after)
+        d_iq = upload(b_lo, b_hi)
+        for i, s in enumerate(specs):
+            per_spec[i] += _ook_call(e, d_iq, b_hi - b_lo, hi, lo, s, P, R, out, buf_index0=b_lo, n_row=n, s_begin=s0, s_end=s1)
+    return _ook_result(specs, per_spec, fs, [(float(hi), float(lo))])
+
+
 # ---- NOAA APT: the image of a 137 MHz capture (the arithmetic of the three device stages: csrc/pss_apt.h)
 _APT_RATE = 62400
 _APT_ENV_RATE = 12480
