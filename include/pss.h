@@ -1143,6 +1143,55 @@ int pss_h_ook_messages(const float *h_iq, long n_rows, long x_stride, long n_buf
                        float hi, float lo, int R, long gap_limit, long span, int mode, int w_short, int w_long, int w_sync, int tol, int phase,
                        int invert, int min_bits, int max_odd, uint8_t *h_bits, int32_t *h_n_bits, int32_t *h_row, int64_t *h_pos, int32_t *h_span,
                        uint32_t *h_meta, int32_t *h_count, int max_msgs);
+/* ---- Packet radio: the AX.25 frames and APRS reports of a 2 m capture — what the reference's command list starts
+ * `rtl_fm -f {freq}M -M fm -s 22050 | direwolf` for (rtlcoms.json, "Decode APRS").  The arithmetic is the project's own, stated once in
+ * csrc/pss_packet.h (PARITY.md "Packet"); the device and the host twins agree on every byte, and every output follows from indices in the
+ * ROW, so no chunking or windowing changes one.  (pss_afsk_bits / pss_ax25_frames below restate the reference's own decode_aprs, which has no
+ * NRZI, no check sequence and no bit timing; this receiver shares nothing with them.)
+ * pss_packet_plan: the route from a capture at fs to 26 400 S/s (22 samples a bit at 1200 bit/s): decim = min(fs / 26 400, 204) for pss_ddc,
+ *   up / down = 26 400 decim / fs reduced for pss_resample (2.4 MS/s and 240 kS/s: 99 / 100).  PSS_E_ARG (reason in pss_last_error(NULL),
+ *   starting "pss_packet: "): an fs that is no integer, below 26 400, or whose reduced factors leave [1, 4096].
+ * pss_packet_default_tones: the correlator table float64 [4][22]: cos and sin of one cycle a window (mark, 1200 Hz), cos and sin of 11 / 6
+ *   cycles a window (space, 2200 Hz), from the host's libm.  The table is always a HOST table handed to the device entry and the twin alike.
+ * pss_packet_front: dev_iq complex64 rows at 26 400 S/s, x_stride samples apart, 8-byte aligned, holding samples [buf_index0, buf_index0 +
+ *   n_buf) of every row of n_row samples -> dev_z float32, sample i of row r at element r z_stride + (i - i_begin), i in [i_begin, i_end):
+ *   d = the float32 polar discriminator (d[0] = 0), four float64 fma chains of the table over d[i - 11 .. i + 10] (zero outside the row),
+ *   E_m = c0 c0 + c1 c1, E_s = space_gain (c2 c2 + c3 c3), z = (float)((E_s - E_m) / (E_s + E_m)), +0 where the sum is 0: the tone balance
+ *   in [-1, 1], positive on space.  The buffer must hold the samples from max(0, i_begin - 12) to min(n_row, i_end + 10).  One kernel,
+ *   k_packet_front.  PSS_E_ARG ("pss_packet_front: "; a refused call writes nothing): n_rows < 1, a buffer or a window outside the row,
+ *   strides below n_buf or the window, i_end < i_begin, a window above 2^30 samples, a null table or a table entry that is not finite, a
+ *   space_gain that is not finite or not > 0, a buffer that does not cover the window's halo, a null or misaligned pointer.
+ * pss_packet_frames: dev_z float32 rows (pss_packet_front's), z_stride samples apart, 4-byte aligned -> the frames whose opening flag's first
+ *   strobe s lies in [s_begin, s_end) of every row.  Every s with s - 22 >= 0 and s + 154 < n_row is tested: the nine strobes z[s + 22 k],
+ *   k = -1 .. 7, sliced at 0 and NRZI-decoded, must read the flag 01111110 with q = min |z| >= q_min (finite, >= 0).  A survivor is walked
+ *   with HDLC destuffing up to the closing flag, its strobes following the sender's bit clock (after each level change the next strobe moves
+ *   one sample toward the middle between changes where it is more than two samples off), and accepted iff its length is a whole number of
+ *   bytes in [17, 330], the CRC-16/X.25 residue is 0xF0B8, and its 2 to 10 addresses are well formed (A-Z, 0-9, space; the extension bit
+ *   first set at the end of an address).  Among accepted starts less than 22 apart in a row with the same bytes the highest q stays, then
+ *   the earliest.  Records in ascending (row, s): dev_msg uint8 [max_frames][332] (the frame with its two check bytes, zero-padded), dev_len
+ *   int32 (bytes), dev_row int32, dev_pos int64 (s), dev_score float32 (q), dev_count int32 [1] (the TRUE count; nothing is written past
+ *   max_frames).  The buffer must hold the samples from max(0, s_begin - 21 - 22) to min(n_row, s_end + 20 + 73 203); starts outside the
+ *   window still count as neighbours.
+ *   PSS_E_ARG ("pss_packet_frames: "; a refused call writes nothing): n_rows outside [1, 2^20], a buffer or a window outside the row,
+ *   z_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows), a q_min that is negative or not finite, a buffer
+ *   that does not cover the window's reach, max_frames < 0, a null or misaligned pointer.
+ *   Kernels: k_packet_detect (the one pass over every start), then k_starts_scan, k_starts_gather, k_packet_walk, k_packet_keep,
+ *   k_starts_scan, k_packet_emit over the survivors of the flag test only.  Scratch on the context (the same buffers as the other
+ *   receivers'), 2 bytes per start of the largest call and 353 bytes per survivor (the start 8, the payload 332, length, score and rank 4
+ *   each, the keep flag 1), grow-only and freed by pss_destroy; the call waits once for the count of survivors.
+ * pss_h_packet_front / pss_h_packet_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL),
+ *   starting with the device entry's name). */
+int pss_packet_plan(double fs, int *decim, int *up, int *down);
+int pss_packet_default_tones(double *tones);
+int pss_packet_front(pss_ctx *ctx, const float *dev_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, const double *tones,
+                     double space_gain, long i_begin, long i_end, float *dev_z, long z_stride);
+int pss_h_packet_front(const float *h_iq, long n_rows, long x_stride, long n_buf, long buf_index0, long n_row, const double *tones,
+                       double space_gain, long i_begin, long i_end, float *h_z, long z_stride);
+int pss_packet_frames(pss_ctx *ctx, const float *dev_z, long n_rows, long z_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                      float q_min, uint8_t *dev_msg, int32_t *dev_len, int32_t *dev_row, int64_t *dev_pos, float *dev_score, int32_t *dev_count,
+                      int max_frames);
+int pss_h_packet_frames(const float *h_z, long n_rows, long z_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, float q_min,
+                        uint8_t *h_msg, int32_t *h_len, int32_t *h_row, int64_t *h_pos, float *h_score, int32_t *h_count, int max_frames);
 /* decode_afsk (decoders.py:94-112) for n_rows independent float64 audio rows of n samples: the two Bell-202 band-passes,
  * the energy of each band per bit period of int(fs/1200) samples, bit = e2200 > e1200.  d_bits uint8 [n_rows][n_bits],
  * n_bits = pss_afsk_n_bits(n, fs) = len(range(0, n - window, window)).  sos1200 / sos2200: HOST tables of nsec rows

@@ -245,6 +245,12 @@ _SIGS = {
     "pss_h_ook_messages": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_int, C.c_float, C.c_float, C.c_int,
                                      C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      _p, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_packet_plan": (C.c_int, [C.c_double, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "pss_packet_default_tones": (C.c_int, [_p]),
+    "pss_packet_front": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, C.c_double, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_h_packet_front": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, _p, C.c_double, C.c_long, C.c_long, _p, C.c_long]),
+    "pss_packet_frames": (C.c_int, [_p, _p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_float, _p, _p, _p, _p, _p, _p, C.c_int]),
+    "pss_h_packet_frames": (C.c_int, [_p, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long, C.c_float, _p, _p, _p, _p, _p, _p, C.c_int]),
     "pss_afsk_n_bits": (C.c_int, [C.c_int, C.c_double]),
     "pss_afsk_bits": (C.c_int, [_p, _p, C.c_long, C.c_int, C.c_double, _p, _p, C.c_int, _p]),
     "pss_row_normalise": (C.c_int, [_p, _p, C.c_long, C.c_int, _p]),

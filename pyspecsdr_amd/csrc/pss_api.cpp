@@ -193,7 +193,7 @@ extern "C" void pss_destroy(pss_ctx *ctx)
     if (ctx->stage) hipFree(ctx->stage);
     for (auto &b : ctx->sq_buf) if (b) hipFree(b);
     if (ctx->sq_pin) hipHostFree(ctx->sq_pin);
-    for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win, &ctx->rds_tab, &ctx->rds_pulse, &ctx->ais_pulse, &ctx->apt_tab}) t->release();
+    for (PssDevTable *t : {&ctx->ddc_tab, &ctx->pfb_tab, &ctx->bank_tab, &ctx->rs_tab, &ctx->welch_win, &ctx->rds_tab, &ctx->rds_pulse, &ctx->ais_pulse, &ctx->apt_tab, &ctx->packet_tones}) t->release();
     if (ctx->welch_part) hipFree(ctx->welch_part);
     for (auto &b : ctx->starts.buf) if (b) hipFree(b);
     if (ctx->starts.pin) hipHostFree(ctx->starts.pin);

@@ -163,6 +163,7 @@ struct pss_ctx {
     PssDevTable rds_pulse;   // pss_rds.hip, pss_rds_bits: the pulse table
     PssDevTable ais_pulse;   // pss_ais.hip, pss_ais_front: the pulse table
     PssDevTable apt_tab;     // pss_apt.hip, pss_apt_front: rotor knots, taps
+    PssDevTable packet_tones;   // pss_packet.hip, pss_packet_front: the tone table
     // pss_adsb.hip and pss_ais.hip, grow-only, shared as the gates share sq_buf (pss_starts.h): [0] the tiles' counts, offsets and lists,
     // [1] the listed starts with what the receiver keeps beside them (ADS-B: ranks and keep flags; AIS: payloads, lengths, scores as well)
     PssStartList starts;

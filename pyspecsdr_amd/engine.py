@@ -1617,6 +1617,108 @@ class Engine:
         k = min(int(count[0]), room)
         return msg[:k], ln[:k], rw[:k], pos[:k], score[:k], int(count[0])
 
+    # -- packet radio: rows of IQ at 26.4 kS/s -> the AX.25 frames that pass their check (pss_packet_*; the arithmetic: csrc/pss_packet.h)
+    PACKET_RATE = 26400
+    PACKET_REC_BYTES = 332
+
+    @staticmethod
+    def packet_plan(fs, lib=None):
+        """pss_packet_plan -> (decim, up, down): the down-converter's decimation min(fs // 26 400, 204) and the resampler's factors to
+        26 400 S/s.  Host code."""
+        lib = lib or L.load()
+        d, u, w = C.c_int(), C.c_int(), C.c_int()
+        if lib.pss_packet_plan(float(fs), C.byref(d), C.byref(u), C.byref(w)) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return d.value, u.value, w.value
+
+    @staticmethod
+    def packet_default_tones(lib=None):
+        """pss_packet_default_tones: float64 [4][22]: cos and sin of 1200 Hz, cos and sin of 2200 Hz over a bit of 22 samples.  Host code."""
+        lib = lib or L.load()
+        t = np.empty((4, 22), np.float64)
+        r = lib.pss_packet_default_tones(_ptr(t))
+        if r != 0:
+            raise PssError(r, "pss_packet_default_tones")
+        return t
+
+    @staticmethod
+    def _packet_tones(tones, lib):
+        if tones is None:
+            return Engine.packet_default_tones(lib)
+        t = np.ascontiguousarray(tones, np.float64)
+        if t.shape != (4, 22):
+            raise ValueError("tones: a float64 table [4][22]")
+        return t
+
+    def packet_front(self, d_iq, n_rows, n_buf, d_z, tones=None, space_gain=1.0, x_stride=None, buf_index0=0, n_row=None, i_begin=0, i_end=None,
+                     z_stride=None):
+        """d_iq complex64 at 26.4 kS/s: n_rows rows x_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of
+        n_row samples (default: the buffer is the row) -> d_z float32: the tone balance (space minus mark over their sum), sample i of row r at
+        element r * z_stride + (i - i_begin), i in [i_begin, i_end) (default: to the row's end; z_stride: default the window).  tones: host
+        float64 table [4][22] (default packet_default_tones()); space_gain: the weight of the 2200 Hz energy."""
+        tones = self._packet_tones(tones, self.lib)
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        self._dev(self.lib.pss_packet_front, _ptr(d_iq), int(n_rows), int(n_buf if x_stride is None else x_stride), int(n_buf), int(buf_index0), n_row,
+                  _ptr(tones), float(space_gain), int(i_begin), i_end, _ptr(d_z), int(i_end - int(i_begin) if z_stride is None else z_stride))
+
+    @staticmethod
+    def h_packet_front(iq, tones=None, space_gain=1.0, buf_index0=0, n_row=None, i_begin=0, i_end=None, lib=None):
+        """pss_h_packet_front on a host array [n_rows][n_buf] or [n_buf] -> float32 [n_rows][i_end - i_begin] or [i_end - i_begin].  Pure host
+        code: the kernel's statements on one thread."""
+        lib = lib or L.load()
+        x = np.asarray(iq, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("iq: a 1-D or 2-D complex array")
+        rows = Engine._as_rows(x)
+        tones = Engine._packet_tones(tones, lib)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        i_end = n_row if i_end is None else int(i_end)
+        width = i_end - int(i_begin)
+        out = np.empty((rows.shape[0], max(width, 0)), np.float32)
+        if lib.pss_h_packet_front(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, _ptr(tones), float(space_gain),
+                                  int(i_begin), i_end, _ptr(out), width) != 0:
+            raise ValueError(lib.pss_last_error(None).decode())
+        return out if x.ndim == 2 else out[0]
+
+    def packet_frames(self, d_z, n_rows, n_buf, d_msg, d_len, d_row, d_pos, d_score, d_count, max_frames, q_min=0.0, z_stride=None, buf_index0=0,
+                      n_row=None, s_begin=0, s_end=None):
+        """d_z float32 at 26.4 kS/s: n_rows rows z_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of
+        n_row samples (default: the buffer is the row) -> the frames whose flag starts in [s_begin, s_end) (default: to the row's end) of every
+        row, ascending in (row, s): d_msg uint8 [max_frames][332], d_len int32 (bytes with the two check bytes), d_row int32, d_pos int64,
+        d_score float32, d_count int32 [1] (the true count).  q_min: the smallest |z| a flag's strobes may show."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_packet_frames, _ptr(d_z), int(n_rows), int(n_buf if z_stride is None else z_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, float(q_min), _ptr(d_msg), _ptr(d_len), _ptr(d_row), _ptr(d_pos), _ptr(d_score), _ptr(d_count), int(max_frames))
+
+    @staticmethod
+    def h_packet_frames(z, q_min=0.0, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_frames=None, lib=None):
+        """pss_h_packet_frames on a host float32 array [n_rows][n_buf] or [n_buf] -> (msg uint8 [k][332], len int32 [k], row int32 [k], pos
+        int64 [k], score float32 [k], count): the first k = min(count, max_frames) records and the true count.  max_frames: default room for
+        every frame.  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(z, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("z: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_frames is None
+        max_frames = 64 if grow else int(max_frames)
+        while True:
+            room = max(max_frames, 0)
+            msg, ln, rw = np.zeros((room, 332), np.uint8), np.zeros(room, np.int32), np.zeros(room, np.int32)
+            pos, score, count = np.zeros(room, np.int64), np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_packet_frames(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end, float(q_min),
+                                       _ptr(msg), _ptr(ln), _ptr(rw), _ptr(pos), _ptr(score), _ptr(count), max_frames) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_frames = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return msg[:k], ln[:k], rw[:k], pos[:k], score[:k], int(count[0])
+
     # -- POCSAG: float32 discriminator rows at 38.4 kS/s -> the batches whose codewords pass their check (pss_pocsag_*; the arithmetic:
     #    csrc/pss_pocsag.h).  The front is ais_front with pocsag_default_pulse(spb).
     POCSAG_RATE = 38400

@@ -2295,6 +2295,224 @@ def apt_recording(samples, fs, center_hz, channels_hz=(137.62e6,), taps=None, fr
     return dict(rows=apt_rows(d_rows.contiguous(), sync_errors, front_taps, tune), fs=_APT_ENV_RATE)
 
 
+# ---- packet radio: the AX.25 frames and APRS reports of a 2 m capture (the arithmetic of the device stages: csrc/pss_packet.h)
+_PACKET_RATE = 26400
+_PACKET_REC = 332
+
+
+def _ax25_address(a):
+    return dict(call=bytes(b >> 1 for b in a[:6]).decode('latin-1').rstrip(), ssid=(a[6] >> 1) & 0xF, repeated=bool(a[6] & 0x80))
+
+
+def ax25_decode(frame):
+    """An AX.25 frame WITHOUT its two check bytes -> dict(dest=..., source=..., path=[...], control=..., pid=..., info=...): every address
+    a dict(call, ssid, repeated: the has-been-repeated bit of a digipeater address, the command / response bit of the first two), pid None
+    where the frame type carries none (everything but I and UI frames), info the bytes behind.  ValueError where the address field does
+    not end inside the frame on a multiple of 7 bytes."""
+    f = bytes(frame)
+    end = next((j for j, b in enumerate(f) if b & 1), None)
+    if end is None or end % 7 != 6 or end < 13 or len(f) < end + 2:
+        raise ValueError("ax25_decode: a malformed address field")
+    addrs = [_ax25_address(f[j:j + 7]) for j in range(0, end + 1, 7)]
+    control = f[end + 1]
+    has_pid = (control & 1) == 0 or (control & 0xEF) == 0x03
+    rest = f[end + 2:]
+    if has_pid and not rest:
+        has_pid = False
+    return dict(dest=addrs[0], source=addrs[1], path=addrs[2:], control=control, pid=rest[0] if has_pid else None, info=rest[1:] if has_pid else rest)
+
+
+def _ax25_name(a):
+    return a['call'] + (f"-{a['ssid']}" if a['ssid'] else "")
+
+
+def aprs_tnc2(frame):
+    """The monitor line direwolf prints for a frame (without check bytes): `SRC-7>DST,WIDE1-1*,WIDE2-2:info`, the star behind the last
+    digipeater that has repeated the frame, the information field as Latin-1."""
+    d = ax25_decode(frame) if not isinstance(frame, dict) else frame
+    last = max((i for i, a in enumerate(d['path']) if a['repeated']), default=-1)
+    hops = "".join("," + _ax25_name(a) + ("*" if i == last else "") for i, a in enumerate(d['path']))
+    return f"{_ax25_name(d['source'])}>{_ax25_name(d['dest'])}{hops}:{bytes(d['info']).decode('latin-1')}"
+
+
+def _b91(s):
+    v = 0
+    for c in s:
+        v = v * 91 + (ord(c) - 33)
+    return v
+
+
+def _aprs_position(body, out):
+    """body: the information field behind the type character and the timestamp."""
+    if len(body) >= 19 and body[0].isdigit():
+        lat, ns, table, lon, ew, code = body[0:7], body[7], body[8], body[9:17], body[17], body[18]
+        try:
+            la = int(lat[0:2]) + float(lat[2:7].replace(' ', '0')) / 60.0
+            lo = int(lon[0:3]) + float(lon[3:8].replace(' ', '0')) / 60.0
+        except ValueError:
+            return
+        if ns not in 'NS' or ew not in 'EW':
+            return
+        out.update(lat=-la if ns == 'S' else la, lon=-lo if ew == 'W' else lo, symbol=table + code, compressed=False, comment=body[19:])
+        c = body[19:26]
+        if len(c) == 7 and c[3] == '/' and c[:3].isdigit() and c[4:].isdigit():
+            out.update(course=int(c[:3]), speed=float(int(c[4:])), comment=body[26:])
+    elif len(body) >= 13 and all(33 <= ord(ch) <= 124 for ch in body[1:9]):
+        table, code, cs, t = body[0], body[9], body[10:12], ord(body[12]) - 33
+        out.update(lat=90.0 - _b91(body[1:5]) / 380926.0, lon=-180.0 + _b91(body[5:9]) / 190463.0, symbol=table + code, compressed=True,
+                   comment=body[13:])
+        c, s = ord(cs[0]) - 33, ord(cs[1]) - 33
+        if cs[0] == ' ':
+            pass
+        elif 0 <= t and (t & 0x18) == 0x10:
+            out['altitude_ft'] = 1.002 ** (c * 91 + s)
+        elif 0 <= c <= 89:
+            out.update(course=c * 4, speed=1.08 ** s - 1.0)
+        elif cs[0] == '{':
+            out['range_miles'] = 2.0 * 1.08 ** s
+
+
+def aprs_decode(info):
+    """An APRS information field (bytes or str) -> dict: 'type' (its first character), 'raw' (the text behind it, Latin-1) and, by type:
+    positions `! = / @` (the last two with 'timestamp', 7 characters), uncompressed or base-91 compressed: 'lat', 'lon' (degrees), 'symbol'
+    (table and code), 'compressed', 'comment', and 'course' (degrees) / 'speed' (knots) where given ('altitude_ft' / 'range_miles' where the
+    compressed form carries those); status `>`: 'status'; messages `:`: 'addressee', 'text', 'number' (None without one).  Everything else,
+    Mic-E (` and ') included, as type and raw text."""
+    text = bytes(info).decode('latin-1') if not isinstance(info, str) else info
+    out = dict(type=text[:1], raw=text[1:])
+    kind, body = text[:1], text[1:]
+    if kind in '!=' and kind:
+        _aprs_position(body, out)
+    elif kind in '/@' and kind and len(body) >= 7:
+        out['timestamp'] = body[:7]
+        _aprs_position(body[7:], out)
+    elif kind == '>':
+        out['status'] = body
+    elif kind == ':' and len(body) >= 10 and body[9] == ':':
+        msg, _, number = body[10:].partition('{')
+        out.update(addressee=body[:9].rstrip(), text=msg, number=number if number else None)
+    return out
+
+
+def aprs_tracks(records, fs=_PACKET_RATE):
+    """records: the frames in order, each a mapping with 'msg' (the frame without check bytes) and 'pos' (packet_recording's 'frames') ->
+    one dict per source call in order of first appearance: 'source', 'position' ((latitude, longitude)), 'symbol', 'course', 'speed',
+    'status' (the last of each, or None), 'frames', 'first' and 'last' (pos / fs, seconds)."""
+    fs = float(fs)
+    tracks = {}
+    for rec in records:
+        ax = ax25_decode(rec['msg'])
+        d = aprs_decode(ax['info'])
+        t = int(rec['pos']) / fs
+        src = _ax25_name(ax['source'])
+        tr = tracks.setdefault(src, dict(source=src, position=None, symbol=None, course=None, speed=None, status=None, frames=0, first=t, last=t))
+        tr['frames'] += 1
+        tr['first'], tr['last'] = min(tr['first'], t), max(tr['last'], t)
+        for key in ('symbol', 'course', 'speed', 'status'):
+            if d.get(key) is not None:
+                tr[key] = d[key]
+        if d.get('lat') is not None:
+            tr['position'] = (d['lat'], d['lon'])
+    return list(tracks.values())
+
+
+def _packet_records(msg, ln, row, pos, score):
+    """The receiver's arrays -> one dict per frame in order of (pos, row): 'msg' (bytes without the check bytes), 'row', 'pos', 'score',
+    ax25_decode's keys, 'tnc2' and 'aprs' (aprs_decode of the information field)."""
+    out = []
+    for m, n, r, p, q in zip(msg, ln, row, pos, score):
+        body = bytes(m[:int(n) - 2])
+        d = ax25_decode(body)
+        d.update(msg=body, row=int(r), pos=int(p), score=float(q), tnc2=aprs_tnc2(d), aprs=aprs_decode(d['info']))
+        out.append(d)
+    out.sort(key=lambda f: (f['pos'], f['row']))
+    return out
+
+
+def h_packet_rows(rows, tones=None, space_gain=1.0, q_min=0.0):
+    """packet_rows through the host twins (pss_h_packet_front, pss_h_packet_frames): no GPU, the same bytes."""
+    from .engine import Engine
+    x = np.asarray(rows, np.complex64)
+    if x.ndim not in (1, 2):
+        raise ValueError("rows: a 1-D or 2-D complex array")
+    x = np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+    if not x.shape[0] or not x.shape[1]:
+        return []
+    z = Engine.h_packet_front(x, tones=tones, space_gain=space_gain)
+    return _packet_records(*Engine.h_packet_frames(z, q_min=q_min)[:5])
+
+
+def packet_rows(rows, tones=None, space_gain=1.0, q_min=0.0):
+    """rows: complex64 rows at 26 400 S/s — a host array [k][n] or [n], or a resident device tensor float32 [k][2 n] — -> the frames, a list
+    of dicts in order of (pos, row): pss_packet_front (tones: default packet_default_tones(); space_gain: the weight of the 2200 Hz energy,
+    below 1 for a pre-emphasised sender heard without de-emphasis) and pss_packet_frames (q_min) on the resident rows, then ax25_decode,
+    aprs_tnc2 and aprs_decode of every record."""
+    import torch
+    e = get_engine()
+    if isinstance(rows, torch.Tensor):
+        d_rows = rows
+    else:
+        x = np.asarray(rows, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("rows: a 1-D or 2-D complex array")
+        x = np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+        d_rows = torch.from_numpy(x.view(np.float32)).to(f"cuda:{e.device}")
+    if d_rows.dim() != 2 or d_rows.dtype != torch.float32 or d_rows.shape[1] % 2 or not d_rows.is_contiguous():
+        raise ValueError("rows: a contiguous device tensor float32 [k][2 n]")
+    k, n = d_rows.shape[0], d_rows.shape[1] // 2
+    if not k or not n:
+        return []
+    dev = d_rows.device
+    d_z = torch.empty((k, n), dtype=torch.float32, device=dev)
+    e.packet_front(d_rows, k, n, d_z, tones=tones, space_gain=space_gain)
+    room = 4096
+    while True:
+        d_msg = torch.empty((room, _PACKET_REC), dtype=torch.uint8, device=dev)
+        d_len = torch.empty(room, dtype=torch.int32, device=dev)
+        d_row = torch.empty(room, dtype=torch.int32, device=dev)
+        d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+        d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        e.packet_frames(d_z, k, n, d_msg, d_len, d_row, d_pos, d_score, d_count, room, q_min=q_min)
+        c = int(d_count.cpu()[0])
+        if c <= room:
+            break
+        room = c   # the true count: again with room for it
+    return _packet_records(*(t[:c].cpu().numpy() for t in (d_msg, d_len, d_row, d_pos, d_score)))
+
+
+def packet_recording(samples, fs, center_hz, channels_hz=(144.8e6,), taps=None, tones=None, chunk_samples=1 << 22, space_gain=1.0, q_min=0.0,
+                     codes_format=None, table=None):
+    """The packets of a 2 m capture centred on center_hz -> dict(frames=..., tracks=..., lines=..., fs=26400): 'frames' packet_rows' dicts in
+    order of 'pos' ('row' is the channel's position in channels_hz), 'tracks' aprs_tracks(frames), 'lines' the monitor line of every frame,
+    'fs' the rate the positions count in.  On the GPU from the upload to the records: pss_ddc puts the listed channels at 0 Hz at
+    packet_plan(fs)'s decimation (streamed in chunks of chunk_samples samples plus their halos; the result does not depend on
+    chunk_samples), pss_resample brings them to 26 400 S/s where the decimated rate is another one, then packet_rows.  taps: the
+    down-converter's float64 low-pass (default firwin(20 decim + 1, 16 000 / fs): half-width 8 kHz, 3 kHz deviation and 2.2 kHz audio by
+    Carson's rule with room for the carrier's error); codes_format / table: as demodulate_recording."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    decim, up, down = e.packet_plan(fs)
+    offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+    if offsets.ndim != 1 or not len(offsets):
+        raise ValueError("channels_hz: a list of frequencies")
+    if taps is None:
+        taps = np.empty(20 * decim + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 16000.0 / fs, taps.ctypes.data) != 0:
+            raise ValueError("packet_recording: the down-converter's filter design failed")
+    d_rows, _ = _tune_device(samples, fs, offsets, decim, taps, None, chunk_samples, codes_format, table)
+    k, m = d_rows.shape[0], d_rows.shape[1] // 2
+    if (up, down) != (1, 1):
+        n = e.resample_out_len(m, up, down)
+        d_bb = torch.empty((k, 2 * max(n, 1)), dtype=torch.float32, device=d_rows.device)
+        if m:
+            e.resample(d_rows, np.complex64, k, m, up, down, d_bb)
+        d_rows, m = d_bb[:, :2 * n].contiguous() if n else d_bb[:, :0], n
+    frames = packet_rows(d_rows.contiguous(), tones, space_gain, q_min) if m else []
+    return dict(frames=frames, tracks=aprs_tracks(frames), lines=[f['tnc2'] for f in frames], fs=_PACKET_RATE)
+
+
 def recording_to_wav(npy_path, wav_path, sample_rate, mode='NFM', frame_len=32768, codes_format=None, table=None):
     """codes_format: npy_path is a raw file of ADC codes (load_iq_codes) instead of the reference's .npy."""
     if codes_format is not None:
