@@ -968,7 +968,7 @@ int pss_ais_frames(pss_ctx *ctx, const float *d_y, long n_rows, long y_stride, l
 int pss_h_ais_frames(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
                      uint8_t *h_msg, int32_t *h_len, int32_t *h_row, int64_t *h_pos, float *h_score, int32_t *h_count, int max_frames);
 /* ---- POCSAG: the pager messages of a VHF capture — what the reference's command list starts `rtl_fm ... | multimon-ng -a POCSAG1200` for
- * (rtlcoms.json, "Decode Pager", "Monitor Pager traffic").  The arithmetic is the project's own, stated once in csrc/pss_pocsag.h (PARITY.md
+ * (rtlcoms.json, "Decode Pager"; "Monitor Pager traffic" is FLEX, below).  The arithmetic is the project's own, stated once in csrc/pss_pocsag.h (PARITY.md
  * "POCSAG"); the device and the host twin agree on every byte, and every output follows from indices in the ROW, so no chunking changes one.
  * The rows run at 38 400 S/s: spb = 75, 32 and 16 samples a bit at 512, 1200 and 2400 bit/s.  The front is pss_ais_front above (it reads no
  * rate) with pss_pocsag_default_pulse's boxcar.
@@ -1011,6 +1011,44 @@ int pss_pocsag_batches(pss_ctx *ctx, const float *d_y, long n_rows, long y_strid
 int pss_h_pocsag_batches(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, int spb,
                          int sync_errors, int fix, int max_bad, uint32_t *h_cw, uint8_t *h_fix, int32_t *h_row, int64_t *h_pos, uint32_t *h_meta,
                          float *h_score, int32_t *h_count, int max_batches);
+/* ---- FLEX: the other pager protocol — what the reference's command list starts `rtl_fm ... | multimon-ng -a FLEX` for (rtlcoms.json,
+ * "Monitor Pager traffic (Def. 138M)").  Two- and four-level FSK at 1600 and 3200 baud, a mode word in the frame's own sync, 11 interleaved
+ * blocks of up to four multiplexed phases.  The arithmetic is the project's own, stated once in csrc/pss_flex.h (PARITY.md "FLEX"); the
+ * air-interface constants there are the published ones written from memory and HAVE NOT BEEN CHECKED AGAINST A TRANSMITTER.  The device and
+ * the host twin agree on every byte, and every output follows from indices in the ROW.  The rows are pss_pocsag_plan's at 38 400 S/s: h = 12
+ * samples a 3200-baud symbol; the front is pss_ais_front with pss_flex_default_pulse's boxcar, one pass for both baud rates.
+ * pss_flex_default_pulse: the post-filter for h samples a 3200-baud symbol (in [1, 64]): P = the largest odd number <= h taps of 1.0 / P.
+ * pss_flex_word: the 32-bit word of 21 data bits: the data in bits 0 .. 20, the BCH(31,21) check bits in 21 .. 30, even parity in bit 31: a
+ *   POCSAG codeword bit-reversed.  Host only.
+ * pss_flex_frames: dev_y float32 rows, y_stride samples apart, 4-byte aligned, holding samples [buf_index0, buf_index0 + n_buf) of rows of
+ *   n_row samples.  Every start s in [s_begin, s_end) of every row with s + 5936 h <= n_row is a candidate: 64 sync bits 2 h apart, each the
+ *   sum of two samples h apart, sliced at their own mean; at most sync_errors (in [0, 3]) mismatches of the marker 0xA6C6AAAA in either
+ *   polarity, of the outer code against its complement, and of the outer code against the nearest of the five mode codes; the frame
+ *   information word through the BCH check with the caller's fix (in [0, 2]) and its nibble sum; of accepted starts less than 2 h apart the
+ *   one with the fewest mismatches plus FIW fixed bits stays (then the larger mean distance from the threshold, then the earlier); its 11
+ *   blocks are sliced at thresholds from the sync's mean and mean distance (four levels: +- 2/3 of it), de-interleaved into the phases A .. D,
+ *   88 words each, every word through the check; a frame with more than max_bad (in [0, 352]) uncorrectable words leaves no record.
+ *   Records in ascending (row, s): dev_words uint32 [max_frames][4][88] (corrected; 0 where uncorrectable and in unused phases), dev_fix uint8
+ *   [max_frames][4][88] (0, 1, 2 or 255), dev_fiw uint32, dev_row int32, dev_pos int64, dev_meta uint32 [max_frames][2] (mismatches | inverted << 8 |
+ *   mode << 12 | FIW fixed bits << 16; n_bad | total fixed bits << 16), dev_score float32 (the mean distance), dev_count int32 [1] (the TRUE
+ *   count; nothing is written past max_frames).  The buffer must hold the samples from max(0, s_begin - (2 h - 1)) to min(n_row, s_end +
+ *   2 h - 2 + 5936 h).
+ *   PSS_E_ARG ("pss_flex_frames: "; a refused call writes nothing): n_rows outside [1, 2^20], h, sync_errors, fix or max_bad outside their
+ *   ranges, a buffer or a window outside the row, y_stride < n_buf, s_end < s_begin, a window above 2^30 starts (2^31 over all rows), a
+ *   buffer that does not cover the window's reach, max_frames < 0, a null or misaligned pointer.
+ *   Kernels: k_flex_detect (the one pass over every start), then k_starts_scan, k_starts_gather, k_flex_head, k_flex_keep, k_flex_walk (a
+ *   workgroup per kept start), k_starts_scan, k_flex_compact.  Scratch on the context (the start list's buffers), 2 bytes per start of the
+ *   largest call and 1796 bytes per survivor, grow-only and freed by pss_destroy; the call waits once for the count of survivors.
+ * pss_h_flex_frames: the same on host buffers, pure host code (no context, no GPU; the reason: pss_last_error(NULL), starting
+ *   "pss_flex_frames: "). */
+int pss_flex_default_pulse(int h, double *pulse, int *n_pulse);
+uint32_t pss_flex_word(uint32_t data21);
+int pss_flex_frames(pss_ctx *ctx, const float *dev_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end,
+                    int h, int sync_errors, int fix, int max_bad, uint32_t *dev_words, uint8_t *dev_fix, uint32_t *dev_fiw, int32_t *dev_row, int64_t *dev_pos,
+                    uint32_t *dev_meta, float *dev_score, int32_t *dev_count, int max_frames);
+int pss_h_flex_frames(const float *h_y, long n_rows, long y_stride, long n_buf, long buf_index0, long n_row, long s_begin, long s_end, int h,
+                      int sync_errors, int fix, int max_bad, uint32_t *h_words, uint8_t *h_fix, uint32_t *h_fiw, int32_t *h_row, int64_t *h_pos,
+                      uint32_t *h_meta, float *h_score, int32_t *h_count, int max_frames);
 /* ---- NOAA APT: the weather-satellite image of a 137 MHz capture — what the reference's command list starts `rtl_fm -f 137.62M -M fm -s 60k ...
  * | sox ... && wxtoimg` for (rtlcoms.json, "Capture NOAA in .wav"; the band is pyspecconst.py's NOAA_SAT preset).  The arithmetic is the
  * project's own, stated once in csrc/pss_apt.h (PARITY.md "APT"); the device and the host twins agree on every byte, and every output follows

@@ -39,6 +39,7 @@ UNITS = [
     ("pss_adsb.hip", ["-ffp-contract=off"]),   # the Mode S receiver: float32 products and sums one by one, strict comparisons
     ("pss_ais.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the AIS receiver: NumPy's float32 arctan2, one fma chain, strict comparisons
     ("pss_pocsag.hip", ["-ffp-contract=off"]),   # the POCSAG receiver: float32 sums one by one, strict comparisons, integer BCH arithmetic
+    ("pss_flex.hip", ["-ffp-contract=off"]),   # the FLEX receiver: float32 sums one by one, strict comparisons, pss_pocsag.h's BCH arithmetic
     ("pss_apt.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the APT receiver: NumPy's float32 arctan2, fma chains, float32 sums and divisions one by one
     ("pss_ook.hip", ["-ffp-contract=off"]),   # the OOK receiver: float32 products and sums one by one, float64 sums in a stated order, integer slicers
     ("pss_packet.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),   # the packet-radio receiver: NumPy's float32 arctan2, four fma chains, float64 products and one division, integer clock tracking

@@ -1793,6 +1793,64 @@ class Engine:
         k = min(int(count[0]), room)
         return cw[:k], fx[:k], rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
 
+    # -- FLEX: float32 discriminator rows at 38.4 kS/s -> the frames whose words pass their check (pss_flex_*; the arithmetic:
+    #    csrc/pss_flex.h).  The front is ais_front with flex_default_pulse(h), one pass for both baud rates.
+    FLEX_MARKER = 0xA6C6AAAA
+    FLEX_MODES = ((0x870C, 1600, 2), (0xB068, 1600, 4), (0x7B18, 3200, 2), (0xDEA0, 3200, 4), (0x4C7C, 3200, 4))   # code, baud, levels
+
+    @staticmethod
+    def flex_default_pulse(h, lib=None):
+        """pss_flex_default_pulse: a boxcar of the largest odd number of taps <= h (h in [1, 64]), each 1 / P (float64).  Host code."""
+        return Engine._default_taps(lib, "pss_flex_default_pulse", "flex_default_pulse: h outside [1, 64]", h)
+
+    @staticmethod
+    def flex_word(data21, lib=None):
+        """pss_flex_word: the 32-bit word of 21 data bits (data in bits 0 .. 20, BCH(31,21) in 21 .. 30, even parity in 31).  Host code."""
+        lib = lib or L.load()
+        return int(lib.pss_flex_word(int(data21) & 0x1FFFFF))
+
+    def flex_frames(self, d_y, n_rows, n_buf, h, d_words, d_fix, d_fiw, d_row, d_pos, d_meta, d_score, d_count, max_frames, sync_errors=2, fix=2,
+                    max_bad=0, y_stride=None, buf_index0=0, n_row=None, s_begin=0, s_end=None):
+        """d_y float32: n_rows rows y_stride samples apart (default n_buf), samples [buf_index0, buf_index0 + n_buf) of rows of n_row samples
+        (default: the buffer is the row), h samples a 3200-baud symbol -> the frames whose sync starts in [s_begin, s_end) (default: to the
+        row's end) of every row, ascending in (row, s): d_words uint32 [max_frames][4][88], d_fix uint8 [max_frames][4][88], d_fiw uint32,
+        d_row int32, d_pos int64, d_meta uint32 [max_frames][2] (mismatches | inverted << 8 | mode << 12 | FIW fixed bits << 16; n_bad |
+        fixed bits << 16), d_score float32, d_count int32 [1] (the true count)."""
+        n_row = int(buf_index0) + int(n_buf) if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        self._dev(self.lib.pss_flex_frames, _ptr(d_y), int(n_rows), int(n_buf if y_stride is None else y_stride), int(n_buf), int(buf_index0), n_row,
+                  int(s_begin), s_end, int(h), int(sync_errors), int(fix), int(max_bad), _ptr(d_words), _ptr(d_fix), _ptr(d_fiw), _ptr(d_row), _ptr(d_pos),
+                  _ptr(d_meta), _ptr(d_score), _ptr(d_count), int(max_frames))
+
+    @staticmethod
+    def h_flex_frames(y, h, sync_errors=2, fix=2, max_bad=0, buf_index0=0, n_row=None, s_begin=0, s_end=None, max_frames=None, lib=None):
+        """pss_h_flex_frames on a host float32 array [n_rows][n_buf] or [n_buf] -> (words uint32 [k][4][88], fix uint8 [k][4][88], fiw uint32
+        [k], row int32 [k], pos int64 [k], meta uint32 [k][2], score float32 [k], count): the first k = min(count, max_frames) records and
+        the true count.  max_frames: default room for every frame.  Pure host code."""
+        lib = lib or L.load()
+        x = np.asarray(y, np.float32)
+        if x.ndim not in (1, 2):
+            raise ValueError("y: a 1-D or 2-D float32 array")
+        rows = Engine._as_rows(x)
+        n_row = int(buf_index0) + rows.shape[1] if n_row is None else int(n_row)
+        s_end = n_row if s_end is None else int(s_end)
+        grow = max_frames is None
+        max_frames = 16 if grow else int(max_frames)
+        while True:
+            room = max(max_frames, 0)
+            words, fx, fiw = np.zeros((room, 4, 88), np.uint32), np.zeros((room, 4, 88), np.uint8), np.zeros(room, np.uint32)
+            rw, pos, meta = np.zeros(room, np.int32), np.zeros(room, np.int64), np.zeros((room, 2), np.uint32)
+            score, count = np.zeros(room, np.float32), np.zeros(1, np.int32)
+            if lib.pss_h_flex_frames(_ptr(rows), rows.shape[0], rows.shape[1], rows.shape[1], int(buf_index0), n_row, int(s_begin), s_end, int(h),
+                                     int(sync_errors), int(fix), int(max_bad), _ptr(words), _ptr(fx), _ptr(fiw), _ptr(rw), _ptr(pos), _ptr(meta),
+                                     _ptr(score), _ptr(count), max_frames) != 0:
+                raise ValueError(lib.pss_last_error(None).decode())
+            if not grow or int(count[0]) <= room:
+                break
+            max_frames = int(count[0])   # the first run gave the true count
+        k = min(int(count[0]), room)
+        return words[:k], fx[:k], fiw[:k], rw[:k], pos[:k], meta[:k], score[:k], int(count[0])
+
     # -- OOK devices: complex64 rows -> the envelope (a stage dump), the block means the thresholds come from, the sliced messages
     #    (pss_ook_*; the arithmetic: csrc/pss_ook.h).  spec: formats.ook_spec's dict, every length in samples.
     OOK_PWM, OOK_PPM, OOK_MC = 0, 1, 2

@@ -1678,6 +1678,202 @@ def pocsag_recording(samples, fs, center_hz, channels_hz, bauds=(512, 1200, 2400
     return dict(messages=messages, lines=pocsag_lines(messages), batches=batches, fs=_POCSAG_RATE)
 
 
+# ---- FLEX: the pager messages of a capture, two- and four-level FSK (the arithmetic of the device stages: csrc/pss_flex.h).  The constants
+#      of the message layer are the published ones as multimon-ng reads them, written from memory: not checked against a transmitter.
+_FLEX_MODES = ((1600, 2), (1600, 4), (3200, 2), (3200, 4), (3200, 4))
+_FLEX_NUMERIC = "0123456789 U -]["
+_FLEX_PHASES = "ABCD"
+_FLEX_H = 12          # samples a 3200-baud symbol at 38 400 S/s
+
+
+def flex_records(words, fix, fiw, row, pos, meta, score):
+    """The arrays of pss_flex_frames / Engine.h_flex_frames -> one dict per frame: 'words' and 'fix' (4 lists of 88 ints), 'fiw', 'row', 'pos',
+    'meta' (2 ints), 'score', and the fields of meta and fiw: 'sync_errors', 'inverted', 'mode', 'baud', 'levels', 'fiw_fixed', 'n_bad',
+    'fixed', 'cycle', 'frame'."""
+    out = []
+    for w, f, i, r, p, m, q in zip(words, fix, fiw, row, pos, meta, score):
+        m0, m1, i = int(m[0]), int(m[1]), int(i)
+        mode = (m0 >> 12) & 15
+        out.append(dict(words=[[int(v) for v in ph] for ph in w], fix=[[int(v) for v in ph] for ph in f], fiw=i, row=int(r), pos=int(p), meta=[m0, m1],
+                        score=float(q), sync_errors=m0 & 0xFF, inverted=bool((m0 >> 8) & 1), mode=mode, baud=_FLEX_MODES[mode][0],
+                        levels=_FLEX_MODES[mode][1], fiw_fixed=(m0 >> 16) & 0xFF, n_bad=m1 & 0xFFFF, fixed=m1 >> 16, cycle=(i >> 4) & 15,
+                        frame=(i >> 8) & 127))
+    return out
+
+
+def _flex_phases(rec):
+    return [p for p in range(4) if p == 0 or (p == 1 and rec['levels'] == 4) or (p == 2 and rec['baud'] == 3200) or
+            (p == 3 and rec['baud'] == 3200 and rec['levels'] == 4)]
+
+
+def flex_messages(records):
+    """records: flex_records' dicts -> the messages in order of (row, pos, phase, address word), each a dict: 'capcode' (short addresses: the
+    address word's data - 0x8000; None for a long one), 'long', 'address' (the raw data of its one or two words), 'type' ('ALN' for vector
+    type 5, 'NUM' for 3, the number otherwise), 'text' (ALN and NUM), 'fragment' and 'cont' (ALN), 'words' (the raw data of its vector
+    word(s) for the other types), 'phase' ('A' .. 'D'), 'row', 'pos', 'cycle', 'frame', 'baud', 'levels', 'damaged' (it touches an
+    uncorrectable word).  Per phase, d = the low 21 bits of each word:
+    word 0 is the block information word: its nibble sum must be 15 (else the phase is skipped); first address word = (d >> 8 & 3) + 1, first
+    vector word = d >> 10 & 63.  An address is short when 0x8001 <= d <= 0x1E0000; any other takes two words, and so does its vector.
+    Address word i's vector sits at the same offset into the vector field; type = d >> 4 & 7.  Type 5: start = d >> 7 & 127, length = d >> 14
+    & 127 words: the first holds fragment (d >> 11 & 3) and continue (d >> 10 & 1), the others three 7-bit characters each from bit 0; the
+    first character is a signature when fragment = 3; ETX (3) is dropped.  Type 3: start = d >> 7 & 127, (d >> 14 & 7) + 1 words read as a bit
+    stream from bit 0: 10 bits skipped, then 4-bit digits, least significant bit first, through "0123456789 U -]["; trailing spaces dropped."""
+    out = []
+    for rec in sorted(records, key=lambda r: (r['row'], r['pos'])):
+        for p in _flex_phases(rec):
+            d = [w & 0x1FFFFF for w in rec['words'][p]]
+            bad = [f == 255 for f in rec['fix'][p]]
+            biw = d[0]
+            s = ((biw & 15) + (biw >> 4 & 15) + (biw >> 8 & 15) + (biw >> 12 & 15) + (biw >> 16 & 15) + (biw >> 20 & 1)) & 15
+            if bad[0] or s != 15:
+                continue
+            first_addr, first_vec = (biw >> 8 & 3) + 1, biw >> 10 & 63
+            i = first_addr
+            while i < first_vec:
+                short = 0x8001 <= d[i] <= 0x1E0000
+                n_a = 1 if short else 2
+                v = first_vec + (i - first_addr)
+                if i + n_a > first_vec or v + n_a > 88:
+                    break
+                touched = list(range(i, i + n_a)) + list(range(v, v + n_a))
+                vec = d[v]
+                kind = vec >> 4 & 7
+                m = dict(capcode=d[i] - 0x8000 if short else None, long=not short, address=d[i:i + n_a], type=kind, phase=_FLEX_PHASES[p], row=rec['row'],
+                         pos=rec['pos'], cycle=rec['cycle'], frame=rec['frame'], baud=rec['baud'], levels=rec['levels'])
+                if kind == 5 and not bad[v]:
+                    start, length = vec >> 7 & 127, vec >> 14 & 127
+                    body = list(range(start, min(start + length, 88)))
+                    touched += body
+                    codes = []
+                    if body:
+                        m['fragment'], m['cont'] = d[body[0]] >> 11 & 3, d[body[0]] >> 10 & 1
+                        for k in body[1:]:
+                            codes += [d[k] & 127, d[k] >> 7 & 127, d[k] >> 14 & 127]
+                        if m['fragment'] == 3:
+                            codes = codes[1:]
+                    m['type'] = 'ALN'
+                    m['text'] = "".join(chr(c) if 32 <= c < 127 else "?" for c in codes if c != 3)
+                elif kind == 3 and not bad[v]:
+                    start, n_w = vec >> 7 & 127, (vec >> 14 & 7) + 1
+                    body = list(range(start, min(start + n_w, 88)))
+                    touched += body
+                    bits = [(d[k] >> b) & 1 for k in body for b in range(21)][10:]
+                    m['type'] = 'NUM'
+                    m['text'] = "".join(_FLEX_NUMERIC[sum(b << u for u, b in enumerate(bits[k:k + 4]))] for k in range(0, len(bits) - 3, 4)).rstrip(" ")
+                else:
+                    m['words'] = d[v:v + n_a]
+                m['damaged'] = any(bad[k] for k in touched)
+                out.append(m)
+                i += n_a
+    return out
+
+
+def flex_lines(messages):
+    """multimon-ng's lines without the clock a capture does not have: `FLEX: 1600/2/A 03.077 [001234567] ALN text`; the vector type's number
+    and the raw words for the other types, `[long aaaaaa bbbbbb]` for a long address."""
+    out = []
+    for m in messages:
+        who = f"[{m['capcode']:09d}]" if not m['long'] else "[long " + " ".join(f"{a:06X}" for a in m['address']) + "]"
+        head = f"FLEX: {m['baud']}/{m['levels']}/{m['phase']} {m['cycle']:02d}.{m['frame']:03d} {who} "
+        out.append(head + (f"{m['type']} {m['text']}" if 'text' in m else f"T{m['type']} " + " ".join(f"{w:06X}" for w in m['words'])))
+    return out
+
+
+def _flex_frames(e, d_y, n_rows, n, h, sync_errors, fix, max_bad):
+    """pss_flex_frames on resident rows -> the records on the host (flex_records)."""
+    import torch
+    dev = d_y.device
+    room = 256
+    while True:
+        d_words = torch.empty((room, 4, 88), dtype=torch.int32, device=dev)
+        d_fix = torch.empty((room, 4, 88), dtype=torch.uint8, device=dev)
+        d_fiw = torch.empty(room, dtype=torch.int32, device=dev)
+        d_row = torch.empty(room, dtype=torch.int32, device=dev)
+        d_pos = torch.empty(room, dtype=torch.int64, device=dev)
+        d_meta = torch.empty((room, 2), dtype=torch.int32, device=dev)
+        d_score = torch.empty(room, dtype=torch.float32, device=dev)
+        d_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        e.flex_frames(d_y, n_rows, n, h, d_words, d_fix, d_fiw, d_row, d_pos, d_meta, d_score, d_count, room, sync_errors=sync_errors, fix=fix,
+                      max_bad=max_bad)
+        k = int(d_count.cpu()[0])
+        if k <= room:
+            break
+        room = k   # the true count: again with room for it
+    words, fx, fiw, row, pos, meta, score = (t[:k].cpu().numpy() for t in (d_words, d_fix, d_fiw, d_row, d_pos, d_meta, d_score))
+    return flex_records(words.view(np.uint32), fx, fiw.view(np.uint32), row, pos, meta.view(np.uint32), score)
+
+
+def h_flex_rows(rows, h=_FLEX_H, sync_errors=2, fix=2, max_bad=0):
+    """flex_rows on the host: pss_h_ais_front and pss_h_flex_frames on complex64 rows [k][n] or [n] -> (messages, frames).  No GPU."""
+    x = np.asarray(rows, np.complex64)
+    if x.ndim not in (1, 2):
+        raise ValueError("rows: a 1-D or 2-D complex array")
+    x = np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+    if not x.shape[0] or not x.shape[1]:
+        return [], []
+    from .engine import Engine
+    y = Engine.h_ais_front(x, pulse=Engine.flex_default_pulse(h))
+    recs = flex_records(*Engine.h_flex_frames(y, h, sync_errors=sync_errors, fix=fix, max_bad=max_bad)[:7])
+    return flex_messages(recs), recs
+
+
+def flex_rows(rows, h=_FLEX_H, sync_errors=2, fix=2, max_bad=0):
+    """rows: complex64 rows at 38 400 S/s (h = 12 samples a 3200-baud symbol) — a host array [k][n] or [n], or a resident device tensor
+    float32 [k][2 n] — -> (messages, frames): pss_ais_front with flex_default_pulse's boxcar once (both baud rates read the same rows), then
+    pss_flex_frames on the resident rows, then flex_messages.  frames: flex_records' dicts."""
+    import torch
+    e = get_engine()
+    if isinstance(rows, torch.Tensor):
+        d_rows = rows
+    else:
+        x = np.asarray(rows, np.complex64)
+        if x.ndim not in (1, 2):
+            raise ValueError("rows: a 1-D or 2-D complex array")
+        x = np.ascontiguousarray(x[None, :] if x.ndim == 1 else x)
+        d_rows = torch.from_numpy(x.view(np.float32)).to(f"cuda:{e.device}")
+    if d_rows.dim() != 2 or d_rows.dtype != torch.float32 or d_rows.shape[1] % 2 or not d_rows.is_contiguous():
+        raise ValueError("rows: a contiguous device tensor float32 [k][2 n]")
+    k, n = d_rows.shape[0], d_rows.shape[1] // 2
+    if not k or not n:
+        return [], []
+    d_y = torch.empty((k, n), dtype=torch.float32, device=d_rows.device)
+    e.ais_front(d_rows, k, n, d_y, pulse=e.flex_default_pulse(h))
+    recs = _flex_frames(e, d_y, k, n, h, sync_errors, fix, max_bad)
+    return flex_messages(recs), recs
+
+
+def flex_recording(samples, fs, center_hz, channels_hz, taps=None, chunk_samples=1 << 22, codes_format=None, table=None, sync_errors=2, fix=2,
+                   max_bad=0):
+    """The FLEX pager messages of a capture centred on center_hz -> dict(messages=..., lines=..., frames=..., fs=38400): 'messages'
+    flex_messages' dicts ('row' is the channel's position in channels_hz), 'lines' flex_lines(messages), 'frames' the receiver's records, 'fs'
+    the rate the positions count in.  On the GPU from the upload to the records: pss_ddc puts the listed channels at 0 Hz at pocsag_plan(fs)'s
+    decimation (streamed in chunks of chunk_samples samples plus their halos; the result does not depend on chunk_samples), pss_resample
+    brings them to 38 400 S/s where the decimated rate is another one, then flex_rows.  taps: the down-converter's float64 low-pass (default
+    firwin(20 decim + 1, 20 000 / fs): half-width 10 kHz, so the outer levels at +-4800 Hz and the 3200-baud sidebands around them pass);
+    codes_format / table: as demodulate_recording."""
+    import torch
+    e = get_engine()
+    fs = float(fs)
+    decim, up, down = e.pocsag_plan(fs)
+    offsets = np.atleast_1d(np.asarray(channels_hz, np.float64)) - float(center_hz)
+    if offsets.ndim != 1 or not len(offsets):
+        raise ValueError("channels_hz: a list of frequencies")
+    if taps is None:
+        taps = np.empty(20 * decim + 1, np.float64)
+        if e.lib.pss_design_firwin(len(taps), 20000.0 / fs, taps.ctypes.data) != 0:
+            raise ValueError("flex_recording: the down-converter's filter design failed")
+    d_rows, _ = _tune_device(samples, fs, offsets, decim, taps, None, chunk_samples, codes_format, table)
+    k, m = d_rows.shape[0], d_rows.shape[1] // 2
+    if (up, down) != (1, 1):
+        n = e.resample_out_len(m, up, down)
+        d_bb = torch.empty((k, 2 * max(n, 1)), dtype=torch.float32, device=d_rows.device)
+        if m:
+            e.resample(d_rows, np.complex64, k, m, up, down, d_bb)
+        d_rows, m = d_bb[:, :2 * n].contiguous() if n else d_bb[:, :0], n
+    messages, frames = flex_rows(d_rows.contiguous(), _FLEX_H, sync_errors, fix, max_bad) if m else ([], [])
+    return dict(messages=messages, lines=flex_lines(messages), frames=frames, fs=_POCSAG_RATE)
+
+
 # ---- OOK devices: the sensor and remote messages of a 433 MHz capture (the arithmetic of the device stages: csrc/pss_ook.h)
 _OOK_MODES = {'OOK_PWM': 0, 'OOK_PPM': 1, 'OOK_MC_ZEROBIT': 2}
 _OOK_FLAGS = ((1 << 22, 'OPEN'), (1 << 23, 'LONG'), (1 << 24, 'MANY'), (1 << 25, 'FULL'))
